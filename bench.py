@@ -10,7 +10,10 @@ N > 1: one process per GPU (torch.distributed launcher), flanks sharded over ran
 BASELINE configs[3]: the same 100,000 flanks split over the ranks, one vote exchange per column; `--scaling weak`
 gives every rank its own 100,000 flanks.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the `roofline` of the
+timed launches.  A plain run sets up, warms up, times --steps steps and writes the outputs of the last step (--dump-outputs DIR);
+everything else -- the repeatability and reference-digest checks, the aligned / tail phase split, seam-1 and real-run timings,
+BASELINE configs[1] and the CPU baseline -- runs only with --full.
 """
 from __future__ import annotations
 
@@ -140,6 +143,26 @@ def host_cpu():
     return {"model": model, "logical_cpus": os.cpu_count(), "usable_cpus": usable}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, ret: int, cons: np.ndarray, ext: np.ndarray, sc: np.ndarray, suffix: str = "") -> None:
+    """What a caller of the timed path receives for the last timed step, as float64 .npy files: the return value, the consensus
+    byte of every executed column, and per flank the extension length and the score increment.  Above DUMP_LIMIT_BYTES the
+    per-flank arrays are a fixed seeded sample (its flank indices go next to them)."""
+    os.makedirs(out_dir, exist_ok=True)
+    per_flank = {"extension_len": ext, "score": sc}
+    budget = DUMP_LIMIT_BYTES - 8 * (1 + len(cons)) - 4096      # (npy headers)
+    if 8 * len(per_flank) * len(ext) > budget:
+        keep = budget // (8 * (len(per_flank) + 1))
+        idx = np.sort(np.random.default_rng(0).choice(len(ext), size=keep, replace=False))
+        per_flank = {k: v[idx] for k, v in per_flank.items()}
+        per_flank["sample_index"] = idx
+    arrays = {"ret": np.array([ret]), "consensus": cons, **per_flank}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -156,10 +179,17 @@ def main():
     ap.add_argument("--cpu-flanks", type=int, default=20000)
     ap.add_argument("--cpu-cols", type=int, default=200)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: repeatability and reference-digest checks, phase split, seam-1 / real-run "
+                         "timings, BASELINE configs[1] and the CPU baseline (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed to DIR/<name>.npy (float64)")
     ap.add_argument("--ragged", type=float, default=0.0,
                     help="development only: this fraction of the flanks ends early (uniform in [0, L)), so that waves "
                          "take the far-end-masked band; the headline workload uses full-length flanks (0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))        # `python3 bench.py --gpus N` with no launcher: start the N ranks ourselves
@@ -258,7 +288,8 @@ def main():
     digest0 = None
     for _ in range(args.warmup):
         dev.run_direction()
-        digest0 = result_digest()
+        if args.full:
+            digest0 = result_digest()
     barrier()
     t0 = time.perf_counter()
     for s in range(args.steps):
@@ -270,12 +301,19 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
 
-    # outside the timed region: every pass over the same resident input must give the same consensus and the same
+    if args.dump_outputs:
+        cons, th, tp = dev.download()
+        ext, sc = writeback_from_trim(th, tp)
+        dump_outputs(args.dump_outputs, dev.last.ret, cons, ext, sc, "" if rank == 0 else f"_rank{rank}")
+
+    # --full, outside the timed region: every pass over the same resident input must give the same consensus and the same
     # per-flank trimmed scores / positions (a race in the vote or the barrier would show up here)
-    digest1 = result_digest()
-    repeatable = (digest0 is None) or (digest0 == digest1)
-    if not repeatable:
-        raise SystemExit(f"bench: results of the timed passes differ from the warm-up pass ({digest0} vs {digest1})")
+    digest1 = None
+    if args.full:
+        digest1 = result_digest()
+        repeatable = (digest0 is None) or (digest0 == digest1)
+        if not repeatable:
+            raise SystemExit(f"bench: results of the timed passes differ from the warm-up pass ({digest0} vs {digest1})")
 
     cols = sum(i.rows_executed for i in infos)
     value = cols * total_flanks / dt
@@ -396,7 +434,7 @@ def main():
     # columns behind the end of the alignment) and the CAPPED TAIL (flanks at their caps: LEAN rows, exact and digest-checked, but
     # cheaper).  One more launch over the first K columns separates them.
     phases = None
-    if world == 1 and persistent and lanes == 1 and L > 1500 and args.ragged == 0 and not args.no_phases:
+    if args.full and world == 1 and persistent and lanes == 1 and L > 1500 and args.ragged == 0 and not args.no_phases:
         K = 1500
         pk = ExtendParams(bandwidth=W, cappenalty=p.cappenalty, minimprovement=p.minimprovement, L=K, when_to_stop=K, l=1,
                           gapopen=go, gapextn=ge, matrix=mat, matrix_name="14p43g")
@@ -414,7 +452,7 @@ def main():
                           "(rows LEAN once the flanks sit at their caps); `value` is the whole launch"}
     # ---- outside the timed region: seam 1 (host buffers in, host results out) on the same set ----------------------
     seam1 = None
-    if world == 1 and not args.no_seam1:
+    if args.full and world == 1 and not args.no_seam1:
         from repeatafterme_amd.datamodel import new_master
         from repeatafterme_amd.extend import extend_alignment
         c1 = fs.cores.copy(); m1 = new_master(L)
@@ -428,7 +466,7 @@ def main():
     # ---- ... and a REAL run: the same set with the reference's default -stopafter 100 (what util/extend-stk.pl:365 runs): the
     # loop stops 100 columns behind the end of the alignment, so prep / download are a large part of the call
     real_run = None
-    if world == 1 and not args.no_seam1 and args.ragged == 0:
+    if args.full and world == 1 and not args.no_seam1 and args.ragged == 0:
         from repeatafterme_amd.datamodel import new_master
         from repeatafterme_amd.extend import extend_alignment
         pr = ExtendParams(bandwidth=W, cappenalty=p.cappenalty, minimprovement=p.minimprovement, L=L, when_to_stop=100, l=1,
@@ -450,7 +488,7 @@ def main():
     # ---- outside the timed region: BASELINE configs[1] (N = 1,000 x L = 2,000: a parity configuration, not the bench
     # line) through seam 1 -- the size class where a column is a latency chain, served by the cell-parallel kernel ------
     cfg1 = None
-    if world == 1 and not args.no_seam1 and args.flanks == 100000 and W == 40:
+    if args.full and world == 1 and not args.no_seam1 and args.flanks == 100000 and W == 40:
         from repeatafterme_amd.datamodel import new_master
         from repeatafterme_amd.extend import extend_alignment
         f1 = synth_family(1000, 2000, W, K=1500, seed=3)
@@ -483,10 +521,10 @@ def main():
         transport = "in-kernel mailboxes, " + ("peer device memory (xGMI)" if getattr(dev, "peer_kind", None) == "device" else "registered host shared memory (PCIe)")
     else:
         transport = "RCCL all-reduce between column launches" if dist.get_backend() == "nccl" else "host all-reduce (gloo rehearsal hook) between column launches"
-    checks = {"result_sha1": digest1, "same_as_warmup_pass": bool(digest0 is not None)}
+    checks = {"result_sha1": digest1, "same_as_warmup_pass": bool(digest0 is not None)} if args.full else None
     # reference parity at full size: the compiled reference's digest of this exact workload (tests/golden/make_fullsize_digest.py)
     gold = os.path.join(ROOT, "tests", "golden", "fullsize_digests.json")
-    if world == 1 and os.path.exists(gold) and args.ragged == 0:
+    if args.full and world == 1 and os.path.exists(gold) and args.ragged == 0:
         for name, g in json.load(open(gold)).items():
             w = g["workload"]
             if (w["n"], w["L"], w["W"], w["K"], w["seed"]) == (N, L, W, 1500, 1) and g["when_to_stop"] == L:
@@ -496,7 +534,7 @@ def main():
                     raise SystemExit(f"bench: result digest {digest1} differs from the compiled reference's {g['sha1']} ({name})")
     out = {
         "metric": "flank_bp_aligned_per_sec (extension columns/s x flanks)", "value": value, "unit": "flank-bp/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "full": args.full,
         "higher_is_better": True, "scaling": (None if world == 1 else ("strong" if strong else "weak")), "vs_baseline": None, "dtype": "int32", "data": "synthetic",
         "config": {"workload": (f"synthetic N={total_flanks} flanks" + (f" split over {world} GPUs" if strong else (" per GPU" if world > 1 else ""))
                                 + f" x L={L} bp, bandwidth={W}, matrix 14p43g, "
@@ -520,7 +558,7 @@ def main():
         "configs1_n1000": cfg1,
         "setup": {"synth_s": t_gen, "upload_pack_s": t_upload},
     }
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cb, m_cpu, sub = cpu_baseline(fs, p, min(args.cpu_flanks, N), args.cpu_cols)
         out["cpu_baseline"] = cb
         out["gpu_over_cpu"] = value / cb["value"]

@@ -3,7 +3,7 @@
 for L in ${LS:-1500 10000}; do
 for lib in repeatafterme_amd/libramx.so ab_tmp/libramx_*.so; do
   echo -n "L $L $lib: "
-  RAMX_LIB=$lib python bench.py --steps 2 --warmup 1 --no-cpu --no-seam1 --L $L 2>/dev/null | python -c "
+  RAMX_LIB=$lib python bench.py --full --steps 2 --warmup 1 --no-cpu --no-seam1 --L $L 2>/dev/null | python -c "
 import sys, json
 try:
   d = json.loads(sys.stdin.read().strip().splitlines()[-1])

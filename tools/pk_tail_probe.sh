@@ -11,4 +11,4 @@ echo -n "product: "; run
 echo -n "RAMX_LEADER_MAX=0: "; RAMX_LEADER_MAX=0 run
 echo -n "no leader rows (probe): "; RAMX_LIB=ab_tmp/libramx_NL.so RAMX_BENCH_NOCHECK=1 run
 echo -n "RAMX_NO_PK_SPEC=1: "; RAMX_NO_PK_SPEC=1 run
-RAMX_LIB=ab_tmp/libramx_TT.so python bench.py --steps 1 --warmup 0 --no-cpu --no-seam1 --L 10000 2>&1 | grep -E "PRK_TIMING"
+RAMX_LIB=ab_tmp/libramx_TT.so python bench.py --full --steps 1 --warmup 0 --no-cpu --no-seam1 --L 10000 2>&1 | grep -E "PRK_TIMING"

@@ -6,7 +6,7 @@ export RAMX_NO_CP_DEVICE=1
 for n in ${NS:-25000 50000 65000}; do
 for v in "RAMX_DUMMY=1" "RAMX_PK_NO_VW=1"; do
 for L in 1500 10000; do
-  env $v python bench.py --steps 2 --warmup 1 --no-cpu --no-seam1 --no-phases --flanks $n --L $L 2>/dev/null | python -c "
+  env $v python bench.py --full --steps 2 --warmup 1 --no-cpu --no-seam1 --no-phases --flanks $n --L $L 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('N', $n, 'L', $L, '[$v] us/col %.3f digest %s' % (d['ms_per_step'] * 1e3 / d['config']['columns_per_step'], d['checks'].get('equals_reference_digest')))"

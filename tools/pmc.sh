@@ -2,7 +2,7 @@
 # PMC counter passes for the column kernel (run ON the GPU box via gpurun).  Each --pmc set is its own
 # run with no other tracing (the pool refuses pmc + sys-trace combinations).  Output: gpurun_out/pmc_<tag>/
 TAG=${1:-r01}
-ARGS=${2:-"--steps 1 --warmup 0 --no-cpu --L 256"}
+ARGS=${2:-"--full --steps 1 --warmup 0 --no-cpu --L 256"}
 OUT=gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT

@@ -6,7 +6,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for L in 256 1024; do
   for c in FETCH_SIZE WRITE_SIZE; do
-    rocprofv3 --pmc $c --output-format csv -d $OUT/L${L}_$c -- python3 bench.py --steps 1 --warmup 0 --no-cpu --L $L > $OUT/L${L}_$c.log 2>&1 || echo "L=$L $c: profiler exit status non-zero (CSV may still be complete)"
+    rocprofv3 --pmc $c --output-format csv -d $OUT/L${L}_$c -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu --L $L > $OUT/L${L}_$c.log 2>&1 || echo "L=$L $c: profiler exit status non-zero (CSV may still be complete)"
   done
 done
 python3 - <<'PY'

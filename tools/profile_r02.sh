@@ -5,7 +5,7 @@
 TAG=${1:-r02}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/$TAG; rm -rf $O; mkdir -p $O
-python3 bench.py > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json; echo
+python3 bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json; echo
 stats() {  # name, command...
   local name=$1; shift
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$name -- "$@" > $O/trace_$name.out 2> $O/trace_$name.err
@@ -13,7 +13,7 @@ stats() {  # name, command...
   f=$(find $O/trace_$name -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/kernel_stats_$name.csv && head -6 $O/kernel_stats_$name.csv
   rm -rf $O/trace_$name
 }
-stats bench python3 bench.py --steps 1 --warmup 1 --no-cpu --no-seam1
+stats bench python3 bench.py --full --steps 1 --warmup 1 --no-cpu --no-seam1
 stats batch_w40 python3 tools/bench_batch.py 500 40
 stats batch_w80 python3 tools/bench_batch.py 500 80
 stats cfg2 python3 tools/cp_dev_timing.py 1000

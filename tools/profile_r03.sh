@@ -5,7 +5,7 @@
 TAG=${1:-r03}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/$TAG; rm -rf $O; mkdir -p $O
-python3 bench.py > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.json; echo
+python3 bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.json; echo
 stats() {  # name, command...
   local name=$1; shift
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$name -- "$@" > $O/trace_$name.out 2> $O/trace_$name.err
@@ -13,7 +13,7 @@ stats() {  # name, command...
   f=$(find $O/trace_$name -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/kernel_stats_$name.csv && head -4 $O/kernel_stats_$name.csv
   rm -rf $O/trace_$name
 }
-stats bench python3 bench.py --steps 1 --warmup 1 --no-cpu --no-seam1
+stats bench python3 bench.py --full --steps 1 --warmup 1 --no-cpu --no-seam1
 stats cp_n1000 python3 tools/cp_spec_timing.py 1000
 stats cp_n12500 python3 tools/cp_spec_timing.py 12500
 pmc() {  # name, command...
@@ -29,7 +29,7 @@ pmc() {  # name, command...
   python3 tools/pmc_summary2.py $O/pmc_$name > $O/pmc_$name.json; rm -rf $O/pmc_$name $O/pmc_$name.pass*.log
   echo "pmc $name done"
 }
-pmc bench python3 bench.py --steps 1 --warmup 0 --no-cpu --no-seam1
+pmc bench python3 bench.py --full --steps 1 --warmup 0 --no-cpu --no-seam1
 pmc cp_n1000 python3 tools/cp_spec_timing.py 1000
 pmc cp_n12500 python3 tools/cp_spec_timing.py 12500
 ls $O

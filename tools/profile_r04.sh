@@ -6,7 +6,7 @@
 TAG=${1:-r04}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/$TAG; rm -rf $O; mkdir -p $O
-python3 bench.py > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.json; echo
+python3 bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.json; echo
 stats() {  # name, command...
   local name=$1; shift
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$name -- "$@" > $O/trace_$name.out 2> $O/trace_$name.err
