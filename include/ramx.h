@@ -145,6 +145,23 @@ typedef struct ramx_run_info
 int ramx_extend_flat(int direction, ramx_flat_cores *cores, const int8_t *sequence, uint64_t seq_len,
                      int8_t *master, const ramx_params *p, ramx_run_info *info);
 
+/* Profile sink of seam 1.  With a sink set, ramx_extend_flat, ramx_extend_alignment and ramx_extend_batch replay every
+ * direction they have run (ramx_dev_profile, below, on the session's device) along the consensus the loop chose, on whatever
+ * route the loop took, and hand the result to the sink once per direction and family before they return: n_cols =
+ * rows_executed columns (ret = the call's return value: columns [0, ret) are the kept ones), n_flanks per-flank entries with
+ * core_index[i] the position of flank i in the core list.  A direction without an extendable core is answered on the host:
+ * rows_executed columns of zeros with base A.  The pointers are valid during the call only.  cb == NULL (the default): off --
+ * nothing is launched or allocated for it. */
+struct ramx_col_profile;
+typedef struct ramx_profile
+{
+  int32_t direction, family /* index in a batch, else 0 */, n_cols, ret, n_flanks;
+  const struct ramx_col_profile *cols;
+  const int32_t *core_index, *last_uncapped_row;
+} ramx_profile;
+typedef void (*ramx_profile_cb)(const ramx_profile *pr, void *user);
+void ramx_set_profile_sink(ramx_profile_cb cb, void *user);
+
 /* Seam 1 keeps the library on the device between calls, keyed on (pointer, length, 64-bit content fingerprint), so
  * the second direction does not upload it again (libraries above 64 MiB are fingerprinted in chunks by worker threads; when
  * pointer and length match the device copy the content check runs beside the direction and is joined before the write-back).
@@ -259,6 +276,39 @@ typedef struct ramx_family
   int8_t *master;
 } ramx_family;
 int ramx_extend_batch(int direction, ramx_family *families, int32_t n_families, const ramx_params *p, ramx_run_info *infos);
+
+/* Support profile of an extension: every flank's band replayed along a GIVEN consensus (no vote, no stop rule), per column
+ * the quantities the loop decides from.  For row r = 0 .. rows-1, exactly as the loop computes them (ram_extend.c:1042-1062,
+ * 1134-1151): total[a] is the true (int64) sum over the flanks of candidate a's contribution -- max(best_a, 0), or
+ * high + CAPPENALTY where that is larger (the flank is then "capped" under a) --; base is the given cons[r]; n_capped counts
+ * the flanks capped under base, n_new_high those whose kept row set a new per-flank high score, n_out_of_seq those whose kept
+ * row has run out of sequence (gap state of the far edge cell < -279000; the far edge is band cell 2W for a flank as
+ * ramx_resolve_flanks makes it for direction 1 -- step +1 uncomplemented or step -1 complemented -- and cell 0 otherwise).
+ * The struct is 48 bytes without padding. */
+typedef struct ramx_col_profile
+{
+  int64_t total[4];
+  int32_t base, n_capped, n_new_high, n_out_of_seq;
+} ramx_col_profile;
+
+/* The replay on the device.  Flank layout as in ramx_dev_run_families: tiles of 64 flanks, every family starting at a
+ * multiple of 64, padding flanks (beyond a family's count) contribute to nothing and are counted nowhere -- but a family
+ * may have ANY number of flanks, and every band width >= 1 and gap sign is served by the same entry (rows on chip for W = 14,
+ * 20, 40, 80 without a positive gap penalty, otherwise in a global buffer private to each wave).  cons is [n_families][L] (p->L), rows[f] <= L the columns to replay of family f; it need not be the
+ * consensus the vote would choose.  cols is [n_families][L]: only the first rows[f] entries of a family are written.
+ * last_uncapped_row is [n_padded] (may be NULL): the last row at which the flank was not capped under the column's base, -1
+ * if none (and for padding flanks).  row_best / row_best_idx: both NULL, or both [max_f rows[f]][n_padded] row-major (row r
+ * of flank i at [r * n_padded + i]): the kept row's unclamped best score and its sequence index row + offset; entries of rows
+ * beyond a family's rows[f] and of padding tiles are 0.  kernel_ms (may be NULL): HIP-event time of the replay and its
+ * reduction.  The call is self-contained: it uploads the flanks and packs their windows itself from the library on the device
+ * (ramx_dev_load_library*), so it can follow any direction, or none; a following ramx_dev_run_direction needs a new
+ * ramx_dev_begin_direction.  With a communicator or mailbox route active the call is rank-local: the sums are those over
+ * this rank's flanks and add up across ranks.  RAMX_ERR_ARG: a family not at a multiple of 64 or outside n_padded,
+ * overlapping families, rows[f] outside [0, L], a consensus base outside 0..3, one row buffer without the other. */
+int ramx_dev_profile(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                     const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                     const int8_t *cons, const int32_t *rows, ramx_col_profile *cols, int32_t *last_uncapped_row,
+                     int32_t *row_best, int32_t *row_best_idx, double *kernel_ms);
 
 /* multi-GPU: flanks are sharded over ranks; each column's 4 candidate sums are all-reduced
  * (4 x int64, RCCL over xGMI).  unique_id is the 128-byte ncclUniqueId made by rank 0

@@ -19,6 +19,7 @@ EXPORTS = [
     "ramx_get_repeatscout_matrix", "ramx_free_scoring_system", "ramx_calculate_lambda",
     "ramx_load_sequence_subset_minimal", "ramx_load_sequence_subset_packed", "ramx_packed_decode", "ramx_dev_load_library_packed", "ramx_preload_library_packed", "ramx_free_library", "ramx_overlap_avoidance",
     "ramx_print_core_edges", "ramx_allocate_score", "ramx_free_score", "ramx_cli_main",
+    "ramx_dev_profile", "ramx_set_profile_sink",
 ]
 
 
@@ -55,6 +56,14 @@ class Flank(C.Structure):
 
 
 ALLREDUCE_CB = C.CFUNCTYPE(None, C.POINTER(C.c_longlong), C.c_void_p)
+
+
+class ProfileRec(C.Structure):      # ramx_profile
+    _fields_ = [(k, C.c_int32) for k in ("direction", "family", "n_cols", "ret", "n_flanks")] + \
+               [("cols", C.c_void_p), ("core_index", C.c_void_p), ("last_uncapped_row", C.c_void_p)]
+
+
+PROFILE_CB = C.CFUNCTYPE(None, C.POINTER(ProfileRec), C.c_void_p)
 
 
 def build(force: bool = False) -> None:
@@ -104,6 +113,12 @@ def lib() -> C.CDLL:
         L.ramx_dev_peer_enable.argtypes = [C.c_void_p, C.c_int]
         L.ramx_dev_hostbox_attach.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int]
         L.ramx_hostbox_unlink.argtypes = [C.c_char_p]
+        L.ramx_dev_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Params),
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(C.c_double)]
+        L.ramx_dev_profile.restype = C.c_int
+        L.ramx_set_profile_sink.argtypes = [PROFILE_CB, C.c_void_p]
+        L.ramx_set_profile_sink.restype = None
         if hasattr(L, "ramx_cli_main"):
             L.ramx_cli_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
         _lib = L

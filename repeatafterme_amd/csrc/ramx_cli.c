@@ -240,7 +240,7 @@ static void warm_start(void)
 /* everything the command line decides */
 struct cli_opts
 {
-  const char *ranges_file, *outtsv, *outfa, *outmat, *cons_file, *seq_file, *matrix_name, *batch_file;
+  const char *ranges_file, *outtsv, *outfa, *outmat, *cons_file, *seq_file, *matrix_name, *batch_file, *outprofile;
   int flanking, L, bandwidth, maxn, when_to_stop, num_threads, verbose;
   int gap_ext, gap_open, match, mismatch, cappenalty, minimprovement, is_rs;
   struct scoringSystem *sp;
@@ -457,13 +457,13 @@ static void write_results(const struct cli_opts *o, struct coreAlignment *cores,
 /*
  * -batch <list>: many families in one process and ONE launch per direction (no counterpart in the reference, whose
  * wrapper util/extend-stk.pl:242-371 starts one RAMExtend per family).  Every non-empty, non-# line of <list> is
- *     ranges.tsv <TAB> log <TAB> cons.fa <TAB> out.tsv <TAB> out.fa          ("-" = not wanted)
+ *     ranges.tsv <TAB> log <TAB> cons.fa <TAB> out.tsv <TAB> out.fa [<TAB> profile.tsv]          ("-" = not wanted)
  * All other options (-twobit, -L, -bandwidth, -matrix ...) are shared.  For every family the log file receives
  * exactly what a stand-alone run prints on stdout, and the three output files are what -cons/-outtsv/-outfa give.
  */
 struct batch_item
 {
-  char *ranges, *log, *cons, *tsv, *fa;
+  char *ranges, *log, *cons, *tsv, *fa, *profile;
   struct coreAlignment *cores;
   struct sequenceLibrary *lib;
   int N, rightbp, leftbp;
@@ -480,6 +480,55 @@ static void to_log(const char *path, int truncate)
 }
 
 static char *field_or_null(char *s) { return (s == NULL || s[0] == 0 || strcmp(s, "-") == 0) ? NULL : s; }
+
+/*
+ * -outprofile <file>: the per-column support profile of both extensions (include/ramx.h, ramx_set_profile_sink) as a TSV, the
+ * right direction's rows first.  score is the reference's curr_extension_score (ram_extend.c:1064-1086), new_max its
+ * MINIMPROVEMENT rule (:1194-1201), kept says whether the column is part of the returned extension.
+ */
+struct profile_out
+{
+  const char *single;          /* one family: its file */
+  char *const *per_family;     /* -batch: the sixth field of every line (NULL: not wanted) */
+  int minimprovement;
+};
+static const char k_profile_header[] =
+  "dir\trow\tbase\ttotal_A\ttotal_C\ttotal_G\ttotal_T\tscore\tmargin\tn_flanks\tn_uncapped\tn_new_high\tn_out_of_seq\tnew_max\tkept\n";
+static void profile_start(const char *path)
+{
+  FILE *fp = fopen(path, "w");
+  if (!fp) { fprintf(stderr, "Could not create the profile file %s\n", path); exit(1); }
+  fputs(k_profile_header, fp);
+  fclose(fp);
+}
+static void profile_sink(const ramx_profile *pr, void *user)
+{
+  const struct profile_out *po = (const struct profile_out *)user;
+  const char *path = po->per_family ? po->per_family[pr->family] : po->single;
+  if (!path) return;
+  FILE *fp = fopen(path, "a");
+  if (!fp) { fprintf(stderr, "Could not append to the profile file %s\n", path); exit(1); }
+  long long max_ext = 0;
+  int max_row = -1;
+  for (int r = 0; r < pr->n_cols; r++)
+  {
+    const ramx_col_profile *c = &pr->cols[r];
+    long long score = 0, other = 0;
+    int have_other = 0;
+    for (int a = 0; a < 4; a++)
+    {
+      if (c->total[a] > score) score = c->total[a];
+      if (a != c->base && (!have_other || c->total[a] > other)) { other = c->total[a]; have_other = 1; }
+    }
+    const int new_max = score >= max_ext + (long long)abs(max_row - r) * po->minimprovement;
+    if (new_max) { max_row = r; max_ext = score; }
+    fprintf(fp, "%s\t%d\t%c\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%d\t%d\t%d\t%d\t%d\t%d\n", pr->direction ? "right" : "left", r,
+            code_to_char(c->base), (long long)c->total[0], (long long)c->total[1], (long long)c->total[2], (long long)c->total[3],
+            score, (long long)c->total[c->base] - other, pr->n_flanks, pr->n_flanks - c->n_capped, c->n_new_high, c->n_out_of_seq,
+            new_max, r < pr->ret ? 1 : 0);
+  }
+  fclose(fp);
+}
 
 /* flat view of a core list for ramx_extend_batch (arrays owned by the caller's arena) */
 static void flatten_cores(struct coreAlignment *cores, int N, ramx_flat_cores *fc)
@@ -532,6 +581,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
 {
   const int L = o->L, l = 1;
   if (o->outmat != NULL) { fprintf(stderr, "RAMExtend(ramx): -outmat traces one family; it cannot be combined with -batch\n"); exit(1); }
+  if (o->outprofile != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's profile file is the sixth field of its line in the list\n"); exit(1); }
   FILE *lf = fopen(o->batch_file, "r");
   if (!lf) { fprintf(stderr, "Could not open batch list %s\n", o->batch_file); exit(1); }
   size_t cap = 64, F = 0;
@@ -543,15 +593,16 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   {
     while (len > 0 && (line[len - 1] == '\n' || line[len - 1] == '\r')) line[--len] = 0;
     if (line[0] == '#' || line[0] == 0) continue;
-    char *f[5] = { NULL, NULL, NULL, NULL, NULL };
+    char *f[6] = { NULL, NULL, NULL, NULL, NULL, NULL };
     char *p = line;
-    for (int k = 0; k < 5 && p; k++) { f[k] = p; char *t = strchr(p, '\t'); if (t) { *t = 0; p = t + 1; } else p = NULL; }
+    for (int k = 0; k < 6 && p; k++) { f[k] = p; char *t = strchr(p, '\t'); if (t) { *t = 0; p = t + 1; } else p = NULL; }
     if (!f[0] || !f[1]) { fprintf(stderr, "batch list: every line needs at least <ranges><TAB><log>\n"); exit(1); }
     if (F == cap) { cap *= 2; it = (struct batch_item *)realloc(it, cap * sizeof(*it)); memset(it + F, 0, (cap - F) * sizeof(*it)); }
     it[F].ranges = strdup(f[0]); it[F].log = strdup(f[1]);
     it[F].cons = field_or_null(f[2]) ? strdup(f[2]) : NULL;
     it[F].tsv = field_or_null(f[3]) ? strdup(f[3]) : NULL;
     it[F].fa = field_or_null(f[4]) ? strdup(f[4]) : NULL;
+    it[F].profile = field_or_null(f[5]) ? strdup(f[5]) : NULL;       /* optional sixth field: the family's -outprofile file */
     F++;
   }
   free(line);
@@ -588,6 +639,12 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   ramx_run_info *ir = (ramx_run_info *)calloc(F ? F : 1, sizeof(*ir)), *il = (ramx_run_info *)calloc(F ? F : 1, sizeof(*il));
 
   warm_join();
+  char **profile_paths = (char **)calloc(F ? F : 1, sizeof(char *));
+  struct profile_out pout = { NULL, profile_paths, o->minimprovement };
+  int any_profile = 0;
+  for (size_t i = 0; i < F; i++)
+    if ((profile_paths[i] = it[i].profile) != NULL) { profile_start(it[i].profile); any_profile = 1; }
+  if (any_profile) ramx_set_profile_sink(profile_sink, &pout);
   /* phase 2: right extension of all families in one launch; phase 3: per family, overlap avoidance */
   for (size_t i = 0; i < F; i++) flatten_cores(it[i].cores, it[i].N, &fam[i].cores);
   if (ramx_extend_batch(1, fam, (int32_t)F, &p, ir) < 0) { fprintf(stderr, "RAMExtend(ramx): batch extension failed: %s\n", ramx_last_error()); exit(1); }
@@ -628,8 +685,10 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   for (size_t i = 0; i < F; i++)
   {
     ramx_free_library(it[i].lib, it[i].cores);
-    free(it[i].master); free(it[i].ranges); free(it[i].log); free(it[i].cons); free(it[i].tsv); free(it[i].fa);
+    free(it[i].master); free(it[i].ranges); free(it[i].log); free(it[i].cons); free(it[i].tsv); free(it[i].fa); free(it[i].profile);
   }
+  ramx_set_profile_sink(NULL, NULL);
+  free(profile_paths);
   free(it); free(fam); free(ir); free(il); free(mflat);
   ramx_free_scoring_system(o->sp);
   return 0;
@@ -656,6 +715,7 @@ int ramx_cli_main(int argc, char **argv)
   opt_string(argc, argv, "-outfa", &o.outfa);
   opt_string(argc, argv, "-outmat", &o.outmat);
   opt_string(argc, argv, "-cons", &o.cons_file);
+  opt_string(argc, argv, "-outprofile", &o.outprofile);
   if (!opt_int(argc, argv, "-L", &o.L)) o.L = 10000;
   if (!opt_int(argc, argv, "-bandwidth", &o.bandwidth)) o.bandwidth = 14;
   if (!opt_int(argc, argv, "-maxoccurrences", &o.maxn)) o.maxn = 10000;
@@ -738,6 +798,12 @@ int ramx_cli_main(int argc, char **argv)
   master[L] = RAMX_SYM_N;   /* the l = 1 spacer, never printed (ram_extend.c:415-416) */
 
   ramx_set_runtime(o.verbose, o.when_to_stop, l);
+  struct profile_out pout = { o.outprofile, NULL, o.minimprovement };
+  if (o.outprofile != NULL)
+  {
+    profile_start(o.outprofile);
+    ramx_set_profile_sink(profile_sink, &pout);
+  }
   fflush(stdout);
   warm_join();
   phase_done("device ready");
@@ -749,6 +815,7 @@ int ramx_cli_main(int argc, char **argv)
   int leftbp = ramx_extend_alignment(0, cores, NULL, lib, master, o.bandwidth, o.cappenalty, o.minimprovement, L, N, o.sp, fp_mat);
   printf("Extended left : %d bp\n", leftbp);
   phase_done("extend left");
+  ramx_set_profile_sink(NULL, NULL);
   write_results(&o, cores, lib, master, rightbp, leftbp, o.cons_file, o.outtsv, o.outfa);
   if (fp_mat != NULL) fclose(fp_mat);     /* ram_extend.c:778-779 */
   phase_done("report + outputs");

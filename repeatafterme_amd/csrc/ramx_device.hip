@@ -50,6 +50,7 @@
 #include "ramx_kernels_resident.h"
 #include "ramx_cp_api.h"
 #include "ramx_pk_api.h"
+#include "ramx_profile_api.h"
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
@@ -147,6 +148,10 @@ struct ramx_dev
   int last_packed_r0;  // last direction: first row of the packed-row kernel, -1 if it did not run
   int cp_flanks_ok;    // begin_direction: every flank is empty or has t_lo <= 0 (what the cell-parallel kernels take)
   int2 *d_cpstate; size_t cap_cpstate; int cpstate_W, cpstate_n;   // RAMX_CP_PEEK=1: final rows of the cell-parallel kernel (tests)
+  // ramx_dev_profile (allocated on its first call): rows, per-wave records, summed columns, consensus / rows / family / tile tables, per-flank outputs
+  int4 *d_pf_state; ramx_col_profile *d_pf_slab, *d_pf_cols; signed char *d_pf_cons; int *d_pf_rows; int4 *d_pf_fam; int2 *d_pf_tile;
+  int *d_pf_last, *d_pf_best, *d_pf_bidx;
+  size_t cap_pf_state, cap_pf_slab, cap_pf_cols, cap_pf_cons, cap_pf_rows, cap_pf_fam, cap_pf_tile, cap_pf_last, cap_pf_best, cap_pf_bidx;
 };
 
 extern "C" int ramx_device_count(void)
@@ -229,6 +234,8 @@ extern "C" void ramx_dev_destroy(ramx_dev *d)
   }
   if (d->devbox) (void)hipFree(d->devbox);
   (void)hipFree(d->d_fam); (void)hipFree(d->d_famctl); (void)hipFree(d->d_cpstate); (void)hipFree(d->d_dbg_codes); (void)hipFree(d->d_dbg_best); (void)hipFree(d->d_dbg_cand); (void)hipFree(d->d_dbg_gap); (void)hipFree(d->d_dbg_band); (void)hipFree(d->d_devdesc); (void)hipFree(d->d_vote_sets); (void)hipFree(d->d_err_sets);
+  (void)hipFree(d->d_pf_state); (void)hipFree(d->d_pf_slab); (void)hipFree(d->d_pf_cols); (void)hipFree(d->d_pf_cons); (void)hipFree(d->d_pf_rows);
+  (void)hipFree(d->d_pf_fam); (void)hipFree(d->d_pf_tile); (void)hipFree(d->d_pf_last); (void)hipFree(d->d_pf_best); (void)hipFree(d->d_pf_bidx);
   if (d->hostbox_mirror) (void)hipFree(d->hostbox_mirror);
   if (d->d_peer) (void)hipFree(d->d_peer);
   for (int i = 0; i < 2; i++) if (d->ev_chk[i]) (void)hipEventDestroy(d->ev_chk[i]);
@@ -1517,6 +1524,135 @@ extern "C" int ramx_dev_run_families(ramx_dev *d, const ramx_flank *flanks, int3
       if (trim_high) trim_high[fam_first[f] + i] = th2[first2[k] + i];
       if (trim_pos) trim_pos[fam_first[f] + i] = tp2[first2[k] + i];
     }
+  }
+  return RAMX_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// support profile: every flank's band replayed along a given consensus (ramx_kernels_profile.h)
+// ------------------------------------------------------------------------------------------
+extern "C" int ramx_dev_profile(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                                const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                                const int8_t *cons, const int32_t *rows, ramx_col_profile *cols, int32_t *last_uncapped_row,
+                                int32_t *row_best, int32_t *row_best_idx, double *kernel_ms)
+{
+  if (kernel_ms) *kernel_ms = 0;
+  if (!d || !p || !p->matrix || n_families < 0 || n_padded < 0 || (n_padded & 63) || (n_padded && !flanks) ||
+      (n_families && (!fam_first || !fam_count || !rows)))
+  { ramx_set_error("ramx_dev_profile: bad argument"); return RAMX_ERR_ARG; }
+  if ((row_best == NULL) != (row_best_idx == NULL)) { ramx_set_error("ramx_dev_profile: row_best and row_best_idx go together"); return RAMX_ERR_ARG; }
+  const int W = p->bandwidth, L = p->L, Q = W + 1;
+  if (W < 1 || L < 0) { ramx_set_error("ramx_dev_profile: bad bandwidth / L"); return RAMX_ERR_ARG; }
+  const int tiles = n_padded / 64;
+  std::vector<int2> tile_fam((size_t)(tiles > 0 ? tiles : 1), make_int2(-1, 0));
+  std::vector<int4> fam_desc((size_t)(n_families > 0 ? n_families : 1));
+  int maxrows = 0;
+  for (int f = 0; f < n_families; f++)
+  {
+    if (fam_count[f] < 0 || fam_first[f] < 0 || (fam_first[f] & 63) || (long long)fam_first[f] + fam_count[f] > n_padded)
+    { ramx_set_error("ramx_dev_profile: bad family layout"); return RAMX_ERR_ARG; }
+    if (rows[f] < 0 || rows[f] > L) { ramx_set_error("ramx_dev_profile: rows[%d] = %d outside [0, L = %d]", f, rows[f], L); return RAMX_ERR_ARG; }
+    if (rows[f] > 0 && (!cons || !cols)) { ramx_set_error("ramx_dev_profile: cons / cols missing"); return RAMX_ERR_ARG; }
+    for (int r = 0; r < rows[f]; r++)
+      if (cons[(size_t)f * L + r] < 0 || cons[(size_t)f * L + r] > 3) { ramx_set_error("ramx_dev_profile: consensus base outside A C G T (family %d, column %d)", f, r); return RAMX_ERR_ARG; }
+    const int t0 = fam_first[f] / 64, nt = (fam_count[f] + 63) / 64;
+    for (int t = 0; t < nt; t++)
+    {
+      if (tile_fam[t0 + t].x >= 0) { ramx_set_error("ramx_dev_profile: families %d and %d overlap", tile_fam[t0 + t].x, f); return RAMX_ERR_ARG; }
+      const int left = fam_count[f] - 64 * t;
+      tile_fam[t0 + t] = make_int2(f, left < 64 ? left : 64);
+    }
+    fam_desc[f] = make_int4(t0, nt, rows[f], 0);
+    if (rows[f] > maxrows) maxrows = rows[f];
+  }
+  if (last_uncapped_row) for (int i = 0; i < n_padded; i++) last_uncapped_row[i] = -1;
+  if (n_families == 0 || maxrows == 0) return RAMX_OK;
+  HIPCHK(hipSetDevice(d->ordinal));
+  const int Np = n_padded > 0 ? n_padded : 64;
+  const int KW = (L + 2 * W + 2) / 8 + 12;
+  int rc;
+  // a piece of the direction before may still be packing into d_bases on the second stream: it must have finished before the
+  // buffer can be reallocated, let alone written
+  if (d->pack_busy) { HIPCHK(hipEventSynchronize(d->pack_done)); d->pack_busy = 0; }
+  if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)Np * sizeof(ramx_flank)))) return rc;
+  if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)KW * Np * sizeof(unsigned)))) return rc;
+  if ((rc = ensure(&d->d_bounds, &d->cap_bounds, (size_t)Np * sizeof(int2)))) return rc;
+  // rows on chip for the band widths that have the instantiation (the conditions of the persistent kernel: no positive gap
+  // penalty, e - m fits int16); RAMX_PROFILE_NO_RESIDENT sends them through the global row buffer like every other case (A/B)
+  const bool chain = p->gapopen > 0 || p->gapextn > 0 || d->force_chain;
+  const bool resident = !chain && ramx_profile_has_resident(W) && p->gapopen + p->gapextn >= -32768 && getenv("RAMX_PROFILE_NO_RESIDENT") == NULL;
+  if (!resident && (rc = ensure(&d->d_pf_state, &d->cap_pf_state, (size_t)Np * Q * sizeof(int4)))) return rc;
+  if ((rc = ensure(&d->d_pf_slab, &d->cap_pf_slab, (size_t)(tiles > 0 ? tiles : 1) * maxrows * sizeof(ramx_col_profile)))) return rc;
+  if ((rc = ensure(&d->d_pf_cols, &d->cap_pf_cols, (size_t)n_families * L * sizeof(ramx_col_profile)))) return rc;
+  if ((rc = ensure(&d->d_pf_cons, &d->cap_pf_cons, (size_t)n_families * L + 16))) return rc;
+  if ((rc = ensure(&d->d_pf_rows, &d->cap_pf_rows, (size_t)n_families * sizeof(int)))) return rc;
+  if ((rc = ensure(&d->d_pf_fam, &d->cap_pf_fam, (size_t)n_families * sizeof(int4)))) return rc;
+  if ((rc = ensure(&d->d_pf_tile, &d->cap_pf_tile, tile_fam.size() * sizeof(int2)))) return rc;
+  if ((rc = ensure(&d->d_pf_last, &d->cap_pf_last, (size_t)Np * sizeof(int)))) return rc;
+  if (row_best)
+  {
+    if ((rc = ensure(&d->d_pf_best, &d->cap_pf_best, (size_t)maxrows * Np * sizeof(int)))) return rc;
+    if ((rc = ensure(&d->d_pf_bidx, &d->cap_pf_bidx, (size_t)maxrows * Np * sizeof(int)))) return rc;
+  }
+  if (n_padded) HIPCHK(hipMemcpyAsync(d->d_flanks, flanks, (size_t)n_padded * sizeof(ramx_flank), hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemcpyAsync(d->d_pf_cons, cons, (size_t)n_families * L, hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemcpyAsync(d->d_pf_rows, rows, (size_t)n_families * sizeof(int), hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemcpyAsync(d->d_pf_fam, fam_desc.data(), (size_t)n_families * sizeof(int4), hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemcpyAsync(d->d_pf_tile, tile_fam.data(), tile_fam.size() * sizeof(int2), hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemsetAsync(d->d_pf_last, 0xff, (size_t)Np * sizeof(int), d->stream));
+  if (row_best)
+  {
+    // tiles outside every family and rows beyond a family's count are never written: they read as 0
+    HIPCHK(hipMemsetAsync(d->d_pf_best, 0, (size_t)maxrows * Np * sizeof(int), d->stream));
+    HIPCHK(hipMemsetAsync(d->d_pf_bidx, 0, (size_t)maxrows * Np * sizeof(int), d->stream));
+  }
+  if ((rc = launch_pack(d, n_padded, Np, W, 0, KW, d->stream)) != RAMX_OK) return rc;
+  d->packed_kw = KW;
+  d->ready = 0;       // the direction's flank and window buffers were reused: begin_direction must be called again before run_direction
+  ProfArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  pa.k.bases = d->d_bases; pa.k.bounds = d->d_bounds; pa.k.S_in = d->d_pf_state; pa.k.S_out = d->d_pf_state;
+  pa.k.Np = Np; pa.k.Nx = Np; pa.k.W = W; pa.k.go = p->gapopen; pa.k.ge = p->gapextn; pa.k.cap = p->cappenalty;
+  for (int c = 0; c < RAMX_NCLASS; c++)
+  {
+    const int code = (c == 8) ? RAMX_SYM_N : c;
+    for (int k = 0; k < 4; k++) pa.k.tab[c][k] = p->matrix[k * 100 + code];
+  }
+  pa.flanks = d->d_flanks; pa.tile_fam = d->d_pf_tile; pa.cons = d->d_pf_cons; pa.rows = d->d_pf_rows; pa.slab = d->d_pf_slab;
+  pa.last_uncapped = d->d_pf_last; pa.row_best = row_best ? d->d_pf_best : NULL; pa.row_best_idx = row_best ? d->d_pf_bidx : NULL;
+  pa.L = L; pa.slab_rows = maxrows;
+  ProfSumArgs sa;
+  sa.slab = d->d_pf_slab; sa.fam = d->d_pf_fam; sa.cons = d->d_pf_cons; sa.cols = d->d_pf_cols; sa.L = L; sa.slab_rows = maxrows;
+  if (resident)
+  {
+    pa.pack_ok = getenv("RAMX_NO_FASTPACK") ? 0 : fast_pack_ok(pa.k.tab, pa.k.go, pa.k.ge, L, W);
+    if (pa.pack_ok && getenv("RAMX_NO_MASKHI") == NULL) pa.pack_ok = 2;
+    pa.lean_p = lean_p_of(pa.k.tab, pa.k.go, pa.k.ge);
+  }
+  HIPCHK(hipEventRecord(d->ev_begin, d->stream));
+  if ((rc = ramx_profile_launch(d->stream, resident, chain, tiles, pa, n_families, sa)) != RAMX_OK)
+  { ramx_set_error("ramx_dev_profile: launch failed (%s)", hipGetErrorString(hipGetLastError())); return rc; }
+  HIPCHK(hipEventRecord(d->ev_end, d->stream));
+  HIPCHK(hipStreamSynchronize(d->stream));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, d->ev_begin, d->ev_end));
+  if (kernel_ms) *kernel_ms = ms;
+  // only rows[f] entries per family are written: one family comes straight into place, several come as one block that is
+  // scattered here
+  if (n_families == 1)
+    HIPCHK(hipMemcpy(cols, d->d_pf_cols, (size_t)rows[0] * sizeof(ramx_col_profile), hipMemcpyDeviceToHost));
+  else
+  {
+    std::vector<ramx_col_profile> stage((size_t)n_families * L);
+    HIPCHK(hipMemcpy(stage.data(), d->d_pf_cols, stage.size() * sizeof(ramx_col_profile), hipMemcpyDeviceToHost));
+    for (int f = 0; f < n_families; f++)
+      if (rows[f] > 0) memcpy(cols + (size_t)f * L, stage.data() + (size_t)f * L, (size_t)rows[f] * sizeof(ramx_col_profile));
+  }
+  if (last_uncapped_row && n_padded) HIPCHK(hipMemcpy(last_uncapped_row, d->d_pf_last, (size_t)n_padded * sizeof(int), hipMemcpyDeviceToHost));
+  if (row_best && n_padded)
+  {
+    HIPCHK(hipMemcpy(row_best, d->d_pf_best, (size_t)maxrows * n_padded * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(row_best_idx, d->d_pf_bidx, (size_t)maxrows * n_padded * sizeof(int), hipMemcpyDeviceToHost));
   }
   return RAMX_OK;
 }

@@ -29,6 +29,15 @@ int ramx_runtime_verbose(void) { return g_verbose; }
 int ramx_runtime_when_to_stop(void) { return g_when_to_stop; }
 int ramx_runtime_l(void) { return g_l; }
 
+/* profile sink (include/ramx.h): off unless set */
+static ramx_profile_cb g_profile_cb = NULL;
+static void *g_profile_user = NULL;
+void ramx_set_profile_sink(ramx_profile_cb cb, void *user)
+{
+  g_profile_cb = cb;
+  g_profile_user = user;
+}
+
 static ramx_dev *g_dev = NULL;
 /* The device keeps the library between calls (the reference's main() runs both directions on one seqLib).  The
  * cache key is (pointer, length, content fingerprint): a caller that rewrites the buffer in place, or whose new
@@ -414,9 +423,45 @@ int ramx_resolve_flanks(int direction, const ramx_flat_cores *c, int bandwidth, 
   return nx;
 }
 
-/* packed != NULL: the device already holds the library (ramx_preload_library_packed); `sequence` is not looked at */
+/* With a profile sink set: replay one direction of one family along the consensus the loop chose and hand it over. */
+static int profile_direction(ramx_dev *d, int direction, int family, const ramx_flank *fl, const int32_t *map, int nx,
+                             const ramx_params *p, const int8_t *cons, int rows, int ret)
+{
+  const int L = p->L;
+  ramx_col_profile *cols = (ramx_col_profile *)calloc((size_t)(L > 0 ? L : 1), sizeof(ramx_col_profile));
+  int32_t *last = NULL;
+  int rc = RAMX_OK;
+  if (nx == 0)
+  {
+    /* no extendable core: every candidate total of every column is 0 and the vote gives A (answered on the host) */
+    for (int r = 0; r < rows; r++) cols[r].base = cons[r];
+  }
+  else
+  {
+    const int npad = (nx + 63) & ~63;
+    ramx_flank *pf = (ramx_flank *)malloc(sizeof(ramx_flank) * (size_t)npad);
+    last = (int32_t *)malloc(sizeof(int32_t) * (size_t)npad);
+    memcpy(pf, fl, sizeof(ramx_flank) * (size_t)nx);
+    for (int i = nx; i < npad; i++) { memset(&pf[i], 0, sizeof(ramx_flank)); pf[i].t_lo = 1; pf[i].t_hi = 0; pf[i].step = 1; }
+    const int32_t first = 0, count = nx, nrows = rows;
+    rc = ramx_dev_profile(d, pf, npad, &first, &count, 1, p, cons, &nrows, cols, last, NULL, NULL, NULL);
+    free(pf);
+  }
+  if (rc == RAMX_OK)
+  {
+    ramx_profile pr;
+    pr.direction = direction; pr.family = family; pr.n_cols = rows; pr.ret = ret; pr.n_flanks = nx;
+    pr.cols = cols; pr.core_index = map; pr.last_uncapped_row = last;
+    g_profile_cb(&pr, g_profile_user);
+  }
+  free(cols); free(last);
+  return rc;
+}
+
+/* packed != NULL: the device already holds the library (ramx_preload_library_packed); `sequence` is not looked at;
+   family: the index a profile sink is told (ramx_extend_batch running a family on its own, else 0) */
 static int extend_flat_impl(int direction, ramx_flat_cores *c, const int8_t *sequence, uint64_t seq_len,
-                            int8_t *master, const ramx_params *p, ramx_run_info *info, const ramx_packed_library *packed)
+                            int8_t *master, const ramx_params *p, ramx_run_info *info, const ramx_packed_library *packed, int family)
 {
   ramx_run_info local;
   if (!info) info = &local;
@@ -591,6 +636,11 @@ run_again:
     }
   }
   SEAM1_PHASE("download + write-back");
+  if (rc == RAMX_OK && g_profile_cb != NULL)
+  {
+    rc = profile_direction(d, direction, family, fl, map, nx, p, cons, info->rows_executed, info->ret);
+    SEAM1_PHASE("profile replay");
+  }
 #undef SEAM1_PHASE
 #undef FP_JOIN
   free(cons); free(th); free(tp); free(map); free(fl);
@@ -600,7 +650,7 @@ run_again:
 int ramx_extend_flat(int direction, ramx_flat_cores *c, const int8_t *sequence, uint64_t seq_len,
                      int8_t *master, const ramx_params *p, ramx_run_info *info)
 {
-  return extend_flat_impl(direction, c, sequence, seq_len, master, p, info, NULL);
+  return extend_flat_impl(direction, c, sequence, seq_len, master, p, info, NULL, 0);
 }
 
 int ramx_extend_alignment(int direction, struct coreAlignment *coreAlign, int ****score,
@@ -690,7 +740,7 @@ int ramx_extend_alignment(int direction, struct coreAlignment *coreAlign, int **
       exit(1);
     }
   }
-  int ret = extend_flat_impl(direction, &fc, (const int8_t *)seqLib->sequence, seqLib->length, (int8_t *)master, &p, &info, packed);
+  int ret = extend_flat_impl(direction, &fc, (const int8_t *)seqLib->sequence, seqLib->length, (int8_t *)master, &p, &info, packed, 0);
   if (ret < 0)
   {
     /* the reference has no error return on this path: print + exit(1) like its other failures */
@@ -862,6 +912,24 @@ int ramx_extend_batch(int direction, ramx_family *fam, int32_t F, const ramx_par
         }
       }
     }
+    if (rc == RAMX_OK && g_profile_cb != NULL)
+    {
+      /* every family of the launch replayed in one call, along its own consensus and over its own number of columns */
+      ramx_col_profile *cols = (ramx_col_profile *)calloc((size_t)nb * (size_t)(L > 0 ? L : 1), sizeof(ramx_col_profile));
+      int32_t *last = (int32_t *)malloc(sizeof(int32_t) * (fpos ? fpos : 1));
+      int32_t *nrows = (int32_t *)malloc(sizeof(int32_t) * (size_t)nb);
+      for (int b = 0; b < nb; b++) nrows[b] = binfo[b].rows_executed;
+      rc = ramx_dev_profile(d, fl, (int32_t)fpos, first, count, nb, p, cons, nrows, cols, last, NULL, NULL, NULL);
+      for (int b = 0; b < nb && rc == RAMX_OK; b++)
+      {
+        ramx_profile pr;
+        pr.direction = direction; pr.family = fidx[b]; pr.n_cols = nrows[b]; pr.ret = binfo[b].ret; pr.n_flanks = count[b];
+        pr.cols = cols + (size_t)b * L; pr.core_index = map + first[b]; pr.last_uncapped_row = last + first[b];
+        g_profile_cb(&pr, g_profile_user);
+      }
+      free(cols); free(last); free(nrows);
+      BATCH_PHASE("profile replay");
+    }
     free(binfo); free(cons); free(th); free(tp);
     BATCH_PHASE("write-back");
   }
@@ -869,7 +937,7 @@ int ramx_extend_batch(int direction, ramx_family *fam, int32_t F, const ramx_par
   for (int f = 0; f < F && rc == RAMX_OK; f++)
   {
     if (take[f]) continue;
-    int r1 = ramx_extend_flat(direction, &fam[f].cores, fam[f].sequence, fam[f].seq_len, fam[f].master, p, &infos[f]);
+    int r1 = extend_flat_impl(direction, &fam[f].cores, fam[f].sequence, fam[f].seq_len, fam[f].master, p, &infos[f], NULL, f);
     if (r1 < 0) rc = r1;
   }
   free(lib); free(at_of); free(fl); free(map); free(first); free(count); free(fidx); free(take); free(own); free(fps);

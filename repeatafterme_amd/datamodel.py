@@ -96,3 +96,25 @@ def new_master(L: int, l: int = 1) -> np.ndarray:
     m = np.zeros(2 * L + l + 1, np.int8)
     m[L:L + l] = SYM_N
     return m
+
+
+# one column of a support profile: C-ABI ramx_col_profile (include/ramx.h), 48 bytes
+COL_PROFILE_DTYPE = np.dtype([("total", np.int64, (4,)), ("base", np.int32), ("n_capped", np.int32),
+                              ("n_new_high", np.int32), ("n_out_of_seq", np.int32)], align=True)
+assert COL_PROFILE_DTYPE.itemsize == 48
+
+
+@dataclass
+class Profile:
+    """Per-column support of one direction of one family (C-ABI ramx_profile / ramx_dev_profile)."""
+    direction: int
+    family: int                      # index in a batch, else 0
+    ret: int                         # columns [0, ret) are the kept ones
+    cols: np.ndarray                 # COL_PROFILE_DTYPE [n_cols]
+    core_index: np.ndarray           # position in the core list of every flank
+    last_uncapped_row: np.ndarray    # per flank: last row at which it was not capped under the column's base, -1: none
+
+    @property
+    def score(self) -> np.ndarray:
+        """curr_extension_score of every column (ram_extend.c:1064-1086): max(0, max_a total[a])."""
+        return np.maximum(self.cols["total"].max(axis=1), 0) if len(self.cols) else np.zeros(0, np.int64)

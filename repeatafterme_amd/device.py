@@ -4,11 +4,13 @@ download / destroy.  Used by bench.py and the parity tests that want to look bel
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 
 from . import _lib
-from .datamodel import CoreSet, ExtendParams
+from .datamodel import COL_PROFILE_DTYPE, CoreSet, ExtendParams
 from .extend import RunInfo, _info, _params
 
 
@@ -22,6 +24,28 @@ def resolve_flanks(direction: int, cores: CoreSet, bandwidth: int, L: int):
     idx = np.zeros(max(cores.n, 1), np.int32)
     nx = L_.ramx_resolve_flanks(int(direction), C.byref(fc), bandwidth, L, flanks, idx.ctypes.data)
     return (flanks, nx), idx[:nx].copy()
+
+
+@dataclass
+class ProfileResult:
+    cols: np.ndarray                       # COL_PROFILE_DTYPE [n_families][L]; only rows[f] entries per family are written
+    last_uncapped_row: np.ndarray          # [n_padded]
+    row_best: Optional[np.ndarray]         # [max rows][n_padded], or None
+    row_best_idx: Optional[np.ndarray]
+    kernel_ms: float
+
+
+def pad_flanks(flanks):
+    """(flank array, n) -> the same flanks padded to a multiple of 64 with empty flanks (t_lo = 1, t_hi = 0)."""
+    arr, nx = flanks
+    npad = max((nx + 63) // 64 * 64, 64)
+    out = (_lib.Flank * npad)()
+    for i in range(npad):
+        if i < nx:
+            out[i] = arr[i]
+        else:
+            out[i].t_lo, out[i].t_hi, out[i].step = 1, 0, 1
+    return out, npad
 
 
 class Device:
@@ -70,6 +94,46 @@ class Device:
         _lib.check(self._L.ramx_dev_download(self._h, cons.ctypes.data, len(cons), th.ctypes.data, tp.ctypes.data),
                    "ramx_dev_download")
         return cons[:rows], th[:self.nx], tp[:self.nx]
+
+    def profile(self, flanks, p: ExtendParams, cons, rows=None, fam_first=None, fam_count=None, row_best: bool = False,
+                out: Optional[np.ndarray] = None) -> ProfileResult:
+        """Replay flanks along a given consensus (C-ABI ramx_dev_profile).  One family: `flanks` = (array, n) as
+        resolve_flanks returns it (padded here), `cons` a 1-D int8 array, `rows` its length unless given.  Several families:
+        `flanks` = (array, n_padded) already laid out in tiles of 64, fam_first / fam_count per family, `cons`
+        [n_families][L], `rows` per family.  `out`: a COL_PROFILE_DTYPE array [n_families][L] to write into (entries beyond
+        rows[f] are left alone)."""
+        cp, keep = _params(p)
+        L = p.L
+        if fam_first is None:
+            n = flanks[1]
+            arr, npad = pad_flanks(flanks)
+            fam_first, fam_count = [0], [n]
+            c1 = np.asarray(cons, np.int8).ravel()
+            rows = [len(c1) if rows is None else int(rows)]
+            cons = np.zeros((1, max(L, 1)), np.int8)
+            cons[0, :min(len(c1), L)] = c1[:L]
+        else:
+            arr, npad = flanks
+        nf = len(fam_first)
+        first = np.ascontiguousarray(fam_first, np.int32)
+        count = np.ascontiguousarray(fam_count, np.int32)
+        rows_a = np.ascontiguousarray(rows, np.int32)
+        cons = np.ascontiguousarray(cons, np.int8)
+        assert cons.size >= nf * L and len(rows_a) == nf
+        cols = out if out is not None else np.zeros((nf, max(L, 1)), COL_PROFILE_DTYPE)
+        assert cols.dtype == COL_PROFILE_DTYPE and cols.flags.c_contiguous and cols.size >= nf * L
+        last = np.full(max(npad, 1), -1, np.int32)
+        rb = rbi = None
+        if row_best:
+            mr = int(rows_a.max()) if nf else 0
+            rb = np.zeros((max(mr, 1), max(npad, 1)), np.int32)
+            rbi = np.zeros((max(mr, 1), max(npad, 1)), np.int32)
+        ms = C.c_double()
+        _lib.check(self._L.ramx_dev_profile(self._h, arr, npad, first.ctypes.data, count.ctypes.data, nf, C.byref(cp),
+                                            cons.ctypes.data, rows_a.ctypes.data, cols.ctypes.data, last.ctypes.data,
+                                            rb.ctypes.data if row_best else None, rbi.ctypes.data if row_best else None,
+                                            C.byref(ms)), "ramx_dev_profile")
+        return ProfileResult(cols, last[:npad], rb, rbi, ms.value)
 
     def peek_state(self, flank: int):
         B = 2 * self.p.bandwidth + 1

@@ -13,7 +13,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .datamodel import CoreSet, ExtendParams
+from .datamodel import COL_PROFILE_DTYPE, CoreSet, ExtendParams, Profile
 
 
 @dataclass
@@ -47,9 +47,43 @@ def _info(ci: _lib.RunInfo) -> RunInfo:
     return RunInfo(**{k: getattr(ci, k) for k, _ in _lib.RunInfo._fields_})
 
 
+class _ProfileSink:
+    """Collects what seam 1 hands to the profile sink (ramx_set_profile_sink) while the block runs."""
+
+    def __init__(self):
+        self.got = []
+
+        def _cb(ptr, _user):
+            pr = ptr.contents
+            cols = np.zeros(pr.n_cols, COL_PROFILE_DTYPE)
+            if pr.n_cols:
+                C.memmove(cols.ctypes.data, pr.cols, pr.n_cols * COL_PROFILE_DTYPE.itemsize)
+            idx = np.zeros(pr.n_flanks, np.int32)
+            last = np.full(pr.n_flanks, -1, np.int32)
+            if pr.n_flanks:
+                C.memmove(idx.ctypes.data, pr.core_index, 4 * pr.n_flanks)
+                C.memmove(last.ctypes.data, pr.last_uncapped_row, 4 * pr.n_flanks)
+            self.got.append(Profile(pr.direction, pr.family, pr.ret, cols, idx, last))
+        self._cb = _lib.PROFILE_CB(_cb)
+
+    def __enter__(self):
+        _lib.lib().ramx_set_profile_sink(self._cb, None)
+        return self
+
+    def __exit__(self, *exc):
+        _lib.lib().ramx_set_profile_sink(_lib.PROFILE_CB(), None)
+        return False
+
+
 def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, master: np.ndarray,
-                     p: ExtendParams) -> RunInfo:
-    """direction: 1 = right, 0 = left (reference ram_extend.c:424,506)."""
+                     p: ExtendParams, profile: bool = False):
+    """direction: 1 = right, 0 = left (reference ram_extend.c:424,506).  profile=True: returns (RunInfo, Profile) -- the
+    direction is replayed along the consensus it chose (C-ABI ramx_dev_profile) after the loop."""
+    if profile:
+        with _ProfileSink() as sink:
+            info = extend_alignment(direction, cores, sequence, master, p)
+        assert len(sink.got) == 1
+        return info, sink.got[0]
     L = _lib.lib()
     assert sequence.dtype == np.int8 and sequence.flags.c_contiguous
     assert master.dtype == np.int8 and len(master) >= 2 * p.L + p.l + 1
@@ -64,9 +98,16 @@ def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, maste
     return _info(ci)
 
 
-def extend_batch(direction: int, families, p: ExtendParams):
+def extend_batch(direction: int, families, p: ExtendParams, profile: bool = False):
     """Many families in one launch (C-ABI ramx_extend_batch).  `families` is a list of (cores, sequence, master);
-    every family is updated in place exactly like extend_alignment does for one.  Returns one RunInfo per family."""
+    every family is updated in place exactly like extend_alignment does for one.  Returns one RunInfo per family;
+    profile=True: (RunInfos, Profiles), one Profile per family in the order of `families`."""
+    if profile:
+        with _ProfileSink() as sink:
+            infos = extend_batch(direction, families, p)
+        by_family = {pr.family: pr for pr in sink.got}
+        assert len(by_family) == len(sink.got) == len(families)
+        return infos, [by_family[i] for i in range(len(families))]
     L = _lib.lib()
     n = len(families)
     arr = (_lib.Family * max(n, 1))()

@@ -8,6 +8,9 @@ wrapper's -onlyextend mode leaves (extend-stk.pl:391-427):
 
     <id>-linup.tsv  <id>-repam.log  <id>-repam-ranges.tsv  <id>-ext-cons.fa  <id>-repam-repseq.fa  <id>-combined-cons.fa
 
+and, with -profile, <id>-profile.tsv: the per-column support of both extensions (RAMExtend -outprofile) -- how many copies
+still carry the extension at every column, which the wrapper can only approximate through -minimprovement.
+
 (the re-alignment and Stockholm rewriting that follow in the wrapper belong to RepeatModeler and are out of scope).
 """
 import argparse
@@ -32,6 +35,7 @@ def main(argv=None):
     ap.add_argument("-min_aligning_seqs", type=int, default=3)          # extend-stk.pl:192
     ap.add_argument("-L", type=int, default=20000)                      # extend-stk.pl:352
     ap.add_argument("-ramextend", default=DEFAULT_EXE)
+    ap.add_argument("-profile", action="store_true", help="also write <id>-profile.tsv per family (RAMExtend -outprofile)")
     ap.add_argument("-one_by_one", action="store_true", help="start one RAMExtend per family, as the wrapper does")
     a = ap.parse_args(argv)
 
@@ -68,7 +72,8 @@ def main(argv=None):
                 with open(base + "-repam.log", "w") as log:
                     rc = subprocess.run([a.ramextend] + common + ["-ranges", base + "-linup.tsv", "-outtsv",
                                         base + "-repam-ranges.tsv", "-outfa", base + "-repam-repseq.fa", "-cons",
-                                        base + "-ext-cons.fa"], stdout=log, stderr=subprocess.STDOUT).returncode
+                                        base + "-ext-cons.fa"] + (["-outprofile", base + "-profile.tsv"] if a.profile else []),
+                                       stdout=log, stderr=subprocess.STDOUT).returncode
                 if rc:
                     sys.exit(f"  RAMExtend failed! [{rc}] see {base}-repam.log")
         else:
@@ -76,7 +81,8 @@ def main(argv=None):
             with open(lst, "w") as fh:
                 for seed, base in fams:
                     fh.write("\t".join([base + "-linup.tsv", base + "-repam.log", base + "-ext-cons.fa",
-                                        base + "-repam-ranges.tsv", base + "-repam-repseq.fa"]) + "\n")
+                                        base + "-repam-ranges.tsv", base + "-repam-repseq.fa"] +
+                                       ([base + "-profile.tsv"] if a.profile else [])) + "\n")
             rc = subprocess.run([a.ramextend] + common + ["-batch", lst]).returncode
             if rc:
                 sys.exit(f"  RAMExtend -batch failed! [{rc}]")
