@@ -13,8 +13,10 @@
 // Why the values fit: an in-bounds cell of row r lies at most 3W (P + |min score| + |ge|) + |go| + W |ge| below the row's best
 // cell (take the best path into the row's best cell, leave it 2W rows earlier, and walk to the cell with substitutions and ONE
 // gap: every step of the detour is in bounds because sequence positions only grow along a path and the target is in bounds;
-// rows below 3W are bounded absolutely), the best cell moves by at most max(P, |min score|) per row, and the base follows it
-// every 16th row once it is more than `rebase` away.  The host admits a scoring system only if all of it fits int16 with the
+// rows below 3W are bounded absolutely), the best cell moves by at most max(16 P, 16 |min score|, |go| + |ge| + 15 max(|min score|,
+// |ge|)) in 16 rows (up by substitutions; down by substitutions or -- the best cell of a flank that ends while aligned sits on the
+// far boundary -- by deletions, whose |go| is paid once: ramx_packed.hip), and the base follows it every 16th row once it is more
+// than `rebase` away.  The host admits a scoring system only if all of it fits int16 with the
 // intermediates (ramx_pk_plan), and the entry check below refuses rows that do not (the direction then runs on the int32 rows).
 //
 // Per pair of cells (bnw_extend.c:892-1018 on the transformed state, see ramx_kernels_common.h):
@@ -773,7 +775,10 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void ramx_packed_kernel(const P
           }, std::make_integer_sequence<int, NP>{});
           const pk_s2 q = pk_v(mn);
           const int lowest = q.x < q.y ? (int)q.x : (int)q.y;
-          if (n < a.Nx && jhi >= 0 && rel - lowest > a.spread_rows) __hip_atomic_fetch_max(a.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          // (and both ends against what the plan lets a value reach: a row that has ALREADY saturated can pass the comparison of
+          // the difference with cells that stuck at the same end)
+          if (n < a.Nx && jhi >= 0 && (rel - lowest > a.spread_rows || rel > RAMX_PK_LIMIT || lowest < -RAMX_PK_LIMIT))
+            __hip_atomic_fetch_max(a.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         // the base follows the row's best cell (every 16th row, when some lane's has moved far enough)
         if ((r & 15) == 15 && __any(jhi >= 0 && (rel > a.rebase || rel < -a.rebase)))

@@ -20,11 +20,18 @@ int ramx_pk_plan(int W, int go, int ge, const int (&tab)[RAMX_NCLASS][4], int *s
     }
   const long long GO = -(long long)go, GE = -(long long)ge;
   // an in-bounds cell lies at most `sp` below its row's best cell (ramx_kernels_packed.h); the base lags the best cell by at most
-  // PK_REBASE + 16 max(P, mn); sub + go of the lowest cell needs mn + GO more, e of it GO + GE
+  // PK_REBASE + what the best cell moves in 16 rows; sub + go of the lowest cell needs mn + GO more, e of it GO + GE.
+  // 16 rows: up by P per row (gaps only lose).  Down: from the best cell of row r, d deletions (cell j - d of row r + d, in
+  // bounds while the flank has bases left) and then 16 - d substitutions reach row r + 16, with d > 0 only where the flank's end
+  // has come closer than cell j -- a flank that ends while aligned has its best cell ON the far boundary, and only a deletion
+  // carries it on.  That path loses at most GO + d GE + (16 - d) mn, linear in d: the maximum is at d = 1 or d = 16.
   const long long sp = 3LL * W * (P + mn + GE) + GO + (long long)W * GE;
-  const long long lag = PK_REBASE + 16 * (P > mn ? P : mn);
-  if (sp + lag + mn + GO + GE + 64 > 32000) return 0;
-  if (lag + P + 64 > 32000) return 0;
+  long long drift = 16 * (P > mn ? P : mn);
+  const long long gapped = GO + GE + 15 * (mn > GE ? mn : GE);
+  if (gapped > drift) drift = gapped;
+  const long long lag = PK_REBASE + drift;
+  if (sp + lag + mn + GO + GE + 64 > RAMX_PK_LIMIT) return 0;
+  if (lag + P + 64 > RAMX_PK_LIMIT) return 0;
   *spread = (int)sp; *rebase = PK_REBASE;
   return 1;
 }

@@ -39,6 +39,10 @@ struct PKArgs
   unsigned long long *dbg;      // -DRAMX_PRK_TIMING builds only: [wave][8] phase sums in 10 ns ticks
 };
 
+// What the plan lets a value of the packed rows reach, intermediates included (int16 with a margin).  The kernel's check of every
+// 64th row refuses a row whose best or lowest in-bounds cell lies outside +- this: such a row may already hold stuck cells.
+#define RAMX_PK_LIMIT 32000
+
 // Can the packed rows hold this scoring system at this band width (int16 relative to a per-flank base)?  Sets spread / rebase.
 // 0: no (the int32 rows serve it).
 int ramx_pk_plan(int W, int go, int ge, const int (&tab)[RAMX_NCLASS][4], int *spread, int *rebase);
