@@ -162,6 +162,24 @@ typedef struct ramx_profile
 typedef void (*ramx_profile_cb)(const ramx_profile *pr, void *user);
 void ramx_set_profile_sink(ramx_profile_cb cb, void *user);
 
+/* Alignment sink of seam 1, as the profile sink: with a sink set every direction that has run is replayed (ramx_dev_align,
+ * below) along the kept consensus -- rows = ret columns -- and handed over once per direction and family.  ends is
+ * [n_flanks]; col_idx / col_ins are [rows][stride] row-major (column r of flank i at [r * stride + i]).  A direction without an
+ * extendable core or with ret = 0 is answered on the host (no flank has an alignment).  cb == NULL (the default): off --
+ * nothing is launched or allocated for it. */
+struct ramx_aln_end;
+typedef struct ramx_alignment
+{
+  int32_t direction, family /* index in a batch, else 0 */, rows /* = ret */, n_flanks, stride;
+  const int8_t *cons;                 /* [rows] */
+  const struct ramx_flank *flanks;    /* [n_flanks], positions in the family's own library */
+  const int32_t *core_index;          /* [n_flanks] */
+  const struct ramx_aln_end *ends;    /* [n_flanks] */
+  const int32_t *col_idx, *col_ins;   /* [rows][stride]; NULL when rows == 0 or n_flanks == 0 */
+} ramx_alignment;
+typedef void (*ramx_align_cb)(const ramx_alignment *al, void *user);
+void ramx_set_align_sink(ramx_align_cb cb, void *user);
+
 /* Seam 1 keeps the library on the device between calls, keyed on (pointer, length, 64-bit content fingerprint), so
  * the second direction does not upload it again (libraries above 64 MiB are fingerprinted in chunks by worker threads; when
  * pointer and length match the device copy the content check runs beside the direction and is joined before the write-back).
@@ -309,6 +327,44 @@ int ramx_dev_profile(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, co
                      const int32_t *fam_count, int32_t n_families, const ramx_params *p,
                      const int8_t *cons, const int32_t *rows, ramx_col_profile *cols, int32_t *last_uncapped_row,
                      int32_t *row_best, int32_t *row_best_idx, double *kernel_ms);
+
+/* Per-copy alignments of an extension: every flank's band replayed along a GIVEN consensus, then walked back from the
+ * flank's end cell.  Positions are flank positions t = offset + row (ramx_flank): t may be negative, the reference's band may
+ * step back into the core.
+ *   End cell: end_row is the first row r < rows whose best cell score is strictly above every earlier row's and above 0 (the
+ *   record setters of ram_extend.c:1140-1150); score is that maximum, end_idx = row + offset of that row's best cell (lowest
+ *   offset on ties, bnw_extend.c:1020-1024).  Along the loop's own consensus with rows = ret these are the loop's trimmed
+ *   high score and position.  No such row: end_row = -1, end_idx = -1, score = 0 -- the flank has no alignment.
+ *   Walk back: the start state is gap iff gap > sub in the end cell (:1015).  Substitution state at (r, j): column r is
+ *   matched to base t = j - W + r; go to (r-1, j); gap next iff S1 > S0 there (:950-956).  Gap state: del =
+ *   max(S0(r-1,j+1)+go+ge, S1(r-1,j+1)+ge) for j < 2W, ins = max(S0(r,j-1)+go+ge, S1(r,j-1)+ge) for j > 0; an insertion iff
+ *   ins > del (:1007): base t is inserted, go to (r, j-1); else column r is deleted, go to (r-1, j+1); gap next iff the
+ *   extension term is strictly larger than the opening term (:896-904, :976-984).  On the boundary row at offset o >= 0 the
+ *   first o bases are a leading insertion; in a cell outside the flank (it holds the matrix-edge fill, :990-994) columns 0..r
+ *   are deletions.  The path's score -- matrix[cons[r]][base] over matched columns plus go + len * ge per run of gap moves,
+ *   without go for a run that begins at the origin cell -- equals `score`.
+ * start_idx is the first consumed position (end_idx + 1 if the path consumes none); consumed positions are contiguous up to
+ * end_idx.  tail_ins: insertions after the last column move. */
+typedef struct ramx_aln_end
+{
+  int32_t end_row, end_idx, score, start_idx, tail_ins;
+} ramx_aln_end;
+#define RAMX_ALN_DELETED INT32_MIN          /* col_idx: the column is deleted in this flank */
+#define RAMX_ALN_NONE    (INT32_MIN + 1)    /* col_idx: a column above end_row, or a flank without an alignment */
+
+/* The replay on the device.  Flank layout, argument checks and self-containedness as ramx_dev_profile (any number of flanks
+ * per family, every band width >= 1 and gap sign; rank-local under a communicator).  ends is [n_padded]; col_idx / col_ins
+ * are both NULL or both [max_f rows[f]][n_padded] row-major: col_idx the matched position of column r, RAMX_ALN_DELETED or
+ * RAMX_ALN_NONE; col_ins the number of bases inserted, in path order, between the moves of column r - 1 and of column r (for
+ * r = 0 the leading run).  Entries of the tiles of a family are all written (padding flanks and rows beyond rows[f]: no
+ * alignment, RAMX_ALN_NONE, 0); entries of tiles outside every family are left as they are.  The decision codes (4 bits a
+ * cell) live in a device buffer of at most RAMX_ALIGN_BYTES bytes (environment; default 1 GiB): tiles are processed in groups
+ * that fit; RAMX_ERR_UNSUPPORTED if one tile alone does not.  kernel_ms (may be NULL): two values, the HIP-event times of the
+ * forward kernels and of the walk kernels. */
+int ramx_dev_align(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                   const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                   const int8_t *cons, const int32_t *rows, ramx_aln_end *ends, int32_t *col_idx, int32_t *col_ins,
+                   double *kernel_ms);
 
 /* multi-GPU: flanks are sharded over ranks; each column's 4 candidate sums are all-reduced
  * (4 x int64, RCCL over xGMI).  unique_id is the 128-byte ncclUniqueId made by rank 0

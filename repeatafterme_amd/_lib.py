@@ -20,6 +20,7 @@ EXPORTS = [
     "ramx_load_sequence_subset_minimal", "ramx_load_sequence_subset_packed", "ramx_packed_decode", "ramx_dev_load_library_packed", "ramx_preload_library_packed", "ramx_free_library", "ramx_overlap_avoidance",
     "ramx_print_core_edges", "ramx_allocate_score", "ramx_free_score", "ramx_cli_main",
     "ramx_dev_profile", "ramx_set_profile_sink",
+    "ramx_dev_align", "ramx_set_align_sink",
 ]
 
 
@@ -64,6 +65,14 @@ class ProfileRec(C.Structure):      # ramx_profile
 
 
 PROFILE_CB = C.CFUNCTYPE(None, C.POINTER(ProfileRec), C.c_void_p)
+
+
+class AlignRec(C.Structure):        # ramx_alignment
+    _fields_ = [(k, C.c_int32) for k in ("direction", "family", "rows", "n_flanks", "stride")] + \
+               [(k, C.c_void_p) for k in ("cons", "flanks", "core_index", "ends", "col_idx", "col_ins")]
+
+
+ALIGN_CB = C.CFUNCTYPE(None, C.POINTER(AlignRec), C.c_void_p)
 
 
 def build(force: bool = False) -> None:
@@ -119,6 +128,11 @@ def lib() -> C.CDLL:
         L.ramx_dev_profile.restype = C.c_int
         L.ramx_set_profile_sink.argtypes = [PROFILE_CB, C.c_void_p]
         L.ramx_set_profile_sink.restype = None
+        L.ramx_dev_align.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Params),
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ramx_dev_align.restype = C.c_int
+        L.ramx_set_align_sink.argtypes = [ALIGN_CB, C.c_void_p]
+        L.ramx_set_align_sink.restype = None
         if hasattr(L, "ramx_cli_main"):
             L.ramx_cli_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
         _lib = L

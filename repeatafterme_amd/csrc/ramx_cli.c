@@ -4,6 +4,7 @@
  * defaults), same stdout / -cons / -outtsv / -outfa bytes; the two extend_alignment calls go to
  * the device path (ramx_extend_alignment).
  */
+#include <ctype.h>
 #include <fcntl.h>
 #include <pthread.h>
 #include <stdlib.h>
@@ -240,7 +241,7 @@ static void warm_start(void)
 /* everything the command line decides */
 struct cli_opts
 {
-  const char *ranges_file, *outtsv, *outfa, *outmat, *cons_file, *seq_file, *matrix_name, *batch_file, *outprofile;
+  const char *ranges_file, *outtsv, *outfa, *outmat, *cons_file, *seq_file, *matrix_name, *batch_file, *outprofile, *outaln;
   int flanking, L, bandwidth, maxn, when_to_stop, num_threads, verbose;
   int gap_ext, gap_open, match, mismatch, cappenalty, minimprovement, is_rs;
   struct scoringSystem *sp;
@@ -457,13 +458,13 @@ static void write_results(const struct cli_opts *o, struct coreAlignment *cores,
 /*
  * -batch <list>: many families in one process and ONE launch per direction (no counterpart in the reference, whose
  * wrapper util/extend-stk.pl:242-371 starts one RAMExtend per family).  Every non-empty, non-# line of <list> is
- *     ranges.tsv <TAB> log <TAB> cons.fa <TAB> out.tsv <TAB> out.fa [<TAB> profile.tsv]          ("-" = not wanted)
+ *     ranges.tsv <TAB> log <TAB> cons.fa <TAB> out.tsv <TAB> out.fa [<TAB> profile.tsv [<TAB> aln.a2m]]   ("-" = not wanted)
  * All other options (-twobit, -L, -bandwidth, -matrix ...) are shared.  For every family the log file receives
  * exactly what a stand-alone run prints on stdout, and the three output files are what -cons/-outtsv/-outfa give.
  */
 struct batch_item
 {
-  char *ranges, *log, *cons, *tsv, *fa, *profile;
+  char *ranges, *log, *cons, *tsv, *fa, *profile, *aln;
   struct coreAlignment *cores;
   struct sequenceLibrary *lib;
   int N, rightbp, leftbp;
@@ -530,6 +531,123 @@ static void profile_sink(const ramx_profile *pr, void *user)
   fclose(fp);
 }
 
+/*
+ * -outaln <file>: every extendable core's alignment to the kept consensus of both extensions (include/ramx.h,
+ * ramx_set_align_sink) as A2M text, the right block first.  A block: ">right-extension <ret> bp" and the kept consensus, then
+ * one record per extendable core in flank order, named as -outfa names the core (up to the two spaces) followed by
+ * "  dir=,end_row=,start=,end=,score=".  A body holds exactly ret column characters -- an upper-case base, or '-' for a deleted
+ * column and for the columns above end_row -- and lower-case inserted bases where they fall; nothing is wrapped.  The left block
+ * reads as the sequence does: rows reversed, and every insertion run with them.  The names need both directions' lengths, so
+ * the sink keeps the bodies and the file is written with the other results.
+ */
+struct aln_rec { int core, end_row, start, end, score; char *body; };
+struct aln_block { int have, ret, n; char *cons; struct aln_rec *rec; };
+struct aln_family { const char *path; struct sequenceLibrary *lib; struct aln_block blk[2]; };
+struct aln_out { struct aln_family *fam; };
+
+static void reverse_chars(char *s, size_t n)
+{
+  for (size_t i = 0; i + 1 < n - i; i++) { const char t = s[i]; s[i] = s[n - 1 - i]; s[n - 1 - i] = t; }
+}
+
+static void aln_sink(const ramx_alignment *al, void *user)
+{
+  struct aln_family *af = &((const struct aln_out *)user)->fam[al->family];
+  if (!af->path) return;
+  struct aln_block *b = &af->blk[al->direction ? 1 : 0];
+  const int rows = al->rows;
+  b->have = 1; b->ret = rows; b->n = al->n_flanks;
+  b->cons = (char *)malloc((size_t)rows + 1);
+  for (int r = 0; r < rows; r++) b->cons[r] = code_to_char(al->cons[r]);
+  b->cons[rows] = 0;
+  if (!al->direction) reverse_chars(b->cons, (size_t)rows);
+  b->rec = (struct aln_rec *)calloc((size_t)(al->n_flanks > 0 ? al->n_flanks : 1), sizeof(struct aln_rec));
+  const uint64_t lib_len = af->lib->length;
+  for (int i = 0; i < al->n_flanks; i++)
+  {
+    const ramx_aln_end *e = &al->ends[i];
+    const ramx_flank *f = &al->flanks[i];
+    struct aln_rec *rc = &b->rec[i];
+    rc->core = al->core_index[i]; rc->end_row = e->end_row; rc->start = e->start_idx; rc->end = e->end_idx; rc->score = e->score;
+    const long consumed = e->end_row >= 0 ? (long)e->end_idx - e->start_idx + 1 : 0;
+    char *body = (char *)malloc((size_t)rows + (size_t)(consumed > 0 ? consumed : 0) + 1);
+    size_t k = 0;
+    long t = e->start_idx;
+#define ALN_BASE(upper) do { \
+      const int64_t at_ = f->start + (int64_t)f->step * t; \
+      int code_ = (at_ >= 0 && (uint64_t)at_ < lib_len) ? ramx_lib_code(af->lib, (uint64_t)at_) : RAMX_SYM_N; \
+      if (f->compl_) code_ = code_compl(code_); \
+      const char ch_ = code_to_char(code_); \
+      body[k++] = (char)((upper) ? toupper((unsigned char)ch_) : tolower((unsigned char)ch_)); \
+      t++; } while (0)
+    for (int r = 0; r < rows; r++)
+    {
+      if (r > e->end_row) { body[k++] = '-'; continue; }
+      const int idx = al->col_idx[(size_t)r * al->stride + i];
+      for (int q = al->col_ins[(size_t)r * al->stride + i]; q > 0 && t <= e->end_idx; q--) ALN_BASE(0);
+      if (idx == RAMX_ALN_DELETED || idx == RAMX_ALN_NONE) body[k++] = '-';
+      else { t = idx; ALN_BASE(1); }
+      if (r == e->end_row) for (int q = e->tail_ins; q > 0 && t <= e->end_idx; q--) ALN_BASE(0);
+    }
+#undef ALN_BASE
+    body[k] = 0;
+    if (!al->direction) reverse_chars(body, k);
+    rc->body = body;
+  }
+}
+
+/* the record id -outfa gives a core (results_rows, above): ident:from-to_orient over the extended range plus the flanking */
+static void aln_record_id(char *buf, size_t n, const struct coreAlignment *s, const struct sequenceLibrary *lib, int flanking)
+{
+  const int si = s->seqIdx;
+  const uint64_t lo = si > 0 ? lib->boundaries[si - 1] : 0;
+  const uint64_t hi = lib->boundaries[si];
+  const uint64_t off = (lib->offsets != NULL && lib->offsets[si] > 0) ? lib->offsets[si] : 0;
+  uint64_t from = s->leftSeqPos - (uint64_t)s->leftExtensionLen, to = s->rightSeqPos + (uint64_t)s->rightExtensionLen;
+  if (s->orient) { to = s->leftSeqPos + (uint64_t)s->leftExtensionLen; from = s->rightSeqPos - (uint64_t)s->rightExtensionLen; }
+  if (flanking > 0)
+  {
+    if (lo == 0 && (uint64_t)flanking > from) from = 1;
+    else from -= (uint64_t)flanking;
+    if (to + (uint64_t)flanking > hi) to = hi;
+    else to += (uint64_t)flanking;
+  }
+  snprintf(buf, n, "%s:%ld-%ld_%c", lib->identifiers[si], (long)(off + from - lo + 1), (long)(off + to - lo + 1), s->orient ? '-' : '+');
+}
+
+/* after both directions: the file, then the buffers are released */
+static void aln_write(struct aln_family *af, struct coreAlignment *cores, int flanking)
+{
+  if (!af->path) return;
+  FILE *fp = fopen(af->path, "w");
+  if (!fp) { fprintf(stderr, "Could not create the alignment file %s\n", af->path); exit(1); }
+  int cnt = 0;
+  for (struct coreAlignment *s = cores; s != NULL; s = s->next) cnt++;
+  struct coreAlignment **arr = (struct coreAlignment **)malloc(sizeof(*arr) * (size_t)(cnt ? cnt : 1));
+  cnt = 0;
+  for (struct coreAlignment *s = cores; s != NULL; s = s->next) arr[cnt++] = s;
+  for (int dir = 1; dir >= 0; dir--)
+  {
+    struct aln_block *b = &af->blk[dir];
+    if (!b->have) continue;
+    fprintf(fp, ">%s-extension %d bp\n%s\n", dir ? "right" : "left", b->ret, b->cons);
+    for (int i = 0; i < b->n; i++)
+    {
+      const struct aln_rec *rc = &b->rec[i];
+      char id[1024];
+      if (rc->core < 0 || rc->core >= cnt) { fprintf(stderr, "RAMExtend(ramx): alignment record of an unknown core %d\n", rc->core); exit(1); }
+      aln_record_id(id, sizeof(id), arr[rc->core], af->lib, flanking);
+      fprintf(fp, ">%s  dir=%s,end_row=%d,start=%d,end=%d,score=%d\n%s\n", id, dir ? "right" : "left", rc->end_row, rc->start, rc->end,
+              rc->score, rc->body);
+      free(rc->body);
+    }
+    free(b->rec); free(b->cons);
+    memset(b, 0, sizeof(*b));
+  }
+  free(arr);
+  fclose(fp);
+}
+
 /* flat view of a core list for ramx_extend_batch (arrays owned by the caller's arena) */
 static void flatten_cores(struct coreAlignment *cores, int N, ramx_flat_cores *fc)
 {
@@ -582,6 +700,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   const int L = o->L, l = 1;
   if (o->outmat != NULL) { fprintf(stderr, "RAMExtend(ramx): -outmat traces one family; it cannot be combined with -batch\n"); exit(1); }
   if (o->outprofile != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's profile file is the sixth field of its line in the list\n"); exit(1); }
+  if (o->outaln != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's alignment file is the seventh field of its line in the list\n"); exit(1); }
   FILE *lf = fopen(o->batch_file, "r");
   if (!lf) { fprintf(stderr, "Could not open batch list %s\n", o->batch_file); exit(1); }
   size_t cap = 64, F = 0;
@@ -593,9 +712,9 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   {
     while (len > 0 && (line[len - 1] == '\n' || line[len - 1] == '\r')) line[--len] = 0;
     if (line[0] == '#' || line[0] == 0) continue;
-    char *f[6] = { NULL, NULL, NULL, NULL, NULL, NULL };
+    char *f[7] = { NULL, NULL, NULL, NULL, NULL, NULL, NULL };
     char *p = line;
-    for (int k = 0; k < 6 && p; k++) { f[k] = p; char *t = strchr(p, '\t'); if (t) { *t = 0; p = t + 1; } else p = NULL; }
+    for (int k = 0; k < 7 && p; k++) { f[k] = p; char *t = strchr(p, '\t'); if (t) { *t = 0; p = t + 1; } else p = NULL; }
     if (!f[0] || !f[1]) { fprintf(stderr, "batch list: every line needs at least <ranges><TAB><log>\n"); exit(1); }
     if (F == cap) { cap *= 2; it = (struct batch_item *)realloc(it, cap * sizeof(*it)); memset(it + F, 0, (cap - F) * sizeof(*it)); }
     it[F].ranges = strdup(f[0]); it[F].log = strdup(f[1]);
@@ -603,6 +722,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
     it[F].tsv = field_or_null(f[3]) ? strdup(f[3]) : NULL;
     it[F].fa = field_or_null(f[4]) ? strdup(f[4]) : NULL;
     it[F].profile = field_or_null(f[5]) ? strdup(f[5]) : NULL;       /* optional sixth field: the family's -outprofile file */
+    it[F].aln = field_or_null(f[6]) ? strdup(f[6]) : NULL;           /* optional seventh field: the family's -outaln file */
     F++;
   }
   free(line);
@@ -645,6 +765,11 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   for (size_t i = 0; i < F; i++)
     if ((profile_paths[i] = it[i].profile) != NULL) { profile_start(it[i].profile); any_profile = 1; }
   if (any_profile) ramx_set_profile_sink(profile_sink, &pout);
+  struct aln_out aout = { (struct aln_family *)calloc(F ? F : 1, sizeof(struct aln_family)) };
+  int any_aln = 0;
+  for (size_t i = 0; i < F; i++)
+    if ((aout.fam[i].path = it[i].aln) != NULL) { aout.fam[i].lib = it[i].lib; any_aln = 1; }
+  if (any_aln) ramx_set_align_sink(aln_sink, &aout);
   /* phase 2: right extension of all families in one launch; phase 3: per family, overlap avoidance */
   for (size_t i = 0; i < F; i++) flatten_cores(it[i].cores, it[i].N, &fam[i].cores);
   if (ramx_extend_batch(1, fam, (int32_t)F, &p, ir) < 0) { fprintf(stderr, "RAMExtend(ramx): batch extension failed: %s\n", ramx_last_error()); exit(1); }
@@ -675,6 +800,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
     print_loop_lines(0, it[i].N, o->verbose, o->when_to_stop, L, &il[i], 0);
     printf("Extended left : %d bp\n", it[i].leftbp);
     write_results(o, it[i].cores, it[i].lib, it[i].master, it[i].rightbp, it[i].leftbp, it[i].cons, it[i].tsv, it[i].fa);
+    aln_write(&aout.fam[i], it[i].cores, o->flanking);
     const double duration = difftime(time(0), t_start);
     printf("Program duration is %.1f sec = %.1f min = %.1f hr\n", duration, duration / 60.0, duration / 3600.0);
   }
@@ -685,9 +811,11 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   for (size_t i = 0; i < F; i++)
   {
     ramx_free_library(it[i].lib, it[i].cores);
-    free(it[i].master); free(it[i].ranges); free(it[i].log); free(it[i].cons); free(it[i].tsv); free(it[i].fa); free(it[i].profile);
+    free(it[i].master); free(it[i].ranges); free(it[i].log); free(it[i].cons); free(it[i].tsv); free(it[i].fa); free(it[i].profile); free(it[i].aln);
   }
   ramx_set_profile_sink(NULL, NULL);
+  ramx_set_align_sink(NULL, NULL);
+  free(aout.fam);
   free(profile_paths);
   free(it); free(fam); free(ir); free(il); free(mflat);
   ramx_free_scoring_system(o->sp);
@@ -716,6 +844,7 @@ int ramx_cli_main(int argc, char **argv)
   opt_string(argc, argv, "-outmat", &o.outmat);
   opt_string(argc, argv, "-cons", &o.cons_file);
   opt_string(argc, argv, "-outprofile", &o.outprofile);
+  opt_string(argc, argv, "-outaln", &o.outaln);
   if (!opt_int(argc, argv, "-L", &o.L)) o.L = 10000;
   if (!opt_int(argc, argv, "-bandwidth", &o.bandwidth)) o.bandwidth = 14;
   if (!opt_int(argc, argv, "-maxoccurrences", &o.maxn)) o.maxn = 10000;
@@ -804,6 +933,11 @@ int ramx_cli_main(int argc, char **argv)
     profile_start(o.outprofile);
     ramx_set_profile_sink(profile_sink, &pout);
   }
+  struct aln_family afam;
+  memset(&afam, 0, sizeof(afam));
+  afam.path = o.outaln; afam.lib = lib;
+  struct aln_out aout = { &afam };
+  if (o.outaln != NULL) ramx_set_align_sink(aln_sink, &aout);
   fflush(stdout);
   warm_join();
   phase_done("device ready");
@@ -816,7 +950,9 @@ int ramx_cli_main(int argc, char **argv)
   printf("Extended left : %d bp\n", leftbp);
   phase_done("extend left");
   ramx_set_profile_sink(NULL, NULL);
+  ramx_set_align_sink(NULL, NULL);
   write_results(&o, cores, lib, master, rightbp, leftbp, o.cons_file, o.outtsv, o.outfa);
+  aln_write(&afam, cores, o.flanking);
   if (fp_mat != NULL) fclose(fp_mat);     /* ram_extend.c:778-779 */
   phase_done("report + outputs");
 

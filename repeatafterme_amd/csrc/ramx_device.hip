@@ -51,6 +51,7 @@
 #include "ramx_cp_api.h"
 #include "ramx_pk_api.h"
 #include "ramx_profile_api.h"
+#include "ramx_align_api.h"
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
@@ -152,6 +153,9 @@ struct ramx_dev
   int4 *d_pf_state; ramx_col_profile *d_pf_slab, *d_pf_cols; signed char *d_pf_cons; int *d_pf_rows; int4 *d_pf_fam; int2 *d_pf_tile;
   int *d_pf_last, *d_pf_best, *d_pf_bidx;
   size_t cap_pf_state, cap_pf_slab, cap_pf_cols, cap_pf_cons, cap_pf_rows, cap_pf_fam, cap_pf_tile, cap_pf_last, cap_pf_best, cap_pf_bidx;
+  // ramx_dev_align (allocated on its first call; rows, consensus and tables are the profile replay's): decision codes, per-flank records, per-column outputs
+  unsigned *d_al_codes; ramx_aln_end *d_al_ends; int *d_al_idx, *d_al_ins;
+  size_t cap_al_codes, cap_al_ends, cap_al_idx, cap_al_ins;
 };
 
 extern "C" int ramx_device_count(void)
@@ -236,6 +240,7 @@ extern "C" void ramx_dev_destroy(ramx_dev *d)
   (void)hipFree(d->d_fam); (void)hipFree(d->d_famctl); (void)hipFree(d->d_cpstate); (void)hipFree(d->d_dbg_codes); (void)hipFree(d->d_dbg_best); (void)hipFree(d->d_dbg_cand); (void)hipFree(d->d_dbg_gap); (void)hipFree(d->d_dbg_band); (void)hipFree(d->d_devdesc); (void)hipFree(d->d_vote_sets); (void)hipFree(d->d_err_sets);
   (void)hipFree(d->d_pf_state); (void)hipFree(d->d_pf_slab); (void)hipFree(d->d_pf_cols); (void)hipFree(d->d_pf_cons); (void)hipFree(d->d_pf_rows);
   (void)hipFree(d->d_pf_fam); (void)hipFree(d->d_pf_tile); (void)hipFree(d->d_pf_last); (void)hipFree(d->d_pf_best); (void)hipFree(d->d_pf_bidx);
+  (void)hipFree(d->d_al_codes); (void)hipFree(d->d_al_ends); (void)hipFree(d->d_al_idx); (void)hipFree(d->d_al_ins);
   if (d->hostbox_mirror) (void)hipFree(d->hostbox_mirror);
   if (d->d_peer) (void)hipFree(d->d_peer);
   for (int i = 0; i < 2; i++) if (d->ev_chk[i]) (void)hipEventDestroy(d->ev_chk[i]);
@@ -1653,6 +1658,155 @@ extern "C" int ramx_dev_profile(ramx_dev *d, const ramx_flank *flanks, int32_t n
   {
     HIPCHK(hipMemcpy(row_best, d->d_pf_best, (size_t)maxrows * n_padded * sizeof(int), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(row_best_idx, d->d_pf_bidx, (size_t)maxrows * n_padded * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  return RAMX_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// per-copy alignments: the band replayed along a given consensus with every cell's decisions kept, then walked back
+// (ramx_kernels_align.h)
+// ------------------------------------------------------------------------------------------
+extern "C" int ramx_dev_align(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                              const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                              const int8_t *cons, const int32_t *rows, ramx_aln_end *ends, int32_t *col_idx, int32_t *col_ins,
+                              double *kernel_ms)
+{
+  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0;
+  if (!d || !p || !p->matrix || n_families < 0 || n_padded < 0 || (n_padded & 63) || (n_padded && (!flanks || !ends)) ||
+      (n_families && (!fam_first || !fam_count || !rows)))
+  { ramx_set_error("ramx_dev_align: bad argument"); return RAMX_ERR_ARG; }
+  if ((col_idx == NULL) != (col_ins == NULL)) { ramx_set_error("ramx_dev_align: col_idx and col_ins go together"); return RAMX_ERR_ARG; }
+  const int W = p->bandwidth, L = p->L, Q = W + 1;
+  if (W < 1 || L < 0) { ramx_set_error("ramx_dev_align: bad bandwidth / L"); return RAMX_ERR_ARG; }
+  const int tiles = n_padded / 64;
+  std::vector<int2> tile_fam((size_t)(tiles > 0 ? tiles : 1), make_int2(-1, 0));
+  int maxrows = 0;
+  for (int f = 0; f < n_families; f++)
+  {
+    if (fam_count[f] < 0 || fam_first[f] < 0 || (fam_first[f] & 63) || (long long)fam_first[f] + fam_count[f] > n_padded)
+    { ramx_set_error("ramx_dev_align: bad family layout"); return RAMX_ERR_ARG; }
+    if (rows[f] < 0 || rows[f] > L) { ramx_set_error("ramx_dev_align: rows[%d] = %d outside [0, L = %d]", f, rows[f], L); return RAMX_ERR_ARG; }
+    if (rows[f] > 0 && !cons) { ramx_set_error("ramx_dev_align: cons missing"); return RAMX_ERR_ARG; }
+    for (int r = 0; r < rows[f]; r++)
+      if (cons[(size_t)f * L + r] < 0 || cons[(size_t)f * L + r] > 3) { ramx_set_error("ramx_dev_align: consensus base outside A C G T (family %d, column %d)", f, r); return RAMX_ERR_ARG; }
+    const int t0 = fam_first[f] / 64, nt = (fam_count[f] + 63) / 64;
+    for (int t = 0; t < nt; t++)
+    {
+      if (tile_fam[t0 + t].x >= 0) { ramx_set_error("ramx_dev_align: families %d and %d overlap", tile_fam[t0 + t].x, f); return RAMX_ERR_ARG; }
+      const int left = fam_count[f] - 64 * t;
+      tile_fam[t0 + t] = make_int2(f, left < 64 ? left : 64);
+    }
+    if (rows[f] > maxrows) maxrows = rows[f];
+  }
+  // the group of tiles whose codes fit the budget
+  const int nd = ramx_align_dwords(W);
+  size_t budget = (size_t)1 << 30;
+  if (const char *e = getenv("RAMX_ALIGN_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+  const size_t tile_bytes = (size_t)(maxrows > 0 ? maxrows : 1) * nd * 64 * sizeof(unsigned);
+  if (tiles > 0 && maxrows > 0 && tile_bytes > budget)
+  {
+    ramx_set_error("ramx_dev_align: the decision codes of one tile of 64 flanks (%d rows, bandwidth %d: %zu bytes) do not fit RAMX_ALIGN_BYTES = %zu",
+                   maxrows, W, tile_bytes, budget);
+    return RAMX_ERR_UNSUPPORTED;
+  }
+  // what the kernels never reach is answered here: no alignment
+  const ramx_aln_end none = { -1, -1, 0, 0, 0 };
+  auto preset_host = [&](int f) {
+    const int t0 = fam_first[f] / 64, nt = (fam_count[f] + 63) / 64;
+    for (int i = t0 * 64; i < (t0 + nt) * 64; i++) ends[i] = none;
+    if (col_idx)
+      for (int r = 0; r < maxrows; r++)
+        for (int i = t0 * 64; i < (t0 + nt) * 64; i++) { col_idx[(size_t)r * n_padded + i] = RAMX_ALN_NONE; col_ins[(size_t)r * n_padded + i] = 0; }
+  };
+  if (n_families == 0 || maxrows == 0 || tiles == 0)
+  {
+    for (int f = 0; f < n_families; f++) preset_host(f);
+    return RAMX_OK;
+  }
+  HIPCHK(hipSetDevice(d->ordinal));
+  const int Np = n_padded;
+  const int KW = (L + 2 * W + 2) / 8 + 12;
+  int group = (int)(budget / tile_bytes < (size_t)tiles ? budget / tile_bytes : (size_t)tiles);
+  int rc;
+  if (d->pack_busy) { HIPCHK(hipEventSynchronize(d->pack_done)); d->pack_busy = 0; }      // see ramx_dev_profile
+  if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)Np * sizeof(ramx_flank)))) return rc;
+  if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)KW * Np * sizeof(unsigned)))) return rc;
+  if ((rc = ensure(&d->d_bounds, &d->cap_bounds, (size_t)Np * sizeof(int2)))) return rc;
+  if ((rc = ensure(&d->d_pf_state, &d->cap_pf_state, (size_t)Np * Q * sizeof(int4)))) return rc;
+  if ((rc = ensure(&d->d_pf_cons, &d->cap_pf_cons, (size_t)n_families * L + 16))) return rc;
+  if ((rc = ensure(&d->d_pf_rows, &d->cap_pf_rows, (size_t)n_families * sizeof(int)))) return rc;
+  if ((rc = ensure(&d->d_pf_tile, &d->cap_pf_tile, tile_fam.size() * sizeof(int2)))) return rc;
+  if ((rc = ensure(&d->d_al_codes, &d->cap_al_codes, (size_t)group * tile_bytes))) return rc;
+  if ((rc = ensure(&d->d_al_ends, &d->cap_al_ends, (size_t)Np * sizeof(ramx_aln_end)))) return rc;
+  const size_t ncol = (size_t)maxrows * Np;
+  if (col_idx)
+  {
+    if ((rc = ensure(&d->d_al_idx, &d->cap_al_idx, ncol * sizeof(int)))) return rc;
+    if ((rc = ensure(&d->d_al_ins, &d->cap_al_ins, ncol * sizeof(int)))) return rc;
+  }
+  HIPCHK(hipMemcpyAsync(d->d_flanks, flanks, (size_t)n_padded * sizeof(ramx_flank), hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemcpyAsync(d->d_pf_cons, cons, (size_t)n_families * L, hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemcpyAsync(d->d_pf_rows, rows, (size_t)n_families * sizeof(int), hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemcpyAsync(d->d_pf_tile, tile_fam.data(), tile_fam.size() * sizeof(int2), hipMemcpyHostToDevice, d->stream));
+  if (col_idx && (rc = ramx_align_launch_preset(d->stream, d->d_al_idx, d->d_al_ins, ncol)) != RAMX_OK) return rc;
+  if ((rc = launch_pack(d, n_padded, Np, W, 0, KW, d->stream)) != RAMX_OK) return rc;
+  d->packed_kw = KW;
+  d->ready = 0;       // the direction's flank and window buffers were reused: begin_direction must be called again before run_direction
+  AlnArgs aa;
+  memset(&aa, 0, sizeof(aa));
+  aa.k.bases = d->d_bases; aa.k.bounds = d->d_bounds; aa.k.S_in = d->d_pf_state; aa.k.S_out = d->d_pf_state;
+  aa.k.Np = Np; aa.k.Nx = Np; aa.k.W = W; aa.k.go = p->gapopen; aa.k.ge = p->gapextn; aa.k.cap = p->cappenalty;
+  for (int c = 0; c < RAMX_NCLASS; c++)
+  {
+    const int code = (c == 8) ? RAMX_SYM_N : c;
+    for (int k = 0; k < 4; k++) aa.k.tab[c][k] = p->matrix[k * 100 + code];
+  }
+  aa.tile_fam = d->d_pf_tile; aa.cons = d->d_pf_cons; aa.rows = d->d_pf_rows; aa.codes = d->d_al_codes; aa.ends = d->d_al_ends;
+  aa.col_idx = col_idx ? d->d_al_idx : NULL; aa.col_ins = col_idx ? d->d_al_ins : NULL;
+  aa.L = L; aa.nd = nd; aa.gn = group * 64;
+  // group after group on one stream: the walk of a group has read its codes before the next group's forward pass writes them
+  const int ngroups = (tiles + group - 1) / group;
+  std::vector<hipEvent_t> ev((size_t)3 * ngroups, (hipEvent_t)NULL);
+  if (kernel_ms) for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+  for (int g = 0; g < ngroups; g++)
+  {
+    aa.tile0 = g * group;
+    const int nt = tiles - aa.tile0 < group ? tiles - aa.tile0 : group;
+    if (kernel_ms) HIPCHK(hipEventRecord(ev[3 * g], d->stream));
+    if ((rc = ramx_align_launch_forward(d->stream, nt, aa)) != RAMX_OK) break;
+    if (kernel_ms) HIPCHK(hipEventRecord(ev[3 * g + 1], d->stream));
+    if ((rc = ramx_align_launch_walk(d->stream, nt, aa)) != RAMX_OK) break;
+    if (kernel_ms) HIPCHK(hipEventRecord(ev[3 * g + 2], d->stream));
+  }
+  if (rc != RAMX_OK) ramx_set_error("ramx_dev_align: launch failed (%s)", hipGetErrorString(hipGetLastError()));
+  const hipError_t se = hipStreamSynchronize(d->stream);
+  if (kernel_ms)
+  {
+    for (int g = 0; g < ngroups && rc == RAMX_OK && se == hipSuccess; g++)
+    {
+      float a = 0, b = 0;
+      (void)hipEventElapsedTime(&a, ev[3 * g], ev[3 * g + 1]);
+      (void)hipEventElapsedTime(&b, ev[3 * g + 1], ev[3 * g + 2]);
+      kernel_ms[0] += a; kernel_ms[1] += b;
+    }
+    for (auto &e : ev) (void)hipEventDestroy(e);
+  }
+  if (rc != RAMX_OK) return rc;
+  HIPCHK(se);
+  // the tiles of every family, all rows; tiles outside every family keep what the caller has there
+  for (int f = 0; f < n_families; f++)
+  {
+    const int t0 = fam_first[f] / 64, nt = (fam_count[f] + 63) / 64;
+    if (nt == 0) continue;
+    if (rows[f] == 0) { preset_host(f); continue; }   // its tiles ran no row: the forward kernel still wrote their records
+    HIPCHK(hipMemcpy(ends + (size_t)t0 * 64, d->d_al_ends + (size_t)t0 * 64, (size_t)nt * 64 * sizeof(ramx_aln_end), hipMemcpyDeviceToHost));
+    if (col_idx)
+    {
+      HIPCHK(hipMemcpy2D(col_idx + (size_t)t0 * 64, (size_t)n_padded * sizeof(int), d->d_al_idx + (size_t)t0 * 64, (size_t)Np * sizeof(int),
+                         (size_t)nt * 64 * sizeof(int), (size_t)maxrows, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy2D(col_ins + (size_t)t0 * 64, (size_t)n_padded * sizeof(int), d->d_al_ins + (size_t)t0 * 64, (size_t)Np * sizeof(int),
+                         (size_t)nt * 64 * sizeof(int), (size_t)maxrows, hipMemcpyDeviceToHost));
+    }
   }
   return RAMX_OK;
 }

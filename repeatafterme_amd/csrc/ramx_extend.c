@@ -38,6 +38,15 @@ void ramx_set_profile_sink(ramx_profile_cb cb, void *user)
   g_profile_user = user;
 }
 
+/* alignment sink (include/ramx.h): off unless set */
+static ramx_align_cb g_align_cb = NULL;
+static void *g_align_user = NULL;
+void ramx_set_align_sink(ramx_align_cb cb, void *user)
+{
+  g_align_cb = cb;
+  g_align_user = user;
+}
+
 static ramx_dev *g_dev = NULL;
 /* The device keeps the library between calls (the reference's main() runs both directions on one seqLib).  The
  * cache key is (pointer, length, content fingerprint): a caller that rewrites the buffer in place, or whose new
@@ -458,6 +467,43 @@ static int profile_direction(ramx_dev *d, int direction, int family, const ramx_
   return rc;
 }
 
+/* With an alignment sink set: replay one direction of one family along the kept consensus (rows = ret), walk every flank
+ * back and hand the alignments over. */
+static int align_direction(ramx_dev *d, int direction, int family, const ramx_flank *fl, const int32_t *map, int nx,
+                           const ramx_params *p, const int8_t *cons, int ret)
+{
+  ramx_alignment al;
+  memset(&al, 0, sizeof(al));
+  al.direction = direction; al.family = family; al.rows = ret > 0 ? ret : 0; al.n_flanks = nx;
+  al.cons = cons; al.flanks = fl; al.core_index = map;
+  if (nx == 0 || ret <= 0)
+  {
+    /* no extendable core, or no kept column: no flank has an alignment (answered on the host) */
+    ramx_aln_end *ends = (ramx_aln_end *)malloc(sizeof(ramx_aln_end) * (size_t)(nx > 0 ? nx : 1));
+    for (int i = 0; i < nx; i++) { ends[i].end_row = -1; ends[i].end_idx = -1; ends[i].score = 0; ends[i].start_idx = 0; ends[i].tail_ins = 0; }
+    al.ends = ends;
+    g_align_cb(&al, g_align_user);
+    free(ends);
+    return RAMX_OK;
+  }
+  const int npad = (nx + 63) & ~63;
+  ramx_flank *pf = (ramx_flank *)malloc(sizeof(ramx_flank) * (size_t)npad);
+  ramx_aln_end *ends = (ramx_aln_end *)malloc(sizeof(ramx_aln_end) * (size_t)npad);
+  int32_t *idx = (int32_t *)malloc(sizeof(int32_t) * (size_t)npad * (size_t)ret);
+  int32_t *ins = (int32_t *)malloc(sizeof(int32_t) * (size_t)npad * (size_t)ret);
+  memcpy(pf, fl, sizeof(ramx_flank) * (size_t)nx);
+  for (int i = nx; i < npad; i++) { memset(&pf[i], 0, sizeof(ramx_flank)); pf[i].t_lo = 1; pf[i].t_hi = 0; pf[i].step = 1; }
+  const int32_t first = 0, count = nx, nrows = ret;
+  const int rc = ramx_dev_align(d, pf, npad, &first, &count, 1, p, cons, &nrows, ends, idx, ins, NULL);
+  if (rc == RAMX_OK)
+  {
+    al.stride = npad; al.ends = ends; al.col_idx = idx; al.col_ins = ins;
+    g_align_cb(&al, g_align_user);
+  }
+  free(pf); free(ends); free(idx); free(ins);
+  return rc;
+}
+
 /* packed != NULL: the device already holds the library (ramx_preload_library_packed); `sequence` is not looked at;
    family: the index a profile sink is told (ramx_extend_batch running a family on its own, else 0) */
 static int extend_flat_impl(int direction, ramx_flat_cores *c, const int8_t *sequence, uint64_t seq_len,
@@ -640,6 +686,11 @@ run_again:
   {
     rc = profile_direction(d, direction, family, fl, map, nx, p, cons, info->rows_executed, info->ret);
     SEAM1_PHASE("profile replay");
+  }
+  if (rc == RAMX_OK && g_align_cb != NULL)
+  {
+    rc = align_direction(d, direction, family, fl, map, nx, p, cons, info->ret);
+    SEAM1_PHASE("alignment replay");
   }
 #undef SEAM1_PHASE
 #undef FP_JOIN
@@ -929,6 +980,33 @@ int ramx_extend_batch(int direction, ramx_family *fam, int32_t F, const ramx_par
       }
       free(cols); free(last); free(nrows);
       BATCH_PHASE("profile replay");
+    }
+    if (rc == RAMX_OK && g_align_cb != NULL)
+    {
+      /* every family of the launch in one call, along its own kept consensus; the sink sees a family's flanks in the
+       * coordinates of the family's own library */
+      int32_t *nrows = (int32_t *)malloc(sizeof(int32_t) * (size_t)nb);
+      int maxret = 0;
+      for (int b = 0; b < nb; b++) { nrows[b] = binfo[b].ret > 0 ? binfo[b].ret : 0; if (nrows[b] > maxret) maxret = nrows[b]; }
+      ramx_aln_end *ends = (ramx_aln_end *)malloc(sizeof(ramx_aln_end) * (fpos ? fpos : 1));
+      int32_t *idx = (int32_t *)malloc(sizeof(int32_t) * (fpos ? fpos : 1) * (size_t)(maxret > 0 ? maxret : 1));
+      int32_t *ins = (int32_t *)malloc(sizeof(int32_t) * (fpos ? fpos : 1) * (size_t)(maxret > 0 ? maxret : 1));
+      for (size_t i = 0; i < fpos; i++) { ends[i].end_row = -1; ends[i].end_idx = -1; ends[i].score = 0; ends[i].start_idx = 0; ends[i].tail_ins = 0; }
+      rc = ramx_dev_align(d, fl, (int32_t)fpos, first, count, nb, p, cons, nrows, ends, idx, ins, NULL);
+      for (int b = 0; b < nb && rc == RAMX_OK; b++)
+      {
+        ramx_flank *own_fl = (ramx_flank *)malloc(sizeof(ramx_flank) * (size_t)(count[b] > 0 ? count[b] : 1));
+        for (int i = 0; i < count[b]; i++) { own_fl[i] = fl[first[b] + i]; own_fl[i].start -= (int64_t)at_of[fidx[b]]; }
+        ramx_alignment al;
+        memset(&al, 0, sizeof(al));
+        al.direction = direction; al.family = fidx[b]; al.rows = nrows[b]; al.n_flanks = count[b]; al.stride = (int32_t)fpos;
+        al.cons = cons + (size_t)b * L; al.flanks = own_fl; al.core_index = map + first[b]; al.ends = ends + first[b];
+        if (nrows[b] > 0 && count[b] > 0) { al.col_idx = idx + first[b]; al.col_ins = ins + first[b]; }
+        g_align_cb(&al, g_align_user);
+        free(own_fl);
+      }
+      free(nrows); free(ends); free(idx); free(ins);
+      BATCH_PHASE("alignment replay");
     }
     free(binfo); free(cons); free(th); free(tp);
     BATCH_PHASE("write-back");

@@ -104,6 +104,32 @@ COL_PROFILE_DTYPE = np.dtype([("total", np.int64, (4,)), ("base", np.int32), ("n
 assert COL_PROFILE_DTYPE.itemsize == 48
 
 
+# per-flank record of an alignment: C-ABI ramx_aln_end (include/ramx.h), 20 bytes
+ALN_END_DTYPE = np.dtype([("end_row", np.int32), ("end_idx", np.int32), ("score", np.int32), ("start_idx", np.int32),
+                          ("tail_ins", np.int32)])
+assert ALN_END_DTYPE.itemsize == 20
+ALN_DELETED = -2 ** 31           # RAMX_ALN_DELETED: the column is deleted in this flank
+ALN_NONE = -2 ** 31 + 1          # RAMX_ALN_NONE: a column above end_row, or a flank without an alignment
+
+
+@dataclass
+class Alignment:
+    """Per-copy alignments of one direction of one family to its kept consensus (C-ABI ramx_alignment / ramx_dev_align)."""
+    direction: int
+    family: int                      # index in a batch, else 0
+    cons: np.ndarray                 # int8 [rows]: the kept consensus (rows = ret)
+    flanks: np.ndarray               # FLANK_DTYPE [n_flanks]
+    core_index: np.ndarray           # position in the core list of every flank
+    ends: np.ndarray                 # ALN_END_DTYPE [n_flanks]
+    col_idx: np.ndarray              # int32 [rows][n_flanks]: matched flank position, ALN_DELETED or ALN_NONE
+    col_ins: np.ndarray              # int32 [rows][n_flanks]: bases inserted before the column's move
+
+
+FLANK_DTYPE = np.dtype([("start", np.int64), ("t_lo", np.int32), ("t_hi", np.int32), ("step", np.int8), ("compl_", np.int8),
+                        ("pad_", np.int8, (6,))])
+assert FLANK_DTYPE.itemsize == 24
+
+
 @dataclass
 class Profile:
     """Per-column support of one direction of one family (C-ABI ramx_profile / ramx_dev_profile)."""

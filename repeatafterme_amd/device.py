@@ -10,7 +10,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .datamodel import COL_PROFILE_DTYPE, CoreSet, ExtendParams
+from .datamodel import ALN_END_DTYPE, ALN_NONE, COL_PROFILE_DTYPE, CoreSet, ExtendParams
 from .extend import RunInfo, _info, _params
 
 
@@ -33,6 +33,15 @@ class ProfileResult:
     row_best: Optional[np.ndarray]         # [max rows][n_padded], or None
     row_best_idx: Optional[np.ndarray]
     kernel_ms: float
+
+
+@dataclass
+class AlignResult:
+    ends: np.ndarray                       # ALN_END_DTYPE [n_padded]
+    col_idx: Optional[np.ndarray]          # int32 [max rows][n_padded], or None
+    col_ins: Optional[np.ndarray]
+    forward_ms: float                      # HIP-event time of the forward kernels
+    walk_ms: float                         # ... and of the walk kernels
 
 
 def pad_flanks(flanks):
@@ -134,6 +143,46 @@ class Device:
                                             rb.ctypes.data if row_best else None, rbi.ctypes.data if row_best else None,
                                             C.byref(ms)), "ramx_dev_profile")
         return ProfileResult(cols, last[:npad], rb, rbi, ms.value)
+
+    def align(self, flanks, p: ExtendParams, cons, rows=None, fam_first=None, fam_count=None, columns: bool = True,
+              out: Optional[AlignResult] = None) -> AlignResult:
+        """Align every flank to a given consensus (C-ABI ramx_dev_align): arguments as profile().  columns=False: only the
+        per-flank records.  `out`: a result to write into (entries of tiles outside every family are left alone)."""
+        cp, keep = _params(p)
+        L = p.L
+        if fam_first is None:
+            n = flanks[1]
+            arr, npad = pad_flanks(flanks)
+            fam_first, fam_count = [0], [n]
+            c1 = np.asarray(cons, np.int8).ravel()
+            rows = [len(c1) if rows is None else int(rows)]
+            cons = np.zeros((1, max(L, 1)), np.int8)
+            cons[0, :min(len(c1), L)] = c1[:L]
+        else:
+            arr, npad = flanks
+        nf = len(fam_first)
+        first = np.ascontiguousarray(fam_first, np.int32)
+        count = np.ascontiguousarray(fam_count, np.int32)
+        rows_a = np.ascontiguousarray(rows, np.int32)
+        cons = np.ascontiguousarray(cons, np.int8)
+        assert cons.size >= nf * L and len(rows_a) == nf
+        mr = max(int(rows_a.max()) if nf else 0, 0)
+        if out is not None:
+            ends, idx, ins = out.ends, out.col_idx, out.col_ins
+            assert ends.dtype == ALN_END_DTYPE and ends.flags.c_contiguous and len(ends) >= npad
+            assert not columns or (idx.shape == ins.shape and idx.shape[0] >= mr and idx.shape[1] == npad and
+                                   idx.flags.c_contiguous and ins.flags.c_contiguous)
+        else:
+            ends = np.zeros(max(npad, 1), ALN_END_DTYPE)
+            ends["end_row"] = ends["end_idx"] = -1
+            idx = np.full((max(mr, 1), max(npad, 1)), ALN_NONE, np.int32) if columns else None
+            ins = np.zeros((max(mr, 1), max(npad, 1)), np.int32) if columns else None
+        ms = (C.c_double * 2)()
+        _lib.check(self._L.ramx_dev_align(self._h, arr, npad, first.ctypes.data, count.ctypes.data, nf, C.byref(cp),
+                                          cons.ctypes.data, rows_a.ctypes.data, ends.ctypes.data,
+                                          idx.ctypes.data if columns else None, ins.ctypes.data if columns else None, ms),
+                   "ramx_dev_align")
+        return AlignResult(ends, idx if columns else None, ins if columns else None, ms[0], ms[1])
 
     def peek_state(self, flank: int):
         B = 2 * self.p.bandwidth + 1

@@ -13,7 +13,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .datamodel import COL_PROFILE_DTYPE, CoreSet, ExtendParams, Profile
+from .datamodel import ALN_END_DTYPE, COL_PROFILE_DTYPE, FLANK_DTYPE, Alignment, CoreSet, ExtendParams, Profile
 
 
 @dataclass
@@ -75,10 +75,53 @@ class _ProfileSink:
         return False
 
 
+class _AlignSink:
+    """Collects what seam 1 hands to the alignment sink (ramx_set_align_sink) while the block runs."""
+
+    def __init__(self):
+        self.got = []
+
+        def _cb(ptr, _user):
+            al = ptr.contents
+            n, rows = al.n_flanks, al.rows
+
+            def grab(src, count, dtype):
+                out = np.zeros(count, dtype)
+                if count and src:
+                    C.memmove(out.ctypes.data, src, count * out.dtype.itemsize)
+                return out
+            idx = np.full((rows, n), -2 ** 31 + 1, np.int32)
+            ins = np.zeros((rows, n), np.int32)
+            if rows and n and al.col_idx:
+                full = grab(al.col_idx, (rows - 1) * al.stride + n, np.int32)
+                full_i = grab(al.col_ins, (rows - 1) * al.stride + n, np.int32)
+                for r in range(rows):
+                    idx[r] = full[r * al.stride:r * al.stride + n]
+                    ins[r] = full_i[r * al.stride:r * al.stride + n]
+            self.got.append(Alignment(al.direction, al.family, grab(al.cons, rows, np.int8), grab(al.flanks, n, FLANK_DTYPE),
+                                      grab(al.core_index, n, np.int32), grab(al.ends, n, ALN_END_DTYPE), idx, ins))
+        self._cb = _lib.ALIGN_CB(_cb)
+
+    def __enter__(self):
+        _lib.lib().ramx_set_align_sink(self._cb, None)
+        return self
+
+    def __exit__(self, *exc):
+        _lib.lib().ramx_set_align_sink(_lib.ALIGN_CB(), None)
+        return False
+
+
 def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, master: np.ndarray,
-                     p: ExtendParams, profile: bool = False):
+                     p: ExtendParams, profile: bool = False, align: bool = False):
     """direction: 1 = right, 0 = left (reference ram_extend.c:424,506).  profile=True: returns (RunInfo, Profile) -- the
-    direction is replayed along the consensus it chose (C-ABI ramx_dev_profile) after the loop."""
+    direction is replayed along the consensus it chose (C-ABI ramx_dev_profile) after the loop.  align=True: returns
+    (RunInfo, Alignment), or (RunInfo, Profile, Alignment) with both -- every flank aligned to the kept consensus (C-ABI
+    ramx_dev_align)."""
+    if align:
+        with _AlignSink() as asink:
+            res = extend_alignment(direction, cores, sequence, master, p, profile=profile)
+        assert len(asink.got) == 1
+        return (res + (asink.got[0],)) if profile else (res, asink.got[0])
     if profile:
         with _ProfileSink() as sink:
             info = extend_alignment(direction, cores, sequence, master, p)
@@ -98,10 +141,18 @@ def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, maste
     return _info(ci)
 
 
-def extend_batch(direction: int, families, p: ExtendParams, profile: bool = False):
+def extend_batch(direction: int, families, p: ExtendParams, profile: bool = False, align: bool = False):
     """Many families in one launch (C-ABI ramx_extend_batch).  `families` is a list of (cores, sequence, master);
     every family is updated in place exactly like extend_alignment does for one.  Returns one RunInfo per family;
-    profile=True: (RunInfos, Profiles), one Profile per family in the order of `families`."""
+    profile=True: (RunInfos, Profiles), one Profile per family in the order of `families`; align=True: (RunInfos,
+    Alignments), or (RunInfos, Profiles, Alignments) with both."""
+    if align:
+        with _AlignSink() as asink:
+            res = extend_batch(direction, families, p, profile=profile)
+        by_family = {al.family: al for al in asink.got}
+        assert len(by_family) == len(asink.got) == len(families)
+        als = [by_family[i] for i in range(len(families))]
+        return (res + (als,)) if profile else (res, als)
     if profile:
         with _ProfileSink() as sink:
             infos = extend_batch(direction, families, p)

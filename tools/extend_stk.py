@@ -9,7 +9,9 @@ wrapper's -onlyextend mode leaves (extend-stk.pl:391-427):
     <id>-linup.tsv  <id>-repam.log  <id>-repam-ranges.tsv  <id>-ext-cons.fa  <id>-repam-repseq.fa  <id>-combined-cons.fa
 
 and, with -profile, <id>-profile.tsv: the per-column support of both extensions (RAMExtend -outprofile) -- how many copies
-still carry the extension at every column, which the wrapper can only approximate through -minimprovement.
+still carry the extension at every column, which the wrapper can only approximate through -minimprovement; with -aln,
+<id>-aln.a2m: every extendable copy aligned to the kept consensus of both extensions (RAMExtend -outaln), which the wrapper
+rebuilds with an external aligner from -cons and -outfa (extend-stk.pl:553-556).
 
 (the re-alignment and Stockholm rewriting that follow in the wrapper belong to RepeatModeler and are out of scope).
 """
@@ -36,6 +38,7 @@ def main(argv=None):
     ap.add_argument("-L", type=int, default=20000)                      # extend-stk.pl:352
     ap.add_argument("-ramextend", default=DEFAULT_EXE)
     ap.add_argument("-profile", action="store_true", help="also write <id>-profile.tsv per family (RAMExtend -outprofile)")
+    ap.add_argument("-aln", action="store_true", help="also write <id>-aln.a2m per family (RAMExtend -outaln)")
     ap.add_argument("-one_by_one", action="store_true", help="start one RAMExtend per family, as the wrapper does")
     a = ap.parse_args(argv)
 
@@ -72,7 +75,8 @@ def main(argv=None):
                 with open(base + "-repam.log", "w") as log:
                     rc = subprocess.run([a.ramextend] + common + ["-ranges", base + "-linup.tsv", "-outtsv",
                                         base + "-repam-ranges.tsv", "-outfa", base + "-repam-repseq.fa", "-cons",
-                                        base + "-ext-cons.fa"] + (["-outprofile", base + "-profile.tsv"] if a.profile else []),
+                                        base + "-ext-cons.fa"] + (["-outprofile", base + "-profile.tsv"] if a.profile else []) +
+                                       (["-outaln", base + "-aln.a2m"] if a.aln else []),
                                        stdout=log, stderr=subprocess.STDOUT).returncode
                 if rc:
                     sys.exit(f"  RAMExtend failed! [{rc}] see {base}-repam.log")
@@ -82,7 +86,8 @@ def main(argv=None):
                 for seed, base in fams:
                     fh.write("\t".join([base + "-linup.tsv", base + "-repam.log", base + "-ext-cons.fa",
                                         base + "-repam-ranges.tsv", base + "-repam-repseq.fa"] +
-                                       ([base + "-profile.tsv"] if a.profile else [])) + "\n")
+                                       ([base + "-profile.tsv" if a.profile else "-"] if a.profile or a.aln else []) +
+                                       ([base + "-aln.a2m"] if a.aln else [])) + "\n")
             rc = subprocess.run([a.ramextend] + common + ["-batch", lst]).returncode
             if rc:
                 sys.exit(f"  RAMExtend -batch failed! [{rc}]")
