@@ -180,6 +180,23 @@ typedef struct ramx_alignment
 typedef void (*ramx_align_cb)(const ramx_alignment *al, void *user);
 void ramx_set_align_sink(ramx_align_cb cb, void *user);
 
+/* Refinement sink of seam 1, as the other sinks: with a sink set the kept consensus of every direction that has run -- rows =
+ * ret columns -- is piled up (ramx_dev_pileup, below) and refined over at most max_replays replays (ramx_dev_refine), and both
+ * are handed over once per direction and family: the kept consensus with its pileup, the refined one with its pileup (the
+ * same when replays == 1), replays and converged.  A direction without an extendable core or with ret = 0 is answered on the
+ * host.  cb == NULL (the default): off -- nothing is launched or allocated for it. */
+struct ramx_col_pileup;
+typedef struct ramx_refinement
+{
+  int32_t direction, family /* index in a batch, else 0 */, rows /* = ret */, refined_rows, replays, converged, n_flanks, pad_;
+  const int8_t *cons;                       /* [rows] */
+  const struct ramx_col_pileup *cols;       /* [rows] */
+  const int8_t *refined_cons;               /* [refined_rows] */
+  const struct ramx_col_pileup *refined_cols;
+} ramx_refinement;
+typedef void (*ramx_refine_cb)(const ramx_refinement *rf, void *user);
+void ramx_set_refine_sink(ramx_refine_cb cb, void *user, int32_t max_replays);
+
 /* Seam 1 keeps the library on the device between calls, keyed on (pointer, length, 64-bit content fingerprint), so
  * the second direction does not upload it again (libraries above 64 MiB are fingerprinted in chunks by worker threads; when
  * pointer and length match the device copy the content check runs beside the direction and is joined before the write-back).
@@ -365,6 +382,63 @@ int ramx_dev_align(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, cons
                    const int32_t *fam_count, int32_t n_families, const ramx_params *p,
                    const int8_t *cons, const int32_t *rows, ramx_aln_end *ends, int32_t *col_idx, int32_t *col_ins,
                    double *kernel_ms);
+
+/* Pileup of an extension: what the alignments of ramx_dev_align put into every column of a GIVEN consensus cons[0..rows).
+ * Everything is defined on each flank's ramx_aln_end, col_idx[r], col_ins[r] and the path order of its inserted bases.
+ *   Base class of flank position t: the code the alignment sees (complemented when compl is set); codes 0..3 are classes
+ *   0..3 (A C G T), lower-case codes 4..7 are code - 4, everything else is class 4 (N, a position outside the flank's bounds
+ *   t_lo..t_hi, a position outside the library).
+ *   The run "before column r" is col_ins[r] (for r = 0 the leading run); tail_ins belongs to no column and is counted
+ *   nowhere.  Padding flanks and flanks without an alignment contribute nothing.
+ * The struct is 128 bytes without padding. */
+#define RAMX_PILEUP_INS 4
+typedef struct ramx_col_pileup
+{
+  int32_t base;                         /* cons[r] */
+  int32_t cover;                        /* flanks with end_row >= r */
+  int32_t match[5];                     /* column r matched to a base of class A C G T N */
+  int32_t del;                          /* col_idx[r] == RAMX_ALN_DELETED */
+  int32_t ins_open;                     /* flanks of the cover with col_ins[r] > 0 */
+  int32_t ins_long;                     /* ... with col_ins[r] > RAMX_PILEUP_INS */
+  int64_t ins_bases;                    /* sum of col_ins[r] over the cover */
+  int32_t ins[RAMX_PILEUP_INS][5];      /* slot k: class of the k-th base, in path order (increasing t), of the run before column r */
+} ramx_col_pileup;
+
+/* The pileup on the device: ramx_dev_align's forward pass and walk, then one wave per tile counts its 64 flanks' columns and a
+ * second kernel adds the tiles of every family.  Flank layout, argument checks and self-containedness as ramx_dev_align.  cols
+ * is [n_families][L]: only the first rows[f] entries of a family are written.  ends is [n_padded] or NULL: what ramx_dev_align
+ * writes there.  The walked columns never exist for the whole flank set: they are held for one group of tiles at a time and
+ * count, with the group's decision codes, against RAMX_ALIGN_BYTES (rows * 64 * (4 * (W / 4 + 1) + 8) bytes per tile;
+ * RAMX_ERR_UNSUPPORTED if one tile alone does not fit); the grouping does not show in the result.  kernel_ms (may be NULL):
+ * three values, the HIP-event times of the forward kernels, of the walk kernels, and of the pileup kernels and the sum.  With a
+ * communicator or mailbox route active the call is rank-local and the counts add up across ranks. */
+int ramx_dev_pileup(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                    const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                    const int8_t *cons, const int32_t *rows, ramx_col_pileup *cols, ramx_aln_end *ends, double *kernel_ms);
+
+/* Re-call of a consensus from its pileup: one pass over the columns in order (plain host C).  Let c = cols[r].cover.
+ *   1. c == 0: the column is kept as it is, and nothing is inserted before it.
+ *   2. Inserted columns: for k = 0, 1, ... RAMX_PILEUP_INS - 1 let n_k = sum_b ins[k][b]; while 2 * n_k > c and some
+ *      ins[k][0..3] > 0, emit the plurality base of ins[k][0..3] (the lowest code wins ties, N is never a candidate); stop at
+ *      the first k that fails.
+ *   3. The column itself is dropped iff 2 * del > c.  Otherwise its base is the plurality of match[0..3]: the current base
+ *      if it is among the maxima or if all four counts are 0, else the lowest code among the maxima.
+ *   4. The output is cut to its first L columns.
+ * Exactly half is not a majority anywhere.  out holds L entries; returns the new length. */
+int32_t ramx_recall_consensus(const int8_t *cons, int32_t rows, const ramx_col_pileup *cols, int32_t L, int8_t *out);
+
+/* Refinement: cons_0 = cons_in; for i = 0, 1, ...: P_i = pileup(cons_i), cons_{i+1} = recall(cons_i, P_i).  If cons_{i+1} ==
+ * cons_i: converged = 1, the result is cons_i with P_i, replays = i + 1.  Else if i + 1 == max_replays: converged = 0, the
+ * result is cons_i with P_i (the last consensus that has a pileup), replays = i + 1.  Families proceed independently, and a
+ * converged family is not replayed again.  max_replays >= 1; 1 is "pileup only".  cons_in / cons_out are [n_families][L],
+ * rows_in / rows_out / replays / converged [n_families], cols [n_families][L] (the result's pileup), ends [n_padded] or NULL
+ * (the alignments along the result).  The library's windows are packed once per call.  kernel_ms as ramx_dev_pileup, summed
+ * over the replays.  RAMX_ERR_UNSUPPORTED with a communicator or mailbox route active: the re-call needs global counts. */
+int ramx_dev_refine(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                    const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                    const int8_t *cons_in, const int32_t *rows_in, int32_t max_replays,
+                    int8_t *cons_out, int32_t *rows_out, int32_t *replays, int32_t *converged,
+                    ramx_col_pileup *cols, ramx_aln_end *ends, double *kernel_ms);
 
 /* multi-GPU: flanks are sharded over ranks; each column's 4 candidate sums are all-reduced
  * (4 x int64, RCCL over xGMI).  unique_id is the 128-byte ncclUniqueId made by rank 0

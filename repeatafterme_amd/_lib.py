@@ -21,6 +21,7 @@ EXPORTS = [
     "ramx_print_core_edges", "ramx_allocate_score", "ramx_free_score", "ramx_cli_main",
     "ramx_dev_profile", "ramx_set_profile_sink",
     "ramx_dev_align", "ramx_set_align_sink",
+    "ramx_dev_pileup", "ramx_recall_consensus", "ramx_dev_refine", "ramx_set_refine_sink",
 ]
 
 
@@ -73,6 +74,14 @@ class AlignRec(C.Structure):        # ramx_alignment
 
 
 ALIGN_CB = C.CFUNCTYPE(None, C.POINTER(AlignRec), C.c_void_p)
+
+
+class RefineRec(C.Structure):       # ramx_refinement
+    _fields_ = [(k, C.c_int32) for k in ("direction", "family", "rows", "refined_rows", "replays", "converged", "n_flanks", "pad_")] + \
+               [(k, C.c_void_p) for k in ("cons", "cols", "refined_cons", "refined_cols")]
+
+
+REFINE_CB = C.CFUNCTYPE(None, C.POINTER(RefineRec), C.c_void_p)
 
 
 def build(force: bool = False) -> None:
@@ -133,6 +142,17 @@ def lib() -> C.CDLL:
         L.ramx_dev_align.restype = C.c_int
         L.ramx_set_align_sink.argtypes = [ALIGN_CB, C.c_void_p]
         L.ramx_set_align_sink.restype = None
+        L.ramx_dev_pileup.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Params),
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ramx_dev_pileup.restype = C.c_int
+        L.ramx_recall_consensus.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        L.ramx_recall_consensus.restype = C.c_int32
+        L.ramx_dev_refine.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Params),
+                                      C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ramx_dev_refine.restype = C.c_int
+        L.ramx_set_refine_sink.argtypes = [REFINE_CB, C.c_void_p, C.c_int32]
+        L.ramx_set_refine_sink.restype = None
         if hasattr(L, "ramx_cli_main"):
             L.ramx_cli_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
         _lib = L

@@ -241,7 +241,8 @@ static void warm_start(void)
 /* everything the command line decides */
 struct cli_opts
 {
-  const char *ranges_file, *outtsv, *outfa, *outmat, *cons_file, *seq_file, *matrix_name, *batch_file, *outprofile, *outaln;
+  const char *ranges_file, *outtsv, *outfa, *outmat, *cons_file, *seq_file, *matrix_name, *batch_file, *outprofile, *outaln, *outpileup, *outrefined;
+  int refine;
   int flanking, L, bandwidth, maxn, when_to_stop, num_threads, verbose;
   int gap_ext, gap_open, match, mismatch, cappenalty, minimprovement, is_rs;
   struct scoringSystem *sp;
@@ -464,7 +465,7 @@ static void write_results(const struct cli_opts *o, struct coreAlignment *cores,
  */
 struct batch_item
 {
-  char *ranges, *log, *cons, *tsv, *fa, *profile, *aln;
+  char *ranges, *log, *cons, *tsv, *fa, *profile, *aln, *pileup, *refined;
   struct coreAlignment *cores;
   struct sequenceLibrary *lib;
   int N, rightbp, leftbp;
@@ -648,6 +649,73 @@ static void aln_write(struct aln_family *af, struct coreAlignment *cores, int fl
   fclose(fp);
 }
 
+/*
+ * -outpileup <file>: the pileup of both extensions' kept consensus (include/ramx.h, ramx_col_pileup, ramx_set_refine_sink) as a
+ * TSV, one line per kept column, the right direction first.  -outrefined <file>: the kept consensus refined over at most
+ * -refine <n> replays (default 10) as FASTA, ">right-extension-refined <n> bp replays=<k> converged=<0|1>" and the left one,
+ * which reads as -cons writes it; nothing is wrapped.  With both files the pileup of a refined consensus that differs from the
+ * kept one follows the kept one's block as right-refined / left-refined lines.
+ */
+struct refine_family { const char *pileup, *refined; int have[2], rows[2], replays[2], converged[2]; char *seq[2]; };
+struct refine_out { struct refine_family *fam; };
+static const char k_pileup_header[] =
+  "dir\trow\tbase\tcover\tA\tC\tG\tT\tN\tdel\tins_open\tins_long\tins_bases"
+  "\ti0_A\ti0_C\ti0_G\ti0_T\ti0_N\ti1_A\ti1_C\ti1_G\ti1_T\ti1_N\ti2_A\ti2_C\ti2_G\ti2_T\ti2_N\ti3_A\ti3_C\ti3_G\ti3_T\ti3_N\n";
+static void pileup_start(const char *path)
+{
+  FILE *fp = fopen(path, "w");
+  if (!fp) { fprintf(stderr, "Could not create the pileup file %s\n", path); exit(1); }
+  fputs(k_pileup_header, fp);
+  fclose(fp);
+}
+static void pileup_block(FILE *fp, const char *tag, const ramx_col_pileup *cols, int rows)
+{
+  for (int r = 0; r < rows; r++)
+  {
+    const ramx_col_pileup *c = &cols[r];
+    fprintf(fp, "%s\t%d\t%c\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%lld", tag, r, code_to_char(c->base), c->cover, c->match[0], c->match[1],
+            c->match[2], c->match[3], c->match[4], c->del, c->ins_open, c->ins_long, (long long)c->ins_bases);
+    for (int k = 0; k < RAMX_PILEUP_INS; k++)
+      for (int b = 0; b < 5; b++) fprintf(fp, "\t%d", c->ins[k][b]);
+    fputc('\n', fp);
+  }
+}
+static void refine_sink(const ramx_refinement *rf, void *user)
+{
+  struct refine_family *f = &((const struct refine_out *)user)->fam[rf->family];
+  const int d = rf->direction ? 1 : 0;
+  if (f->pileup)
+  {
+    FILE *fp = fopen(f->pileup, "a");
+    if (!fp) { fprintf(stderr, "Could not append to the pileup file %s\n", f->pileup); exit(1); }
+    pileup_block(fp, d ? "right" : "left", rf->cols, rf->rows);
+    if (f->refined && rf->replays > 1) pileup_block(fp, d ? "right-refined" : "left-refined", rf->refined_cols, rf->refined_rows);
+    fclose(fp);
+  }
+  if (f->refined)
+  {
+    const int n = rf->refined_rows;
+    f->have[d] = 1; f->rows[d] = n; f->replays[d] = rf->replays; f->converged[d] = rf->converged;
+    f->seq[d] = (char *)malloc((size_t)n + 1);
+    for (int r = 0; r < n; r++) f->seq[d][r] = code_to_char(rf->refined_cons[d ? r : n - 1 - r]);
+    f->seq[d][n] = 0;
+  }
+}
+static void refined_write(struct refine_family *f)
+{
+  if (!f->refined) return;
+  FILE *fp = fopen(f->refined, "w");
+  if (!fp) { fprintf(stderr, "Could not create the refined consensus file %s\n", f->refined); exit(1); }
+  for (int d = 1; d >= 0; d--)
+  {
+    if (!f->have[d]) continue;
+    fprintf(fp, ">%s-extension-refined %d bp replays=%d converged=%d\n%s\n", d ? "right" : "left", f->rows[d], f->replays[d], f->converged[d], f->seq[d]);
+    free(f->seq[d]);
+    f->seq[d] = NULL; f->have[d] = 0;
+  }
+  fclose(fp);
+}
+
 /* flat view of a core list for ramx_extend_batch (arrays owned by the caller's arena) */
 static void flatten_cores(struct coreAlignment *cores, int N, ramx_flat_cores *fc)
 {
@@ -701,6 +769,8 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   if (o->outmat != NULL) { fprintf(stderr, "RAMExtend(ramx): -outmat traces one family; it cannot be combined with -batch\n"); exit(1); }
   if (o->outprofile != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's profile file is the sixth field of its line in the list\n"); exit(1); }
   if (o->outaln != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's alignment file is the seventh field of its line in the list\n"); exit(1); }
+  if (o->outpileup != NULL || o->outrefined != NULL)
+  { fprintf(stderr, "RAMExtend(ramx): with -batch every family's pileup file is the eighth field of its line in the list and its refined consensus the ninth\n"); exit(1); }
   FILE *lf = fopen(o->batch_file, "r");
   if (!lf) { fprintf(stderr, "Could not open batch list %s\n", o->batch_file); exit(1); }
   size_t cap = 64, F = 0;
@@ -712,9 +782,9 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   {
     while (len > 0 && (line[len - 1] == '\n' || line[len - 1] == '\r')) line[--len] = 0;
     if (line[0] == '#' || line[0] == 0) continue;
-    char *f[7] = { NULL, NULL, NULL, NULL, NULL, NULL, NULL };
+    char *f[9] = { NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL };
     char *p = line;
-    for (int k = 0; k < 7 && p; k++) { f[k] = p; char *t = strchr(p, '\t'); if (t) { *t = 0; p = t + 1; } else p = NULL; }
+    for (int k = 0; k < 9 && p; k++) { f[k] = p; char *t = strchr(p, '\t'); if (t) { *t = 0; p = t + 1; } else p = NULL; }
     if (!f[0] || !f[1]) { fprintf(stderr, "batch list: every line needs at least <ranges><TAB><log>\n"); exit(1); }
     if (F == cap) { cap *= 2; it = (struct batch_item *)realloc(it, cap * sizeof(*it)); memset(it + F, 0, (cap - F) * sizeof(*it)); }
     it[F].ranges = strdup(f[0]); it[F].log = strdup(f[1]);
@@ -723,6 +793,8 @@ static int run_batch(struct cli_opts *o, time_t t_start)
     it[F].fa = field_or_null(f[4]) ? strdup(f[4]) : NULL;
     it[F].profile = field_or_null(f[5]) ? strdup(f[5]) : NULL;       /* optional sixth field: the family's -outprofile file */
     it[F].aln = field_or_null(f[6]) ? strdup(f[6]) : NULL;           /* optional seventh field: the family's -outaln file */
+    it[F].pileup = field_or_null(f[7]) ? strdup(f[7]) : NULL;        /* optional eighth field: the family's -outpileup file */
+    it[F].refined = field_or_null(f[8]) ? strdup(f[8]) : NULL;       /* optional ninth field: the family's -outrefined file */
     F++;
   }
   free(line);
@@ -770,6 +842,14 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   for (size_t i = 0; i < F; i++)
     if ((aout.fam[i].path = it[i].aln) != NULL) { aout.fam[i].lib = it[i].lib; any_aln = 1; }
   if (any_aln) ramx_set_align_sink(aln_sink, &aout);
+  struct refine_out rout = { (struct refine_family *)calloc(F ? F : 1, sizeof(struct refine_family)) };
+  int any_pileup = 0, any_refined = 0;
+  for (size_t i = 0; i < F; i++)
+  {
+    if ((rout.fam[i].pileup = it[i].pileup) != NULL) { pileup_start(it[i].pileup); any_pileup = 1; }
+    if ((rout.fam[i].refined = it[i].refined) != NULL) any_refined = 1;
+  }
+  if (any_pileup || any_refined) ramx_set_refine_sink(refine_sink, &rout, any_refined ? o->refine : 1);
   /* phase 2: right extension of all families in one launch; phase 3: per family, overlap avoidance */
   for (size_t i = 0; i < F; i++) flatten_cores(it[i].cores, it[i].N, &fam[i].cores);
   if (ramx_extend_batch(1, fam, (int32_t)F, &p, ir) < 0) { fprintf(stderr, "RAMExtend(ramx): batch extension failed: %s\n", ramx_last_error()); exit(1); }
@@ -801,6 +881,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
     printf("Extended left : %d bp\n", it[i].leftbp);
     write_results(o, it[i].cores, it[i].lib, it[i].master, it[i].rightbp, it[i].leftbp, it[i].cons, it[i].tsv, it[i].fa);
     aln_write(&aout.fam[i], it[i].cores, o->flanking);
+    refined_write(&rout.fam[i]);
     const double duration = difftime(time(0), t_start);
     printf("Program duration is %.1f sec = %.1f min = %.1f hr\n", duration, duration / 60.0, duration / 3600.0);
   }
@@ -812,10 +893,12 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   {
     ramx_free_library(it[i].lib, it[i].cores);
     free(it[i].master); free(it[i].ranges); free(it[i].log); free(it[i].cons); free(it[i].tsv); free(it[i].fa); free(it[i].profile); free(it[i].aln);
+    free(it[i].pileup); free(it[i].refined);
   }
   ramx_set_profile_sink(NULL, NULL);
   ramx_set_align_sink(NULL, NULL);
-  free(aout.fam);
+  ramx_set_refine_sink(NULL, NULL, 1);
+  free(aout.fam); free(rout.fam);
   free(profile_paths);
   free(it); free(fam); free(ir); free(il); free(mflat);
   ramx_free_scoring_system(o->sp);
@@ -845,6 +928,10 @@ int ramx_cli_main(int argc, char **argv)
   opt_string(argc, argv, "-cons", &o.cons_file);
   opt_string(argc, argv, "-outprofile", &o.outprofile);
   opt_string(argc, argv, "-outaln", &o.outaln);
+  opt_string(argc, argv, "-outpileup", &o.outpileup);
+  opt_string(argc, argv, "-outrefined", &o.outrefined);
+  if (!opt_int(argc, argv, "-refine", &o.refine)) o.refine = 10;
+  if (o.refine < 1) { fprintf(stderr, "RAMExtend(ramx): -refine takes the largest number of replays, at least 1\n"); exit(1); }
   if (!opt_int(argc, argv, "-L", &o.L)) o.L = 10000;
   if (!opt_int(argc, argv, "-bandwidth", &o.bandwidth)) o.bandwidth = 14;
   if (!opt_int(argc, argv, "-maxoccurrences", &o.maxn)) o.maxn = 10000;
@@ -938,6 +1025,12 @@ int ramx_cli_main(int argc, char **argv)
   afam.path = o.outaln; afam.lib = lib;
   struct aln_out aout = { &afam };
   if (o.outaln != NULL) ramx_set_align_sink(aln_sink, &aout);
+  struct refine_family rfam;
+  memset(&rfam, 0, sizeof(rfam));
+  rfam.pileup = o.outpileup; rfam.refined = o.outrefined;
+  struct refine_out rout = { &rfam };
+  if (o.outpileup != NULL) pileup_start(o.outpileup);
+  if (o.outpileup != NULL || o.outrefined != NULL) ramx_set_refine_sink(refine_sink, &rout, o.outrefined != NULL ? o.refine : 1);
   fflush(stdout);
   warm_join();
   phase_done("device ready");
@@ -951,8 +1044,10 @@ int ramx_cli_main(int argc, char **argv)
   phase_done("extend left");
   ramx_set_profile_sink(NULL, NULL);
   ramx_set_align_sink(NULL, NULL);
+  ramx_set_refine_sink(NULL, NULL, 1);
   write_results(&o, cores, lib, master, rightbp, leftbp, o.cons_file, o.outtsv, o.outfa);
   aln_write(&afam, cores, o.flanking);
+  refined_write(&rfam);
   if (fp_mat != NULL) fclose(fp_mat);     /* ram_extend.c:778-779 */
   phase_done("report + outputs");
 

@@ -52,6 +52,7 @@
 #include "ramx_pk_api.h"
 #include "ramx_profile_api.h"
 #include "ramx_align_api.h"
+#include "ramx_pileup_api.h"
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
@@ -156,6 +157,9 @@ struct ramx_dev
   // ramx_dev_align (allocated on its first call; rows, consensus and tables are the profile replay's): decision codes, per-flank records, per-column outputs
   unsigned *d_al_codes; ramx_aln_end *d_al_ends; int *d_al_idx, *d_al_ins;
   size_t cap_al_codes, cap_al_ends, cap_al_idx, cap_al_ins;
+  // ramx_dev_pileup / ramx_dev_refine (allocated on their first call): one group's walked columns, per-tile records, summed columns, family table
+  int *d_pl_idx, *d_pl_ins; ramx_col_pileup *d_pl_slab, *d_pl_cols; int4 *d_pl_fam;
+  size_t cap_pl_idx, cap_pl_ins, cap_pl_slab, cap_pl_cols, cap_pl_fam;
 };
 
 extern "C" int ramx_device_count(void)
@@ -241,6 +245,7 @@ extern "C" void ramx_dev_destroy(ramx_dev *d)
   (void)hipFree(d->d_pf_state); (void)hipFree(d->d_pf_slab); (void)hipFree(d->d_pf_cols); (void)hipFree(d->d_pf_cons); (void)hipFree(d->d_pf_rows);
   (void)hipFree(d->d_pf_fam); (void)hipFree(d->d_pf_tile); (void)hipFree(d->d_pf_last); (void)hipFree(d->d_pf_best); (void)hipFree(d->d_pf_bidx);
   (void)hipFree(d->d_al_codes); (void)hipFree(d->d_al_ends); (void)hipFree(d->d_al_idx); (void)hipFree(d->d_al_ins);
+  (void)hipFree(d->d_pl_idx); (void)hipFree(d->d_pl_ins); (void)hipFree(d->d_pl_slab); (void)hipFree(d->d_pl_cols); (void)hipFree(d->d_pl_fam);
   if (d->hostbox_mirror) (void)hipFree(d->hostbox_mirror);
   if (d->d_peer) (void)hipFree(d->d_peer);
   for (int i = 0; i < 2; i++) if (d->ev_chk[i]) (void)hipEventDestroy(d->ev_chk[i]);
@@ -1807,6 +1812,290 @@ extern "C" int ramx_dev_align(ramx_dev *d, const ramx_flank *flanks, int32_t n_p
       HIPCHK(hipMemcpy2D(col_ins + (size_t)t0 * 64, (size_t)n_padded * sizeof(int), d->d_al_ins + (size_t)t0 * 64, (size_t)Np * sizeof(int),
                          (size_t)nt * 64 * sizeof(int), (size_t)maxrows, hipMemcpyDeviceToHost));
     }
+  }
+  return RAMX_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// pileup and consensus refinement: ramx_dev_align's forward pass and walk group after group, the group's columns counted on the
+// device next to the walk (ramx_kernels_pileup.h); the re-call is host C (ramx_recall.c)
+// ------------------------------------------------------------------------------------------
+struct PileupPlan
+{
+  int tiles, maxrows;
+  std::vector<int2> tile_fam;
+  std::vector<int4> fam_desc;
+};
+
+// argument checks of ramx_dev_align, and the tile / family tables of the families with run[f] != 0 (run == NULL: all)
+static int pileup_plan(const char *who, int32_t n_padded, const int32_t *fam_first, const int32_t *fam_count, int32_t n_families,
+                       int L, const int8_t *cons, const int32_t *rows, const char *run, bool check, PileupPlan &pl)
+{
+  pl.tiles = n_padded / 64;
+  pl.maxrows = 0;
+  pl.tile_fam.assign((size_t)(pl.tiles > 0 ? pl.tiles : 1), make_int2(-1, 0));
+  pl.fam_desc.assign((size_t)(n_families > 0 ? n_families : 1), make_int4(0, 0, 0, 0));
+  for (int f = 0; f < n_families; f++)
+  {
+    if (check)
+    {
+      if (fam_count[f] < 0 || fam_first[f] < 0 || (fam_first[f] & 63) || (long long)fam_first[f] + fam_count[f] > n_padded)
+      { ramx_set_error("%s: bad family layout", who); return RAMX_ERR_ARG; }
+      if (rows[f] < 0 || rows[f] > L) { ramx_set_error("%s: rows[%d] = %d outside [0, L = %d]", who, f, rows[f], L); return RAMX_ERR_ARG; }
+      if (rows[f] > 0 && !cons) { ramx_set_error("%s: cons missing", who); return RAMX_ERR_ARG; }
+      for (int r = 0; r < rows[f]; r++)
+        if (cons[(size_t)f * L + r] < 0 || cons[(size_t)f * L + r] > 3) { ramx_set_error("%s: consensus base outside A C G T (family %d, column %d)", who, f, r); return RAMX_ERR_ARG; }
+    }
+    const int t0 = fam_first[f] / 64, nt = (fam_count[f] + 63) / 64;
+    if (check)
+      for (int t = 0; t < nt; t++)
+      {
+        if (pl.tile_fam[t0 + t].x >= 0) { ramx_set_error("%s: families %d and %d overlap", who, pl.tile_fam[t0 + t].x, f); return RAMX_ERR_ARG; }
+        pl.tile_fam[t0 + t].x = f;
+      }
+    if (run && !run[f]) continue;
+    for (int t = 0; t < nt; t++)
+    {
+      const int left = fam_count[f] - 64 * t;
+      pl.tile_fam[t0 + t] = make_int2(f, left < 64 ? left : 64);
+    }
+    pl.fam_desc[f] = make_int4(t0, nt, rows[f], 0);
+    if (rows[f] > pl.maxrows) pl.maxrows = rows[f];
+  }
+  if (check && run)       // the overlap check marked every family's tiles: those that do not run belong to none
+    for (int f = 0; f < n_families; f++)
+      if (!run[f])
+        for (int t = 0; t < (fam_count[f] + 63) / 64; t++) pl.tile_fam[fam_first[f] / 64 + t] = make_int2(-1, 0);
+  return RAMX_OK;
+}
+
+// once per call: the flanks uploaded, their windows packed, the tables that do not depend on the consensus
+static int pileup_setup(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, int32_t n_families, const ramx_params *p, AlnArgs &aa, int *KW_out)
+{
+  HIPCHK(hipSetDevice(d->ordinal));
+  const int W = p->bandwidth, L = p->L, Q = W + 1, Np = n_padded, tiles = n_padded / 64;
+  const int KW = (L + 2 * W + 2) / 8 + 12;
+  int rc;
+  if (d->pack_busy) { HIPCHK(hipEventSynchronize(d->pack_done)); d->pack_busy = 0; }      // see ramx_dev_profile
+  if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)Np * sizeof(ramx_flank)))) return rc;
+  if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)KW * Np * sizeof(unsigned)))) return rc;
+  if ((rc = ensure(&d->d_bounds, &d->cap_bounds, (size_t)Np * sizeof(int2)))) return rc;
+  if ((rc = ensure(&d->d_pf_state, &d->cap_pf_state, (size_t)Np * Q * sizeof(int4)))) return rc;
+  if ((rc = ensure(&d->d_pf_cons, &d->cap_pf_cons, (size_t)n_families * L + 16))) return rc;
+  if ((rc = ensure(&d->d_pf_rows, &d->cap_pf_rows, (size_t)n_families * sizeof(int)))) return rc;
+  if ((rc = ensure(&d->d_pf_tile, &d->cap_pf_tile, (size_t)tiles * sizeof(int2)))) return rc;
+  if ((rc = ensure(&d->d_pl_fam, &d->cap_pl_fam, (size_t)n_families * sizeof(int4)))) return rc;
+  if ((rc = ensure(&d->d_pl_cols, &d->cap_pl_cols, (size_t)n_families * L * sizeof(ramx_col_pileup)))) return rc;
+  if ((rc = ensure(&d->d_al_ends, &d->cap_al_ends, (size_t)Np * sizeof(ramx_aln_end)))) return rc;
+  HIPCHK(hipMemcpyAsync(d->d_flanks, flanks, (size_t)n_padded * sizeof(ramx_flank), hipMemcpyHostToDevice, d->stream));
+  if ((rc = launch_pack(d, n_padded, Np, W, 0, KW, d->stream)) != RAMX_OK) return rc;
+  d->packed_kw = KW;
+  d->ready = 0;       // the direction's flank and window buffers were reused: begin_direction must be called again before run_direction
+  memset(&aa, 0, sizeof(aa));
+  aa.k.bases = d->d_bases; aa.k.bounds = d->d_bounds; aa.k.S_in = d->d_pf_state; aa.k.S_out = d->d_pf_state;
+  aa.k.Np = Np; aa.k.Nx = Np; aa.k.W = W; aa.k.go = p->gapopen; aa.k.ge = p->gapextn; aa.k.cap = p->cappenalty;
+  for (int c = 0; c < RAMX_NCLASS; c++)
+  {
+    const int code = (c == 8) ? RAMX_SYM_N : c;
+    for (int k = 0; k < 4; k++) aa.k.tab[c][k] = p->matrix[k * 100 + code];
+  }
+  aa.tile_fam = d->d_pf_tile; aa.cons = d->d_pf_cons; aa.rows = d->d_pf_rows; aa.ends = d->d_al_ends;
+  aa.L = L; aa.nd = ramx_align_dwords(W);
+  *KW_out = KW;
+  return RAMX_OK;
+}
+
+// one replay of the plan's families along cons / rows: forward, walk and pileup per group of tiles, then the sum; on return
+// the stream is idle, d_pl_cols holds the families' columns and d_al_ends their flanks' records.  pl.tiles > 0, pl.maxrows > 0.
+static int pileup_replay(ramx_dev *d, const char *who, AlnArgs aa, int KW, const PileupPlan &pl, int32_t n_families,
+                         const int8_t *cons, const int32_t *rows, double *kernel_ms)
+{
+  const int tiles = pl.tiles, maxrows = pl.maxrows, L = aa.L, W = aa.k.W, nd = aa.nd;
+  size_t budget = (size_t)1 << 30;
+  if (const char *e = getenv("RAMX_ALIGN_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+  // per tile: the decision codes and the walked columns (col_idx, col_ins) of its 64 flanks
+  const size_t code_bytes = (size_t)maxrows * nd * 64 * sizeof(unsigned), col_bytes = (size_t)maxrows * 64 * sizeof(int);
+  const size_t tile_bytes = code_bytes + 2 * col_bytes;
+  if (tile_bytes > budget)
+  {
+    ramx_set_error("%s: the decision codes and columns of one tile of 64 flanks (%d rows, bandwidth %d: %zu bytes) do not fit RAMX_ALIGN_BYTES = %zu",
+                   who, maxrows, W, tile_bytes, budget);
+    return RAMX_ERR_UNSUPPORTED;
+  }
+  const int group = (int)(budget / tile_bytes < (size_t)tiles ? budget / tile_bytes : (size_t)tiles);
+  int rc;
+  if ((rc = ensure(&d->d_al_codes, &d->cap_al_codes, (size_t)group * code_bytes))) return rc;
+  if ((rc = ensure(&d->d_pl_idx, &d->cap_pl_idx, (size_t)group * col_bytes))) return rc;
+  if ((rc = ensure(&d->d_pl_ins, &d->cap_pl_ins, (size_t)group * col_bytes))) return rc;
+  if ((rc = ensure(&d->d_pl_slab, &d->cap_pl_slab, (size_t)tiles * maxrows * sizeof(ramx_col_pileup)))) return rc;
+  HIPCHK(hipMemcpyAsync(d->d_pf_cons, cons, (size_t)n_families * L, hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemcpyAsync(d->d_pf_rows, rows, (size_t)n_families * sizeof(int), hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemcpyAsync(d->d_pf_tile, pl.tile_fam.data(), (size_t)tiles * sizeof(int2), hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemcpyAsync(d->d_pl_fam, pl.fam_desc.data(), (size_t)n_families * sizeof(int4), hipMemcpyHostToDevice, d->stream));
+  const int gn = group * 64;
+  aa.codes = d->d_al_codes; aa.gn = gn;
+  PileArgs pa;
+  pa.bases = d->d_bases; pa.tile_fam = d->d_pf_tile; pa.cons = d->d_pf_cons; pa.rows = d->d_pf_rows; pa.ends = d->d_al_ends;
+  pa.col_idx = d->d_pl_idx; pa.col_ins = d->d_pl_ins; pa.slab = d->d_pl_slab;
+  pa.L = L; pa.Np = aa.k.Np; pa.W = W; pa.KW = KW; pa.gn = gn; pa.slab_rows = maxrows;
+  PileSumArgs sa;
+  sa.slab = d->d_pl_slab; sa.fam = d->d_pl_fam; sa.cons = d->d_pf_cons; sa.cols = d->d_pl_cols; sa.L = L; sa.slab_rows = maxrows;
+  // group after group on one stream: a group's pileup has read its columns, and its walk its codes, before the next group's
+  // kernels write them
+  const int ngroups = (tiles + group - 1) / group;
+  std::vector<hipEvent_t> ev((size_t)4 * ngroups + 1, (hipEvent_t)NULL);
+  if (kernel_ms) for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+  rc = RAMX_OK;
+  for (int g = 0; g < ngroups && rc == RAMX_OK; g++)
+  {
+    const int tile0 = g * group, nt = tiles - tile0 < group ? tiles - tile0 : group;
+    aa.tile0 = pa.tile0 = tile0;
+    // the walk addresses its columns as [r * k.Np + n] with n the flank's index in the whole set: given the group's width for
+    // k.Np and the arrays' origin moved back by the group's first flank, it writes the group's own [maxrows][gn] arrays
+    AlnArgs aw = aa;
+    aw.k.Np = gn;
+    aw.col_idx = d->d_pl_idx - (ptrdiff_t)tile0 * 64; aw.col_ins = d->d_pl_ins - (ptrdiff_t)tile0 * 64;
+    if (kernel_ms) HIPCHK(hipEventRecord(ev[4 * g], d->stream));
+    if ((rc = ramx_align_launch_forward(d->stream, nt, aa)) != RAMX_OK) break;
+    if (kernel_ms) HIPCHK(hipEventRecord(ev[4 * g + 1], d->stream));
+    if ((rc = ramx_align_launch_preset(d->stream, d->d_pl_idx, d->d_pl_ins, (size_t)maxrows * gn)) != RAMX_OK) break;
+    if ((rc = ramx_align_launch_walk(d->stream, nt, aw)) != RAMX_OK) break;
+    if (kernel_ms) HIPCHK(hipEventRecord(ev[4 * g + 2], d->stream));
+    if ((rc = ramx_pileup_launch(d->stream, nt, pa)) != RAMX_OK) break;
+    if (kernel_ms) HIPCHK(hipEventRecord(ev[4 * g + 3], d->stream));
+  }
+  if (rc == RAMX_OK) rc = ramx_pileup_launch_sum(d->stream, n_families, maxrows, sa);
+  if (rc == RAMX_OK && kernel_ms) HIPCHK(hipEventRecord(ev[4 * ngroups], d->stream));
+  if (rc != RAMX_OK) ramx_set_error("%s: launch failed (%s)", who, hipGetErrorString(hipGetLastError()));
+  const hipError_t se = hipStreamSynchronize(d->stream);
+  if (kernel_ms)
+  {
+    for (int g = 0; g < ngroups && rc == RAMX_OK && se == hipSuccess; g++)
+    {
+      float a = 0, b = 0, c = 0;
+      (void)hipEventElapsedTime(&a, ev[4 * g], ev[4 * g + 1]);
+      (void)hipEventElapsedTime(&b, ev[4 * g + 1], ev[4 * g + 2]);
+      (void)hipEventElapsedTime(&c, ev[4 * g + 2], ev[4 * g + 3]);
+      kernel_ms[0] += a; kernel_ms[1] += b; kernel_ms[2] += c;
+    }
+    if (rc == RAMX_OK && se == hipSuccess)
+    {
+      float c = 0;
+      (void)hipEventElapsedTime(&c, ev[4 * ngroups - 1], ev[4 * ngroups]);
+      kernel_ms[2] += c;
+    }
+    for (auto &e : ev) (void)hipEventDestroy(e);
+  }
+  if (rc != RAMX_OK) return rc;
+  HIPCHK(se);
+  return RAMX_OK;
+}
+
+// the columns and flank records of the families with run[f] != 0 (NULL: all) after a replay, or answered here where nothing ran
+static int pileup_fetch(ramx_dev *d, bool ran, int32_t n_padded, const int32_t *fam_first, const int32_t *fam_count, int32_t n_families,
+                        int L, const int8_t *cons, const int32_t *rows, const char *run, ramx_col_pileup *cols, ramx_aln_end *ends)
+{
+  const ramx_aln_end none = { -1, -1, 0, 0, 0 };
+  for (int f = 0; f < n_families; f++)
+  {
+    if (run && !run[f]) continue;
+    const int t0 = fam_first[f] / 64, nt = (fam_count[f] + 63) / 64;
+    if (rows[f] > 0)
+    {
+      ramx_col_pileup *c = cols + (size_t)f * L;
+      if (ran) HIPCHK(hipMemcpy(c, d->d_pl_cols + (size_t)f * L, (size_t)rows[f] * sizeof(ramx_col_pileup), hipMemcpyDeviceToHost));
+      else
+      {
+        memset(c, 0, (size_t)rows[f] * sizeof(ramx_col_pileup));
+        for (int r = 0; r < rows[f]; r++) c[r].base = cons[(size_t)f * L + r];
+      }
+    }
+    if (!ends || nt == 0) continue;
+    if (!ran || rows[f] == 0) for (int i = t0 * 64; i < (t0 + nt) * 64; i++) ends[i] = none;
+    else HIPCHK(hipMemcpy(ends + (size_t)t0 * 64, d->d_al_ends + (size_t)t0 * 64, (size_t)nt * 64 * sizeof(ramx_aln_end), hipMemcpyDeviceToHost));
+  }
+  return RAMX_OK;
+}
+
+extern "C" int ramx_dev_pileup(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                               const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                               const int8_t *cons, const int32_t *rows, ramx_col_pileup *cols, ramx_aln_end *ends, double *kernel_ms)
+{
+  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0;
+  if (!d || !p || !p->matrix || n_families < 0 || n_padded < 0 || (n_padded & 63) || (n_padded && !flanks) ||
+      (n_families && (!fam_first || !fam_count || !rows)))
+  { ramx_set_error("ramx_dev_pileup: bad argument"); return RAMX_ERR_ARG; }
+  if (p->bandwidth < 1 || p->L < 0) { ramx_set_error("ramx_dev_pileup: bad bandwidth / L"); return RAMX_ERR_ARG; }
+  PileupPlan pl;
+  int rc;
+  if ((rc = pileup_plan("ramx_dev_pileup", n_padded, fam_first, fam_count, n_families, p->L, cons, rows, NULL, true, pl)) != RAMX_OK) return rc;
+  if (pl.maxrows > 0 && !cols) { ramx_set_error("ramx_dev_pileup: cols missing"); return RAMX_ERR_ARG; }
+  const bool run = n_families > 0 && pl.maxrows > 0 && pl.tiles > 0;
+  if (run)
+  {
+    AlnArgs aa;
+    int KW = 0;
+    if ((rc = pileup_setup(d, flanks, n_padded, n_families, p, aa, &KW)) != RAMX_OK) return rc;
+    if ((rc = pileup_replay(d, "ramx_dev_pileup", aa, KW, pl, n_families, cons, rows, kernel_ms)) != RAMX_OK) return rc;
+  }
+  return pileup_fetch(d, run, n_padded, fam_first, fam_count, n_families, p->L, cons, rows, NULL, cols, ends);
+}
+
+extern "C" int ramx_dev_refine(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                               const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                               const int8_t *cons_in, const int32_t *rows_in, int32_t max_replays,
+                               int8_t *cons_out, int32_t *rows_out, int32_t *replays, int32_t *converged,
+                               ramx_col_pileup *cols, ramx_aln_end *ends, double *kernel_ms)
+{
+  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0;
+  if (!d || !p || !p->matrix || n_families < 0 || n_padded < 0 || (n_padded & 63) || (n_padded && !flanks) ||
+      (n_families && (!fam_first || !fam_count || !rows_in || !rows_out || !replays || !converged)) || max_replays < 1)
+  { ramx_set_error("ramx_dev_refine: bad argument"); return RAMX_ERR_ARG; }
+  if (p->bandwidth < 1 || p->L < 0) { ramx_set_error("ramx_dev_refine: bad bandwidth / L"); return RAMX_ERR_ARG; }
+  if (dev_is_multi(d))
+  { ramx_set_error("ramx_dev_refine: not with a communicator or mailbox route active (the re-call needs the counts of every rank)"); return RAMX_ERR_UNSUPPORTED; }
+  const int L = p->L;
+  PileupPlan pl;
+  int rc;
+  if ((rc = pileup_plan("ramx_dev_refine", n_padded, fam_first, fam_count, n_families, L, cons_in, rows_in, NULL, true, pl)) != RAMX_OK) return rc;
+  if (pl.maxrows > 0 && (!cols || !cons_out)) { ramx_set_error("ramx_dev_refine: cons_out / cols missing"); return RAMX_ERR_ARG; }
+  std::vector<int8_t> cur((size_t)(n_families > 0 ? n_families : 1) * (L > 0 ? L : 1), 0), next((size_t)(L > 0 ? L : 1));
+  std::vector<int32_t> rows(rows_in, rows_in + n_families);
+  std::vector<char> active((size_t)n_families, 1);
+  for (int f = 0; f < n_families; f++)
+  {
+    if (rows[f] > 0) memcpy(cur.data() + (size_t)f * L, cons_in + (size_t)f * L, (size_t)rows[f]);
+    replays[f] = 0; converged[f] = 0;
+  }
+  AlnArgs aa;
+  int KW = 0, left = n_families;
+  bool set_up = false;
+  for (int it = 0; it < max_replays && left > 0; it++)
+  {
+    if ((rc = pileup_plan("ramx_dev_refine", n_padded, fam_first, fam_count, n_families, L, cur.data(), rows.data(), active.data(), false, pl)) != RAMX_OK) return rc;
+    const bool run = pl.maxrows > 0 && pl.tiles > 0;
+    if (run)
+    {
+      if (!set_up && (rc = pileup_setup(d, flanks, n_padded, n_families, p, aa, &KW)) != RAMX_OK) return rc;
+      set_up = true;
+      if ((rc = pileup_replay(d, "ramx_dev_refine", aa, KW, pl, n_families, cur.data(), rows.data(), kernel_ms)) != RAMX_OK) return rc;
+    }
+    if ((rc = pileup_fetch(d, run, n_padded, fam_first, fam_count, n_families, L, cur.data(), rows.data(), active.data(), cols, ends)) != RAMX_OK) return rc;
+    for (int f = 0; f < n_families; f++)
+    {
+      if (!active[f]) continue;
+      int8_t *c = cur.data() + (size_t)f * L;
+      const int32_t n = ramx_recall_consensus(c, rows[f], cols + (size_t)f * L, L, next.data());
+      replays[f] = it + 1;
+      if (n == rows[f] && (n == 0 || memcmp(c, next.data(), (size_t)n) == 0)) { converged[f] = 1; active[f] = 0; left--; }
+      else if (it + 1 == max_replays) { active[f] = 0; left--; }
+      else { memcpy(c, next.data(), (size_t)n); rows[f] = n; }
+    }
+  }
+  for (int f = 0; f < n_families; f++)
+  {
+    rows_out[f] = rows[f];
+    if (rows[f] > 0) memcpy(cons_out + (size_t)f * L, cur.data() + (size_t)f * L, (size_t)rows[f]);
   }
   return RAMX_OK;
 }

@@ -432,6 +432,63 @@ int ramx_resolve_flanks(int direction, const ramx_flat_cores *c, int bandwidth, 
   return nx;
 }
 
+static ramx_refine_cb g_refine_cb = NULL;
+static void *g_refine_user = NULL;
+static int g_refine_replays = 10;
+void ramx_set_refine_sink(ramx_refine_cb cb, void *user, int32_t max_replays)
+{
+  g_refine_cb = cb;
+  g_refine_user = user;
+  g_refine_replays = max_replays >= 1 ? max_replays : 1;
+}
+
+/* With a refinement sink set: the pileup of nb families' kept consensus (rows = ret) and their refinement, handed over family
+ * by family.  The refinement's first replay IS the kept consensus' pileup: only when some family's consensus moved is the kept
+ * one piled up in a call of its own.  fl is laid out in tiles (npad flanks); cons is [nb][L]. */
+static int refine_families(ramx_dev *d, int direction, const int *fidx, int nb, const ramx_flank *fl, int32_t npad,
+                           const int32_t *first, const int32_t *count, const ramx_params *p, const int8_t *cons, const int32_t *ret)
+{
+  const size_t L = (size_t)(p->L > 0 ? p->L : 1);
+  int32_t *nrows = (int32_t *)calloc((size_t)(nb > 0 ? nb : 1) * 4, sizeof(int32_t)), *rrows = nrows + nb, *replays = rrows + nb, *conv = replays + nb;
+  ramx_col_pileup *kept = (ramx_col_pileup *)calloc((size_t)nb * L, sizeof(ramx_col_pileup));
+  ramx_col_pileup *refd = (ramx_col_pileup *)calloc((size_t)nb * L, sizeof(ramx_col_pileup));
+  int8_t *rcons = (int8_t *)calloc((size_t)nb * L, 1);
+  int moved = 0;
+  for (int b = 0; b < nb; b++) nrows[b] = ret[b] > 0 ? ret[b] : 0;
+  int rc = ramx_dev_refine(d, fl, npad, first, count, nb, p, cons, nrows, g_refine_replays, rcons, rrows, replays, conv, refd, NULL, NULL);
+  for (int b = 0; b < nb && rc == RAMX_OK; b++) moved |= replays[b] > 1;
+  if (rc == RAMX_OK && moved) rc = ramx_dev_pileup(d, fl, npad, first, count, nb, p, cons, nrows, kept, NULL, NULL);
+  for (int b = 0; b < nb && rc == RAMX_OK; b++)
+  {
+    ramx_refinement rf;
+    memset(&rf, 0, sizeof(rf));
+    rf.direction = direction; rf.family = fidx ? fidx[b] : 0; rf.rows = nrows[b]; rf.refined_rows = rrows[b];
+    rf.replays = replays[b]; rf.converged = conv[b]; rf.n_flanks = count[b];
+    rf.cons = cons + (size_t)b * p->L; rf.cols = (moved ? kept : refd) + (size_t)b * p->L;
+    rf.refined_cons = rcons + (size_t)b * p->L; rf.refined_cols = refd + (size_t)b * p->L;
+    g_refine_cb(&rf, g_refine_user);
+  }
+  free(nrows); free(kept); free(refd); free(rcons);
+  return rc;
+}
+
+/* one direction of one family: its flanks padded to whole tiles (no extendable core or ret = 0: answered by the calls on the host) */
+static int refine_direction(ramx_dev *d, int direction, int family, const ramx_flank *fl, int nx, const ramx_params *p,
+                            const int8_t *cons, int ret)
+{
+  const int npad = (nx + 63) & ~63;
+  ramx_flank *pf = (ramx_flank *)malloc(sizeof(ramx_flank) * (size_t)(npad > 0 ? npad : 1));
+  if (nx > 0) memcpy(pf, fl, sizeof(ramx_flank) * (size_t)nx);
+  for (int i = nx; i < npad; i++) { memset(&pf[i], 0, sizeof(ramx_flank)); pf[i].t_lo = 1; pf[i].t_hi = 0; pf[i].step = 1; }
+  const int32_t first = 0, count = nx, r = ret;
+  /* cons holds at least L entries only in the batch; here it is the direction's own buffer, copied into an [1][L] block */
+  int8_t *c1 = (int8_t *)calloc((size_t)(p->L > 0 ? p->L : 1), 1);
+  if (ret > 0) memcpy(c1, cons, (size_t)ret);
+  const int rc = refine_families(d, direction, &family, 1, pf, npad, &first, &count, p, c1, &r);
+  free(pf); free(c1);
+  return rc;
+}
+
 /* With a profile sink set: replay one direction of one family along the consensus the loop chose and hand it over. */
 static int profile_direction(ramx_dev *d, int direction, int family, const ramx_flank *fl, const int32_t *map, int nx,
                              const ramx_params *p, const int8_t *cons, int rows, int ret)
@@ -691,6 +748,11 @@ run_again:
   {
     rc = align_direction(d, direction, family, fl, map, nx, p, cons, info->ret);
     SEAM1_PHASE("alignment replay");
+  }
+  if (rc == RAMX_OK && g_refine_cb != NULL)
+  {
+    rc = refine_direction(d, direction, family, fl, nx, p, cons, info->ret);
+    SEAM1_PHASE("pileup + refinement");
   }
 #undef SEAM1_PHASE
 #undef FP_JOIN
@@ -1007,6 +1069,14 @@ int ramx_extend_batch(int direction, ramx_family *fam, int32_t F, const ramx_par
       }
       free(nrows); free(ends); free(idx); free(ins);
       BATCH_PHASE("alignment replay");
+    }
+    if (rc == RAMX_OK && g_refine_cb != NULL)
+    {
+      int32_t *rets = (int32_t *)malloc(sizeof(int32_t) * (size_t)nb);
+      for (int b = 0; b < nb; b++) rets[b] = binfo[b].ret;
+      rc = refine_families(d, direction, fidx, nb, fl, (int32_t)fpos, first, count, p, cons, rets);
+      free(rets);
+      BATCH_PHASE("pileup + refinement");
     }
     free(binfo); free(cons); free(th); free(tp);
     BATCH_PHASE("write-back");

@@ -125,6 +125,27 @@ class Alignment:
     col_ins: np.ndarray              # int32 [rows][n_flanks]: bases inserted before the column's move
 
 
+# one column of a pileup: C-ABI ramx_col_pileup (include/ramx.h), 128 bytes
+PILEUP_INS = 4                   # RAMX_PILEUP_INS: inserted-base slots kept per column
+PILEUP_DTYPE = np.dtype([("base", np.int32), ("cover", np.int32), ("match", np.int32, (5,)), ("del", np.int32),
+                         ("ins_open", np.int32), ("ins_long", np.int32), ("ins_bases", np.int64),
+                         ("ins", np.int32, (PILEUP_INS, 5))], align=True)
+assert PILEUP_DTYPE.itemsize == 128 and PILEUP_DTYPE.fields["ins_bases"][1] == 40
+
+
+@dataclass
+class Refinement:
+    """Pileup and refinement of one direction of one family (C-ABI ramx_refinement / ramx_dev_pileup / ramx_dev_refine)."""
+    direction: int
+    family: int                      # index in a batch, else 0
+    cons: np.ndarray                 # int8 [ret]: the kept consensus
+    cols: np.ndarray                 # PILEUP_DTYPE [ret]: its pileup
+    refined_cons: np.ndarray         # int8 [refined rows]
+    refined_cols: np.ndarray         # PILEUP_DTYPE [refined rows]
+    replays: int
+    converged: int
+
+
 FLANK_DTYPE = np.dtype([("start", np.int64), ("t_lo", np.int32), ("t_hi", np.int32), ("step", np.int8), ("compl_", np.int8),
                         ("pad_", np.int8, (6,))])
 assert FLANK_DTYPE.itemsize == 24

@@ -10,7 +10,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .datamodel import ALN_END_DTYPE, ALN_NONE, COL_PROFILE_DTYPE, CoreSet, ExtendParams
+from .datamodel import ALN_END_DTYPE, ALN_NONE, COL_PROFILE_DTYPE, PILEUP_DTYPE, CoreSet, ExtendParams
 from .extend import RunInfo, _info, _params
 
 
@@ -42,6 +42,38 @@ class AlignResult:
     col_ins: Optional[np.ndarray]
     forward_ms: float                      # HIP-event time of the forward kernels
     walk_ms: float                         # ... and of the walk kernels
+
+
+@dataclass
+class PileupResult:
+    cols: np.ndarray                       # PILEUP_DTYPE [n_families][L]; only rows[f] entries per family are written
+    ends: np.ndarray                       # ALN_END_DTYPE [n_padded]
+    forward_ms: float                      # HIP-event times of the forward kernels, the walk kernels, the pileup kernels + sum
+    walk_ms: float
+    pileup_ms: float
+
+
+@dataclass
+class RefineResult:
+    cons: np.ndarray                       # int8 [n_families][L]: the refined consensus, rows[f] entries per family
+    rows: np.ndarray                       # int32 [n_families]
+    replays: np.ndarray                    # int32 [n_families]
+    converged: np.ndarray                  # int32 [n_families]
+    cols: np.ndarray                       # PILEUP_DTYPE [n_families][L]: the pileup of `cons`
+    ends: np.ndarray                       # ALN_END_DTYPE [n_padded]: the alignments along `cons`
+    forward_ms: float                      # summed over the replays
+    walk_ms: float
+    pileup_ms: float
+
+
+def recall_consensus(cons, cols, L: int) -> np.ndarray:
+    """Re-call a consensus from its pileup (C-ABI ramx_recall_consensus, host C): -> the new consensus, at most L columns."""
+    c = np.ascontiguousarray(cons, np.int8)
+    cols = np.ascontiguousarray(cols, PILEUP_DTYPE)
+    assert len(cols) >= len(c)
+    out = np.zeros(max(L, 1), np.int8)
+    n = _lib.lib().ramx_recall_consensus(c.ctypes.data, len(c), cols.ctypes.data, int(L), out.ctypes.data)
+    return out[:n].copy()
 
 
 def pad_flanks(flanks):
@@ -183,6 +215,64 @@ class Device:
                                           idx.ctypes.data if columns else None, ins.ctypes.data if columns else None, ms),
                    "ramx_dev_align")
         return AlignResult(ends, idx if columns else None, ins if columns else None, ms[0], ms[1])
+
+    def _families(self, flanks, p, cons, rows, fam_first, fam_count):
+        """The argument forms of profile() -> (flank array, n_padded, first, count, cons [nf][L], rows)."""
+        L = p.L
+        if fam_first is None:
+            n = flanks[1]
+            arr, npad = pad_flanks(flanks)
+            fam_first, fam_count = [0], [n]
+            c1 = np.asarray(cons, np.int8).ravel()
+            rows = [len(c1) if rows is None else int(rows)]
+            cons = np.zeros((1, max(L, 1)), np.int8)
+            cons[0, :min(len(c1), L)] = c1[:L]
+        else:
+            arr, npad = flanks
+        nf = len(fam_first)
+        first = np.ascontiguousarray(fam_first, np.int32)
+        count = np.ascontiguousarray(fam_count, np.int32)
+        rows_a = np.ascontiguousarray(rows, np.int32)
+        cons = np.ascontiguousarray(cons, np.int8)
+        assert cons.size >= nf * L and len(rows_a) == nf
+        return arr, npad, first, count, cons, rows_a
+
+    @staticmethod
+    def _no_ends(npad):
+        ends = np.zeros(max(npad, 1), ALN_END_DTYPE)
+        ends["end_row"] = ends["end_idx"] = -1
+        return ends
+
+    def pileup(self, flanks, p: ExtendParams, cons, rows=None, fam_first=None, fam_count=None) -> PileupResult:
+        """Pileup of every family along a given consensus (C-ABI ramx_dev_pileup): arguments as profile()."""
+        cp, keep = _params(p)
+        arr, npad, first, count, cons, rows_a = self._families(flanks, p, cons, rows, fam_first, fam_count)
+        nf = len(first)
+        cols = np.zeros((nf, max(p.L, 1)), PILEUP_DTYPE)
+        ends = self._no_ends(npad)
+        ms = (C.c_double * 3)()
+        _lib.check(self._L.ramx_dev_pileup(self._h, arr, npad, first.ctypes.data, count.ctypes.data, nf, C.byref(cp),
+                                           cons.ctypes.data, rows_a.ctypes.data, cols.ctypes.data, ends.ctypes.data, ms),
+                   "ramx_dev_pileup")
+        return PileupResult(cols, ends, ms[0], ms[1], ms[2])
+
+    def refine(self, flanks, p: ExtendParams, cons, rows=None, fam_first=None, fam_count=None,
+               max_replays: int = 10) -> RefineResult:
+        """Replay -> re-call -> replay until the consensus is stable or max_replays replays have run (C-ABI ramx_dev_refine):
+        arguments as profile()."""
+        cp, keep = _params(p)
+        arr, npad, first, count, cons, rows_a = self._families(flanks, p, cons, rows, fam_first, fam_count)
+        nf = len(first)
+        out = np.zeros((nf, max(p.L, 1)), np.int8)
+        rows_out, replays, conv = (np.zeros(max(nf, 1), np.int32) for _ in range(3))
+        cols = np.zeros((nf, max(p.L, 1)), PILEUP_DTYPE)
+        ends = self._no_ends(npad)
+        ms = (C.c_double * 3)()
+        _lib.check(self._L.ramx_dev_refine(self._h, arr, npad, first.ctypes.data, count.ctypes.data, nf, C.byref(cp),
+                                           cons.ctypes.data, rows_a.ctypes.data, int(max_replays), out.ctypes.data,
+                                           rows_out.ctypes.data, replays.ctypes.data, conv.ctypes.data, cols.ctypes.data,
+                                           ends.ctypes.data, ms), "ramx_dev_refine")
+        return RefineResult(out, rows_out[:nf], replays[:nf], conv[:nf], cols, ends, ms[0], ms[1], ms[2])
 
     def peek_state(self, flank: int):
         B = 2 * self.p.bandwidth + 1

@@ -13,7 +13,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .datamodel import ALN_END_DTYPE, COL_PROFILE_DTYPE, FLANK_DTYPE, Alignment, CoreSet, ExtendParams, Profile
+from .datamodel import (ALN_END_DTYPE, COL_PROFILE_DTYPE, FLANK_DTYPE, PILEUP_DTYPE, Alignment, CoreSet, ExtendParams, Profile,
+                        Refinement)
 
 
 @dataclass
@@ -111,12 +112,47 @@ class _AlignSink:
         return False
 
 
+class _RefineSink:
+    """Collects what seam 1 hands to the refinement sink (ramx_set_refine_sink) while the block runs."""
+
+    def __init__(self, max_replays):
+        self.got = []
+        self.max_replays = int(max_replays)
+
+        def _cb(ptr, _user):
+            rf = ptr.contents
+
+            def grab(src, count, dtype):
+                out = np.zeros(count, dtype)
+                if count and src:
+                    C.memmove(out.ctypes.data, src, count * out.dtype.itemsize)
+                return out
+            self.got.append(Refinement(rf.direction, rf.family, grab(rf.cons, rf.rows, np.int8), grab(rf.cols, rf.rows, PILEUP_DTYPE),
+                                       grab(rf.refined_cons, rf.refined_rows, np.int8),
+                                       grab(rf.refined_cols, rf.refined_rows, PILEUP_DTYPE), rf.replays, rf.converged))
+        self._cb = _lib.REFINE_CB(_cb)
+
+    def __enter__(self):
+        _lib.lib().ramx_set_refine_sink(self._cb, None, self.max_replays)
+        return self
+
+    def __exit__(self, *exc):
+        _lib.lib().ramx_set_refine_sink(_lib.REFINE_CB(), None, 1)
+        return False
+
+
 def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, master: np.ndarray,
-                     p: ExtendParams, profile: bool = False, align: bool = False):
+                     p: ExtendParams, profile: bool = False, align: bool = False, refine: int = 0):
     """direction: 1 = right, 0 = left (reference ram_extend.c:424,506).  profile=True: returns (RunInfo, Profile) -- the
     direction is replayed along the consensus it chose (C-ABI ramx_dev_profile) after the loop.  align=True: returns
     (RunInfo, Alignment), or (RunInfo, Profile, Alignment) with both -- every flank aligned to the kept consensus (C-ABI
-    ramx_dev_align)."""
+    ramx_dev_align).  refine=n > 0: a Refinement comes last in the tuple -- the kept consensus' pileup and its refinement over at
+    most n replays (C-ABI ramx_dev_pileup / ramx_dev_refine)."""
+    if refine:
+        with _RefineSink(refine) as rsink:
+            res = extend_alignment(direction, cores, sequence, master, p, profile=profile, align=align)
+        assert len(rsink.got) == 1
+        return (res + (rsink.got[0],)) if isinstance(res, tuple) else (res, rsink.got[0])
     if align:
         with _AlignSink() as asink:
             res = extend_alignment(direction, cores, sequence, master, p, profile=profile)

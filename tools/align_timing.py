@@ -74,7 +74,9 @@ def _measure(name, W, call_profile, call_align, loop_ms, rows_total, repeats, pr
     os.environ.pop("RAMX_ALIGN_BYTES", None)
 
 
-def big(repeats, profile_only, n=100000, L=2000, W=40):
+def big(repeats, profile_only, n=100000, L=2000, W=40, measure=None):
+    """measure (tools/pileup_timing.py): called as measure(name, W, dev, flanks, p, cons, kw, loop_ms, rows_total, repeats) in place
+    of the measurements of this tool"""
     t0 = time.time()
     fs = synth_family(n, L, W, K=1500, seed=1)
     p = named_params("14p43g", bandwidth=W, L=L, when_to_stop=L)
@@ -91,12 +93,16 @@ def big(repeats, profile_only, n=100000, L=2000, W=40):
     print(f"big: loop (persistent={loops[-1].persistent}, packed rows {loops[-1].packed_rows}) {best:9.2f} ms, {rows} rows", flush=True)
     cons = _fixed_rows(cons, rows, L)
     tiles = (flanks[1] + 63) // 64
+    if measure is not None:
+        measure("big", W, dev, flanks, p, cons, dict(rows=L), best, tiles * L, repeats)
+        dev.close()
+        return
     _measure("big", W, lambda: dev.profile(flanks, p, cons, rows=L), None if profile_only else lambda: dev.align(flanks, p, cons, rows=L, columns=False),
              best, tiles * L, repeats, profile_only)
     dev.close()
 
 
-def batch(name, W, repeats, profile_only, F=500, L=1000):
+def batch(name, W, repeats, profile_only, F=500, L=1000, measure=None):
     t0 = time.time()
     p = named_params("20p43g", bandwidth=W, L=L)
     fams = [synth_family(int(60 + (i * 37) % 90), L, W, K=300 + (i * 53) % 500, seed=1000 + i) for i in range(F)]
@@ -130,6 +136,10 @@ def batch(name, W, repeats, profile_only, F=500, L=1000):
     dev = Device(0)
     dev.load_library(lib)
     kw = dict(rows=rows, fam_first=first, fam_count=count)
+    if measure is not None:
+        measure(name, W, dev, (arr, at), p, cons, kw, best, (at // 64) * L, repeats)
+        dev.close()
+        return
     _measure(name, W, lambda: dev.profile((arr, at), p, cons, **kw), None if profile_only else lambda: dev.align((arr, at), p, cons, columns=False, **kw),
              best, (at // 64) * L, repeats, profile_only)
     dev.close()

@@ -11,7 +11,9 @@ wrapper's -onlyextend mode leaves (extend-stk.pl:391-427):
 and, with -profile, <id>-profile.tsv: the per-column support of both extensions (RAMExtend -outprofile) -- how many copies
 still carry the extension at every column, which the wrapper can only approximate through -minimprovement; with -aln,
 <id>-aln.a2m: every extendable copy aligned to the kept consensus of both extensions (RAMExtend -outaln), which the wrapper
-rebuilds with an external aligner from -cons and -outfa (extend-stk.pl:553-556).
+rebuilds with an external aligner from -cons and -outfa (extend-stk.pl:553-556); with --refine N, <id>-pileup.tsv and
+<id>-refined-cons.fa: the per-column composition of both extensions and their consensus re-called from it over at most N
+replays (RAMExtend -outpileup / -outrefined / -refine), the wrapper's `alignAndCallConsensus.pl -refine 10` step (:553-555).
 
 (the re-alignment and Stockholm rewriting that follow in the wrapper belong to RepeatModeler and are out of scope).
 """
@@ -39,6 +41,8 @@ def main(argv=None):
     ap.add_argument("-ramextend", default=DEFAULT_EXE)
     ap.add_argument("-profile", action="store_true", help="also write <id>-profile.tsv per family (RAMExtend -outprofile)")
     ap.add_argument("-aln", action="store_true", help="also write <id>-aln.a2m per family (RAMExtend -outaln)")
+    ap.add_argument("--refine", type=int, default=0, metavar="N",
+                    help="also write <id>-pileup.tsv and <id>-refined-cons.fa per family (RAMExtend -outpileup / -outrefined / -refine N)")
     ap.add_argument("-one_by_one", action="store_true", help="start one RAMExtend per family, as the wrapper does")
     a = ap.parse_args(argv)
 
@@ -76,7 +80,9 @@ def main(argv=None):
                     rc = subprocess.run([a.ramextend] + common + ["-ranges", base + "-linup.tsv", "-outtsv",
                                         base + "-repam-ranges.tsv", "-outfa", base + "-repam-repseq.fa", "-cons",
                                         base + "-ext-cons.fa"] + (["-outprofile", base + "-profile.tsv"] if a.profile else []) +
-                                       (["-outaln", base + "-aln.a2m"] if a.aln else []),
+                                       (["-outaln", base + "-aln.a2m"] if a.aln else []) +
+                                       (["-outpileup", base + "-pileup.tsv", "-outrefined", base + "-refined-cons.fa", "-refine",
+                                         str(a.refine)] if a.refine > 0 else []),
                                        stdout=log, stderr=subprocess.STDOUT).returncode
                 if rc:
                     sys.exit(f"  RAMExtend failed! [{rc}] see {base}-repam.log")
@@ -86,9 +92,10 @@ def main(argv=None):
                 for seed, base in fams:
                     fh.write("\t".join([base + "-linup.tsv", base + "-repam.log", base + "-ext-cons.fa",
                                         base + "-repam-ranges.tsv", base + "-repam-repseq.fa"] +
-                                       ([base + "-profile.tsv" if a.profile else "-"] if a.profile or a.aln else []) +
-                                       ([base + "-aln.a2m"] if a.aln else [])) + "\n")
-            rc = subprocess.run([a.ramextend] + common + ["-batch", lst]).returncode
+                                       ([base + "-profile.tsv" if a.profile else "-"] if a.profile or a.aln or a.refine > 0 else []) +
+                                       ([base + "-aln.a2m" if a.aln else "-"] if a.aln or a.refine > 0 else []) +
+                                       ([base + "-pileup.tsv", base + "-refined-cons.fa"] if a.refine > 0 else [])) + "\n")
+            rc = subprocess.run([a.ramextend] + common + (["-refine", str(a.refine)] if a.refine > 0 else []) + ["-batch", lst]).returncode
             if rc:
                 sys.exit(f"  RAMExtend -batch failed! [{rc}]")
         for seed, base in fams:                                         # extend-stk.pl:397-417
