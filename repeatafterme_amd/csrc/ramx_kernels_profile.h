@@ -250,8 +250,12 @@ __global__ __launch_bounds__(64, (W > 40 ? 1 : 2)) void ramx_profile_resident_ke
       const int n_new = __popcll(__ballot(new_high)), n_out = __popcll(__ballot(out));
       if (pa.row_best != nullptr)
       {
-        pa.row_best[(size_t)r * a.Np + n] = D.bestF;
-        pa.row_best_idx[(size_t)r * a.Np + n] = r + D.jbest - W;
+        // a row that lies behind the flank's last base altogether (every fill is the sentinel from row W on, bnw_extend.c:990-1002):
+        // the reference's best cell is the row's first, holding the sentinel.  prk_band_fast ranks such cells below every score
+        // by their keys and keeps no value for them (its bestF is then INT_MIN >> 4, its jbest 15), so the row is answered here
+        const bool behind = r >= W && jhi < 0;
+        pa.row_best[(size_t)r * a.Np + n] = behind ? SENT : D.bestF;
+        pa.row_best_idx[(size_t)r * a.Np + n] = behind ? r - W : r + D.jbest - W;
       }
       prof_store_record(slab + r, lane, tot, besta, n_cap, n_new, n_out);
     }

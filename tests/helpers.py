@@ -57,6 +57,19 @@ def oracle_extend(direction, cores, sequence, master, p):
     return po.oracle_extend(direction, cores, sequence, master, p)
 
 
+def ragged_family(n, L, W, K, seed, clip=True):
+    """synth_family gives every copy the same length K; clipping every window to 40..L bases beyond its core (drawn per copy
+    from `seed`) makes the copies end at different columns of a long extension.  -> (FlankSet, its cores or the clipped ones)"""
+    from repeatafterme_amd.synth import synth_family
+    fs = synth_family(n, L, W, K=K, seed=seed, both_sides=True, minus_frac=0.4, n_run_frac=0.1)
+    cores = fs.cores.copy()
+    if clip:
+        q = np.random.default_rng(seed).integers(40, L + 1, cores.n)
+        cores.upper = np.minimum(cores.upper, cores.right_pos + q)
+        cores.lower = np.maximum(cores.lower, cores.left_pos - q)
+    return fs, cores
+
+
 def make_genome(seed: int):
     """A few contigs, each with several diverged copies of one family (cores 3-25 bp), both strands,
     some copies close together / at contig ends, N runs, mixed extendable flags."""
