@@ -150,16 +150,18 @@ struct ramx_dev
   int last_packed_r0;  // last direction: first row of the packed-row kernel, -1 if it did not run
   int cp_flanks_ok;    // begin_direction: every flank is empty or has t_lo <= 0 (what the cell-parallel kernels take)
   int2 *d_cpstate; size_t cap_cpstate; int cpstate_W, cpstate_n;   // RAMX_CP_PEEK=1: final rows of the cell-parallel kernel (tests)
-  // ramx_dev_profile (allocated on its first call): rows, per-wave records, summed columns, consensus / rows / family / tile tables, per-flank outputs
-  int4 *d_pf_state; ramx_col_profile *d_pf_slab, *d_pf_cols; signed char *d_pf_cons; int *d_pf_rows; int4 *d_pf_fam; int2 *d_pf_tile;
-  int *d_pf_last, *d_pf_best, *d_pf_bidx;
-  size_t cap_pf_state, cap_pf_slab, cap_pf_cols, cap_pf_cons, cap_pf_rows, cap_pf_fam, cap_pf_tile, cap_pf_last, cap_pf_best, cap_pf_bidx;
-  // ramx_dev_align (allocated on its first call; rows, consensus and tables are the profile replay's): decision codes, per-flank records, per-column outputs
+  // every replay along a given consensus (replay_setup, allocated on the first call): rows, consensus / rows / family / tile tables
+  int4 *d_rp_state; signed char *d_rp_cons; int *d_rp_rows; int4 *d_rp_fam; int2 *d_rp_tile;
+  size_t cap_rp_state, cap_rp_cons, cap_rp_rows, cap_rp_fam, cap_rp_tile;
+  // ramx_dev_profile (allocated on its first call): per-wave records, summed columns, per-flank outputs
+  ramx_col_profile *d_pf_slab, *d_pf_cols; int *d_pf_last, *d_pf_best, *d_pf_bidx;
+  size_t cap_pf_slab, cap_pf_cols, cap_pf_last, cap_pf_best, cap_pf_bidx;
+  // ramx_dev_align (allocated on its first call): decision codes, per-flank records (both also the pileup's), per-column outputs
   unsigned *d_al_codes; ramx_aln_end *d_al_ends; int *d_al_idx, *d_al_ins;
   size_t cap_al_codes, cap_al_ends, cap_al_idx, cap_al_ins;
-  // ramx_dev_pileup / ramx_dev_refine (allocated on their first call): one group's walked columns, per-tile records, summed columns, family table
-  int *d_pl_idx, *d_pl_ins; ramx_col_pileup *d_pl_slab, *d_pl_cols; int4 *d_pl_fam;
-  size_t cap_pl_idx, cap_pl_ins, cap_pl_slab, cap_pl_cols, cap_pl_fam;
+  // ramx_dev_pileup / ramx_dev_refine (allocated on their first call): one group's walked columns, per-tile records, summed columns
+  int *d_pl_idx, *d_pl_ins; ramx_col_pileup *d_pl_slab, *d_pl_cols;
+  size_t cap_pl_idx, cap_pl_ins, cap_pl_slab, cap_pl_cols;
 };
 
 extern "C" int ramx_device_count(void)
@@ -242,10 +244,10 @@ extern "C" void ramx_dev_destroy(ramx_dev *d)
   }
   if (d->devbox) (void)hipFree(d->devbox);
   (void)hipFree(d->d_fam); (void)hipFree(d->d_famctl); (void)hipFree(d->d_cpstate); (void)hipFree(d->d_dbg_codes); (void)hipFree(d->d_dbg_best); (void)hipFree(d->d_dbg_cand); (void)hipFree(d->d_dbg_gap); (void)hipFree(d->d_dbg_band); (void)hipFree(d->d_devdesc); (void)hipFree(d->d_vote_sets); (void)hipFree(d->d_err_sets);
-  (void)hipFree(d->d_pf_state); (void)hipFree(d->d_pf_slab); (void)hipFree(d->d_pf_cols); (void)hipFree(d->d_pf_cons); (void)hipFree(d->d_pf_rows);
-  (void)hipFree(d->d_pf_fam); (void)hipFree(d->d_pf_tile); (void)hipFree(d->d_pf_last); (void)hipFree(d->d_pf_best); (void)hipFree(d->d_pf_bidx);
+  (void)hipFree(d->d_rp_state); (void)hipFree(d->d_rp_cons); (void)hipFree(d->d_rp_rows); (void)hipFree(d->d_rp_fam); (void)hipFree(d->d_rp_tile);
+  (void)hipFree(d->d_pf_slab); (void)hipFree(d->d_pf_cols); (void)hipFree(d->d_pf_last); (void)hipFree(d->d_pf_best); (void)hipFree(d->d_pf_bidx);
   (void)hipFree(d->d_al_codes); (void)hipFree(d->d_al_ends); (void)hipFree(d->d_al_idx); (void)hipFree(d->d_al_ins);
-  (void)hipFree(d->d_pl_idx); (void)hipFree(d->d_pl_ins); (void)hipFree(d->d_pl_slab); (void)hipFree(d->d_pl_cols); (void)hipFree(d->d_pl_fam);
+  (void)hipFree(d->d_pl_idx); (void)hipFree(d->d_pl_ins); (void)hipFree(d->d_pl_slab); (void)hipFree(d->d_pl_cols);
   if (d->hostbox_mirror) (void)hipFree(d->hostbox_mirror);
   if (d->d_peer) (void)hipFree(d->d_peer);
   for (int i = 0; i < 2; i++) if (d->ev_chk[i]) (void)hipEventDestroy(d->ev_chk[i]);
@@ -311,6 +313,19 @@ extern "C" int ramx_dev_load_library_packed(ramx_dev *d, const struct ramx_packe
 
 // flank descriptors (already on the device) -> transposed, pre-oriented 4-bit windows + bounds, from either kind of library:
 // words [k_lo, k_hi) of every flank's window, on stream `st`
+// class table: tab[class][cand] = matrix[cand][code(class)], reference index order [cons][seq]
+static void class_tab(const ramx_params *p, int (&tab)[RAMX_NCLASS][4])
+{
+  for (int c = 0; c < RAMX_NCLASS; c++)
+  {
+    const int code = (c == 8) ? RAMX_SYM_N : c;
+    for (int k = 0; k < 4; k++) tab[c][k] = p->matrix[k * 100 + code];
+  }
+}
+
+// words of a packed window: t'' = o + r + W + 8 runs over [7, L + 2W + 9]; + pad word in front, + lookahead words read by the kernels
+static int window_words(int L, int W) { return (L + 2 * W + 2) / 8 + 12; }
+
 static int launch_pack(ramx_dev *d, int Nx, int Np, int W, int k_lo, int k_hi, hipStream_t st)
 {
   if (k_hi <= k_lo) return RAMX_OK;
@@ -382,15 +397,9 @@ extern "C" int ramx_dev_begin_direction(ramx_dev *d, const ramx_flank *flanks, i
   const int W = p->bandwidth, Q = W + 1;
   const int Nx = n_flanks;
   const int Np = ((Nx + 63) / 64) * 64 > 0 ? ((Nx + 63) / 64) * 64 : 64;
-  // t'' = o + r + W + 8 runs over [7, L + 2W + 9]
-  const int KW = (p->L + 2 * W + 2) / 8 + 12;  // + pad word in front, + lookahead words read by the kernels
+  const int KW = window_words(p->L, W);
   d->Nx = Nx; d->Np = Np; d->KW = KW; d->p = *p;
-  // class table: tab[class][cand] = matrix[cand][code(class)], reference index order [cons][seq]
-  for (int c = 0; c < RAMX_NCLASS; c++)
-  {
-    const int code = (c == 8) ? RAMX_SYM_N : c;
-    for (int k = 0; k < 4; k++) d->tab[c][k] = p->matrix[k * 100 + code];
-  }
+  class_tab(p, d->tab);
   int rc;
   if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)Np * sizeof(ramx_flank)))) return rc;
   if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)KW * Np * sizeof(unsigned)))) return rc;
@@ -1127,7 +1136,7 @@ static int run_families_pass(ramx_dev *d, const ramx_flank *flanks, int32_t n_pa
   if (maxn > 512) { ramx_set_error("batch mode: a family has more than 512 flanks"); return RAMX_ERR_UNSUPPORTED; }
   if (n_families == 0) return RAMX_OK;
   const int Np = n_padded > 0 ? n_padded : 64;
-  const int KW = (L + 2 * W + 2) / 8 + 12;
+  const int KW = window_words(L, W);
   int rc;
   if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)Np * sizeof(ramx_flank)))) return rc;
   if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)KW * Np * sizeof(unsigned)))) return rc;
@@ -1140,11 +1149,7 @@ static int run_families_pass(ramx_dev *d, const ramx_flank *flanks, int32_t n_pa
   // masked band's carry argument needs the out-of-bounds prefix to end at or before the band centre).  Groups
   // RAMX_CP_NCLASS ..: one lane per flank, by workgroup shape (64, 128, 256, 512 threads = 1, 2, 4, 8 tiles).
   int tab9[RAMX_NCLASS][4];
-  for (int c = 0; c < RAMX_NCLASS; c++)
-  {
-    const int code = (c == 8) ? RAMX_SYM_N : c;
-    for (int k = 0; k < 4; k++) tab9[c][k] = p->matrix[k * 100 + code];
-  }
+  class_tab(p, tab9);
   const int cp_max = d->force_chain ? 0 : ramx_cp_max_family(W, p->gapopen, p->gapextn, tab9, L);
   FamDesc *hfd = (FamDesc *)malloc(sizeof(FamDesc) * n_families);
   int *grp = (int *)malloc(sizeof(int) * n_families);
@@ -1539,297 +1544,19 @@ extern "C" int ramx_dev_run_families(ramx_dev *d, const ramx_flank *flanks, int3
 }
 
 // ------------------------------------------------------------------------------------------
-// support profile: every flank's band replayed along a given consensus (ramx_kernels_profile.h)
+// replays along a given consensus: what ramx_dev_profile, ramx_dev_align, ramx_dev_pileup and ramx_dev_refine share on the host
 // ------------------------------------------------------------------------------------------
-extern "C" int ramx_dev_profile(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
-                                const int32_t *fam_count, int32_t n_families, const ramx_params *p,
-                                const int8_t *cons, const int32_t *rows, ramx_col_profile *cols, int32_t *last_uncapped_row,
-                                int32_t *row_best, int32_t *row_best_idx, double *kernel_ms)
-{
-  if (kernel_ms) *kernel_ms = 0;
-  if (!d || !p || !p->matrix || n_families < 0 || n_padded < 0 || (n_padded & 63) || (n_padded && !flanks) ||
-      (n_families && (!fam_first || !fam_count || !rows)))
-  { ramx_set_error("ramx_dev_profile: bad argument"); return RAMX_ERR_ARG; }
-  if ((row_best == NULL) != (row_best_idx == NULL)) { ramx_set_error("ramx_dev_profile: row_best and row_best_idx go together"); return RAMX_ERR_ARG; }
-  const int W = p->bandwidth, L = p->L, Q = W + 1;
-  if (W < 1 || L < 0) { ramx_set_error("ramx_dev_profile: bad bandwidth / L"); return RAMX_ERR_ARG; }
-  const int tiles = n_padded / 64;
-  std::vector<int2> tile_fam((size_t)(tiles > 0 ? tiles : 1), make_int2(-1, 0));
-  std::vector<int4> fam_desc((size_t)(n_families > 0 ? n_families : 1));
-  int maxrows = 0;
-  for (int f = 0; f < n_families; f++)
-  {
-    if (fam_count[f] < 0 || fam_first[f] < 0 || (fam_first[f] & 63) || (long long)fam_first[f] + fam_count[f] > n_padded)
-    { ramx_set_error("ramx_dev_profile: bad family layout"); return RAMX_ERR_ARG; }
-    if (rows[f] < 0 || rows[f] > L) { ramx_set_error("ramx_dev_profile: rows[%d] = %d outside [0, L = %d]", f, rows[f], L); return RAMX_ERR_ARG; }
-    if (rows[f] > 0 && (!cons || !cols)) { ramx_set_error("ramx_dev_profile: cons / cols missing"); return RAMX_ERR_ARG; }
-    for (int r = 0; r < rows[f]; r++)
-      if (cons[(size_t)f * L + r] < 0 || cons[(size_t)f * L + r] > 3) { ramx_set_error("ramx_dev_profile: consensus base outside A C G T (family %d, column %d)", f, r); return RAMX_ERR_ARG; }
-    const int t0 = fam_first[f] / 64, nt = (fam_count[f] + 63) / 64;
-    for (int t = 0; t < nt; t++)
-    {
-      if (tile_fam[t0 + t].x >= 0) { ramx_set_error("ramx_dev_profile: families %d and %d overlap", tile_fam[t0 + t].x, f); return RAMX_ERR_ARG; }
-      const int left = fam_count[f] - 64 * t;
-      tile_fam[t0 + t] = make_int2(f, left < 64 ? left : 64);
-    }
-    fam_desc[f] = make_int4(t0, nt, rows[f], 0);
-    if (rows[f] > maxrows) maxrows = rows[f];
-  }
-  if (last_uncapped_row) for (int i = 0; i < n_padded; i++) last_uncapped_row[i] = -1;
-  if (n_families == 0 || maxrows == 0) return RAMX_OK;
-  HIPCHK(hipSetDevice(d->ordinal));
-  const int Np = n_padded > 0 ? n_padded : 64;
-  const int KW = (L + 2 * W + 2) / 8 + 12;
-  int rc;
-  // a piece of the direction before may still be packing into d_bases on the second stream: it must have finished before the
-  // buffer can be reallocated, let alone written
-  if (d->pack_busy) { HIPCHK(hipEventSynchronize(d->pack_done)); d->pack_busy = 0; }
-  if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)Np * sizeof(ramx_flank)))) return rc;
-  if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)KW * Np * sizeof(unsigned)))) return rc;
-  if ((rc = ensure(&d->d_bounds, &d->cap_bounds, (size_t)Np * sizeof(int2)))) return rc;
-  // rows on chip for the band widths that have the instantiation (the conditions of the persistent kernel: no positive gap
-  // penalty, e - m fits int16); RAMX_PROFILE_NO_RESIDENT sends them through the global row buffer like every other case (A/B)
-  const bool chain = p->gapopen > 0 || p->gapextn > 0 || d->force_chain;
-  const bool resident = !chain && ramx_profile_has_resident(W) && p->gapopen + p->gapextn >= -32768 && getenv("RAMX_PROFILE_NO_RESIDENT") == NULL;
-  if (!resident && (rc = ensure(&d->d_pf_state, &d->cap_pf_state, (size_t)Np * Q * sizeof(int4)))) return rc;
-  if ((rc = ensure(&d->d_pf_slab, &d->cap_pf_slab, (size_t)(tiles > 0 ? tiles : 1) * maxrows * sizeof(ramx_col_profile)))) return rc;
-  if ((rc = ensure(&d->d_pf_cols, &d->cap_pf_cols, (size_t)n_families * L * sizeof(ramx_col_profile)))) return rc;
-  if ((rc = ensure(&d->d_pf_cons, &d->cap_pf_cons, (size_t)n_families * L + 16))) return rc;
-  if ((rc = ensure(&d->d_pf_rows, &d->cap_pf_rows, (size_t)n_families * sizeof(int)))) return rc;
-  if ((rc = ensure(&d->d_pf_fam, &d->cap_pf_fam, (size_t)n_families * sizeof(int4)))) return rc;
-  if ((rc = ensure(&d->d_pf_tile, &d->cap_pf_tile, tile_fam.size() * sizeof(int2)))) return rc;
-  if ((rc = ensure(&d->d_pf_last, &d->cap_pf_last, (size_t)Np * sizeof(int)))) return rc;
-  if (row_best)
-  {
-    if ((rc = ensure(&d->d_pf_best, &d->cap_pf_best, (size_t)maxrows * Np * sizeof(int)))) return rc;
-    if ((rc = ensure(&d->d_pf_bidx, &d->cap_pf_bidx, (size_t)maxrows * Np * sizeof(int)))) return rc;
-  }
-  if (n_padded) HIPCHK(hipMemcpyAsync(d->d_flanks, flanks, (size_t)n_padded * sizeof(ramx_flank), hipMemcpyHostToDevice, d->stream));
-  HIPCHK(hipMemcpyAsync(d->d_pf_cons, cons, (size_t)n_families * L, hipMemcpyHostToDevice, d->stream));
-  HIPCHK(hipMemcpyAsync(d->d_pf_rows, rows, (size_t)n_families * sizeof(int), hipMemcpyHostToDevice, d->stream));
-  HIPCHK(hipMemcpyAsync(d->d_pf_fam, fam_desc.data(), (size_t)n_families * sizeof(int4), hipMemcpyHostToDevice, d->stream));
-  HIPCHK(hipMemcpyAsync(d->d_pf_tile, tile_fam.data(), tile_fam.size() * sizeof(int2), hipMemcpyHostToDevice, d->stream));
-  HIPCHK(hipMemsetAsync(d->d_pf_last, 0xff, (size_t)Np * sizeof(int), d->stream));
-  if (row_best)
-  {
-    // tiles outside every family and rows beyond a family's count are never written: they read as 0
-    HIPCHK(hipMemsetAsync(d->d_pf_best, 0, (size_t)maxrows * Np * sizeof(int), d->stream));
-    HIPCHK(hipMemsetAsync(d->d_pf_bidx, 0, (size_t)maxrows * Np * sizeof(int), d->stream));
-  }
-  if ((rc = launch_pack(d, n_padded, Np, W, 0, KW, d->stream)) != RAMX_OK) return rc;
-  d->packed_kw = KW;
-  d->ready = 0;       // the direction's flank and window buffers were reused: begin_direction must be called again before run_direction
-  ProfArgs pa;
-  memset(&pa, 0, sizeof(pa));
-  pa.k.bases = d->d_bases; pa.k.bounds = d->d_bounds; pa.k.S_in = d->d_pf_state; pa.k.S_out = d->d_pf_state;
-  pa.k.Np = Np; pa.k.Nx = Np; pa.k.W = W; pa.k.go = p->gapopen; pa.k.ge = p->gapextn; pa.k.cap = p->cappenalty;
-  for (int c = 0; c < RAMX_NCLASS; c++)
-  {
-    const int code = (c == 8) ? RAMX_SYM_N : c;
-    for (int k = 0; k < 4; k++) pa.k.tab[c][k] = p->matrix[k * 100 + code];
-  }
-  pa.flanks = d->d_flanks; pa.tile_fam = d->d_pf_tile; pa.cons = d->d_pf_cons; pa.rows = d->d_pf_rows; pa.slab = d->d_pf_slab;
-  pa.last_uncapped = d->d_pf_last; pa.row_best = row_best ? d->d_pf_best : NULL; pa.row_best_idx = row_best ? d->d_pf_bidx : NULL;
-  pa.L = L; pa.slab_rows = maxrows;
-  ProfSumArgs sa;
-  sa.slab = d->d_pf_slab; sa.fam = d->d_pf_fam; sa.cons = d->d_pf_cons; sa.cols = d->d_pf_cols; sa.L = L; sa.slab_rows = maxrows;
-  if (resident)
-  {
-    pa.pack_ok = getenv("RAMX_NO_FASTPACK") ? 0 : fast_pack_ok(pa.k.tab, pa.k.go, pa.k.ge, L, W);
-    if (pa.pack_ok && getenv("RAMX_NO_MASKHI") == NULL) pa.pack_ok = 2;
-    pa.lean_p = lean_p_of(pa.k.tab, pa.k.go, pa.k.ge);
-  }
-  HIPCHK(hipEventRecord(d->ev_begin, d->stream));
-  if ((rc = ramx_profile_launch(d->stream, resident, chain, tiles, pa, n_families, sa)) != RAMX_OK)
-  { ramx_set_error("ramx_dev_profile: launch failed (%s)", hipGetErrorString(hipGetLastError())); return rc; }
-  HIPCHK(hipEventRecord(d->ev_end, d->stream));
-  HIPCHK(hipStreamSynchronize(d->stream));
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, d->ev_begin, d->ev_end));
-  if (kernel_ms) *kernel_ms = ms;
-  // only rows[f] entries per family are written: one family comes straight into place, several come as one block that is
-  // scattered here
-  if (n_families == 1)
-    HIPCHK(hipMemcpy(cols, d->d_pf_cols, (size_t)rows[0] * sizeof(ramx_col_profile), hipMemcpyDeviceToHost));
-  else
-  {
-    std::vector<ramx_col_profile> stage((size_t)n_families * L);
-    HIPCHK(hipMemcpy(stage.data(), d->d_pf_cols, stage.size() * sizeof(ramx_col_profile), hipMemcpyDeviceToHost));
-    for (int f = 0; f < n_families; f++)
-      if (rows[f] > 0) memcpy(cols + (size_t)f * L, stage.data() + (size_t)f * L, (size_t)rows[f] * sizeof(ramx_col_profile));
-  }
-  if (last_uncapped_row && n_padded) HIPCHK(hipMemcpy(last_uncapped_row, d->d_pf_last, (size_t)n_padded * sizeof(int), hipMemcpyDeviceToHost));
-  if (row_best && n_padded)
-  {
-    HIPCHK(hipMemcpy(row_best, d->d_pf_best, (size_t)maxrows * n_padded * sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(row_best_idx, d->d_pf_bidx, (size_t)maxrows * n_padded * sizeof(int), hipMemcpyDeviceToHost));
-  }
-  return RAMX_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// per-copy alignments: the band replayed along a given consensus with every cell's decisions kept, then walked back
-// (ramx_kernels_align.h)
-// ------------------------------------------------------------------------------------------
-extern "C" int ramx_dev_align(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
-                              const int32_t *fam_count, int32_t n_families, const ramx_params *p,
-                              const int8_t *cons, const int32_t *rows, ramx_aln_end *ends, int32_t *col_idx, int32_t *col_ins,
-                              double *kernel_ms)
-{
-  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0;
-  if (!d || !p || !p->matrix || n_families < 0 || n_padded < 0 || (n_padded & 63) || (n_padded && (!flanks || !ends)) ||
-      (n_families && (!fam_first || !fam_count || !rows)))
-  { ramx_set_error("ramx_dev_align: bad argument"); return RAMX_ERR_ARG; }
-  if ((col_idx == NULL) != (col_ins == NULL)) { ramx_set_error("ramx_dev_align: col_idx and col_ins go together"); return RAMX_ERR_ARG; }
-  const int W = p->bandwidth, L = p->L, Q = W + 1;
-  if (W < 1 || L < 0) { ramx_set_error("ramx_dev_align: bad bandwidth / L"); return RAMX_ERR_ARG; }
-  const int tiles = n_padded / 64;
-  std::vector<int2> tile_fam((size_t)(tiles > 0 ? tiles : 1), make_int2(-1, 0));
-  int maxrows = 0;
-  for (int f = 0; f < n_families; f++)
-  {
-    if (fam_count[f] < 0 || fam_first[f] < 0 || (fam_first[f] & 63) || (long long)fam_first[f] + fam_count[f] > n_padded)
-    { ramx_set_error("ramx_dev_align: bad family layout"); return RAMX_ERR_ARG; }
-    if (rows[f] < 0 || rows[f] > L) { ramx_set_error("ramx_dev_align: rows[%d] = %d outside [0, L = %d]", f, rows[f], L); return RAMX_ERR_ARG; }
-    if (rows[f] > 0 && !cons) { ramx_set_error("ramx_dev_align: cons missing"); return RAMX_ERR_ARG; }
-    for (int r = 0; r < rows[f]; r++)
-      if (cons[(size_t)f * L + r] < 0 || cons[(size_t)f * L + r] > 3) { ramx_set_error("ramx_dev_align: consensus base outside A C G T (family %d, column %d)", f, r); return RAMX_ERR_ARG; }
-    const int t0 = fam_first[f] / 64, nt = (fam_count[f] + 63) / 64;
-    for (int t = 0; t < nt; t++)
-    {
-      if (tile_fam[t0 + t].x >= 0) { ramx_set_error("ramx_dev_align: families %d and %d overlap", tile_fam[t0 + t].x, f); return RAMX_ERR_ARG; }
-      const int left = fam_count[f] - 64 * t;
-      tile_fam[t0 + t] = make_int2(f, left < 64 ? left : 64);
-    }
-    if (rows[f] > maxrows) maxrows = rows[f];
-  }
-  // the group of tiles whose codes fit the budget
-  const int nd = ramx_align_dwords(W);
-  size_t budget = (size_t)1 << 30;
-  if (const char *e = getenv("RAMX_ALIGN_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
-  const size_t tile_bytes = (size_t)(maxrows > 0 ? maxrows : 1) * nd * 64 * sizeof(unsigned);
-  if (tiles > 0 && maxrows > 0 && tile_bytes > budget)
-  {
-    ramx_set_error("ramx_dev_align: the decision codes of one tile of 64 flanks (%d rows, bandwidth %d: %zu bytes) do not fit RAMX_ALIGN_BYTES = %zu",
-                   maxrows, W, tile_bytes, budget);
-    return RAMX_ERR_UNSUPPORTED;
-  }
-  // what the kernels never reach is answered here: no alignment
-  const ramx_aln_end none = { -1, -1, 0, 0, 0 };
-  auto preset_host = [&](int f) {
-    const int t0 = fam_first[f] / 64, nt = (fam_count[f] + 63) / 64;
-    for (int i = t0 * 64; i < (t0 + nt) * 64; i++) ends[i] = none;
-    if (col_idx)
-      for (int r = 0; r < maxrows; r++)
-        for (int i = t0 * 64; i < (t0 + nt) * 64; i++) { col_idx[(size_t)r * n_padded + i] = RAMX_ALN_NONE; col_ins[(size_t)r * n_padded + i] = 0; }
-  };
-  if (n_families == 0 || maxrows == 0 || tiles == 0)
-  {
-    for (int f = 0; f < n_families; f++) preset_host(f);
-    return RAMX_OK;
-  }
-  HIPCHK(hipSetDevice(d->ordinal));
-  const int Np = n_padded;
-  const int KW = (L + 2 * W + 2) / 8 + 12;
-  int group = (int)(budget / tile_bytes < (size_t)tiles ? budget / tile_bytes : (size_t)tiles);
-  int rc;
-  if (d->pack_busy) { HIPCHK(hipEventSynchronize(d->pack_done)); d->pack_busy = 0; }      // see ramx_dev_profile
-  if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)Np * sizeof(ramx_flank)))) return rc;
-  if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)KW * Np * sizeof(unsigned)))) return rc;
-  if ((rc = ensure(&d->d_bounds, &d->cap_bounds, (size_t)Np * sizeof(int2)))) return rc;
-  if ((rc = ensure(&d->d_pf_state, &d->cap_pf_state, (size_t)Np * Q * sizeof(int4)))) return rc;
-  if ((rc = ensure(&d->d_pf_cons, &d->cap_pf_cons, (size_t)n_families * L + 16))) return rc;
-  if ((rc = ensure(&d->d_pf_rows, &d->cap_pf_rows, (size_t)n_families * sizeof(int)))) return rc;
-  if ((rc = ensure(&d->d_pf_tile, &d->cap_pf_tile, tile_fam.size() * sizeof(int2)))) return rc;
-  if ((rc = ensure(&d->d_al_codes, &d->cap_al_codes, (size_t)group * tile_bytes))) return rc;
-  if ((rc = ensure(&d->d_al_ends, &d->cap_al_ends, (size_t)Np * sizeof(ramx_aln_end)))) return rc;
-  const size_t ncol = (size_t)maxrows * Np;
-  if (col_idx)
-  {
-    if ((rc = ensure(&d->d_al_idx, &d->cap_al_idx, ncol * sizeof(int)))) return rc;
-    if ((rc = ensure(&d->d_al_ins, &d->cap_al_ins, ncol * sizeof(int)))) return rc;
-  }
-  HIPCHK(hipMemcpyAsync(d->d_flanks, flanks, (size_t)n_padded * sizeof(ramx_flank), hipMemcpyHostToDevice, d->stream));
-  HIPCHK(hipMemcpyAsync(d->d_pf_cons, cons, (size_t)n_families * L, hipMemcpyHostToDevice, d->stream));
-  HIPCHK(hipMemcpyAsync(d->d_pf_rows, rows, (size_t)n_families * sizeof(int), hipMemcpyHostToDevice, d->stream));
-  HIPCHK(hipMemcpyAsync(d->d_pf_tile, tile_fam.data(), tile_fam.size() * sizeof(int2), hipMemcpyHostToDevice, d->stream));
-  if (col_idx && (rc = ramx_align_launch_preset(d->stream, d->d_al_idx, d->d_al_ins, ncol)) != RAMX_OK) return rc;
-  if ((rc = launch_pack(d, n_padded, Np, W, 0, KW, d->stream)) != RAMX_OK) return rc;
-  d->packed_kw = KW;
-  d->ready = 0;       // the direction's flank and window buffers were reused: begin_direction must be called again before run_direction
-  AlnArgs aa;
-  memset(&aa, 0, sizeof(aa));
-  aa.k.bases = d->d_bases; aa.k.bounds = d->d_bounds; aa.k.S_in = d->d_pf_state; aa.k.S_out = d->d_pf_state;
-  aa.k.Np = Np; aa.k.Nx = Np; aa.k.W = W; aa.k.go = p->gapopen; aa.k.ge = p->gapextn; aa.k.cap = p->cappenalty;
-  for (int c = 0; c < RAMX_NCLASS; c++)
-  {
-    const int code = (c == 8) ? RAMX_SYM_N : c;
-    for (int k = 0; k < 4; k++) aa.k.tab[c][k] = p->matrix[k * 100 + code];
-  }
-  aa.tile_fam = d->d_pf_tile; aa.cons = d->d_pf_cons; aa.rows = d->d_pf_rows; aa.codes = d->d_al_codes; aa.ends = d->d_al_ends;
-  aa.col_idx = col_idx ? d->d_al_idx : NULL; aa.col_ins = col_idx ? d->d_al_ins : NULL;
-  aa.L = L; aa.nd = nd; aa.gn = group * 64;
-  // group after group on one stream: the walk of a group has read its codes before the next group's forward pass writes them
-  const int ngroups = (tiles + group - 1) / group;
-  std::vector<hipEvent_t> ev((size_t)3 * ngroups, (hipEvent_t)NULL);
-  if (kernel_ms) for (auto &e : ev) HIPCHK(hipEventCreate(&e));
-  for (int g = 0; g < ngroups; g++)
-  {
-    aa.tile0 = g * group;
-    const int nt = tiles - aa.tile0 < group ? tiles - aa.tile0 : group;
-    if (kernel_ms) HIPCHK(hipEventRecord(ev[3 * g], d->stream));
-    if ((rc = ramx_align_launch_forward(d->stream, nt, aa)) != RAMX_OK) break;
-    if (kernel_ms) HIPCHK(hipEventRecord(ev[3 * g + 1], d->stream));
-    if ((rc = ramx_align_launch_walk(d->stream, nt, aa)) != RAMX_OK) break;
-    if (kernel_ms) HIPCHK(hipEventRecord(ev[3 * g + 2], d->stream));
-  }
-  if (rc != RAMX_OK) ramx_set_error("ramx_dev_align: launch failed (%s)", hipGetErrorString(hipGetLastError()));
-  const hipError_t se = hipStreamSynchronize(d->stream);
-  if (kernel_ms)
-  {
-    for (int g = 0; g < ngroups && rc == RAMX_OK && se == hipSuccess; g++)
-    {
-      float a = 0, b = 0;
-      (void)hipEventElapsedTime(&a, ev[3 * g], ev[3 * g + 1]);
-      (void)hipEventElapsedTime(&b, ev[3 * g + 1], ev[3 * g + 2]);
-      kernel_ms[0] += a; kernel_ms[1] += b;
-    }
-    for (auto &e : ev) (void)hipEventDestroy(e);
-  }
-  if (rc != RAMX_OK) return rc;
-  HIPCHK(se);
-  // the tiles of every family, all rows; tiles outside every family keep what the caller has there
-  for (int f = 0; f < n_families; f++)
-  {
-    const int t0 = fam_first[f] / 64, nt = (fam_count[f] + 63) / 64;
-    if (nt == 0) continue;
-    if (rows[f] == 0) { preset_host(f); continue; }   // its tiles ran no row: the forward kernel still wrote their records
-    HIPCHK(hipMemcpy(ends + (size_t)t0 * 64, d->d_al_ends + (size_t)t0 * 64, (size_t)nt * 64 * sizeof(ramx_aln_end), hipMemcpyDeviceToHost));
-    if (col_idx)
-    {
-      HIPCHK(hipMemcpy2D(col_idx + (size_t)t0 * 64, (size_t)n_padded * sizeof(int), d->d_al_idx + (size_t)t0 * 64, (size_t)Np * sizeof(int),
-                         (size_t)nt * 64 * sizeof(int), (size_t)maxrows, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy2D(col_ins + (size_t)t0 * 64, (size_t)n_padded * sizeof(int), d->d_al_ins + (size_t)t0 * 64, (size_t)Np * sizeof(int),
-                         (size_t)nt * 64 * sizeof(int), (size_t)maxrows, hipMemcpyDeviceToHost));
-    }
-  }
-  return RAMX_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// pileup and consensus refinement: ramx_dev_align's forward pass and walk group after group, the group's columns counted on the
-// device next to the walk (ramx_kernels_pileup.h); the re-call is host C (ramx_recall.c)
-// ------------------------------------------------------------------------------------------
-struct PileupPlan
+struct ReplayPlan
 {
   int tiles, maxrows;
-  std::vector<int2> tile_fam;
-  std::vector<int4> fam_desc;
+  std::vector<int2> tile_fam;       // per tile: (family, flanks in the tile), (-1, 0) outside every family
+  std::vector<int4> fam_desc;       // per family: (first tile, tiles, rows, 0)
 };
 
-// argument checks of ramx_dev_align, and the tile / family tables of the families with run[f] != 0 (run == NULL: all)
-static int pileup_plan(const char *who, int32_t n_padded, const int32_t *fam_first, const int32_t *fam_count, int32_t n_families,
-                       int L, const int8_t *cons, const int32_t *rows, const char *run, bool check, PileupPlan &pl)
+// the checks of the family layout, the rows and the consensus (check), and the tile / family tables of the families with
+// run[f] != 0 (run == NULL: all)
+static int replay_plan(const char *who, int32_t n_padded, const int32_t *fam_first, const int32_t *fam_count, int32_t n_families,
+                       int L, const int8_t *cons, const int32_t *rows, const char *run, bool check, ReplayPlan &pl)
 {
   pl.tiles = n_padded / 64;
   pl.maxrows = 0;
@@ -1869,133 +1596,349 @@ static int pileup_plan(const char *who, int32_t n_padded, const int32_t *fam_fir
   return RAMX_OK;
 }
 
-// once per call: the flanks uploaded, their windows packed, the tables that do not depend on the consensus
-static int pileup_setup(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, int32_t n_families, const ramx_params *p, AlnArgs &aa, int *KW_out)
+// once per call: the flanks uploaded and their windows packed as Np flanks, the buffers of what replay_upload sends, and what
+// run_band reads (k); need_state: the rows go through the global row buffer
+static int replay_setup(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, int Np, int32_t n_families, const ramx_params *p,
+                        bool need_state, KArgs &k, int *KW_out)
 {
   HIPCHK(hipSetDevice(d->ordinal));
-  const int W = p->bandwidth, L = p->L, Q = W + 1, Np = n_padded, tiles = n_padded / 64;
-  const int KW = (L + 2 * W + 2) / 8 + 12;
+  const int W = p->bandwidth, L = p->L, KW = window_words(L, W);
   int rc;
-  if (d->pack_busy) { HIPCHK(hipEventSynchronize(d->pack_done)); d->pack_busy = 0; }      // see ramx_dev_profile
+  // a piece of the direction before may still be packing into d_bases on the second stream: it must have finished before the
+  // buffer can be reallocated, let alone written
+  if (d->pack_busy) { HIPCHK(hipEventSynchronize(d->pack_done)); d->pack_busy = 0; }
   if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)Np * sizeof(ramx_flank)))) return rc;
   if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)KW * Np * sizeof(unsigned)))) return rc;
   if ((rc = ensure(&d->d_bounds, &d->cap_bounds, (size_t)Np * sizeof(int2)))) return rc;
-  if ((rc = ensure(&d->d_pf_state, &d->cap_pf_state, (size_t)Np * Q * sizeof(int4)))) return rc;
-  if ((rc = ensure(&d->d_pf_cons, &d->cap_pf_cons, (size_t)n_families * L + 16))) return rc;
-  if ((rc = ensure(&d->d_pf_rows, &d->cap_pf_rows, (size_t)n_families * sizeof(int)))) return rc;
-  if ((rc = ensure(&d->d_pf_tile, &d->cap_pf_tile, (size_t)tiles * sizeof(int2)))) return rc;
-  if ((rc = ensure(&d->d_pl_fam, &d->cap_pl_fam, (size_t)n_families * sizeof(int4)))) return rc;
-  if ((rc = ensure(&d->d_pl_cols, &d->cap_pl_cols, (size_t)n_families * L * sizeof(ramx_col_pileup)))) return rc;
-  if ((rc = ensure(&d->d_al_ends, &d->cap_al_ends, (size_t)Np * sizeof(ramx_aln_end)))) return rc;
-  HIPCHK(hipMemcpyAsync(d->d_flanks, flanks, (size_t)n_padded * sizeof(ramx_flank), hipMemcpyHostToDevice, d->stream));
+  if (need_state && (rc = ensure(&d->d_rp_state, &d->cap_rp_state, (size_t)Np * (W + 1) * sizeof(int4)))) return rc;
+  if ((rc = ensure(&d->d_rp_cons, &d->cap_rp_cons, (size_t)n_families * L + 16))) return rc;
+  if ((rc = ensure(&d->d_rp_rows, &d->cap_rp_rows, (size_t)n_families * sizeof(int)))) return rc;
+  if ((rc = ensure(&d->d_rp_tile, &d->cap_rp_tile, (size_t)(Np / 64) * sizeof(int2)))) return rc;
+  if ((rc = ensure(&d->d_rp_fam, &d->cap_rp_fam, (size_t)n_families * sizeof(int4)))) return rc;
+  if (n_padded) HIPCHK(hipMemcpyAsync(d->d_flanks, flanks, (size_t)n_padded * sizeof(ramx_flank), hipMemcpyHostToDevice, d->stream));
   if ((rc = launch_pack(d, n_padded, Np, W, 0, KW, d->stream)) != RAMX_OK) return rc;
   d->packed_kw = KW;
   d->ready = 0;       // the direction's flank and window buffers were reused: begin_direction must be called again before run_direction
-  memset(&aa, 0, sizeof(aa));
-  aa.k.bases = d->d_bases; aa.k.bounds = d->d_bounds; aa.k.S_in = d->d_pf_state; aa.k.S_out = d->d_pf_state;
-  aa.k.Np = Np; aa.k.Nx = Np; aa.k.W = W; aa.k.go = p->gapopen; aa.k.ge = p->gapextn; aa.k.cap = p->cappenalty;
-  for (int c = 0; c < RAMX_NCLASS; c++)
-  {
-    const int code = (c == 8) ? RAMX_SYM_N : c;
-    for (int k = 0; k < 4; k++) aa.k.tab[c][k] = p->matrix[k * 100 + code];
-  }
-  aa.tile_fam = d->d_pf_tile; aa.cons = d->d_pf_cons; aa.rows = d->d_pf_rows; aa.ends = d->d_al_ends;
-  aa.L = L; aa.nd = ramx_align_dwords(W);
+  memset(&k, 0, sizeof(k));
+  k.bases = d->d_bases; k.bounds = d->d_bounds; k.S_in = d->d_rp_state; k.S_out = d->d_rp_state;
+  k.Np = Np; k.Nx = Np; k.W = W; k.go = p->gapopen; k.ge = p->gapextn; k.cap = p->cappenalty;
+  class_tab(p, k.tab);
   *KW_out = KW;
   return RAMX_OK;
 }
 
-// one replay of the plan's families along cons / rows: forward, walk and pileup per group of tiles, then the sum; on return
-// the stream is idle, d_pl_cols holds the families' columns and d_al_ends their flanks' records.  pl.tiles > 0, pl.maxrows > 0.
-static int pileup_replay(ramx_dev *d, const char *who, AlnArgs aa, int KW, const PileupPlan &pl, int32_t n_families,
-                         const int8_t *cons, const int32_t *rows, double *kernel_ms)
+// once per replay: the consensus, the rows and the plan's two tables
+static int replay_upload(ramx_dev *d, const ReplayPlan &pl, int32_t n_families, int L, const int8_t *cons, const int32_t *rows)
 {
-  const int tiles = pl.tiles, maxrows = pl.maxrows, L = aa.L, W = aa.k.W, nd = aa.nd;
+  HIPCHK(hipMemcpyAsync(d->d_rp_cons, cons, (size_t)n_families * L, hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemcpyAsync(d->d_rp_rows, rows, (size_t)n_families * sizeof(int), hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemcpyAsync(d->d_rp_tile, pl.tile_fam.data(), pl.tile_fam.size() * sizeof(int2), hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemcpyAsync(d->d_rp_fam, pl.fam_desc.data(), (size_t)n_families * sizeof(int4), hipMemcpyHostToDevice, d->stream));
+  return RAMX_OK;
+}
+
+// the group of tiles whose `what` (tile_bytes per tile of 64 flanks) fit RAMX_ALIGN_BYTES
+static int replay_group(const char *who, const char *what, int tiles, size_t tile_bytes, int maxrows, int W, int *group)
+{
   size_t budget = (size_t)1 << 30;
   if (const char *e = getenv("RAMX_ALIGN_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
-  // per tile: the decision codes and the walked columns (col_idx, col_ins) of its 64 flanks
-  const size_t code_bytes = (size_t)maxrows * nd * 64 * sizeof(unsigned), col_bytes = (size_t)maxrows * 64 * sizeof(int);
-  const size_t tile_bytes = code_bytes + 2 * col_bytes;
   if (tile_bytes > budget)
   {
-    ramx_set_error("%s: the decision codes and columns of one tile of 64 flanks (%d rows, bandwidth %d: %zu bytes) do not fit RAMX_ALIGN_BYTES = %zu",
-                   who, maxrows, W, tile_bytes, budget);
+    ramx_set_error("%s: the %s of one tile of 64 flanks (%d rows, bandwidth %d: %zu bytes) do not fit RAMX_ALIGN_BYTES = %zu",
+                   who, what, maxrows, W, tile_bytes, budget);
     return RAMX_ERR_UNSUPPORTED;
   }
-  const int group = (int)(budget / tile_bytes < (size_t)tiles ? budget / tile_bytes : (size_t)tiles);
+  *group = (int)(budget / tile_bytes < (size_t)tiles ? budget / tile_bytes : (size_t)tiles);
+  return RAMX_OK;
+}
+
+// group after group on one stream: a group's later stages have read what its earlier ones wrote before the next group's kernels
+// write it again.  body(tile0, nt, mark) launches the nstage stages of one group and calls mark() after each; with kernel_ms
+// the marks are HIP events and stage i's time, summed over the groups, is added to kernel_ms[i].  On return the stream is idle.
+template <class Body>
+static int replay_groups(ramx_dev *d, const char *who, int tiles, int group, int nstage, double *kernel_ms, Body body)
+{
+  const int ngroups = (tiles + group - 1) / group;
+  std::vector<hipEvent_t> ev(kernel_ms ? (size_t)(nstage + 1) * ngroups : 0, (hipEvent_t)NULL);
+  hipError_t he = hipSuccess;
+  for (auto &e : ev) if (he == hipSuccess) he = hipEventCreate(&e);
+  size_t marks = 0;
+  auto mark = [&]() { if (marks < ev.size() && he == hipSuccess) he = hipEventRecord(ev[marks++], d->stream); };
+  int rc = RAMX_OK;
+  for (int g = 0; g < ngroups && rc == RAMX_OK && he == hipSuccess; g++)
+  {
+    const int tile0 = g * group;
+    mark();
+    rc = body(tile0, tiles - tile0 < group ? tiles - tile0 : group, mark);
+  }
+  if (rc != RAMX_OK) ramx_set_error("%s: launch failed (%s)", who, hipGetErrorString(hipGetLastError()));
+  const hipError_t se = hipStreamSynchronize(d->stream);
+  for (size_t i = 0; i + 1 < ev.size() && rc == RAMX_OK && he == hipSuccess && se == hipSuccess; i++)
+  {
+    if ((int)(i % (nstage + 1)) == nstage) continue;       // from a group's last mark to the next group's first: no stage
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
+    kernel_ms[i % (nstage + 1)] += ms;
+  }
+  for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+  if (rc != RAMX_OK) return rc;
+  HIPCHK(he);
+  HIPCHK(se);
+  return RAMX_OK;
+}
+
+// what the kernels never reach is answered on the host: flanks [i0, i1) have no alignment (ends, col_idx / col_ins may be NULL)
+static void replay_no_alignment(ramx_aln_end *ends, int32_t *col_idx, int32_t *col_ins, int i0, int i1, int maxrows, int32_t n_padded)
+{
+  const ramx_aln_end none = { -1, -1, 0, 0, 0 };
+  if (ends) for (int i = i0; i < i1; i++) ends[i] = none;
+  if (col_idx)
+    for (int r = 0; r < maxrows; r++)
+      for (int i = i0; i < i1; i++) { col_idx[(size_t)r * n_padded + i] = RAMX_ALN_NONE; col_ins[(size_t)r * n_padded + i] = 0; }
+}
+
+// what both alignment replays hand the forward kernel and the walk: run_band's arguments, the shared tables, the flanks' records
+static int aln_args(ramx_dev *d, const KArgs &k, int L, AlnArgs &aa)
+{
   int rc;
+  if ((rc = ensure(&d->d_al_ends, &d->cap_al_ends, (size_t)k.Np * sizeof(ramx_aln_end)))) return rc;
+  memset(&aa, 0, sizeof(aa));
+  aa.k = k;
+  aa.tile_fam = d->d_rp_tile; aa.cons = d->d_rp_cons; aa.rows = d->d_rp_rows; aa.ends = d->d_al_ends;
+  aa.L = L; aa.nd = ramx_align_dwords(k.W);
+  return RAMX_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// support profile: every flank's band replayed along a given consensus (ramx_kernels_profile.h)
+// ------------------------------------------------------------------------------------------
+extern "C" int ramx_dev_profile(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                                const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                                const int8_t *cons, const int32_t *rows, ramx_col_profile *cols, int32_t *last_uncapped_row,
+                                int32_t *row_best, int32_t *row_best_idx, double *kernel_ms)
+{
+  if (kernel_ms) *kernel_ms = 0;
+  if (!d || !p || !p->matrix || n_families < 0 || n_padded < 0 || (n_padded & 63) || (n_padded && !flanks) ||
+      (n_families && (!fam_first || !fam_count || !rows)))
+  { ramx_set_error("ramx_dev_profile: bad argument"); return RAMX_ERR_ARG; }
+  if ((row_best == NULL) != (row_best_idx == NULL)) { ramx_set_error("ramx_dev_profile: row_best and row_best_idx go together"); return RAMX_ERR_ARG; }
+  const int W = p->bandwidth, L = p->L;
+  if (W < 1 || L < 0) { ramx_set_error("ramx_dev_profile: bad bandwidth / L"); return RAMX_ERR_ARG; }
+  ReplayPlan pl;
+  int rc;
+  if ((rc = replay_plan("ramx_dev_profile", n_padded, fam_first, fam_count, n_families, L, cons, rows, NULL, true, pl)) != RAMX_OK) return rc;
+  const int tiles = pl.tiles, maxrows = pl.maxrows;
+  if (maxrows > 0 && !cols) { ramx_set_error("ramx_dev_profile: cols missing"); return RAMX_ERR_ARG; }
+  if (last_uncapped_row) for (int i = 0; i < n_padded; i++) last_uncapped_row[i] = -1;
+  // no return on tiles == 0: a family without flanks still gets its bases from the sum kernel (align and pileup answer it on the host)
+  if (n_families == 0 || maxrows == 0) return RAMX_OK;
+  const int Np = n_padded > 0 ? n_padded : 64;        // ... and a set without flanks is packed and run as one tile of nothing
+  // rows on chip for the band widths that have the instantiation (the conditions of the persistent kernel: no positive gap
+  // penalty, e - m fits int16); RAMX_PROFILE_NO_RESIDENT sends them through the global row buffer like every other case (A/B)
+  const bool chain = p->gapopen > 0 || p->gapextn > 0 || d->force_chain;
+  const bool resident = !chain && ramx_profile_has_resident(W) && p->gapopen + p->gapextn >= -32768 && getenv("RAMX_PROFILE_NO_RESIDENT") == NULL;
+  ProfArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  int KW;
+  if ((rc = replay_setup(d, flanks, n_padded, Np, n_families, p, !resident, pa.k, &KW)) != RAMX_OK) return rc;     // rows on chip need no row buffer
+  if ((rc = ensure(&d->d_pf_slab, &d->cap_pf_slab, (size_t)(tiles > 0 ? tiles : 1) * maxrows * sizeof(ramx_col_profile)))) return rc;
+  if ((rc = ensure(&d->d_pf_cols, &d->cap_pf_cols, (size_t)n_families * L * sizeof(ramx_col_profile)))) return rc;
+  if ((rc = ensure(&d->d_pf_last, &d->cap_pf_last, (size_t)Np * sizeof(int)))) return rc;
+  if (row_best)
+  {
+    if ((rc = ensure(&d->d_pf_best, &d->cap_pf_best, (size_t)maxrows * Np * sizeof(int)))) return rc;
+    if ((rc = ensure(&d->d_pf_bidx, &d->cap_pf_bidx, (size_t)maxrows * Np * sizeof(int)))) return rc;
+  }
+  if ((rc = replay_upload(d, pl, n_families, L, cons, rows)) != RAMX_OK) return rc;
+  HIPCHK(hipMemsetAsync(d->d_pf_last, 0xff, (size_t)Np * sizeof(int), d->stream));
+  if (row_best)
+  {
+    // tiles outside every family and rows beyond a family's count are never written: they read as 0
+    HIPCHK(hipMemsetAsync(d->d_pf_best, 0, (size_t)maxrows * Np * sizeof(int), d->stream));
+    HIPCHK(hipMemsetAsync(d->d_pf_bidx, 0, (size_t)maxrows * Np * sizeof(int), d->stream));
+  }
+  // the profile kernels read the flank descriptors as well as their packed windows
+  pa.flanks = d->d_flanks; pa.tile_fam = d->d_rp_tile; pa.cons = d->d_rp_cons; pa.rows = d->d_rp_rows; pa.slab = d->d_pf_slab;
+  pa.last_uncapped = d->d_pf_last; pa.row_best = row_best ? d->d_pf_best : NULL; pa.row_best_idx = row_best ? d->d_pf_bidx : NULL;
+  pa.L = L; pa.slab_rows = maxrows;
+  ProfSumArgs sa;
+  sa.slab = d->d_pf_slab; sa.fam = d->d_rp_fam; sa.cons = d->d_rp_cons; sa.cols = d->d_pf_cols; sa.L = L; sa.slab_rows = maxrows;
+  if (resident)
+  {
+    pa.pack_ok = getenv("RAMX_NO_FASTPACK") ? 0 : fast_pack_ok(pa.k.tab, pa.k.go, pa.k.ge, L, W);
+    if (pa.pack_ok && getenv("RAMX_NO_MASKHI") == NULL) pa.pack_ok = 2;
+    pa.lean_p = lean_p_of(pa.k.tab, pa.k.go, pa.k.ge);
+  }
+  // one launch over all tiles, no groups: timed with the session's events
+  HIPCHK(hipEventRecord(d->ev_begin, d->stream));
+  if ((rc = ramx_profile_launch(d->stream, resident, chain, tiles, pa, n_families, sa)) != RAMX_OK)
+  { ramx_set_error("ramx_dev_profile: launch failed (%s)", hipGetErrorString(hipGetLastError())); return rc; }
+  HIPCHK(hipEventRecord(d->ev_end, d->stream));
+  HIPCHK(hipStreamSynchronize(d->stream));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, d->ev_begin, d->ev_end));
+  if (kernel_ms) *kernel_ms = ms;
+  // only rows[f] entries per family are written: one family comes straight into place, several come as one block that is
+  // scattered here
+  if (n_families == 1)
+    HIPCHK(hipMemcpy(cols, d->d_pf_cols, (size_t)rows[0] * sizeof(ramx_col_profile), hipMemcpyDeviceToHost));
+  else
+  {
+    std::vector<ramx_col_profile> stage((size_t)n_families * L);
+    HIPCHK(hipMemcpy(stage.data(), d->d_pf_cols, stage.size() * sizeof(ramx_col_profile), hipMemcpyDeviceToHost));
+    for (int f = 0; f < n_families; f++)
+      if (rows[f] > 0) memcpy(cols + (size_t)f * L, stage.data() + (size_t)f * L, (size_t)rows[f] * sizeof(ramx_col_profile));
+  }
+  if (last_uncapped_row && n_padded) HIPCHK(hipMemcpy(last_uncapped_row, d->d_pf_last, (size_t)n_padded * sizeof(int), hipMemcpyDeviceToHost));
+  if (row_best && n_padded)
+  {
+    HIPCHK(hipMemcpy(row_best, d->d_pf_best, (size_t)maxrows * n_padded * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(row_best_idx, d->d_pf_bidx, (size_t)maxrows * n_padded * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  return RAMX_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// per-copy alignments: the band replayed along a given consensus with every cell's decisions kept, then walked back
+// (ramx_kernels_align.h)
+// ------------------------------------------------------------------------------------------
+extern "C" int ramx_dev_align(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                              const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                              const int8_t *cons, const int32_t *rows, ramx_aln_end *ends, int32_t *col_idx, int32_t *col_ins,
+                              double *kernel_ms)
+{
+  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0;
+  // the records are the result: ends is required wherever there are flanks
+  if (!d || !p || !p->matrix || n_families < 0 || n_padded < 0 || (n_padded & 63) || (n_padded && (!flanks || !ends)) ||
+      (n_families && (!fam_first || !fam_count || !rows)))
+  { ramx_set_error("ramx_dev_align: bad argument"); return RAMX_ERR_ARG; }
+  if ((col_idx == NULL) != (col_ins == NULL)) { ramx_set_error("ramx_dev_align: col_idx and col_ins go together"); return RAMX_ERR_ARG; }
+  const int W = p->bandwidth, L = p->L;
+  if (W < 1 || L < 0) { ramx_set_error("ramx_dev_align: bad bandwidth / L"); return RAMX_ERR_ARG; }
+  ReplayPlan pl;
+  int rc;
+  if ((rc = replay_plan("ramx_dev_align", n_padded, fam_first, fam_count, n_families, L, cons, rows, NULL, true, pl)) != RAMX_OK) return rc;
+  const int tiles = pl.tiles, maxrows = pl.maxrows;
+  auto no_alignment = [&](int f) {
+    const int t0 = fam_first[f] / 64, nt = (fam_count[f] + 63) / 64;
+    replay_no_alignment(ends, col_idx, col_ins, t0 * 64, (t0 + nt) * 64, maxrows, n_padded);
+  };
+  if (n_families == 0 || maxrows == 0 || tiles == 0)
+  {
+    for (int f = 0; f < n_families; f++) no_alignment(f);
+    return RAMX_OK;
+  }
+  // the budget counts the decision codes only: the columns are whole-set [maxrows][Np] arrays of their own
+  const size_t tile_bytes = (size_t)maxrows * ramx_align_dwords(W) * 64 * sizeof(unsigned);
+  int group, KW;
+  if ((rc = replay_group("ramx_dev_align", "decision codes", tiles, tile_bytes, maxrows, W, &group)) != RAMX_OK) return rc;
+  KArgs k;
+  AlnArgs aa;
+  if ((rc = replay_setup(d, flanks, n_padded, n_padded, n_families, p, true, k, &KW)) != RAMX_OK) return rc;
+  if ((rc = aln_args(d, k, L, aa)) != RAMX_OK) return rc;
+  if ((rc = ensure(&d->d_al_codes, &d->cap_al_codes, (size_t)group * tile_bytes))) return rc;
+  const size_t ncol = (size_t)maxrows * n_padded;
+  if (col_idx)
+  {
+    if ((rc = ensure(&d->d_al_idx, &d->cap_al_idx, ncol * sizeof(int)))) return rc;
+    if ((rc = ensure(&d->d_al_ins, &d->cap_al_ins, ncol * sizeof(int)))) return rc;
+  }
+  if ((rc = replay_upload(d, pl, n_families, L, cons, rows)) != RAMX_OK) return rc;
+  // the columns are preset once, for the whole set
+  if (col_idx && (rc = ramx_align_launch_preset(d->stream, d->d_al_idx, d->d_al_ins, ncol)) != RAMX_OK) return rc;
+  aa.codes = d->d_al_codes; aa.gn = group * 64;
+  aa.col_idx = col_idx ? d->d_al_idx : NULL; aa.col_ins = col_idx ? d->d_al_ins : NULL;
+  rc = replay_groups(d, "ramx_dev_align", tiles, group, 2, kernel_ms, [&](int tile0, int nt, auto &mark) {
+    int lrc;
+    aa.tile0 = tile0;
+    if ((lrc = ramx_align_launch_forward(d->stream, nt, aa)) != RAMX_OK) return lrc;
+    mark();
+    if ((lrc = ramx_align_launch_walk(d->stream, nt, aa)) != RAMX_OK) return lrc;
+    mark();
+    return RAMX_OK;
+  });
+  if (rc != RAMX_OK) return rc;
+  // the tiles of every family, all rows, copied back per family; tiles outside every family keep what the caller has there
+  for (int f = 0; f < n_families; f++)
+  {
+    const int t0 = fam_first[f] / 64, nt = (fam_count[f] + 63) / 64;
+    if (nt == 0) continue;
+    if (rows[f] == 0) { no_alignment(f); continue; }   // its tiles ran no row: the forward kernel still wrote their records
+    HIPCHK(hipMemcpy(ends + (size_t)t0 * 64, d->d_al_ends + (size_t)t0 * 64, (size_t)nt * 64 * sizeof(ramx_aln_end), hipMemcpyDeviceToHost));
+    if (col_idx)
+    {
+      HIPCHK(hipMemcpy2D(col_idx + (size_t)t0 * 64, (size_t)n_padded * sizeof(int), d->d_al_idx + (size_t)t0 * 64, (size_t)n_padded * sizeof(int),
+                         (size_t)nt * 64 * sizeof(int), (size_t)maxrows, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy2D(col_ins + (size_t)t0 * 64, (size_t)n_padded * sizeof(int), d->d_al_ins + (size_t)t0 * 64, (size_t)n_padded * sizeof(int),
+                         (size_t)nt * 64 * sizeof(int), (size_t)maxrows, hipMemcpyDeviceToHost));
+    }
+  }
+  return RAMX_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// pileup and consensus refinement: ramx_dev_align's forward pass and walk group after group, the group's columns counted on the
+// device next to the walk (ramx_kernels_pileup.h); the re-call is host C (ramx_recall.c)
+// ------------------------------------------------------------------------------------------
+// once per call (not per replay): the shared setup, the walk's arguments and the families' summed columns
+static int pileup_setup(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, int32_t n_families, const ramx_params *p, AlnArgs &aa, int *KW)
+{
+  KArgs k;
+  int rc;
+  if ((rc = replay_setup(d, flanks, n_padded, n_padded, n_families, p, true, k, KW)) != RAMX_OK) return rc;
+  if ((rc = ensure(&d->d_pl_cols, &d->cap_pl_cols, (size_t)n_families * p->L * sizeof(ramx_col_pileup)))) return rc;
+  return aln_args(d, k, p->L, aa);
+}
+
+// one replay of the plan's families along cons / rows: forward, walk and pileup per group of tiles, then the sum; on return
+// the stream is idle, d_pl_cols holds the families' columns and d_al_ends their flanks' records.  pl.tiles > 0, pl.maxrows > 0.
+static int pileup_replay(ramx_dev *d, const char *who, AlnArgs aa, int KW, const ReplayPlan &pl, int32_t n_families,
+                         const int8_t *cons, const int32_t *rows, double *kernel_ms)
+{
+  const int tiles = pl.tiles, maxrows = pl.maxrows, L = aa.L, W = aa.k.W;
+  // the budget counts, per tile, the decision codes and the walked columns (col_idx, col_ins) of its 64 flanks: the columns
+  // exist for one group at a time
+  const size_t code_bytes = (size_t)maxrows * aa.nd * 64 * sizeof(unsigned), col_bytes = (size_t)maxrows * 64 * sizeof(int);
+  int group, rc;
+  if ((rc = replay_group(who, "decision codes and columns", tiles, code_bytes + 2 * col_bytes, maxrows, W, &group)) != RAMX_OK) return rc;
   if ((rc = ensure(&d->d_al_codes, &d->cap_al_codes, (size_t)group * code_bytes))) return rc;
   if ((rc = ensure(&d->d_pl_idx, &d->cap_pl_idx, (size_t)group * col_bytes))) return rc;
   if ((rc = ensure(&d->d_pl_ins, &d->cap_pl_ins, (size_t)group * col_bytes))) return rc;
   if ((rc = ensure(&d->d_pl_slab, &d->cap_pl_slab, (size_t)tiles * maxrows * sizeof(ramx_col_pileup)))) return rc;
-  HIPCHK(hipMemcpyAsync(d->d_pf_cons, cons, (size_t)n_families * L, hipMemcpyHostToDevice, d->stream));
-  HIPCHK(hipMemcpyAsync(d->d_pf_rows, rows, (size_t)n_families * sizeof(int), hipMemcpyHostToDevice, d->stream));
-  HIPCHK(hipMemcpyAsync(d->d_pf_tile, pl.tile_fam.data(), (size_t)tiles * sizeof(int2), hipMemcpyHostToDevice, d->stream));
-  HIPCHK(hipMemcpyAsync(d->d_pl_fam, pl.fam_desc.data(), (size_t)n_families * sizeof(int4), hipMemcpyHostToDevice, d->stream));
+  if ((rc = replay_upload(d, pl, n_families, L, cons, rows)) != RAMX_OK) return rc;
   const int gn = group * 64;
   aa.codes = d->d_al_codes; aa.gn = gn;
   PileArgs pa;
-  pa.bases = d->d_bases; pa.tile_fam = d->d_pf_tile; pa.cons = d->d_pf_cons; pa.rows = d->d_pf_rows; pa.ends = d->d_al_ends;
+  pa.bases = d->d_bases; pa.tile_fam = d->d_rp_tile; pa.cons = d->d_rp_cons; pa.rows = d->d_rp_rows; pa.ends = d->d_al_ends;
   pa.col_idx = d->d_pl_idx; pa.col_ins = d->d_pl_ins; pa.slab = d->d_pl_slab;
   pa.L = L; pa.Np = aa.k.Np; pa.W = W; pa.KW = KW; pa.gn = gn; pa.slab_rows = maxrows;
   PileSumArgs sa;
-  sa.slab = d->d_pl_slab; sa.fam = d->d_pl_fam; sa.cons = d->d_pf_cons; sa.cols = d->d_pl_cols; sa.L = L; sa.slab_rows = maxrows;
-  // group after group on one stream: a group's pileup has read its columns, and its walk its codes, before the next group's
-  // kernels write them
-  const int ngroups = (tiles + group - 1) / group;
-  std::vector<hipEvent_t> ev((size_t)4 * ngroups + 1, (hipEvent_t)NULL);
-  if (kernel_ms) for (auto &e : ev) HIPCHK(hipEventCreate(&e));
-  rc = RAMX_OK;
-  for (int g = 0; g < ngroups && rc == RAMX_OK; g++)
-  {
-    const int tile0 = g * group, nt = tiles - tile0 < group ? tiles - tile0 : group;
+  sa.slab = d->d_pl_slab; sa.fam = d->d_rp_fam; sa.cons = d->d_rp_cons; sa.cols = d->d_pl_cols; sa.L = L; sa.slab_rows = maxrows;
+  return replay_groups(d, who, tiles, group, 3, kernel_ms, [&](int tile0, int nt, auto &mark) {
+    int lrc;
     aa.tile0 = pa.tile0 = tile0;
     // the walk addresses its columns as [r * k.Np + n] with n the flank's index in the whole set: given the group's width for
     // k.Np and the arrays' origin moved back by the group's first flank, it writes the group's own [maxrows][gn] arrays
     AlnArgs aw = aa;
     aw.k.Np = gn;
     aw.col_idx = d->d_pl_idx - (ptrdiff_t)tile0 * 64; aw.col_ins = d->d_pl_ins - (ptrdiff_t)tile0 * 64;
-    if (kernel_ms) HIPCHK(hipEventRecord(ev[4 * g], d->stream));
-    if ((rc = ramx_align_launch_forward(d->stream, nt, aa)) != RAMX_OK) break;
-    if (kernel_ms) HIPCHK(hipEventRecord(ev[4 * g + 1], d->stream));
-    if ((rc = ramx_align_launch_preset(d->stream, d->d_pl_idx, d->d_pl_ins, (size_t)maxrows * gn)) != RAMX_OK) break;
-    if ((rc = ramx_align_launch_walk(d->stream, nt, aw)) != RAMX_OK) break;
-    if (kernel_ms) HIPCHK(hipEventRecord(ev[4 * g + 2], d->stream));
-    if ((rc = ramx_pileup_launch(d->stream, nt, pa)) != RAMX_OK) break;
-    if (kernel_ms) HIPCHK(hipEventRecord(ev[4 * g + 3], d->stream));
-  }
-  if (rc == RAMX_OK) rc = ramx_pileup_launch_sum(d->stream, n_families, maxrows, sa);
-  if (rc == RAMX_OK && kernel_ms) HIPCHK(hipEventRecord(ev[4 * ngroups], d->stream));
-  if (rc != RAMX_OK) ramx_set_error("%s: launch failed (%s)", who, hipGetErrorString(hipGetLastError()));
-  const hipError_t se = hipStreamSynchronize(d->stream);
-  if (kernel_ms)
-  {
-    for (int g = 0; g < ngroups && rc == RAMX_OK && se == hipSuccess; g++)
-    {
-      float a = 0, b = 0, c = 0;
-      (void)hipEventElapsedTime(&a, ev[4 * g], ev[4 * g + 1]);
-      (void)hipEventElapsedTime(&b, ev[4 * g + 1], ev[4 * g + 2]);
-      (void)hipEventElapsedTime(&c, ev[4 * g + 2], ev[4 * g + 3]);
-      kernel_ms[0] += a; kernel_ms[1] += b; kernel_ms[2] += c;
-    }
-    if (rc == RAMX_OK && se == hipSuccess)
-    {
-      float c = 0;
-      (void)hipEventElapsedTime(&c, ev[4 * ngroups - 1], ev[4 * ngroups]);
-      kernel_ms[2] += c;
-    }
-    for (auto &e : ev) (void)hipEventDestroy(e);
-  }
-  if (rc != RAMX_OK) return rc;
-  HIPCHK(se);
-  return RAMX_OK;
+    if ((lrc = ramx_align_launch_forward(d->stream, nt, aa)) != RAMX_OK) return lrc;
+    mark();
+    if ((lrc = ramx_align_launch_preset(d->stream, d->d_pl_idx, d->d_pl_ins, (size_t)maxrows * gn)) != RAMX_OK) return lrc;     // per group
+    if ((lrc = ramx_align_launch_walk(d->stream, nt, aw)) != RAMX_OK) return lrc;
+    mark();
+    if ((lrc = ramx_pileup_launch(d->stream, nt, pa)) != RAMX_OK) return lrc;
+    // the last group's pileup stage ends with the sum over the tiles of every family
+    if (tile0 + nt == tiles && (lrc = ramx_pileup_launch_sum(d->stream, n_families, maxrows, sa)) != RAMX_OK) return lrc;
+    mark();
+    return RAMX_OK;
+  });
 }
 
 // the columns and flank records of the families with run[f] != 0 (NULL: all) after a replay, or answered here where nothing ran
 static int pileup_fetch(ramx_dev *d, bool ran, int32_t n_padded, const int32_t *fam_first, const int32_t *fam_count, int32_t n_families,
                         int L, const int8_t *cons, const int32_t *rows, const char *run, ramx_col_pileup *cols, ramx_aln_end *ends)
 {
-  const ramx_aln_end none = { -1, -1, 0, 0, 0 };
   for (int f = 0; f < n_families; f++)
   {
     if (run && !run[f]) continue;
@@ -2010,8 +1953,8 @@ static int pileup_fetch(ramx_dev *d, bool ran, int32_t n_padded, const int32_t *
         for (int r = 0; r < rows[f]; r++) c[r].base = cons[(size_t)f * L + r];
       }
     }
-    if (!ends || nt == 0) continue;
-    if (!ran || rows[f] == 0) for (int i = t0 * 64; i < (t0 + nt) * 64; i++) ends[i] = none;
+    if (!ends || nt == 0) continue;        // ends is optional here
+    if (!ran || rows[f] == 0) replay_no_alignment(ends, NULL, NULL, t0 * 64, (t0 + nt) * 64, 0, n_padded);
     else HIPCHK(hipMemcpy(ends + (size_t)t0 * 64, d->d_al_ends + (size_t)t0 * 64, (size_t)nt * 64 * sizeof(ramx_aln_end), hipMemcpyDeviceToHost));
   }
   return RAMX_OK;
@@ -2026,9 +1969,9 @@ extern "C" int ramx_dev_pileup(ramx_dev *d, const ramx_flank *flanks, int32_t n_
       (n_families && (!fam_first || !fam_count || !rows)))
   { ramx_set_error("ramx_dev_pileup: bad argument"); return RAMX_ERR_ARG; }
   if (p->bandwidth < 1 || p->L < 0) { ramx_set_error("ramx_dev_pileup: bad bandwidth / L"); return RAMX_ERR_ARG; }
-  PileupPlan pl;
+  ReplayPlan pl;
   int rc;
-  if ((rc = pileup_plan("ramx_dev_pileup", n_padded, fam_first, fam_count, n_families, p->L, cons, rows, NULL, true, pl)) != RAMX_OK) return rc;
+  if ((rc = replay_plan("ramx_dev_pileup", n_padded, fam_first, fam_count, n_families, p->L, cons, rows, NULL, true, pl)) != RAMX_OK) return rc;
   if (pl.maxrows > 0 && !cols) { ramx_set_error("ramx_dev_pileup: cols missing"); return RAMX_ERR_ARG; }
   const bool run = n_families > 0 && pl.maxrows > 0 && pl.tiles > 0;
   if (run)
@@ -2055,9 +1998,9 @@ extern "C" int ramx_dev_refine(ramx_dev *d, const ramx_flank *flanks, int32_t n_
   if (dev_is_multi(d))
   { ramx_set_error("ramx_dev_refine: not with a communicator or mailbox route active (the re-call needs the counts of every rank)"); return RAMX_ERR_UNSUPPORTED; }
   const int L = p->L;
-  PileupPlan pl;
+  ReplayPlan pl;
   int rc;
-  if ((rc = pileup_plan("ramx_dev_refine", n_padded, fam_first, fam_count, n_families, L, cons_in, rows_in, NULL, true, pl)) != RAMX_OK) return rc;
+  if ((rc = replay_plan("ramx_dev_refine", n_padded, fam_first, fam_count, n_families, L, cons_in, rows_in, NULL, true, pl)) != RAMX_OK) return rc;
   if (pl.maxrows > 0 && (!cols || !cons_out)) { ramx_set_error("ramx_dev_refine: cons_out / cols missing"); return RAMX_ERR_ARG; }
   std::vector<int8_t> cur((size_t)(n_families > 0 ? n_families : 1) * (L > 0 ? L : 1), 0), next((size_t)(L > 0 ? L : 1));
   std::vector<int32_t> rows(rows_in, rows_in + n_families);
@@ -2072,10 +2015,12 @@ extern "C" int ramx_dev_refine(ramx_dev *d, const ramx_flank *flanks, int32_t n_
   bool set_up = false;
   for (int it = 0; it < max_replays && left > 0; it++)
   {
-    if ((rc = pileup_plan("ramx_dev_refine", n_padded, fam_first, fam_count, n_families, L, cur.data(), rows.data(), active.data(), false, pl)) != RAMX_OK) return rc;
+    // only the families that have not converged replay: the tiles of the others belong to none in this replay's table
+    if ((rc = replay_plan("ramx_dev_refine", n_padded, fam_first, fam_count, n_families, L, cur.data(), rows.data(), active.data(), false, pl)) != RAMX_OK) return rc;
     const bool run = pl.maxrows > 0 && pl.tiles > 0;
     if (run)
     {
+      // once per call, not per replay: the flanks and their windows do not change
       if (!set_up && (rc = pileup_setup(d, flanks, n_padded, n_families, p, aa, &KW)) != RAMX_OK) return rc;
       set_up = true;
       if ((rc = pileup_replay(d, "ramx_dev_refine", aa, KW, pl, n_families, cur.data(), rows.data(), kernel_ms)) != RAMX_OK) return rc;
@@ -2635,11 +2580,7 @@ extern "C" int ramx_dev_family_route_max(ramx_dev *d, const ramx_params *p)
 {
   if (!d || !p || !p->matrix) return 512;
   int tab9[RAMX_NCLASS][4];
-  for (int c = 0; c < RAMX_NCLASS; c++)
-  {
-    const int code = (c == 8) ? RAMX_SYM_N : c;
-    for (int k = 0; k < 4; k++) tab9[c][k] = p->matrix[k * 100 + code];
-  }
+  class_tab(p, tab9);
   if (d->force_chain || getenv("RAMX_NO_CP_DEVICE") != NULL || getenv("RAMX_NO_PERSISTENT") != NULL) return 512;
   const int m = ramx_cp_max_family(p->bandwidth, p->gapopen, p->gapextn, tab9, p->L);
   if (m <= 0) return 512;

@@ -472,14 +472,22 @@ static int refine_families(ramx_dev *d, int direction, const int *fidx, int nb, 
   return rc;
 }
 
+/* nx flanks padded to whole tiles of 64 with empty flanks (no base: t_lo > t_hi): a malloc'ed copy, for nx = 0 too; *npad its length */
+static ramx_flank empty_flank(void) { ramx_flank x; memset(&x, 0, sizeof(x)); x.t_lo = 1; x.t_hi = 0; x.step = 1; return x; }
+static ramx_flank *pad_to_tiles(const ramx_flank *fl, int nx, int *npad)
+{
+  const int n = *npad = (nx + 63) & ~63;
+  ramx_flank *pf = (ramx_flank *)malloc(sizeof(ramx_flank) * (size_t)(n > 0 ? n : 1));
+  if (nx > 0) memcpy(pf, fl, sizeof(ramx_flank) * (size_t)nx);
+  for (int i = nx; i < n; i++) pf[i] = empty_flank();
+  return pf;
+}
+
 /* one direction of one family: its flanks padded to whole tiles (no extendable core or ret = 0: answered by the calls on the host) */
 static int refine_direction(ramx_dev *d, int direction, int family, const ramx_flank *fl, int nx, const ramx_params *p,
                             const int8_t *cons, int ret)
 {
-  const int npad = (nx + 63) & ~63;
-  ramx_flank *pf = (ramx_flank *)malloc(sizeof(ramx_flank) * (size_t)(npad > 0 ? npad : 1));
-  if (nx > 0) memcpy(pf, fl, sizeof(ramx_flank) * (size_t)nx);
-  for (int i = nx; i < npad; i++) { memset(&pf[i], 0, sizeof(ramx_flank)); pf[i].t_lo = 1; pf[i].t_hi = 0; pf[i].step = 1; }
+  int npad; ramx_flank *pf = pad_to_tiles(fl, nx, &npad);
   const int32_t first = 0, count = nx, r = ret;
   /* cons holds at least L entries only in the batch; here it is the direction's own buffer, copied into an [1][L] block */
   int8_t *c1 = (int8_t *)calloc((size_t)(p->L > 0 ? p->L : 1), 1);
@@ -504,11 +512,8 @@ static int profile_direction(ramx_dev *d, int direction, int family, const ramx_
   }
   else
   {
-    const int npad = (nx + 63) & ~63;
-    ramx_flank *pf = (ramx_flank *)malloc(sizeof(ramx_flank) * (size_t)npad);
+    int npad; ramx_flank *pf = pad_to_tiles(fl, nx, &npad);
     last = (int32_t *)malloc(sizeof(int32_t) * (size_t)npad);
-    memcpy(pf, fl, sizeof(ramx_flank) * (size_t)nx);
-    for (int i = nx; i < npad; i++) { memset(&pf[i], 0, sizeof(ramx_flank)); pf[i].t_lo = 1; pf[i].t_hi = 0; pf[i].step = 1; }
     const int32_t first = 0, count = nx, nrows = rows;
     rc = ramx_dev_profile(d, pf, npad, &first, &count, 1, p, cons, &nrows, cols, last, NULL, NULL, NULL);
     free(pf);
@@ -543,13 +548,10 @@ static int align_direction(ramx_dev *d, int direction, int family, const ramx_fl
     free(ends);
     return RAMX_OK;
   }
-  const int npad = (nx + 63) & ~63;
-  ramx_flank *pf = (ramx_flank *)malloc(sizeof(ramx_flank) * (size_t)npad);
+  int npad; ramx_flank *pf = pad_to_tiles(fl, nx, &npad);
   ramx_aln_end *ends = (ramx_aln_end *)malloc(sizeof(ramx_aln_end) * (size_t)npad);
   int32_t *idx = (int32_t *)malloc(sizeof(int32_t) * (size_t)npad * (size_t)ret);
   int32_t *ins = (int32_t *)malloc(sizeof(int32_t) * (size_t)npad * (size_t)ret);
-  memcpy(pf, fl, sizeof(ramx_flank) * (size_t)nx);
-  for (int i = nx; i < npad; i++) { memset(&pf[i], 0, sizeof(ramx_flank)); pf[i].t_lo = 1; pf[i].t_hi = 0; pf[i].step = 1; }
   const int32_t first = 0, count = nx, nrows = ret;
   const int rc = ramx_dev_align(d, pf, npad, &first, &count, 1, p, cons, &nrows, ends, idx, ins, NULL);
   if (rc == RAMX_OK)
@@ -676,10 +678,7 @@ run_again:
   else if (g_trace_file == NULL && !verbose_rows && nx > 0 && nx <= ramx_dev_family_route_max(d, p) && L > 0 && W >= 1 && getenv("RAMX_NO_FAMILY_ROUTE") == NULL)
   {
     /* a family that fits one workgroup needs no device-wide barrier: run it as a batch of one (block-local vote) */
-    const int npad = (nx + 63) & ~63;
-    ramx_flank *pf = (ramx_flank *)malloc(sizeof(ramx_flank) * (size_t)npad);
-    memcpy(pf, fl, sizeof(ramx_flank) * (size_t)nx);
-    for (int i = nx; i < npad; i++) { memset(&pf[i], 0, sizeof(ramx_flank)); pf[i].t_lo = 1; pf[i].t_hi = 0; pf[i].step = 1; }
+    int npad; ramx_flank *pf = pad_to_tiles(fl, nx, &npad);
     th = (int32_t *)malloc(sizeof(int32_t) * (size_t)npad);
     tp = (int32_t *)malloc(sizeof(int32_t) * (size_t)npad);
     const int32_t first = 0, count = nx;
@@ -971,7 +970,7 @@ int ramx_extend_batch(int direction, ramx_family *fam, int32_t F, const ramx_par
     const int nx = ramx_resolve_flanks(direction, &fam[f].cores, W, L, tmp, tmap);
     first[nb] = (int32_t)fpos; count[nb] = nx; fidx[nb] = f;
     for (int i = 0; i < nx; i++) { fl[fpos] = tmp[i]; fl[fpos].start += (int64_t)at; map[fpos] = tmap[i]; fpos++; }
-    while (fpos & 63) { memset(&fl[fpos], 0, sizeof(ramx_flank)); fl[fpos].t_lo = 1; fl[fpos].t_hi = 0; fl[fpos].step = 1; map[fpos] = -1; fpos++; }
+    while (fpos & 63) { fl[fpos] = empty_flank(); map[fpos] = -1; fpos++; }
     free(tmp); free(tmap);
     nb++;
   }

@@ -136,86 +136,6 @@ class Device:
                    "ramx_dev_download")
         return cons[:rows], th[:self.nx], tp[:self.nx]
 
-    def profile(self, flanks, p: ExtendParams, cons, rows=None, fam_first=None, fam_count=None, row_best: bool = False,
-                out: Optional[np.ndarray] = None) -> ProfileResult:
-        """Replay flanks along a given consensus (C-ABI ramx_dev_profile).  One family: `flanks` = (array, n) as
-        resolve_flanks returns it (padded here), `cons` a 1-D int8 array, `rows` its length unless given.  Several families:
-        `flanks` = (array, n_padded) already laid out in tiles of 64, fam_first / fam_count per family, `cons`
-        [n_families][L], `rows` per family.  `out`: a COL_PROFILE_DTYPE array [n_families][L] to write into (entries beyond
-        rows[f] are left alone)."""
-        cp, keep = _params(p)
-        L = p.L
-        if fam_first is None:
-            n = flanks[1]
-            arr, npad = pad_flanks(flanks)
-            fam_first, fam_count = [0], [n]
-            c1 = np.asarray(cons, np.int8).ravel()
-            rows = [len(c1) if rows is None else int(rows)]
-            cons = np.zeros((1, max(L, 1)), np.int8)
-            cons[0, :min(len(c1), L)] = c1[:L]
-        else:
-            arr, npad = flanks
-        nf = len(fam_first)
-        first = np.ascontiguousarray(fam_first, np.int32)
-        count = np.ascontiguousarray(fam_count, np.int32)
-        rows_a = np.ascontiguousarray(rows, np.int32)
-        cons = np.ascontiguousarray(cons, np.int8)
-        assert cons.size >= nf * L and len(rows_a) == nf
-        cols = out if out is not None else np.zeros((nf, max(L, 1)), COL_PROFILE_DTYPE)
-        assert cols.dtype == COL_PROFILE_DTYPE and cols.flags.c_contiguous and cols.size >= nf * L
-        last = np.full(max(npad, 1), -1, np.int32)
-        rb = rbi = None
-        if row_best:
-            mr = int(rows_a.max()) if nf else 0
-            rb = np.zeros((max(mr, 1), max(npad, 1)), np.int32)
-            rbi = np.zeros((max(mr, 1), max(npad, 1)), np.int32)
-        ms = C.c_double()
-        _lib.check(self._L.ramx_dev_profile(self._h, arr, npad, first.ctypes.data, count.ctypes.data, nf, C.byref(cp),
-                                            cons.ctypes.data, rows_a.ctypes.data, cols.ctypes.data, last.ctypes.data,
-                                            rb.ctypes.data if row_best else None, rbi.ctypes.data if row_best else None,
-                                            C.byref(ms)), "ramx_dev_profile")
-        return ProfileResult(cols, last[:npad], rb, rbi, ms.value)
-
-    def align(self, flanks, p: ExtendParams, cons, rows=None, fam_first=None, fam_count=None, columns: bool = True,
-              out: Optional[AlignResult] = None) -> AlignResult:
-        """Align every flank to a given consensus (C-ABI ramx_dev_align): arguments as profile().  columns=False: only the
-        per-flank records.  `out`: a result to write into (entries of tiles outside every family are left alone)."""
-        cp, keep = _params(p)
-        L = p.L
-        if fam_first is None:
-            n = flanks[1]
-            arr, npad = pad_flanks(flanks)
-            fam_first, fam_count = [0], [n]
-            c1 = np.asarray(cons, np.int8).ravel()
-            rows = [len(c1) if rows is None else int(rows)]
-            cons = np.zeros((1, max(L, 1)), np.int8)
-            cons[0, :min(len(c1), L)] = c1[:L]
-        else:
-            arr, npad = flanks
-        nf = len(fam_first)
-        first = np.ascontiguousarray(fam_first, np.int32)
-        count = np.ascontiguousarray(fam_count, np.int32)
-        rows_a = np.ascontiguousarray(rows, np.int32)
-        cons = np.ascontiguousarray(cons, np.int8)
-        assert cons.size >= nf * L and len(rows_a) == nf
-        mr = max(int(rows_a.max()) if nf else 0, 0)
-        if out is not None:
-            ends, idx, ins = out.ends, out.col_idx, out.col_ins
-            assert ends.dtype == ALN_END_DTYPE and ends.flags.c_contiguous and len(ends) >= npad
-            assert not columns or (idx.shape == ins.shape and idx.shape[0] >= mr and idx.shape[1] == npad and
-                                   idx.flags.c_contiguous and ins.flags.c_contiguous)
-        else:
-            ends = np.zeros(max(npad, 1), ALN_END_DTYPE)
-            ends["end_row"] = ends["end_idx"] = -1
-            idx = np.full((max(mr, 1), max(npad, 1)), ALN_NONE, np.int32) if columns else None
-            ins = np.zeros((max(mr, 1), max(npad, 1)), np.int32) if columns else None
-        ms = (C.c_double * 2)()
-        _lib.check(self._L.ramx_dev_align(self._h, arr, npad, first.ctypes.data, count.ctypes.data, nf, C.byref(cp),
-                                          cons.ctypes.data, rows_a.ctypes.data, ends.ctypes.data,
-                                          idx.ctypes.data if columns else None, ins.ctypes.data if columns else None, ms),
-                   "ramx_dev_align")
-        return AlignResult(ends, idx if columns else None, ins if columns else None, ms[0], ms[1])
-
     def _families(self, flanks, p, cons, rows, fam_first, fam_count):
         """The argument forms of profile() -> (flank array, n_padded, first, count, cons [nf][L], rows)."""
         L = p.L
@@ -242,6 +162,55 @@ class Device:
         ends = np.zeros(max(npad, 1), ALN_END_DTYPE)
         ends["end_row"] = ends["end_idx"] = -1
         return ends
+
+    def profile(self, flanks, p: ExtendParams, cons, rows=None, fam_first=None, fam_count=None, row_best: bool = False,
+                out: Optional[np.ndarray] = None) -> ProfileResult:
+        """Replay flanks along a given consensus (C-ABI ramx_dev_profile).  One family: `flanks` = (array, n) as
+        resolve_flanks returns it (padded here), `cons` a 1-D int8 array, `rows` its length unless given.  Several families:
+        `flanks` = (array, n_padded) already laid out in tiles of 64, fam_first / fam_count per family, `cons`
+        [n_families][L], `rows` per family.  `out`: a COL_PROFILE_DTYPE array [n_families][L] to write into (entries beyond
+        rows[f] are left alone)."""
+        cp, keep = _params(p)
+        arr, npad, first, count, cons, rows_a = self._families(flanks, p, cons, rows, fam_first, fam_count)
+        nf, L = len(first), p.L
+        cols = out if out is not None else np.zeros((nf, max(L, 1)), COL_PROFILE_DTYPE)
+        assert cols.dtype == COL_PROFILE_DTYPE and cols.flags.c_contiguous and cols.size >= nf * L
+        last = np.full(max(npad, 1), -1, np.int32)
+        rb = rbi = None
+        if row_best:
+            mr = int(rows_a.max()) if nf else 0
+            rb = np.zeros((max(mr, 1), max(npad, 1)), np.int32)
+            rbi = np.zeros((max(mr, 1), max(npad, 1)), np.int32)
+        ms = C.c_double()
+        _lib.check(self._L.ramx_dev_profile(self._h, arr, npad, first.ctypes.data, count.ctypes.data, nf, C.byref(cp),
+                                            cons.ctypes.data, rows_a.ctypes.data, cols.ctypes.data, last.ctypes.data,
+                                            rb.ctypes.data if row_best else None, rbi.ctypes.data if row_best else None,
+                                            C.byref(ms)), "ramx_dev_profile")
+        return ProfileResult(cols, last[:npad], rb, rbi, ms.value)
+
+    def align(self, flanks, p: ExtendParams, cons, rows=None, fam_first=None, fam_count=None, columns: bool = True,
+              out: Optional[AlignResult] = None) -> AlignResult:
+        """Align every flank to a given consensus (C-ABI ramx_dev_align): arguments as profile().  columns=False: only the
+        per-flank records.  `out`: a result to write into (entries of tiles outside every family are left alone)."""
+        cp, keep = _params(p)
+        arr, npad, first, count, cons, rows_a = self._families(flanks, p, cons, rows, fam_first, fam_count)
+        nf = len(first)
+        mr = max(int(rows_a.max()) if nf else 0, 0)
+        if out is not None:
+            ends, idx, ins = out.ends, out.col_idx, out.col_ins
+            assert ends.dtype == ALN_END_DTYPE and ends.flags.c_contiguous and len(ends) >= npad
+            assert not columns or (idx.shape == ins.shape and idx.shape[0] >= mr and idx.shape[1] == npad and
+                                   idx.flags.c_contiguous and ins.flags.c_contiguous)
+        else:
+            ends = self._no_ends(npad)
+            idx = np.full((max(mr, 1), max(npad, 1)), ALN_NONE, np.int32) if columns else None
+            ins = np.zeros((max(mr, 1), max(npad, 1)), np.int32) if columns else None
+        ms = (C.c_double * 2)()
+        _lib.check(self._L.ramx_dev_align(self._h, arr, npad, first.ctypes.data, count.ctypes.data, nf, C.byref(cp),
+                                          cons.ctypes.data, rows_a.ctypes.data, ends.ctypes.data,
+                                          idx.ctypes.data if columns else None, ins.ctypes.data if columns else None, ms),
+                   "ramx_dev_align")
+        return AlignResult(ends, idx if columns else None, ins if columns else None, ms[0], ms[1])
 
     def pileup(self, flanks, p: ExtendParams, cons, rows=None, fam_first=None, fam_count=None) -> PileupResult:
         """Pileup of every family along a given consensus (C-ABI ramx_dev_pileup): arguments as profile()."""

@@ -1,0 +1,20 @@
+#!/bin/bash
+# Host code of the replays under AddressSanitizer + UBSan, as stand-alone programs on the CPU (no GPU is opened, nothing is
+# loaded into python): replay_plan of ramx_device.hip and pad_to_tiles of ramx_extend.c, both static, so each program includes
+# its source file and takes the rest of the library from the built libramx.so.
+# usage: tools/host_asan/run.sh        (after the library has been built)
+set -euo pipefail
+here=$(cd "$(dirname "$0")" && pwd)
+root=$(cd "$here/../.." && pwd)
+rocm=${ROCM:-/opt/rocm}
+out=$(mktemp -d)
+trap 'rm -rf "$out"' EXIT
+inc="-I$root/include -I$root/repeatafterme_amd/csrc"
+lib="-L$root/repeatafterme_amd -lramx -Wl,-rpath,$root/repeatafterme_amd -Wl,-rpath,$rocm/lib"
+san="-fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g"
+gcc -std=gnu11 -O1 -Wno-alloc-size-larger-than $san $inc -o "$out/pad_to_tiles" "$here/pad_to_tiles_main.c" $lib -lm -lpthread
+"$out/pad_to_tiles"
+# (the device side of ramx_device.hip is compiled too, which takes a minute or two: the host object refers to its code object)
+"$rocm/bin/hipcc" --offload-arch=gfx950 -x hip -std=c++17 -O1 -g -fno-omit-frame-pointer $inc -Xarch_host -fsanitize=address,undefined \
+  -Xarch_host -fno-sanitize-recover=undefined -o "$out/replay_plan" "$here/replay_plan_main.cpp" $lib -L"$rocm/lib" -lrccl -lpthread
+"$out/replay_plan"
