@@ -197,6 +197,23 @@ typedef struct ramx_refinement
 typedef void (*ramx_refine_cb)(const ramx_refinement *rf, void *user);
 void ramx_set_refine_sink(ramx_refine_cb cb, void *user, int32_t max_replays);
 
+/* Copies sink of seam 1, as the other sinks: with a sink set the per-copy statistics of every direction that has run
+ * (ramx_dev_copy_stats, below) are taken along the kept consensus -- rows = ret columns, rows_reversed = !direction -- and
+ * handed over once per direction and family.  ends and stats are [n_flanks].  A direction without an extendable core or with
+ * ret = 0 is answered on the host (zero records).  cb == NULL (the default): off -- nothing is launched or allocated for it. */
+struct ramx_copy_stats;
+typedef struct ramx_copies
+{
+  int32_t direction, family /* index in a batch, else 0 */, rows /* = ret */, n_flanks;
+  const int8_t *cons;                 /* [rows] */
+  const struct ramx_flank *flanks;    /* [n_flanks], positions in the family's own library */
+  const int32_t *core_index;          /* [n_flanks] */
+  const struct ramx_aln_end *ends;    /* [n_flanks] */
+  const struct ramx_copy_stats *stats;/* [n_flanks] */
+} ramx_copies;
+typedef void (*ramx_copies_cb)(const ramx_copies *cp, void *user);
+void ramx_set_copies_sink(ramx_copies_cb cb, void *user);
+
 /* Seam 1 keeps the library on the device between calls, keyed on (pointer, length, 64-bit content fingerprint), so
  * the second direction does not upload it again (libraries above 64 MiB are fingerprinted in chunks by worker threads; when
  * pointer and length match the device copy the content check runs beside the direction and is joined before the write-back).
@@ -439,6 +456,51 @@ int ramx_dev_refine(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, con
                     const int8_t *cons_in, const int32_t *rows_in, int32_t max_replays,
                     int8_t *cons_out, int32_t *rows_out, int32_t *replays, int32_t *converged,
                     ramx_col_pileup *cols, ramx_aln_end *ends, double *kernel_ms);
+
+/* Per-copy statistics of an extension: how the alignment of every flank to a GIVEN consensus cons[0..rows) divides up -- the
+ * pileup's transpose, summed over the rows of a flank where the pileup sums over the flanks of a column.  Everything is defined
+ * on the flank's ramx_aln_end, col_idx[r] and col_ins[r]; base classes are the pileup's.
+ *   CpG: with rows_reversed == 0 the rows run 5'->3' (the right extension), with 1 against the reading order (the left
+ *   extension, whose rows run outward from the core): the next column of r in reading order is r + 1, or r - 1 when reversed.
+ *   Column r lies in a CpG if cons[r] is C and its next column exists and is G, or if cons[r] is G and its previous column
+ *   exists and is C; only columns < rows exist.
+ * match + ts + tv + n_match + del == cols for every flank.  Padding flanks and flanks without an alignment: all zero.  The
+ * struct is 48 bytes without padding. */
+typedef struct ramx_copy_stats
+{
+  int32_t cols;       /* columns the copy's path covers: end_row + 1; 0 without an alignment */
+  int32_t match;      /* column matched to a base of class A C G T equal to cons[r] */
+  int32_t ts;         /* ... to the other purine / the other pyrimidine (A<->G, C<->T) */
+  int32_t tv;         /* ... to a base of the other kind */
+  int32_t n_match;    /* column matched to class 4 (N, outside the flank's bounds, outside the library) */
+  int32_t del;        /* col_idx[r] == RAMX_ALN_DELETED, r <= end_row */
+  int32_t del_open;   /* ... of which r == 0, or col_idx[r-1] != RAMX_ALN_DELETED, or col_ins[r] > 0 */
+  int32_t ins;        /* sum of col_ins[r] over r <= end_row (tail_ins is counted nowhere, as in the pileup) */
+  int32_t ins_open;   /* rows r <= end_row with col_ins[r] > 0 */
+  int32_t cpg_cols;   /* columns counted in match + ts + tv that lie in a CpG of the consensus */
+  int32_t cpg_ts;     /* ... of which counted in ts */
+  int32_t score;      /* ramx_aln_end.score */
+} ramx_copy_stats;
+
+/* The statistics on the device: ramx_dev_align's forward pass and walk, then one wave per tile with one lane per flank goes down
+ * the tile's columns and every lane writes its flank's record.  Flank layout, argument checks, self-containedness and the
+ * budget of RAMX_ALIGN_BYTES as ramx_dev_pileup.  stats is [n_padded]: the records of the tiles of every family are all
+ * written, those of tiles outside every family are left as they are; ends is [n_padded] or NULL.  A family with rows[f] == 0 is
+ * answered on the host (zero records, no alignment).  kernel_ms (may be NULL): three values, the HIP-event times of the forward
+ * kernels, of the walk kernels and of the statistics kernel.  With a communicator or mailbox route active the call is
+ * rank-local, which is all there is to it: the records are per flank. */
+int ramx_dev_copy_stats(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                        const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                        const int8_t *cons, const int32_t *rows, int32_t rows_reversed,
+                        ramx_copy_stats *stats, ramx_aln_end *ends, double *kernel_ms);
+
+/* Kimura two-parameter divergence of a copy from its consensus, in percent (plain host C).  sites = match + ts + tv,
+ * p = ts / sites, q = tv / sites, a = 1 - 2p - q, b = 1 - 2q: -1/2 ln(a sqrt(b)) * 100; -1 (undefined) if sites == 0, a <= 0
+ * or b <= 0. */
+double ramx_copy_kimura(const ramx_copy_stats *s);
+/* The mean of ramx_copy_kimura over the copies with sites >= max(min_sites, 1) and a defined value; n_used (may be NULL)
+ * receives their number.  0.0 when there are none. */
+double ramx_family_divergence(const ramx_copy_stats *stats, int32_t n, int32_t min_sites, int32_t *n_used);
 
 /* multi-GPU: flanks are sharded over ranks; each column's 4 candidate sums are all-reduced
  * (4 x int64, RCCL over xGMI).  unique_id is the 128-byte ncclUniqueId made by rank 0

@@ -22,6 +22,7 @@ EXPORTS = [
     "ramx_dev_profile", "ramx_set_profile_sink",
     "ramx_dev_align", "ramx_set_align_sink",
     "ramx_dev_pileup", "ramx_recall_consensus", "ramx_dev_refine", "ramx_set_refine_sink",
+    "ramx_dev_copy_stats", "ramx_copy_kimura", "ramx_family_divergence", "ramx_set_copies_sink",
 ]
 
 
@@ -82,6 +83,19 @@ class RefineRec(C.Structure):       # ramx_refinement
 
 
 REFINE_CB = C.CFUNCTYPE(None, C.POINTER(RefineRec), C.c_void_p)
+
+
+class CopyStats(C.Structure):       # ramx_copy_stats
+    _fields_ = [(k, C.c_int32) for k in ("cols", "match", "ts", "tv", "n_match", "del_", "del_open", "ins", "ins_open", "cpg_cols",
+                                          "cpg_ts", "score")]
+
+
+class CopiesRec(C.Structure):       # ramx_copies
+    _fields_ = [(k, C.c_int32) for k in ("direction", "family", "rows", "n_flanks")] + \
+               [(k, C.c_void_p) for k in ("cons", "flanks", "core_index", "ends", "stats")]
+
+
+COPIES_CB = C.CFUNCTYPE(None, C.POINTER(CopiesRec), C.c_void_p)
 
 
 def build(force: bool = False) -> None:
@@ -153,6 +167,15 @@ def lib() -> C.CDLL:
         L.ramx_dev_refine.restype = C.c_int
         L.ramx_set_refine_sink.argtypes = [REFINE_CB, C.c_void_p, C.c_int32]
         L.ramx_set_refine_sink.restype = None
+        L.ramx_dev_copy_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Params),
+                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ramx_dev_copy_stats.restype = C.c_int
+        L.ramx_copy_kimura.argtypes = [C.c_void_p]
+        L.ramx_copy_kimura.restype = C.c_double
+        L.ramx_family_divergence.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+        L.ramx_family_divergence.restype = C.c_double
+        L.ramx_set_copies_sink.argtypes = [COPIES_CB, C.c_void_p]
+        L.ramx_set_copies_sink.restype = None
         if hasattr(L, "ramx_cli_main"):
             L.ramx_cli_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
         _lib = L

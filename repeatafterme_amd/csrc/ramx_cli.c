@@ -90,6 +90,8 @@ static void usage(void)
     "     -stopafter <num>      # Stop the alignment after this number of no-progress columns (100).\n"
     "     -minlength <num>      # Minimum required length for a sequence to be reported (50).\n"
     "     -outmat <file>        # Dump the dp matrix paths to a file for debugging.\n"
+    "     -outcopies <file>     # Save every copy's divergence from the extension consensus\n"
+    "                           #   ( matches, transitions, transversions, gaps, Kimura ) to a TSV file.\n"
     "     -version              # Print out one-line version information\n"
     "     -v[v[v[v]]]           # How verbose do you want it to be?  -vvvv is super-verbose.\n"
     "\n"
@@ -241,7 +243,7 @@ static void warm_start(void)
 /* everything the command line decides */
 struct cli_opts
 {
-  const char *ranges_file, *outtsv, *outfa, *outmat, *cons_file, *seq_file, *matrix_name, *batch_file, *outprofile, *outaln, *outpileup, *outrefined;
+  const char *ranges_file, *outtsv, *outfa, *outmat, *cons_file, *seq_file, *matrix_name, *batch_file, *outprofile, *outaln, *outpileup, *outrefined, *outcopies;
   int refine;
   int flanking, L, bandwidth, maxn, when_to_stop, num_threads, verbose;
   int gap_ext, gap_open, match, mismatch, cappenalty, minimprovement, is_rs;
@@ -465,7 +467,7 @@ static void write_results(const struct cli_opts *o, struct coreAlignment *cores,
  */
 struct batch_item
 {
-  char *ranges, *log, *cons, *tsv, *fa, *profile, *aln, *pileup, *refined;
+  char *ranges, *log, *cons, *tsv, *fa, *profile, *aln, *pileup, *refined, *copies;
   struct coreAlignment *cores;
   struct sequenceLibrary *lib;
   int N, rightbp, leftbp;
@@ -716,6 +718,77 @@ static void refined_write(struct refine_family *f)
   fclose(fp);
 }
 
+/*
+ * -outcopies <file>: every extendable core's divergence from the kept consensus of both extensions (include/ramx.h,
+ * ramx_copy_stats, ramx_set_copies_sink) as a TSV, the right block first: one line per extendable core in flank order, named as
+ * -outaln names it, then one summary line "#<dir> copies= used= kimura=" with the family's mean Kimura divergence over the
+ * copies that have one (min_sites = 1).  The names need both directions' lengths, so the sink keeps the records and the file
+ * is written with the other results.
+ */
+struct copies_rec { int core, end_row, start, end; ramx_copy_stats st; };
+struct copies_block { int have, n; struct copies_rec *rec; };
+struct copies_family { const char *path; struct sequenceLibrary *lib; struct copies_block blk[2]; };
+struct copies_out { struct copies_family *fam; };
+static const char k_copies_header[] =
+  "dir\tcopy\tend_row\tstart\tend\tscore\tcols\tmatch\tts\ttv\tn\tdel\tdel_open\tins\tins_open\tcpg_cols\tcpg_ts\tkimura\n";
+
+static void copies_sink(const ramx_copies *cp, void *user)
+{
+  struct copies_family *cf = &((const struct copies_out *)user)->fam[cp->family];
+  if (!cf->path) return;
+  struct copies_block *b = &cf->blk[cp->direction ? 1 : 0];
+  b->have = 1; b->n = cp->n_flanks;
+  b->rec = (struct copies_rec *)calloc((size_t)(cp->n_flanks > 0 ? cp->n_flanks : 1), sizeof(struct copies_rec));
+  for (int i = 0; i < cp->n_flanks; i++)
+  {
+    const ramx_aln_end *e = &cp->ends[i];
+    struct copies_rec *rc = &b->rec[i];
+    rc->core = cp->core_index[i]; rc->end_row = e->end_row; rc->start = e->start_idx; rc->end = e->end_idx; rc->st = cp->stats[i];
+  }
+}
+
+/* after both directions: the file, then the buffers are released */
+static void copies_write(struct copies_family *cf, struct coreAlignment *cores, int flanking)
+{
+  if (!cf->path) return;
+  FILE *fp = fopen(cf->path, "w");
+  if (!fp) { fprintf(stderr, "Could not create the copies file %s\n", cf->path); exit(1); }
+  fputs(k_copies_header, fp);
+  int cnt = 0;
+  for (struct coreAlignment *s = cores; s != NULL; s = s->next) cnt++;
+  struct coreAlignment **arr = (struct coreAlignment **)malloc(sizeof(*arr) * (size_t)(cnt ? cnt : 1));
+  cnt = 0;
+  for (struct coreAlignment *s = cores; s != NULL; s = s->next) arr[cnt++] = s;
+  for (int dir = 1; dir >= 0; dir--)
+  {
+    struct copies_block *b = &cf->blk[dir];
+    if (!b->have) continue;
+    const char *tag = dir ? "right" : "left";
+    ramx_copy_stats *all = (ramx_copy_stats *)malloc(sizeof(ramx_copy_stats) * (size_t)(b->n > 0 ? b->n : 1));
+    for (int i = 0; i < b->n; i++)
+    {
+      const struct copies_rec *rc = &b->rec[i];
+      const ramx_copy_stats *t = &rc->st;
+      char id[1024];
+      if (rc->core < 0 || rc->core >= cnt) { fprintf(stderr, "RAMExtend(ramx): copy record of an unknown core %d\n", rc->core); exit(1); }
+      aln_record_id(id, sizeof(id), arr[rc->core], cf->lib, flanking);
+      fprintf(fp, "%s\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t", tag, id, rc->end_row, rc->start, rc->end, t->score,
+              t->cols, t->match, t->ts, t->tv, t->n_match, t->del, t->del_open, t->ins, t->ins_open, t->cpg_cols, t->cpg_ts);
+      const double k = ramx_copy_kimura(t);
+      if (k < 0) fputs("NA\n", fp);
+      else fprintf(fp, "%.4f\n", k);
+      all[i] = *t;
+    }
+    int32_t used = 0;
+    const double div = ramx_family_divergence(all, b->n, 1, &used);
+    fprintf(fp, "#%s\tcopies=%d\tused=%d\tkimura=%.4f\n", tag, b->n, (int)used, div);
+    free(all); free(b->rec);
+    memset(b, 0, sizeof(*b));
+  }
+  free(arr);
+  fclose(fp);
+}
+
 /* flat view of a core list for ramx_extend_batch (arrays owned by the caller's arena) */
 static void flatten_cores(struct coreAlignment *cores, int N, ramx_flat_cores *fc)
 {
@@ -771,6 +844,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   if (o->outaln != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's alignment file is the seventh field of its line in the list\n"); exit(1); }
   if (o->outpileup != NULL || o->outrefined != NULL)
   { fprintf(stderr, "RAMExtend(ramx): with -batch every family's pileup file is the eighth field of its line in the list and its refined consensus the ninth\n"); exit(1); }
+  if (o->outcopies != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's copies file is the tenth field of its line in the list\n"); exit(1); }
   FILE *lf = fopen(o->batch_file, "r");
   if (!lf) { fprintf(stderr, "Could not open batch list %s\n", o->batch_file); exit(1); }
   size_t cap = 64, F = 0;
@@ -782,9 +856,9 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   {
     while (len > 0 && (line[len - 1] == '\n' || line[len - 1] == '\r')) line[--len] = 0;
     if (line[0] == '#' || line[0] == 0) continue;
-    char *f[9] = { NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL };
+    char *f[10] = { NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL };
     char *p = line;
-    for (int k = 0; k < 9 && p; k++) { f[k] = p; char *t = strchr(p, '\t'); if (t) { *t = 0; p = t + 1; } else p = NULL; }
+    for (int k = 0; k < 10 && p; k++) { f[k] = p; char *t = strchr(p, '\t'); if (t) { *t = 0; p = t + 1; } else p = NULL; }
     if (!f[0] || !f[1]) { fprintf(stderr, "batch list: every line needs at least <ranges><TAB><log>\n"); exit(1); }
     if (F == cap) { cap *= 2; it = (struct batch_item *)realloc(it, cap * sizeof(*it)); memset(it + F, 0, (cap - F) * sizeof(*it)); }
     it[F].ranges = strdup(f[0]); it[F].log = strdup(f[1]);
@@ -795,6 +869,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
     it[F].aln = field_or_null(f[6]) ? strdup(f[6]) : NULL;           /* optional seventh field: the family's -outaln file */
     it[F].pileup = field_or_null(f[7]) ? strdup(f[7]) : NULL;        /* optional eighth field: the family's -outpileup file */
     it[F].refined = field_or_null(f[8]) ? strdup(f[8]) : NULL;       /* optional ninth field: the family's -outrefined file */
+    it[F].copies = field_or_null(f[9]) ? strdup(f[9]) : NULL;        /* optional tenth field: the family's -outcopies file */
     F++;
   }
   free(line);
@@ -850,6 +925,11 @@ static int run_batch(struct cli_opts *o, time_t t_start)
     if ((rout.fam[i].refined = it[i].refined) != NULL) any_refined = 1;
   }
   if (any_pileup || any_refined) ramx_set_refine_sink(refine_sink, &rout, any_refined ? o->refine : 1);
+  struct copies_out cout = { (struct copies_family *)calloc(F ? F : 1, sizeof(struct copies_family)) };
+  int any_copies = 0;
+  for (size_t i = 0; i < F; i++)
+    if ((cout.fam[i].path = it[i].copies) != NULL) { cout.fam[i].lib = it[i].lib; any_copies = 1; }
+  if (any_copies) ramx_set_copies_sink(copies_sink, &cout);
   /* phase 2: right extension of all families in one launch; phase 3: per family, overlap avoidance */
   for (size_t i = 0; i < F; i++) flatten_cores(it[i].cores, it[i].N, &fam[i].cores);
   if (ramx_extend_batch(1, fam, (int32_t)F, &p, ir) < 0) { fprintf(stderr, "RAMExtend(ramx): batch extension failed: %s\n", ramx_last_error()); exit(1); }
@@ -882,6 +962,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
     write_results(o, it[i].cores, it[i].lib, it[i].master, it[i].rightbp, it[i].leftbp, it[i].cons, it[i].tsv, it[i].fa);
     aln_write(&aout.fam[i], it[i].cores, o->flanking);
     refined_write(&rout.fam[i]);
+    copies_write(&cout.fam[i], it[i].cores, o->flanking);
     const double duration = difftime(time(0), t_start);
     printf("Program duration is %.1f sec = %.1f min = %.1f hr\n", duration, duration / 60.0, duration / 3600.0);
   }
@@ -893,12 +974,13 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   {
     ramx_free_library(it[i].lib, it[i].cores);
     free(it[i].master); free(it[i].ranges); free(it[i].log); free(it[i].cons); free(it[i].tsv); free(it[i].fa); free(it[i].profile); free(it[i].aln);
-    free(it[i].pileup); free(it[i].refined);
+    free(it[i].pileup); free(it[i].refined); free(it[i].copies);
   }
   ramx_set_profile_sink(NULL, NULL);
   ramx_set_align_sink(NULL, NULL);
   ramx_set_refine_sink(NULL, NULL, 1);
-  free(aout.fam); free(rout.fam);
+  ramx_set_copies_sink(NULL, NULL);
+  free(aout.fam); free(rout.fam); free(cout.fam);
   free(profile_paths);
   free(it); free(fam); free(ir); free(il); free(mflat);
   ramx_free_scoring_system(o->sp);
@@ -930,6 +1012,7 @@ int ramx_cli_main(int argc, char **argv)
   opt_string(argc, argv, "-outaln", &o.outaln);
   opt_string(argc, argv, "-outpileup", &o.outpileup);
   opt_string(argc, argv, "-outrefined", &o.outrefined);
+  opt_string(argc, argv, "-outcopies", &o.outcopies);
   if (!opt_int(argc, argv, "-refine", &o.refine)) o.refine = 10;
   if (o.refine < 1) { fprintf(stderr, "RAMExtend(ramx): -refine takes the largest number of replays, at least 1\n"); exit(1); }
   if (!opt_int(argc, argv, "-L", &o.L)) o.L = 10000;
@@ -1031,6 +1114,11 @@ int ramx_cli_main(int argc, char **argv)
   struct refine_out rout = { &rfam };
   if (o.outpileup != NULL) pileup_start(o.outpileup);
   if (o.outpileup != NULL || o.outrefined != NULL) ramx_set_refine_sink(refine_sink, &rout, o.outrefined != NULL ? o.refine : 1);
+  struct copies_family cfam;
+  memset(&cfam, 0, sizeof(cfam));
+  cfam.path = o.outcopies; cfam.lib = lib;
+  struct copies_out cout = { &cfam };
+  if (o.outcopies != NULL) ramx_set_copies_sink(copies_sink, &cout);
   fflush(stdout);
   warm_join();
   phase_done("device ready");
@@ -1045,9 +1133,11 @@ int ramx_cli_main(int argc, char **argv)
   ramx_set_profile_sink(NULL, NULL);
   ramx_set_align_sink(NULL, NULL);
   ramx_set_refine_sink(NULL, NULL, 1);
+  ramx_set_copies_sink(NULL, NULL);
   write_results(&o, cores, lib, master, rightbp, leftbp, o.cons_file, o.outtsv, o.outfa);
   aln_write(&afam, cores, o.flanking);
   refined_write(&rfam);
+  copies_write(&cfam, cores, o.flanking);
   if (fp_mat != NULL) fclose(fp_mat);     /* ram_extend.c:778-779 */
   phase_done("report + outputs");
 

@@ -53,6 +53,7 @@
 #include "ramx_profile_api.h"
 #include "ramx_align_api.h"
 #include "ramx_pileup_api.h"
+#include "ramx_copystats_api.h"
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
@@ -161,7 +162,9 @@ struct ramx_dev
   size_t cap_al_codes, cap_al_ends, cap_al_idx, cap_al_ins;
   // ramx_dev_pileup / ramx_dev_refine (allocated on their first call): one group's walked columns, per-tile records, summed columns
   int *d_pl_idx, *d_pl_ins; ramx_col_pileup *d_pl_slab, *d_pl_cols;
-  size_t cap_pl_idx, cap_pl_ins, cap_pl_slab, cap_pl_cols;
+  // ramx_dev_copy_stats (allocated on its first call): one record per flank
+  ramx_copy_stats *d_cs_stats;
+  size_t cap_pl_idx, cap_pl_ins, cap_pl_slab, cap_pl_cols, cap_cs_stats;
 };
 
 extern "C" int ramx_device_count(void)
@@ -248,6 +251,7 @@ extern "C" void ramx_dev_destroy(ramx_dev *d)
   (void)hipFree(d->d_pf_slab); (void)hipFree(d->d_pf_cols); (void)hipFree(d->d_pf_last); (void)hipFree(d->d_pf_best); (void)hipFree(d->d_pf_bidx);
   (void)hipFree(d->d_al_codes); (void)hipFree(d->d_al_ends); (void)hipFree(d->d_al_idx); (void)hipFree(d->d_al_ins);
   (void)hipFree(d->d_pl_idx); (void)hipFree(d->d_pl_ins); (void)hipFree(d->d_pl_slab); (void)hipFree(d->d_pl_cols);
+  (void)hipFree(d->d_cs_stats);
   if (d->hostbox_mirror) (void)hipFree(d->hostbox_mirror);
   if (d->d_peer) (void)hipFree(d->d_peer);
   for (int i = 0; i < 2; i++) if (d->ev_chk[i]) (void)hipEventDestroy(d->ev_chk[i]);
@@ -1881,19 +1885,23 @@ extern "C" int ramx_dev_align(ramx_dev *d, const ramx_flank *flanks, int32_t n_p
 // device next to the walk (ramx_kernels_pileup.h); the re-call is host C (ramx_recall.c)
 // ------------------------------------------------------------------------------------------
 // once per call (not per replay): the shared setup, the walk's arguments and the families' summed columns
-static int pileup_setup(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, int32_t n_families, const ramx_params *p, AlnArgs &aa, int *KW)
+// (cols == false: the per-copy statistics, which have no columns)
+static int pileup_setup(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, int32_t n_families, const ramx_params *p, AlnArgs &aa, int *KW,
+                        bool cols = true)
 {
   KArgs k;
   int rc;
   if ((rc = replay_setup(d, flanks, n_padded, n_padded, n_families, p, true, k, KW)) != RAMX_OK) return rc;
-  if ((rc = ensure(&d->d_pl_cols, &d->cap_pl_cols, (size_t)n_families * p->L * sizeof(ramx_col_pileup)))) return rc;
+  if (cols && (rc = ensure(&d->d_pl_cols, &d->cap_pl_cols, (size_t)n_families * p->L * sizeof(ramx_col_pileup)))) return rc;
   return aln_args(d, k, p->L, aa);
 }
 
 // one replay of the plan's families along cons / rows: forward, walk and pileup per group of tiles, then the sum; on return
 // the stream is idle, d_pl_cols holds the families' columns and d_al_ends their flanks' records.  pl.tiles > 0, pl.maxrows > 0.
+// With cs (ramx_dev_copy_stats; its stats and reversed set by the caller) the third stage is the per-copy statistics kernel
+// instead: it reads the same group's columns, needs no per-tile records and no sum, and leaves cs->stats filled.
 static int pileup_replay(ramx_dev *d, const char *who, AlnArgs aa, int KW, const ReplayPlan &pl, int32_t n_families,
-                         const int8_t *cons, const int32_t *rows, double *kernel_ms)
+                         const int8_t *cons, const int32_t *rows, double *kernel_ms, const CopyStatsArgs *cs = NULL)
 {
   const int tiles = pl.tiles, maxrows = pl.maxrows, L = aa.L, W = aa.k.W;
   // the budget counts, per tile, the decision codes and the walked columns (col_idx, col_ins) of its 64 flanks: the columns
@@ -1904,10 +1912,19 @@ static int pileup_replay(ramx_dev *d, const char *who, AlnArgs aa, int KW, const
   if ((rc = ensure(&d->d_al_codes, &d->cap_al_codes, (size_t)group * code_bytes))) return rc;
   if ((rc = ensure(&d->d_pl_idx, &d->cap_pl_idx, (size_t)group * col_bytes))) return rc;
   if ((rc = ensure(&d->d_pl_ins, &d->cap_pl_ins, (size_t)group * col_bytes))) return rc;
-  if ((rc = ensure(&d->d_pl_slab, &d->cap_pl_slab, (size_t)tiles * maxrows * sizeof(ramx_col_pileup)))) return rc;
+  if (!cs && (rc = ensure(&d->d_pl_slab, &d->cap_pl_slab, (size_t)tiles * maxrows * sizeof(ramx_col_pileup)))) return rc;
   if ((rc = replay_upload(d, pl, n_families, L, cons, rows)) != RAMX_OK) return rc;
   const int gn = group * 64;
   aa.codes = d->d_al_codes; aa.gn = gn;
+  CopyStatsArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  if (cs)
+  {
+    ca = *cs;
+    ca.bases = d->d_bases; ca.tile_fam = d->d_rp_tile; ca.cons = d->d_rp_cons; ca.rows = d->d_rp_rows; ca.ends = d->d_al_ends;
+    ca.col_idx = d->d_pl_idx; ca.col_ins = d->d_pl_ins;
+    ca.L = L; ca.Np = aa.k.Np; ca.W = W; ca.KW = KW; ca.gn = gn;
+  }
   PileArgs pa;
   pa.bases = d->d_bases; pa.tile_fam = d->d_rp_tile; pa.cons = d->d_rp_cons; pa.rows = d->d_rp_rows; pa.ends = d->d_al_ends;
   pa.col_idx = d->d_pl_idx; pa.col_ins = d->d_pl_ins; pa.slab = d->d_pl_slab;
@@ -1927,6 +1944,13 @@ static int pileup_replay(ramx_dev *d, const char *who, AlnArgs aa, int KW, const
     if ((lrc = ramx_align_launch_preset(d->stream, d->d_pl_idx, d->d_pl_ins, (size_t)maxrows * gn)) != RAMX_OK) return lrc;     // per group
     if ((lrc = ramx_align_launch_walk(d->stream, nt, aw)) != RAMX_OK) return lrc;
     mark();
+    if (cs)
+    {
+      ca.tile0 = tile0;
+      if ((lrc = ramx_copystats_launch(d->stream, nt, ca)) != RAMX_OK) return lrc;
+      mark();
+      return RAMX_OK;
+    }
     if ((lrc = ramx_pileup_launch(d->stream, nt, pa)) != RAMX_OK) return lrc;
     // the last group's pileup stage ends with the sum over the tiles of every family
     if (tile0 + nt == tiles && (lrc = ramx_pileup_launch_sum(d->stream, n_families, maxrows, sa)) != RAMX_OK) return lrc;
@@ -1982,6 +2006,52 @@ extern "C" int ramx_dev_pileup(ramx_dev *d, const ramx_flank *flanks, int32_t n_
     if ((rc = pileup_replay(d, "ramx_dev_pileup", aa, KW, pl, n_families, cons, rows, kernel_ms)) != RAMX_OK) return rc;
   }
   return pileup_fetch(d, run, n_padded, fam_first, fam_count, n_families, p->L, cons, rows, NULL, cols, ends);
+}
+
+// ------------------------------------------------------------------------------------------
+// per-copy statistics: the pileup's replay with the statistics kernel as its third stage (ramx_kernels_copystats.h)
+// ------------------------------------------------------------------------------------------
+extern "C" int ramx_dev_copy_stats(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                                   const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                                   const int8_t *cons, const int32_t *rows, int32_t rows_reversed,
+                                   ramx_copy_stats *stats, ramx_aln_end *ends, double *kernel_ms)
+{
+  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0;
+  // the records are the result: stats is required wherever there are flanks
+  if (!d || !p || !p->matrix || n_families < 0 || n_padded < 0 || (n_padded & 63) || (n_padded && (!flanks || !stats)) ||
+      (n_families && (!fam_first || !fam_count || !rows)))
+  { ramx_set_error("ramx_dev_copy_stats: bad argument"); return RAMX_ERR_ARG; }
+  if (p->bandwidth < 1 || p->L < 0) { ramx_set_error("ramx_dev_copy_stats: bad bandwidth / L"); return RAMX_ERR_ARG; }
+  ReplayPlan pl;
+  int rc;
+  if ((rc = replay_plan("ramx_dev_copy_stats", n_padded, fam_first, fam_count, n_families, p->L, cons, rows, NULL, true, pl)) != RAMX_OK) return rc;
+  const bool run = n_families > 0 && pl.maxrows > 0 && pl.tiles > 0;
+  if (run)
+  {
+    AlnArgs aa;
+    int KW = 0;
+    if ((rc = pileup_setup(d, flanks, n_padded, n_families, p, aa, &KW, false)) != RAMX_OK) return rc;
+    if ((rc = ensure(&d->d_cs_stats, &d->cap_cs_stats, (size_t)n_padded * sizeof(ramx_copy_stats)))) return rc;
+    CopyStatsArgs cs;
+    memset(&cs, 0, sizeof(cs));
+    cs.stats = d->d_cs_stats; cs.reversed = rows_reversed != 0;
+    if ((rc = pileup_replay(d, "ramx_dev_copy_stats", aa, KW, pl, n_families, cons, rows, kernel_ms, &cs)) != RAMX_OK) return rc;
+  }
+  // the tiles of every family, copied back per family; tiles outside every family keep what the caller has there
+  for (int f = 0; f < n_families; f++)
+  {
+    const int t0 = fam_first[f] / 64, nt = (fam_count[f] + 63) / 64;
+    if (nt == 0) continue;
+    if (!run || rows[f] == 0)
+    {
+      memset(stats + (size_t)t0 * 64, 0, (size_t)nt * 64 * sizeof(ramx_copy_stats));
+      replay_no_alignment(ends, NULL, NULL, t0 * 64, (t0 + nt) * 64, 0, n_padded);
+      continue;
+    }
+    HIPCHK(hipMemcpy(stats + (size_t)t0 * 64, d->d_cs_stats + (size_t)t0 * 64, (size_t)nt * 64 * sizeof(ramx_copy_stats), hipMemcpyDeviceToHost));
+    if (ends) HIPCHK(hipMemcpy(ends + (size_t)t0 * 64, d->d_al_ends + (size_t)t0 * 64, (size_t)nt * 64 * sizeof(ramx_aln_end), hipMemcpyDeviceToHost));
+  }
+  return RAMX_OK;
 }
 
 extern "C" int ramx_dev_refine(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,

@@ -472,6 +472,42 @@ static int refine_families(ramx_dev *d, int direction, const int *fidx, int nb, 
   return rc;
 }
 
+static ramx_copies_cb g_copies_cb = NULL;
+static void *g_copies_user = NULL;
+void ramx_set_copies_sink(ramx_copies_cb cb, void *user)
+{
+  g_copies_cb = cb;
+  g_copies_user = user;
+}
+
+/* With a copies sink set: the per-copy statistics of nb families along their kept consensus (rows = ret), handed over family by
+ * family.  fl is laid out in tiles (npad flanks); cons is [nb][L]; map the flanks' positions in their core lists; lib_at (NULL:
+ * all 0) where a family's own library begins in the one the flanks address. */
+static int copies_families(ramx_dev *d, int direction, const int *fidx, int nb, const ramx_flank *fl, const int32_t *map, int32_t npad,
+                           const int32_t *first, const int32_t *count, const ramx_params *p, const int8_t *cons, const int32_t *ret,
+                           const uint64_t *lib_at)
+{
+  int32_t *nrows = (int32_t *)calloc((size_t)(nb > 0 ? nb : 1), sizeof(int32_t));
+  ramx_copy_stats *stats = (ramx_copy_stats *)calloc((size_t)(npad > 0 ? npad : 1), sizeof(ramx_copy_stats));
+  ramx_aln_end *ends = (ramx_aln_end *)malloc(sizeof(ramx_aln_end) * (size_t)(npad > 0 ? npad : 1));
+  for (int b = 0; b < nb; b++) nrows[b] = ret[b] > 0 ? ret[b] : 0;
+  const int rc = ramx_dev_copy_stats(d, fl, npad, first, count, nb, p, cons, nrows, !direction, stats, ends, NULL);
+  for (int b = 0; b < nb && rc == RAMX_OK; b++)
+  {
+    ramx_flank *own_fl = (ramx_flank *)malloc(sizeof(ramx_flank) * (size_t)(count[b] > 0 ? count[b] : 1));
+    for (int i = 0; i < count[b]; i++) { own_fl[i] = fl[first[b] + i]; if (lib_at) own_fl[i].start -= (int64_t)lib_at[fidx[b]]; }
+    ramx_copies cp;
+    memset(&cp, 0, sizeof(cp));
+    cp.direction = direction; cp.family = fidx ? fidx[b] : 0; cp.rows = nrows[b]; cp.n_flanks = count[b];
+    cp.cons = cons + (size_t)b * p->L; cp.flanks = own_fl; cp.core_index = map + first[b];
+    cp.ends = ends + first[b]; cp.stats = stats + first[b];
+    g_copies_cb(&cp, g_copies_user);
+    free(own_fl);
+  }
+  free(nrows); free(stats); free(ends);
+  return rc;
+}
+
 /* nx flanks padded to whole tiles of 64 with empty flanks (no base: t_lo > t_hi): a malloc'ed copy, for nx = 0 too; *npad its length */
 static ramx_flank empty_flank(void) { ramx_flank x; memset(&x, 0, sizeof(x)); x.t_lo = 1; x.t_hi = 0; x.step = 1; return x; }
 static ramx_flank *pad_to_tiles(const ramx_flank *fl, int nx, int *npad)
@@ -493,6 +529,19 @@ static int refine_direction(ramx_dev *d, int direction, int family, const ramx_f
   int8_t *c1 = (int8_t *)calloc((size_t)(p->L > 0 ? p->L : 1), 1);
   if (ret > 0) memcpy(c1, cons, (size_t)ret);
   const int rc = refine_families(d, direction, &family, 1, pf, npad, &first, &count, p, c1, &r);
+  free(pf); free(c1);
+  return rc;
+}
+
+/* one direction of one family, as refine_direction */
+static int copies_direction(ramx_dev *d, int direction, int family, const ramx_flank *fl, const int32_t *map, int nx,
+                            const ramx_params *p, const int8_t *cons, int ret)
+{
+  int npad; ramx_flank *pf = pad_to_tiles(fl, nx, &npad);
+  const int32_t first = 0, count = nx, r = ret;
+  int8_t *c1 = (int8_t *)calloc((size_t)(p->L > 0 ? p->L : 1), 1);
+  if (ret > 0) memcpy(c1, cons, (size_t)ret);
+  const int rc = copies_families(d, direction, &family, 1, pf, map, npad, &first, &count, p, c1, &r, NULL);
   free(pf); free(c1);
   return rc;
 }
@@ -752,6 +801,11 @@ run_again:
   {
     rc = refine_direction(d, direction, family, fl, nx, p, cons, info->ret);
     SEAM1_PHASE("pileup + refinement");
+  }
+  if (rc == RAMX_OK && g_copies_cb != NULL)
+  {
+    rc = copies_direction(d, direction, family, fl, map, nx, p, cons, info->ret);
+    SEAM1_PHASE("per-copy statistics");
   }
 #undef SEAM1_PHASE
 #undef FP_JOIN
@@ -1076,6 +1130,14 @@ int ramx_extend_batch(int direction, ramx_family *fam, int32_t F, const ramx_par
       rc = refine_families(d, direction, fidx, nb, fl, (int32_t)fpos, first, count, p, cons, rets);
       free(rets);
       BATCH_PHASE("pileup + refinement");
+    }
+    if (rc == RAMX_OK && g_copies_cb != NULL)
+    {
+      int32_t *rets = (int32_t *)malloc(sizeof(int32_t) * (size_t)nb);
+      for (int b = 0; b < nb; b++) rets[b] = binfo[b].ret;
+      rc = copies_families(d, direction, fidx, nb, fl, map, (int32_t)fpos, first, count, p, cons, rets, at_of);
+      free(rets);
+      BATCH_PHASE("per-copy statistics");
     }
     free(binfo); free(cons); free(th); free(tp);
     BATCH_PHASE("write-back");

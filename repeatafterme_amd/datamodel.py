@@ -133,6 +133,24 @@ PILEUP_DTYPE = np.dtype([("base", np.int32), ("cover", np.int32), ("match", np.i
 assert PILEUP_DTYPE.itemsize == 128 and PILEUP_DTYPE.fields["ins_bases"][1] == 40
 
 
+# per-copy statistics of an alignment: C-ABI ramx_copy_stats (include/ramx.h), 48 bytes
+COPY_STATS_FIELDS = ("cols", "match", "ts", "tv", "n_match", "del", "del_open", "ins", "ins_open", "cpg_cols", "cpg_ts", "score")
+COPY_STATS_DTYPE = np.dtype([(k, np.int32) for k in COPY_STATS_FIELDS])
+assert COPY_STATS_DTYPE.itemsize == 48
+
+
+@dataclass
+class Copies:
+    """Per-copy statistics of one direction of one family along its kept consensus (C-ABI ramx_copies / ramx_dev_copy_stats)."""
+    direction: int
+    family: int                      # index in a batch, else 0
+    cons: np.ndarray                 # int8 [rows]: the kept consensus (rows = ret)
+    flanks: np.ndarray               # FLANK_DTYPE [n_flanks]
+    core_index: np.ndarray           # position in the core list of every flank
+    ends: np.ndarray                 # ALN_END_DTYPE [n_flanks]
+    stats: np.ndarray                # COPY_STATS_DTYPE [n_flanks]
+
+
 @dataclass
 class Refinement:
     """Pileup and refinement of one direction of one family (C-ABI ramx_refinement / ramx_dev_pileup / ramx_dev_refine)."""

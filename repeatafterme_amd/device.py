@@ -10,7 +10,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .datamodel import ALN_END_DTYPE, ALN_NONE, COL_PROFILE_DTYPE, PILEUP_DTYPE, CoreSet, ExtendParams
+from .datamodel import ALN_END_DTYPE, ALN_NONE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, PILEUP_DTYPE, CoreSet, ExtendParams
 from .extend import RunInfo, _info, _params
 
 
@@ -64,6 +64,29 @@ class RefineResult:
     forward_ms: float                      # summed over the replays
     walk_ms: float
     pileup_ms: float
+
+
+@dataclass
+class CopyStatsResult:
+    stats: np.ndarray                      # COPY_STATS_DTYPE [n_padded]
+    ends: np.ndarray                       # ALN_END_DTYPE [n_padded]
+    kernel_ms: tuple                       # HIP-event times of the forward kernels, the walk kernels, the statistics kernel
+
+
+def copy_kimura(stats) -> float:
+    """Kimura two-parameter divergence (percent) of one COPY_STATS_DTYPE record (C-ABI ramx_copy_kimura); < 0: undefined."""
+    s = np.ascontiguousarray(stats, COPY_STATS_DTYPE).reshape(-1)
+    assert len(s) == 1
+    return float(_lib.lib().ramx_copy_kimura(s.ctypes.data))
+
+
+def family_divergence_of(stats, min_sites: int = 1):
+    """Mean Kimura divergence over the records with at least min_sites sites and a defined value (C-ABI
+    ramx_family_divergence): -> (percent, number of records used)."""
+    s = np.ascontiguousarray(stats, COPY_STATS_DTYPE).reshape(-1)
+    used = C.c_int32()
+    div = _lib.lib().ramx_family_divergence(s.ctypes.data if len(s) else None, len(s), int(min_sites), C.byref(used))
+    return float(div), int(used.value)
 
 
 def recall_consensus(cons, cols, L: int) -> np.ndarray:
@@ -224,6 +247,23 @@ class Device:
                                            cons.ctypes.data, rows_a.ctypes.data, cols.ctypes.data, ends.ctypes.data, ms),
                    "ramx_dev_pileup")
         return PileupResult(cols, ends, ms[0], ms[1], ms[2])
+
+    def copy_stats(self, flanks, p: ExtendParams, cons, rows=None, fam_first=None, fam_count=None, rows_reversed: bool = False,
+                   out: Optional[np.ndarray] = None) -> CopyStatsResult:
+        """Per-copy statistics of every family along a given consensus (C-ABI ramx_dev_copy_stats): arguments as profile().
+        rows_reversed: the rows run against the reading order (a left extension).  `out`: a COPY_STATS_DTYPE array [n_padded]
+        to write into (records of tiles outside every family are left alone)."""
+        cp, keep = _params(p)
+        arr, npad, first, count, cons, rows_a = self._families(flanks, p, cons, rows, fam_first, fam_count)
+        nf = len(first)
+        stats = out if out is not None else np.zeros(max(npad, 1), COPY_STATS_DTYPE)
+        assert stats.dtype == COPY_STATS_DTYPE and stats.flags.c_contiguous and len(stats) >= npad
+        ends = self._no_ends(npad)
+        ms = (C.c_double * 3)()
+        _lib.check(self._L.ramx_dev_copy_stats(self._h, arr, npad, first.ctypes.data, count.ctypes.data, nf, C.byref(cp),
+                                               cons.ctypes.data, rows_a.ctypes.data, int(bool(rows_reversed)), stats.ctypes.data,
+                                               ends.ctypes.data, ms), "ramx_dev_copy_stats")
+        return CopyStatsResult(stats, ends, (ms[0], ms[1], ms[2]))
 
     def refine(self, flanks, p: ExtendParams, cons, rows=None, fam_first=None, fam_count=None,
                max_replays: int = 10) -> RefineResult:

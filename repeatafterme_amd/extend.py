@@ -13,8 +13,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .datamodel import (ALN_END_DTYPE, COL_PROFILE_DTYPE, FLANK_DTYPE, PILEUP_DTYPE, Alignment, CoreSet, ExtendParams, Profile,
-                        Refinement)
+from .datamodel import (ALN_END_DTYPE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, FLANK_DTYPE, PILEUP_DTYPE, Alignment, Copies, CoreSet,
+                        ExtendParams, Profile, Refinement)
 
 
 @dataclass
@@ -141,13 +141,48 @@ class _RefineSink:
         return False
 
 
+class _CopiesSink:
+    """Collects what seam 1 hands to the copies sink (ramx_set_copies_sink) while the block runs."""
+
+    def __init__(self):
+        self.got = []
+
+        def _cb(ptr, _user):
+            cp = ptr.contents
+            n = cp.n_flanks
+
+            def grab(src, count, dtype):
+                out = np.zeros(count, dtype)
+                if count and src:
+                    C.memmove(out.ctypes.data, src, count * out.dtype.itemsize)
+                return out
+            self.got.append(Copies(cp.direction, cp.family, grab(cp.cons, cp.rows, np.int8), grab(cp.flanks, n, FLANK_DTYPE),
+                                   grab(cp.core_index, n, np.int32), grab(cp.ends, n, ALN_END_DTYPE),
+                                   grab(cp.stats, n, COPY_STATS_DTYPE)))
+        self._cb = _lib.COPIES_CB(_cb)
+
+    def __enter__(self):
+        _lib.lib().ramx_set_copies_sink(self._cb, None)
+        return self
+
+    def __exit__(self, *exc):
+        _lib.lib().ramx_set_copies_sink(_lib.COPIES_CB(), None)
+        return False
+
+
 def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, master: np.ndarray,
-                     p: ExtendParams, profile: bool = False, align: bool = False, refine: int = 0):
+                     p: ExtendParams, profile: bool = False, align: bool = False, refine: int = 0, copies: bool = False):
     """direction: 1 = right, 0 = left (reference ram_extend.c:424,506).  profile=True: returns (RunInfo, Profile) -- the
     direction is replayed along the consensus it chose (C-ABI ramx_dev_profile) after the loop.  align=True: returns
     (RunInfo, Alignment), or (RunInfo, Profile, Alignment) with both -- every flank aligned to the kept consensus (C-ABI
     ramx_dev_align).  refine=n > 0: a Refinement comes last in the tuple -- the kept consensus' pileup and its refinement over at
-    most n replays (C-ABI ramx_dev_pileup / ramx_dev_refine)."""
+    most n replays (C-ABI ramx_dev_pileup / ramx_dev_refine).  copies=True: a Copies comes last of all -- every copy's
+    statistics along the kept consensus (C-ABI ramx_dev_copy_stats)."""
+    if copies:
+        with _CopiesSink() as csink:
+            res = extend_alignment(direction, cores, sequence, master, p, profile=profile, align=align, refine=refine)
+        assert len(csink.got) == 1
+        return (res + (csink.got[0],)) if isinstance(res, tuple) else (res, csink.got[0])
     if refine:
         with _RefineSink(refine) as rsink:
             res = extend_alignment(direction, cores, sequence, master, p, profile=profile, align=align)
@@ -177,11 +212,18 @@ def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, maste
     return _info(ci)
 
 
-def extend_batch(direction: int, families, p: ExtendParams, profile: bool = False, align: bool = False):
+def extend_batch(direction: int, families, p: ExtendParams, profile: bool = False, align: bool = False, copies: bool = False):
     """Many families in one launch (C-ABI ramx_extend_batch).  `families` is a list of (cores, sequence, master);
     every family is updated in place exactly like extend_alignment does for one.  Returns one RunInfo per family;
     profile=True: (RunInfos, Profiles), one Profile per family in the order of `families`; align=True: (RunInfos,
-    Alignments), or (RunInfos, Profiles, Alignments) with both."""
+    Alignments), or (RunInfos, Profiles, Alignments) with both.  copies=True: the families' Copies come last in the tuple."""
+    if copies:
+        with _CopiesSink() as csink:
+            res = extend_batch(direction, families, p, profile=profile, align=align)
+        by_family = {cp.family: cp for cp in csink.got}
+        assert len(by_family) == len(csink.got) == len(families)
+        cps = [by_family[i] for i in range(len(families))]
+        return (res + (cps,)) if isinstance(res, tuple) else (res, cps)
     if align:
         with _AlignSink() as asink:
             res = extend_batch(direction, families, p, profile=profile)

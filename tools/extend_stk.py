@@ -13,7 +13,10 @@ still carry the extension at every column, which the wrapper can only approximat
 <id>-aln.a2m: every extendable copy aligned to the kept consensus of both extensions (RAMExtend -outaln), which the wrapper
 rebuilds with an external aligner from -cons and -outfa (extend-stk.pl:553-556); with --refine N, <id>-pileup.tsv and
 <id>-refined-cons.fa: the per-column composition of both extensions and their consensus re-called from it over at most N
-replays (RAMExtend -outpileup / -outrefined / -refine), the wrapper's `alignAndCallConsensus.pl -refine 10` step (:553-555).
+replays (RAMExtend -outpileup / -outrefined / -refine), the wrapper's `alignAndCallConsensus.pl -refine 10` step (:553-555);
+with -copies, <id>-copies.tsv: every copy's divergence from the kept consensus of both extensions (RAMExtend -outcopies), and
+per direction the family's mean Kimura divergence over the extension beside the matrix the wrapper's ladder would pick for it
+-- the check that the matrix chosen from the seed alignment was the right one for the extended part.
 
 (the re-alignment and Stockholm rewriting that follow in the wrapper belong to RepeatModeler and are out of scope).
 """
@@ -43,6 +46,8 @@ def main(argv=None):
     ap.add_argument("-aln", action="store_true", help="also write <id>-aln.a2m per family (RAMExtend -outaln)")
     ap.add_argument("--refine", type=int, default=0, metavar="N",
                     help="also write <id>-pileup.tsv and <id>-refined-cons.fa per family (RAMExtend -outpileup / -outrefined / -refine N)")
+    ap.add_argument("-copies", action="store_true", help="also write <id>-copies.tsv per family (RAMExtend -outcopies) and print "
+                    "each extension's divergence with the matrix it would call for")
     ap.add_argument("-one_by_one", action="store_true", help="start one RAMExtend per family, as the wrapper does")
     a = ap.parse_args(argv)
 
@@ -82,7 +87,8 @@ def main(argv=None):
                                         base + "-ext-cons.fa"] + (["-outprofile", base + "-profile.tsv"] if a.profile else []) +
                                        (["-outaln", base + "-aln.a2m"] if a.aln else []) +
                                        (["-outpileup", base + "-pileup.tsv", "-outrefined", base + "-refined-cons.fa", "-refine",
-                                         str(a.refine)] if a.refine > 0 else []),
+                                         str(a.refine)] if a.refine > 0 else []) +
+                                       (["-outcopies", base + "-copies.tsv"] if a.copies else []),
                                        stdout=log, stderr=subprocess.STDOUT).returncode
                 if rc:
                     sys.exit(f"  RAMExtend failed! [{rc}] see {base}-repam.log")
@@ -90,11 +96,14 @@ def main(argv=None):
             lst = os.path.join(a.outdir, f"batch-{matrix}-{minimp}.list")
             with open(lst, "w") as fh:
                 for seed, base in fams:
+                    # fields six to ten are optional: "-" holds the place of one that is not asked for before one that is
+                    opt = [base + "-profile.tsv" if a.profile else "-", base + "-aln.a2m" if a.aln else "-",
+                           base + "-pileup.tsv" if a.refine > 0 else "-", base + "-refined-cons.fa" if a.refine > 0 else "-",
+                           base + "-copies.tsv" if a.copies else "-"]
+                    while opt and opt[-1] == "-":
+                        opt.pop()
                     fh.write("\t".join([base + "-linup.tsv", base + "-repam.log", base + "-ext-cons.fa",
-                                        base + "-repam-ranges.tsv", base + "-repam-repseq.fa"] +
-                                       ([base + "-profile.tsv" if a.profile else "-"] if a.profile or a.aln or a.refine > 0 else []) +
-                                       ([base + "-aln.a2m" if a.aln else "-"] if a.aln or a.refine > 0 else []) +
-                                       ([base + "-pileup.tsv", base + "-refined-cons.fa"] if a.refine > 0 else [])) + "\n")
+                                        base + "-repam-ranges.tsv", base + "-repam-repseq.fa"] + opt) + "\n")
             rc = subprocess.run([a.ramextend] + common + (["-refine", str(a.refine)] if a.refine > 0 else []) + ["-batch", lst]).returncode
             if rc:
                 sys.exit(f"  RAMExtend -batch failed! [{rc}]")
@@ -117,6 +126,15 @@ def main(argv=None):
                 fh.writelines(out)
             t = [l.strip() for l in open(base + "-repam.log") if l.startswith("Extended ")]
             print(f"RAMExtend Results [{seed.name}]: " + "  ".join(t))
+            if a.copies and os.path.exists(base + "-copies.tsv"):
+                for line in open(base + "-copies.tsv"):                 # the summary line of each direction
+                    if not line.startswith("#"):
+                        continue
+                    tag, copies, used, kim = line[1:].rstrip("\n").split("\t")
+                    div = float(kim.split("=")[1])
+                    would = stk.choose_scoring(div, a.min_aligning_seqs)[0]
+                    print(f"  - Extension divergence [{tag}]: {div:.2f} % over {used.split('=')[1]} of {copies.split('=')[1]} copies: "
+                          f"matrix {would} (used: {matrix})" + ("" if would == matrix or used.endswith("=0") else "  **differs**"))
     return 0
 
 
