@@ -502,6 +502,80 @@ double ramx_copy_kimura(const ramx_copy_stats *s);
  * receives their number.  0.0 when there are none. */
 double ramx_family_divergence(const ramx_copy_stats *stats, int32_t n, int32_t min_sites, int32_t *n_used);
 
+/* Co-segregation of an extension's variants: do the copies that differ from the consensus at column i also differ at column j?
+ * The pileup and the per-copy statistics look at every position on its own; this is their second-order sibling.  A PLANE is
+ * one bit per flank of a family: bit i is set iff flank i is a non-padding flank with an alignment, row <= its end_row, and
+ *   cls 0..3: column row is matched to a base of class A C G T (the pileup's classes)
+ *       4: matched to class N
+ *       5: deleted (col_idx[row] == RAMX_ALN_DELETED)
+ *       6: covered (end_row >= row)
+ *       7: bases inserted before it (col_ins[row] > 0)
+ * so every plane is a subset of the cover plane of its row, and tail_ins sets nothing. */
+typedef struct ramx_plane { int32_t row, cls; } ramx_plane;
+#define RAMX_PLANE_COVER 6
+#define RAMX_LINKAGE_MAX_PLANES 2048        /* planes of one family in one Gram matrix: a 16 MB result */
+
+/* The planes on the device: ramx_dev_pileup with a fourth stage.  Arguments, checks, self-containedness, the budget of
+ * RAMX_ALIGN_BYTES and what is returned in cols / ends exactly as ramx_dev_pileup (rank-local under a communicator).  The fourth
+ * stage takes, per tile and row, the eight ballots of one wave and keeps the planes of ALL rows and classes of every family
+ * RESIDENT on the device, rows[f] * 8 * tiles_f 64-bit words a family, so that variants can be chosen afterwards without a
+ * second replay.  That buffer does not count against RAMX_ALIGN_BYTES; it has a cap of its own, RAMX_LINKAGE_BYTES
+ * (environment; default 2 GiB): RAMX_ERR_UNSUPPORTED beyond it.  The planes stay resident until the next replay that runs on
+ * this device (ramx_dev_profile / _align / _pileup / _copy_stats / _refine / _planes), ramx_dev_begin_direction or
+ * ramx_dev_run_families.  kernel_ms (may be NULL): FOUR values, forward, walk, pileup + sum, planes. */
+int ramx_dev_planes(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                    const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                    const int8_t *cons, const int32_t *rows, ramx_col_pileup *cols, ramx_aln_end *ends, double *kernel_ms);
+
+/* The Gram matrix of chosen planes of the resident replay (n_families as in that ramx_dev_planes call).  Family f's planes are
+ * planes[plane_first[f] .. + plane_count[f]): strictly increasing in (row, cls), row < rows[f], cls in 0..7, at most
+ * RAMX_LINKAGE_MAX_PLANES of them -- anything else is RAMX_ERR_ARG; RAMX_ERR_STATE without resident planes.  All lists are
+ * checked before anything is launched or written.  co + co_first[f] receives [P_f][P_f] row-major: entry [p][q] is the number
+ * of flanks of the family that have both bits set -- symmetric, the diagonal a plane's own count; exact integers (popcounts
+ * summed over the tiles in registers, no atomics), so the result does not depend on any order.  bits (may be NULL) receives
+ * the chosen planes' words themselves, family f at bits_first[f] as [P_f][T_f], T_f = (fam_count[f] + 63) / 64, bit i % 64 of
+ * word i / 64 flank i.  A family with P_f == 0 or without tiles writes nothing.  The call may be repeated with other lists.
+ * Rank-local under a communicator: for equal plane lists the counts add up across ranks. */
+int ramx_dev_plane_gram(ramx_dev *d, int32_t n_families, const ramx_plane *planes, const int32_t *plane_first,
+                        const int32_t *plane_count, int32_t *co, const int64_t *co_first, uint64_t *bits, const int64_t *bits_first);
+/* HIP-event time (ms) of the Gram kernel of the last ramx_dev_plane_gram on this device; 0 if none was launched. */
+double ramx_dev_plane_gram_ms(ramx_dev *d);
+
+/* Which planes to ask for (plain host C): the variants of a pileup.  The candidates of row r are cls a in 0..3 with
+ * a != cons[r] (count match[a]), cls 5 (count del) and cls 7 (count ins_open); class N and the consensus base are never
+ * candidates.  A candidate is a VARIANT iff count >= min_count and 1000 * count >= min_permille * cover.  If more than
+ * max_variants qualify, those with the largest count are kept, ties to the lower (row, cls).  out (room for 2 * max_variants)
+ * receives, sorted by (row, cls), the variants and the cover plane (r, 6) of every row that has one; returns their number. */
+int32_t ramx_select_planes(const int8_t *cons, int32_t rows, const ramx_col_pileup *cols, int32_t min_count, int32_t min_permille,
+                           int32_t max_variants, ramx_plane *out);
+
+/* The pair statistic (plain host C) over every pair of variant planes p < q (indices into planes[0..P), cls != 6) on DIFFERENT
+ * rows whose rows' cover planes cp, cq are in the list: among the n = co[cp][cq] copies that cover both columns, n_p =
+ * co[p][cq] carry the first variant, n_q = co[q][cp] the second and n_pq = co[p][q] both.  expected = n_p * n_q / n;
+ * mlog10p = -log10 of the hypergeometric upper tail P(X >= n_pq), summed in log space with lgamma; 0 when n == 0 or n_pq == 0.
+ * Pairs with mlog10p >= min_mlog10p are written to out[0..cap) in (p, q) order -- not sorted by score; the return value is
+ * their number, even beyond cap.  There is NO multiple-testing correction: P (P - 1) / 2 pairs are tested, and the threshold is
+ * the caller's to set with that in mind. */
+typedef struct ramx_link { int32_t p, q, n, n_p, n_q, n_pq; double expected, mlog10p; } ramx_link;
+int32_t ramx_link_pairs(const ramx_plane *planes, int32_t P, const int32_t *co, double min_mlog10p, ramx_link *out, int32_t cap);
+
+/* Linkage sink of seam 1, as the other sinks: with a sink set, per direction and family that has run, along the kept consensus
+ * (rows = ret): ramx_dev_planes, ramx_select_planes(min_count, min_permille, max_variants) on the pileup it returned, and
+ * ramx_dev_plane_gram of the selection.  co is [n_planes][n_planes].  A direction without an extendable core or with ret = 0
+ * is answered on the host with n_planes = 0.  With a communicator or mailbox route active the direction fails with
+ * RAMX_ERR_UNSUPPORTED: the selection needs the counts of every rank.  max_variants is held to RAMX_LINKAGE_MAX_PLANES / 2 (the
+ * cover planes double the list).  cb == NULL (the default): off. */
+typedef struct ramx_linkage
+{
+  int32_t direction, family /* index in a batch, else 0 */, rows /* = ret */, n_planes;
+  const int8_t *cons;                 /* [rows] */
+  const ramx_col_pileup *cols;        /* [rows] */
+  const ramx_plane *planes;           /* [n_planes] */
+  const int32_t *co;                  /* [n_planes][n_planes] */
+} ramx_linkage;
+typedef void (*ramx_linkage_cb)(const ramx_linkage *lk, void *user);
+void ramx_set_linkage_sink(ramx_linkage_cb cb, void *user, int32_t min_count, int32_t min_permille, int32_t max_variants);
+
 /* multi-GPU: flanks are sharded over ranks; each column's 4 candidate sums are all-reduced
  * (4 x int64, RCCL over xGMI).  unique_id is the 128-byte ncclUniqueId made by rank 0
  * (ramx_comm_unique_id) and handed to the other ranks by the launcher (e.g. torch.distributed). */

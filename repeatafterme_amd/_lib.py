@@ -23,6 +23,7 @@ EXPORTS = [
     "ramx_dev_align", "ramx_set_align_sink",
     "ramx_dev_pileup", "ramx_recall_consensus", "ramx_dev_refine", "ramx_set_refine_sink",
     "ramx_dev_copy_stats", "ramx_copy_kimura", "ramx_family_divergence", "ramx_set_copies_sink",
+    "ramx_dev_planes", "ramx_dev_plane_gram", "ramx_dev_plane_gram_ms", "ramx_select_planes", "ramx_link_pairs", "ramx_set_linkage_sink",
 ]
 
 
@@ -96,6 +97,22 @@ class CopiesRec(C.Structure):       # ramx_copies
 
 
 COPIES_CB = C.CFUNCTYPE(None, C.POINTER(CopiesRec), C.c_void_p)
+
+
+class Plane(C.Structure):           # ramx_plane
+    _fields_ = [("row", C.c_int32), ("cls", C.c_int32)]
+
+
+class Link(C.Structure):            # ramx_link
+    _fields_ = [(k, C.c_int32) for k in ("p", "q", "n", "n_p", "n_q", "n_pq")] + [("expected", C.c_double), ("mlog10p", C.c_double)]
+
+
+class LinkageRec(C.Structure):      # ramx_linkage
+    _fields_ = [(k, C.c_int32) for k in ("direction", "family", "rows", "n_planes")] + \
+               [(k, C.c_void_p) for k in ("cons", "cols", "planes", "co")]
+
+
+LINKAGE_CB = C.CFUNCTYPE(None, C.POINTER(LinkageRec), C.c_void_p)
 
 
 def build(force: bool = False) -> None:
@@ -176,6 +193,20 @@ def lib() -> C.CDLL:
         L.ramx_family_divergence.restype = C.c_double
         L.ramx_set_copies_sink.argtypes = [COPIES_CB, C.c_void_p]
         L.ramx_set_copies_sink.restype = None
+        L.ramx_dev_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Params),
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ramx_dev_planes.restype = C.c_int
+        L.ramx_dev_plane_gram.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
+        L.ramx_dev_plane_gram.restype = C.c_int
+        L.ramx_dev_plane_gram_ms.argtypes = [C.c_void_p]
+        L.ramx_dev_plane_gram_ms.restype = C.c_double
+        L.ramx_select_planes.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+        L.ramx_select_planes.restype = C.c_int32
+        L.ramx_link_pairs.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_int32]
+        L.ramx_link_pairs.restype = C.c_int32
+        L.ramx_set_linkage_sink.argtypes = [LINKAGE_CB, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        L.ramx_set_linkage_sink.restype = None
         if hasattr(L, "ramx_cli_main"):
             L.ramx_cli_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
         _lib = L

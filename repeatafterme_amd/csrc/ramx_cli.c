@@ -92,6 +92,11 @@ static void usage(void)
     "     -outmat <file>        # Dump the dp matrix paths to a file for debugging.\n"
     "     -outcopies <file>     # Save every copy's divergence from the extension consensus\n"
     "                           #   ( matches, transitions, transversions, gaps, Kimura ) to a TSV file.\n"
+    "     -outlinkage <file>    # Save the pairs of variant columns of the extension consensus whose variants\n"
+    "                           #   travel together in the copies ( a sign of subfamilies ) to a TSV file.\n"
+    "     -linkcount <num>      # ... a variant needs this many copies (4),\n"
+    "     -linkfrac <num>       # ... and this many per thousand of the copies that cover its column (100).\n"
+    "     -linkscore <num>      # ... a pair is written from this -log10 p of its hypergeometric test (3).\n"
     "     -version              # Print out one-line version information\n"
     "     -v[v[v[v]]]           # How verbose do you want it to be?  -vvvv is super-verbose.\n"
     "\n"
@@ -243,8 +248,8 @@ static void warm_start(void)
 /* everything the command line decides */
 struct cli_opts
 {
-  const char *ranges_file, *outtsv, *outfa, *outmat, *cons_file, *seq_file, *matrix_name, *batch_file, *outprofile, *outaln, *outpileup, *outrefined, *outcopies;
-  int refine;
+  const char *ranges_file, *outtsv, *outfa, *outmat, *cons_file, *seq_file, *matrix_name, *batch_file, *outprofile, *outaln, *outpileup, *outrefined, *outcopies, *outlinkage;
+  int refine, linkcount, linkfrac, linkscore;
   int flanking, L, bandwidth, maxn, when_to_stop, num_threads, verbose;
   int gap_ext, gap_open, match, mismatch, cappenalty, minimprovement, is_rs;
   struct scoringSystem *sp;
@@ -467,7 +472,7 @@ static void write_results(const struct cli_opts *o, struct coreAlignment *cores,
  */
 struct batch_item
 {
-  char *ranges, *log, *cons, *tsv, *fa, *profile, *aln, *pileup, *refined, *copies;
+  char *ranges, *log, *cons, *tsv, *fa, *profile, *aln, *pileup, *refined, *copies, *linkage;
   struct coreAlignment *cores;
   struct sequenceLibrary *lib;
   int N, rightbp, leftbp;
@@ -789,6 +794,64 @@ static void copies_write(struct copies_family *cf, struct coreAlignment *cores, 
   fclose(fp);
 }
 
+/*
+ * -outlinkage <file>: the co-segregation of the variants of both extensions (include/ramx.h, ramx_set_linkage_sink,
+ * ramx_link_pairs) as a TSV, the right block first: one line per pair of variants on different columns whose -log10 p reaches
+ * -linkscore, in (p, q) order, then one summary line "#<dir> variants= pairs= linked=": the variants selected, the pairs tested
+ * and the pairs written.
+ */
+struct linkage_block { int have, P; ramx_plane *planes; int32_t *co; };
+struct linkage_family { const char *path; struct linkage_block blk[2]; };
+struct linkage_out { struct linkage_family *fam; };
+static const char k_linkage_header[] = "dir\trow_a\tvar_a\tcount_a\trow_b\tvar_b\tcount_b\tn\tn_a\tn_b\tn_ab\texpected\tmlog10p\n";
+
+static void linkage_sink(const ramx_linkage *lk, void *user)
+{
+  struct linkage_family *lf = &((const struct linkage_out *)user)->fam[lk->family];
+  if (!lf->path) return;
+  struct linkage_block *b = &lf->blk[lk->direction ? 1 : 0];
+  const size_t P = (size_t)lk->n_planes;
+  b->have = 1; b->P = lk->n_planes;
+  b->planes = (ramx_plane *)malloc(sizeof(ramx_plane) * (P ? P : 1));
+  b->co = (int32_t *)malloc(sizeof(int32_t) * (P ? P * P : 1));
+  if (P) { memcpy(b->planes, lk->planes, sizeof(ramx_plane) * P); memcpy(b->co, lk->co, sizeof(int32_t) * P * P); }
+}
+
+/* after both directions: the file, then the buffers are released */
+static void linkage_write(struct linkage_family *lf, int min_score)
+{
+  static const char *const var_name[8] = { "A", "C", "G", "T", "N", "del", "cover", "ins" };
+  if (!lf->path) return;
+  FILE *fp = fopen(lf->path, "w");
+  if (!fp) { fprintf(stderr, "Could not create the linkage file %s\n", lf->path); exit(1); }
+  fputs(k_linkage_header, fp);
+  for (int dir = 1; dir >= 0; dir--)
+  {
+    struct linkage_block *b = &lf->blk[dir];
+    if (!b->have) continue;
+    const char *tag = dir ? "right" : "left";
+    const int32_t P = b->P;
+    /* the pairs tested: every pair scores at least 0 */
+    const int32_t tested = ramx_link_pairs(b->planes, P, b->co, 0.0, NULL, 0);
+    ramx_link *ln = (ramx_link *)malloc(sizeof(ramx_link) * (size_t)(tested > 0 ? tested : 1));
+    const int32_t linked = ramx_link_pairs(b->planes, P, b->co, (double)min_score, ln, tested);
+    int variants = 0;
+    for (int32_t i = 0; i < P; i++) variants += b->planes[i].cls != RAMX_PLANE_COVER;
+    for (int32_t i = 0; i < linked; i++)
+    {
+      const ramx_link *l = &ln[i];
+      const ramx_plane *a = &b->planes[l->p], *c = &b->planes[l->q];
+      fprintf(fp, "%s\t%d\t%s\t%d\t%d\t%s\t%d\t%d\t%d\t%d\t%d\t%.4f\t%.4f\n", tag, a->row, var_name[a->cls & 7],
+              b->co[(size_t)l->p * P + l->p], c->row, var_name[c->cls & 7], b->co[(size_t)l->q * P + l->q], l->n, l->n_p, l->n_q, l->n_pq,
+              l->expected, l->mlog10p);
+    }
+    fprintf(fp, "#%s\tvariants=%d\tpairs=%d\tlinked=%d\n", tag, variants, (int)tested, (int)linked);
+    free(ln); free(b->planes); free(b->co);
+    memset(b, 0, sizeof(*b));
+  }
+  fclose(fp);
+}
+
 /* flat view of a core list for ramx_extend_batch (arrays owned by the caller's arena) */
 static void flatten_cores(struct coreAlignment *cores, int N, ramx_flat_cores *fc)
 {
@@ -845,6 +908,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   if (o->outpileup != NULL || o->outrefined != NULL)
   { fprintf(stderr, "RAMExtend(ramx): with -batch every family's pileup file is the eighth field of its line in the list and its refined consensus the ninth\n"); exit(1); }
   if (o->outcopies != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's copies file is the tenth field of its line in the list\n"); exit(1); }
+  if (o->outlinkage != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's linkage file is the eleventh field of its line in the list\n"); exit(1); }
   FILE *lf = fopen(o->batch_file, "r");
   if (!lf) { fprintf(stderr, "Could not open batch list %s\n", o->batch_file); exit(1); }
   size_t cap = 64, F = 0;
@@ -856,9 +920,9 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   {
     while (len > 0 && (line[len - 1] == '\n' || line[len - 1] == '\r')) line[--len] = 0;
     if (line[0] == '#' || line[0] == 0) continue;
-    char *f[10] = { NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL };
+    char *f[11] = { NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL };
     char *p = line;
-    for (int k = 0; k < 10 && p; k++) { f[k] = p; char *t = strchr(p, '\t'); if (t) { *t = 0; p = t + 1; } else p = NULL; }
+    for (int k = 0; k < 11 && p; k++) { f[k] = p; char *t = strchr(p, '\t'); if (t) { *t = 0; p = t + 1; } else p = NULL; }
     if (!f[0] || !f[1]) { fprintf(stderr, "batch list: every line needs at least <ranges><TAB><log>\n"); exit(1); }
     if (F == cap) { cap *= 2; it = (struct batch_item *)realloc(it, cap * sizeof(*it)); memset(it + F, 0, (cap - F) * sizeof(*it)); }
     it[F].ranges = strdup(f[0]); it[F].log = strdup(f[1]);
@@ -870,6 +934,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
     it[F].pileup = field_or_null(f[7]) ? strdup(f[7]) : NULL;        /* optional eighth field: the family's -outpileup file */
     it[F].refined = field_or_null(f[8]) ? strdup(f[8]) : NULL;       /* optional ninth field: the family's -outrefined file */
     it[F].copies = field_or_null(f[9]) ? strdup(f[9]) : NULL;        /* optional tenth field: the family's -outcopies file */
+    it[F].linkage = field_or_null(f[10]) ? strdup(f[10]) : NULL;     /* optional eleventh field: the family's -outlinkage file */
     F++;
   }
   free(line);
@@ -930,6 +995,11 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   for (size_t i = 0; i < F; i++)
     if ((cout.fam[i].path = it[i].copies) != NULL) { cout.fam[i].lib = it[i].lib; any_copies = 1; }
   if (any_copies) ramx_set_copies_sink(copies_sink, &cout);
+  struct linkage_out lout = { (struct linkage_family *)calloc(F ? F : 1, sizeof(struct linkage_family)) };
+  int any_linkage = 0;
+  for (size_t i = 0; i < F; i++)
+    if ((lout.fam[i].path = it[i].linkage) != NULL) any_linkage = 1;
+  if (any_linkage) ramx_set_linkage_sink(linkage_sink, &lout, o->linkcount, o->linkfrac, 1024);
   /* phase 2: right extension of all families in one launch; phase 3: per family, overlap avoidance */
   for (size_t i = 0; i < F; i++) flatten_cores(it[i].cores, it[i].N, &fam[i].cores);
   if (ramx_extend_batch(1, fam, (int32_t)F, &p, ir) < 0) { fprintf(stderr, "RAMExtend(ramx): batch extension failed: %s\n", ramx_last_error()); exit(1); }
@@ -963,6 +1033,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
     aln_write(&aout.fam[i], it[i].cores, o->flanking);
     refined_write(&rout.fam[i]);
     copies_write(&cout.fam[i], it[i].cores, o->flanking);
+    linkage_write(&lout.fam[i], o->linkscore);
     const double duration = difftime(time(0), t_start);
     printf("Program duration is %.1f sec = %.1f min = %.1f hr\n", duration, duration / 60.0, duration / 3600.0);
   }
@@ -974,13 +1045,14 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   {
     ramx_free_library(it[i].lib, it[i].cores);
     free(it[i].master); free(it[i].ranges); free(it[i].log); free(it[i].cons); free(it[i].tsv); free(it[i].fa); free(it[i].profile); free(it[i].aln);
-    free(it[i].pileup); free(it[i].refined); free(it[i].copies);
+    free(it[i].pileup); free(it[i].refined); free(it[i].copies); free(it[i].linkage);
   }
   ramx_set_profile_sink(NULL, NULL);
   ramx_set_align_sink(NULL, NULL);
   ramx_set_refine_sink(NULL, NULL, 1);
   ramx_set_copies_sink(NULL, NULL);
-  free(aout.fam); free(rout.fam); free(cout.fam);
+  ramx_set_linkage_sink(NULL, NULL, 4, 100, 1024);
+  free(aout.fam); free(rout.fam); free(cout.fam); free(lout.fam);
   free(profile_paths);
   free(it); free(fam); free(ir); free(il); free(mflat);
   ramx_free_scoring_system(o->sp);
@@ -1013,6 +1085,10 @@ int ramx_cli_main(int argc, char **argv)
   opt_string(argc, argv, "-outpileup", &o.outpileup);
   opt_string(argc, argv, "-outrefined", &o.outrefined);
   opt_string(argc, argv, "-outcopies", &o.outcopies);
+  opt_string(argc, argv, "-outlinkage", &o.outlinkage);
+  if (!opt_int(argc, argv, "-linkcount", &o.linkcount)) o.linkcount = 4;
+  if (!opt_int(argc, argv, "-linkfrac", &o.linkfrac)) o.linkfrac = 100;
+  if (!opt_int(argc, argv, "-linkscore", &o.linkscore)) o.linkscore = 3;
   if (!opt_int(argc, argv, "-refine", &o.refine)) o.refine = 10;
   if (o.refine < 1) { fprintf(stderr, "RAMExtend(ramx): -refine takes the largest number of replays, at least 1\n"); exit(1); }
   if (!opt_int(argc, argv, "-L", &o.L)) o.L = 10000;
@@ -1119,6 +1195,11 @@ int ramx_cli_main(int argc, char **argv)
   cfam.path = o.outcopies; cfam.lib = lib;
   struct copies_out cout = { &cfam };
   if (o.outcopies != NULL) ramx_set_copies_sink(copies_sink, &cout);
+  struct linkage_family lfam;
+  memset(&lfam, 0, sizeof(lfam));
+  lfam.path = o.outlinkage;
+  struct linkage_out lout = { &lfam };
+  if (o.outlinkage != NULL) ramx_set_linkage_sink(linkage_sink, &lout, o.linkcount, o.linkfrac, 1024);
   fflush(stdout);
   warm_join();
   phase_done("device ready");
@@ -1134,10 +1215,12 @@ int ramx_cli_main(int argc, char **argv)
   ramx_set_align_sink(NULL, NULL);
   ramx_set_refine_sink(NULL, NULL, 1);
   ramx_set_copies_sink(NULL, NULL);
+  ramx_set_linkage_sink(NULL, NULL, 4, 100, 1024);
   write_results(&o, cores, lib, master, rightbp, leftbp, o.cons_file, o.outtsv, o.outfa);
   aln_write(&afam, cores, o.flanking);
   refined_write(&rfam);
   copies_write(&cfam, cores, o.flanking);
+  linkage_write(&lfam, o.linkscore);
   if (fp_mat != NULL) fclose(fp_mat);     /* ram_extend.c:778-779 */
   phase_done("report + outputs");
 

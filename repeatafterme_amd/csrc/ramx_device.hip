@@ -54,6 +54,7 @@
 #include "ramx_align_api.h"
 #include "ramx_pileup_api.h"
 #include "ramx_copystats_api.h"
+#include "ramx_linkage_api.h"
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
@@ -165,6 +166,13 @@ struct ramx_dev
   // ramx_dev_copy_stats (allocated on its first call): one record per flank
   ramx_copy_stats *d_cs_stats;
   size_t cap_pl_idx, cap_pl_ins, cap_pl_slab, cap_pl_cols, cap_cs_stats;
+  // ramx_dev_planes / ramx_dev_plane_gram (allocated on their first call): the bit planes of the whole flank set, which stay
+  // resident between the two calls (planes_ready, dropped like `ready` by whatever reuses the replays' buffers); the host keeps
+  // the resident families' rows, tiles and places (lk_fam: 3 x int64 per family)
+  unsigned long long *d_lk_planes; long long *d_lk_base, *d_lk_at, *d_lk_coat; int4 *d_lk_block, *d_lk_gfam; int *d_lk_co;
+  size_t cap_lk_planes, cap_lk_base, cap_lk_at, cap_lk_coat, cap_lk_block, cap_lk_gfam, cap_lk_co;
+  int planes_ready, lk_families; long long *lk_fam;
+  double lk_gram_ms;        // HIP-event time of the last Gram kernel (ramx_dev_plane_gram_ms)
 };
 
 extern "C" int ramx_device_count(void)
@@ -252,6 +260,9 @@ extern "C" void ramx_dev_destroy(ramx_dev *d)
   (void)hipFree(d->d_al_codes); (void)hipFree(d->d_al_ends); (void)hipFree(d->d_al_idx); (void)hipFree(d->d_al_ins);
   (void)hipFree(d->d_pl_idx); (void)hipFree(d->d_pl_ins); (void)hipFree(d->d_pl_slab); (void)hipFree(d->d_pl_cols);
   (void)hipFree(d->d_cs_stats);
+  (void)hipFree(d->d_lk_planes); (void)hipFree(d->d_lk_base); (void)hipFree(d->d_lk_at); (void)hipFree(d->d_lk_coat);
+  (void)hipFree(d->d_lk_block); (void)hipFree(d->d_lk_gfam); (void)hipFree(d->d_lk_co);
+  free(d->lk_fam);
   if (d->hostbox_mirror) (void)hipFree(d->hostbox_mirror);
   if (d->d_peer) (void)hipFree(d->d_peer);
   for (int i = 0; i < 2; i++) if (d->ev_chk[i]) (void)hipEventDestroy(d->ev_chk[i]);
@@ -403,6 +414,7 @@ extern "C" int ramx_dev_begin_direction(ramx_dev *d, const ramx_flank *flanks, i
   const int Np = ((Nx + 63) / 64) * 64 > 0 ? ((Nx + 63) / 64) * 64 : 64;
   const int KW = window_words(p->L, W);
   d->Nx = Nx; d->Np = Np; d->KW = KW; d->p = *p;
+  d->planes_ready = 0;        // the flank and window buffers the resident bit planes were made from are reused
   class_tab(p, d->tab);
   int rc;
   if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)Np * sizeof(ramx_flank)))) return rc;
@@ -486,6 +498,8 @@ static bool dev_is_multi(const ramx_dev *d)
 {
   return (d->comm != NULL && (d->nranks > 1 || getenv("RAMX_FORCE_COLLECTIVE") != NULL)) || d->cb != NULL;
 }
+
+extern "C" int ramx_dev_is_multi(ramx_dev *d) { return d && dev_is_multi(d) ? 1 : 0; }
 
 // ---- host-side collective on 4 x int64 in device memory (RCCL, or the test hook) ---------------
 static int host_allreduce_shards(ramx_dev *d, long long *dptr)   // dptr: NSHARD x 4 int64, summed over ranks in place
@@ -1493,6 +1507,7 @@ done:
   if (cp_dbg) (void)hipFree(cp_dbg);
   free(hctl); free(tmp); free(hfd); free(grp);
   d->ready = 0;       // the single-family buffers were reused: begin_direction must be called again before run_direction
+  d->planes_ready = 0;
   return rc;
 }
 
@@ -1623,6 +1638,7 @@ static int replay_setup(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded,
   if ((rc = launch_pack(d, n_padded, Np, W, 0, KW, d->stream)) != RAMX_OK) return rc;
   d->packed_kw = KW;
   d->ready = 0;       // the direction's flank and window buffers were reused: begin_direction must be called again before run_direction
+  d->planes_ready = 0;        // ... and the resident bit planes belong to the replay before this one
   memset(&k, 0, sizeof(k));
   k.bases = d->d_bases; k.bounds = d->d_bounds; k.S_in = d->d_rp_state; k.S_out = d->d_rp_state;
   k.Np = Np; k.Nx = Np; k.W = W; k.go = p->gapopen; k.ge = p->gapextn; k.cap = p->cappenalty;
@@ -1900,8 +1916,11 @@ static int pileup_setup(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded,
 // the stream is idle, d_pl_cols holds the families' columns and d_al_ends their flanks' records.  pl.tiles > 0, pl.maxrows > 0.
 // With cs (ramx_dev_copy_stats; its stats and reversed set by the caller) the third stage is the per-copy statistics kernel
 // instead: it reads the same group's columns, needs no per-tile records and no sum, and leaves cs->stats filled.
+// With lk (ramx_dev_planes; its planes and fam_base set by the caller, the buffer zeroed) a fourth stage follows the pileup's:
+// the group's bit planes, written into the buffer of the whole flank set.
 static int pileup_replay(ramx_dev *d, const char *who, AlnArgs aa, int KW, const ReplayPlan &pl, int32_t n_families,
-                         const int8_t *cons, const int32_t *rows, double *kernel_ms, const CopyStatsArgs *cs = NULL)
+                         const int8_t *cons, const int32_t *rows, double *kernel_ms, const CopyStatsArgs *cs = NULL,
+                         const PlanesArgs *lk = NULL)
 {
   const int tiles = pl.tiles, maxrows = pl.maxrows, L = aa.L, W = aa.k.W;
   // the budget counts, per tile, the decision codes and the walked columns (col_idx, col_ins) of its 64 flanks: the columns
@@ -1925,13 +1944,22 @@ static int pileup_replay(ramx_dev *d, const char *who, AlnArgs aa, int KW, const
     ca.col_idx = d->d_pl_idx; ca.col_ins = d->d_pl_ins;
     ca.L = L; ca.Np = aa.k.Np; ca.W = W; ca.KW = KW; ca.gn = gn;
   }
+  PlanesArgs la;
+  memset(&la, 0, sizeof(la));
+  if (lk)
+  {
+    la = *lk;
+    la.bases = d->d_bases; la.tile_fam = d->d_rp_tile; la.fam = d->d_rp_fam; la.rows = d->d_rp_rows; la.ends = d->d_al_ends;
+    la.col_idx = d->d_pl_idx; la.col_ins = d->d_pl_ins;
+    la.Np = aa.k.Np; la.W = W; la.KW = KW; la.gn = gn;
+  }
   PileArgs pa;
   pa.bases = d->d_bases; pa.tile_fam = d->d_rp_tile; pa.cons = d->d_rp_cons; pa.rows = d->d_rp_rows; pa.ends = d->d_al_ends;
   pa.col_idx = d->d_pl_idx; pa.col_ins = d->d_pl_ins; pa.slab = d->d_pl_slab;
   pa.L = L; pa.Np = aa.k.Np; pa.W = W; pa.KW = KW; pa.gn = gn; pa.slab_rows = maxrows;
   PileSumArgs sa;
   sa.slab = d->d_pl_slab; sa.fam = d->d_rp_fam; sa.cons = d->d_rp_cons; sa.cols = d->d_pl_cols; sa.L = L; sa.slab_rows = maxrows;
-  return replay_groups(d, who, tiles, group, 3, kernel_ms, [&](int tile0, int nt, auto &mark) {
+  return replay_groups(d, who, tiles, group, lk ? 4 : 3, kernel_ms, [&](int tile0, int nt, auto &mark) {
     int lrc;
     aa.tile0 = pa.tile0 = tile0;
     // the walk addresses its columns as [r * k.Np + n] with n the flank's index in the whole set: given the group's width for
@@ -1955,6 +1983,12 @@ static int pileup_replay(ramx_dev *d, const char *who, AlnArgs aa, int KW, const
     // the last group's pileup stage ends with the sum over the tiles of every family
     if (tile0 + nt == tiles && (lrc = ramx_pileup_launch_sum(d->stream, n_families, maxrows, sa)) != RAMX_OK) return lrc;
     mark();
+    if (lk)
+    {
+      la.tile0 = tile0;
+      if ((lrc = ramx_planes_launch(d->stream, nt, la)) != RAMX_OK) return lrc;
+      mark();
+    }
     return RAMX_OK;
   });
 }
@@ -2053,6 +2087,156 @@ extern "C" int ramx_dev_copy_stats(ramx_dev *d, const ramx_flank *flanks, int32_
   }
   return RAMX_OK;
 }
+
+// ------------------------------------------------------------------------------------------
+// co-segregation of variants: the pileup's replay with the bit planes as a fourth stage, kept resident, and the Gram matrix of
+// chosen planes (ramx_kernels_linkage.h)
+// ------------------------------------------------------------------------------------------
+static size_t linkage_budget(void)
+{
+  size_t budget = (size_t)2 << 30;
+  if (const char *e = getenv("RAMX_LINKAGE_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+  return budget;
+}
+
+extern "C" int ramx_dev_planes(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                               const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                               const int8_t *cons, const int32_t *rows, ramx_col_pileup *cols, ramx_aln_end *ends, double *kernel_ms)
+{
+  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = kernel_ms[3] = 0;
+  if (!d || !p || !p->matrix || n_families < 0 || n_padded < 0 || (n_padded & 63) || (n_padded && !flanks) ||
+      (n_families && (!fam_first || !fam_count || !rows)))
+  { ramx_set_error("ramx_dev_planes: bad argument"); return RAMX_ERR_ARG; }
+  if (p->bandwidth < 1 || p->L < 0) { ramx_set_error("ramx_dev_planes: bad bandwidth / L"); return RAMX_ERR_ARG; }
+  ReplayPlan pl;
+  int rc;
+  if ((rc = replay_plan("ramx_dev_planes", n_padded, fam_first, fam_count, n_families, p->L, cons, rows, NULL, true, pl)) != RAMX_OK) return rc;
+  if (pl.maxrows > 0 && !cols) { ramx_set_error("ramx_dev_planes: cols missing"); return RAMX_ERR_ARG; }
+  d->planes_ready = 0;
+  // where every family's planes lie: rows * 8 planes of its tiles' words each, family after family
+  std::vector<long long> lay((size_t)(n_families > 0 ? n_families : 1) * 3, 0), base((size_t)(n_families > 0 ? n_families : 1), 0);
+  size_t words = 0;
+  const size_t budget = linkage_budget();
+  for (int f = 0; f < n_families; f++)
+  {
+    const size_t nt = (size_t)((fam_count[f] + 63) / 64), need = (size_t)rows[f] * RAMX_PLANE_CLASSES * nt;
+    lay[3 * (size_t)f] = rows[f]; lay[3 * (size_t)f + 1] = (long long)nt; lay[3 * (size_t)f + 2] = base[f] = (long long)words;
+    words += need;
+    if (words * sizeof(unsigned long long) > budget)
+    {
+      ramx_set_error("ramx_dev_planes: the bit planes of families 0..%d (family %d: %d rows x 8 classes x %zu tiles; %zu bytes so far) do not fit RAMX_LINKAGE_BYTES = %zu",
+                     f, f, rows[f], nt, words * sizeof(unsigned long long), budget);
+      return RAMX_ERR_UNSUPPORTED;
+    }
+  }
+  const bool run = n_families > 0 && pl.maxrows > 0 && pl.tiles > 0;
+  if (run)
+  {
+    AlnArgs aa;
+    int KW = 0;
+    if ((rc = pileup_setup(d, flanks, n_padded, n_families, p, aa, &KW)) != RAMX_OK) return rc;
+    if ((rc = ensure(&d->d_lk_planes, &d->cap_lk_planes, (words ? words : 1) * sizeof(unsigned long long)))) return rc;
+    if ((rc = ensure(&d->d_lk_base, &d->cap_lk_base, (size_t)n_families * sizeof(long long)))) return rc;
+    HIPCHK(hipMemsetAsync(d->d_lk_planes, 0, (words ? words : 1) * sizeof(unsigned long long), d->stream));
+    // a blocking copy: `base` is a local, and pileup_replay may return on an error before it has synchronised
+    HIPCHK(hipMemcpy(d->d_lk_base, base.data(), (size_t)n_families * sizeof(long long), hipMemcpyHostToDevice));
+    PlanesArgs lk;
+    memset(&lk, 0, sizeof(lk));
+    lk.planes = d->d_lk_planes; lk.fam_base = d->d_lk_base;
+    if ((rc = pileup_replay(d, "ramx_dev_planes", aa, KW, pl, n_families, cons, rows, kernel_ms, NULL, &lk)) != RAMX_OK) return rc;
+  }
+  if ((rc = pileup_fetch(d, run, n_padded, fam_first, fam_count, n_families, p->L, cons, rows, NULL, cols, ends)) != RAMX_OK) return rc;
+  // resident from here on (where nothing ran there is no plane a Gram could be asked for)
+  long long *keep = (long long *)realloc(d->lk_fam, lay.size() * sizeof(long long));
+  if (!keep) { ramx_set_error("ramx_dev_planes: out of memory"); return RAMX_ERR_ARG; }
+  memcpy(keep, lay.data(), lay.size() * sizeof(long long));
+  d->lk_fam = keep; d->lk_families = n_families;
+  d->planes_ready = 1;
+  return RAMX_OK;
+}
+
+extern "C" int ramx_dev_plane_gram(ramx_dev *d, int32_t n_families, const ramx_plane *planes, const int32_t *plane_first,
+                                   const int32_t *plane_count, int32_t *co, const int64_t *co_first, uint64_t *bits, const int64_t *bits_first)
+{
+  if (!d || n_families < 0 || (n_families && (!plane_first || !plane_count)))
+  { ramx_set_error("ramx_dev_plane_gram: bad argument"); return RAMX_ERR_ARG; }
+  if (!d->planes_ready)
+  { ramx_set_error("ramx_dev_plane_gram: no resident bit planes (ramx_dev_planes has not run on this device, or a later call dropped them)"); return RAMX_ERR_STATE; }
+  if (n_families != d->lk_families)
+  { ramx_set_error("ramx_dev_plane_gram: %d families, the resident replay has %d", n_families, d->lk_families); return RAMX_ERR_ARG; }
+  // everything is checked before anything is launched or written
+  std::vector<long long> at, co_at((size_t)(n_families > 0 ? n_families : 1), 0);
+  std::vector<int4> gfam((size_t)(n_families > 0 ? n_families : 1), make_int4(0, 0, 0, 0)), block;
+  size_t co_words = 0;
+  for (int f = 0; f < n_families; f++)
+  {
+    const int P = plane_count[f];
+    const long long frows = d->lk_fam[3 * (size_t)f], T = d->lk_fam[3 * (size_t)f + 1], base = d->lk_fam[3 * (size_t)f + 2];
+    if (P < 0 || P > RAMX_LINKAGE_MAX_PLANES)
+    { ramx_set_error("ramx_dev_plane_gram: family %d: %d planes outside [0, %d]", f, P, RAMX_LINKAGE_MAX_PLANES); return RAMX_ERR_ARG; }
+    if (P == 0) continue;
+    if (plane_first[f] < 0 || !planes || !co || !co_first || co_first[f] < 0 || (bits && (!bits_first || bits_first[f] < 0)))
+    { ramx_set_error("ramx_dev_plane_gram: family %d: bad argument", f); return RAMX_ERR_ARG; }
+    const ramx_plane *pp = planes + plane_first[f];
+    for (int i = 0; i < P; i++)
+    {
+      if (pp[i].row < 0 || pp[i].row >= frows || pp[i].cls < 0 || pp[i].cls >= RAMX_PLANE_CLASSES)
+      { ramx_set_error("ramx_dev_plane_gram: family %d, plane %d: (row %d, class %d) outside the resident replay (%lld rows, classes 0..7)", f, i, pp[i].row, pp[i].cls, frows); return RAMX_ERR_ARG; }
+      if (i > 0 && (pp[i].row < pp[i - 1].row || (pp[i].row == pp[i - 1].row && pp[i].cls <= pp[i - 1].cls)))
+      { ramx_set_error("ramx_dev_plane_gram: family %d, plane %d: the planes are not strictly increasing in (row, class)", f, i); return RAMX_ERR_ARG; }
+    }
+    if (T == 0) continue;                             // a family without tiles writes nothing
+    gfam[f] = make_int4((int)at.size(), P, (int)T, 0);
+    co_at[f] = (long long)co_words;
+    co_words += (size_t)P * P;
+    for (int i = 0; i < P; i++) at.push_back(base + ((long long)pp[i].row * RAMX_PLANE_CLASSES + pp[i].cls) * T);
+    const int nb = (P + RAMX_GRAM_BLOCK - 1) / RAMX_GRAM_BLOCK;
+    for (int bi = 0; bi < nb; bi++)
+      for (int bj = bi; bj < nb; bj++) block.push_back(make_int4(f, bi, bj, 0));
+  }
+  if (block.empty()) return RAMX_OK;
+  // a plane to count has passed row < rows[f] of a family with tiles: that replay has run and its buffer exists
+  HIPCHK(hipSetDevice(d->ordinal));
+  int rc;
+  if ((rc = ensure(&d->d_lk_at, &d->cap_lk_at, at.size() * sizeof(long long)))) return rc;
+  if ((rc = ensure(&d->d_lk_coat, &d->cap_lk_coat, co_at.size() * sizeof(long long)))) return rc;
+  if ((rc = ensure(&d->d_lk_gfam, &d->cap_lk_gfam, gfam.size() * sizeof(int4)))) return rc;
+  if ((rc = ensure(&d->d_lk_block, &d->cap_lk_block, block.size() * sizeof(int4)))) return rc;
+  if ((rc = ensure(&d->d_lk_co, &d->cap_lk_co, co_words * sizeof(int)))) return rc;
+  HIPCHK(hipMemcpyAsync(d->d_lk_at, at.data(), at.size() * sizeof(long long), hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemcpyAsync(d->d_lk_coat, co_at.data(), co_at.size() * sizeof(long long), hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemcpyAsync(d->d_lk_gfam, gfam.data(), gfam.size() * sizeof(int4), hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemcpyAsync(d->d_lk_block, block.data(), block.size() * sizeof(int4), hipMemcpyHostToDevice, d->stream));
+  GramArgs ga;
+  ga.planes = d->d_lk_planes; ga.block = d->d_lk_block; ga.fam = d->d_lk_gfam; ga.at = d->d_lk_at; ga.co_at = d->d_lk_coat; ga.co = d->d_lk_co;
+  hipEvent_t ev[2] = { NULL, NULL };
+  const bool timed = hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
+  if (timed) (void)hipEventRecord(ev[0], d->stream);
+  rc = ramx_plane_gram_launch(d->stream, (int)block.size(), ga);
+  if (timed && rc == RAMX_OK) (void)hipEventRecord(ev[1], d->stream);
+  const hipError_t se = hipStreamSynchronize(d->stream);           // the uploads above read this function's vectors
+  float ms = 0;
+  d->lk_gram_ms = timed && rc == RAMX_OK && se == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess ? ms : 0;
+  for (int i = 0; i < 2; i++) if (ev[i]) (void)hipEventDestroy(ev[i]);
+  if (rc != RAMX_OK)
+  {
+    ramx_set_error("ramx_dev_plane_gram: the launch of %d workgroups failed", (int)block.size());
+    return rc;
+  }
+  HIPCHK(se);
+  for (int f = 0; f < n_families; f++)
+  {
+    const int P = gfam[f].y, T = gfam[f].z;
+    if (P == 0) continue;
+    HIPCHK(hipMemcpy(co + co_first[f], d->d_lk_co + co_at[f], (size_t)P * P * sizeof(int), hipMemcpyDeviceToHost));
+    // the chosen planes' own words, plane after plane (a diagnostic: one copy a plane)
+    for (int i = 0; bits && i < P; i++)
+      HIPCHK(hipMemcpy(bits + bits_first[f] + (size_t)i * T, d->d_lk_planes + at[(size_t)gfam[f].x + i], (size_t)T * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  }
+  return RAMX_OK;
+}
+
+extern "C" double ramx_dev_plane_gram_ms(ramx_dev *d) { return d ? d->lk_gram_ms : 0; }
 
 extern "C" int ramx_dev_refine(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
                                const int32_t *fam_count, int32_t n_families, const ramx_params *p,

@@ -508,6 +508,59 @@ static int copies_families(ramx_dev *d, int direction, const int *fidx, int nb, 
   return rc;
 }
 
+static ramx_linkage_cb g_linkage_cb = NULL;
+static void *g_linkage_user = NULL;
+static int32_t g_linkage_count = 4, g_linkage_permille = 100, g_linkage_max = 1024;
+void ramx_set_linkage_sink(ramx_linkage_cb cb, void *user, int32_t min_count, int32_t min_permille, int32_t max_variants)
+{
+  g_linkage_cb = cb;
+  g_linkage_user = user;
+  g_linkage_count = min_count; g_linkage_permille = min_permille;
+  g_linkage_max = max_variants < 0 ? 0 : max_variants > RAMX_LINKAGE_MAX_PLANES / 2 ? RAMX_LINKAGE_MAX_PLANES / 2 : max_variants;
+}
+
+/* With a linkage sink set: the bit planes of nb families along their kept consensus (rows = ret), the variants selected from the
+ * pileup of that replay and their Gram matrix, handed over family by family.  Layout as copies_families. */
+static int linkage_families(ramx_dev *d, int direction, const int *fidx, int nb, const ramx_flank *fl, int32_t npad,
+                            const int32_t *first, const int32_t *count, const ramx_params *p, const int8_t *cons, const int32_t *ret)
+{
+  if (ramx_dev_is_multi(d))
+  { ramx_set_error("linkage sink: not with a communicator or mailbox route active (the selection needs the counts of every rank)"); return RAMX_ERR_UNSUPPORTED; }
+  const size_t L = (size_t)(p->L > 0 ? p->L : 1), n = (size_t)(nb > 0 ? nb : 1);
+  int32_t *nrows = (int32_t *)calloc(n, sizeof(int32_t)), *pfirst = (int32_t *)calloc(n, sizeof(int32_t)), *pcount = (int32_t *)calloc(n, sizeof(int32_t));
+  int64_t *cfirst = (int64_t *)calloc(n, sizeof(int64_t));
+  ramx_col_pileup *cols = (ramx_col_pileup *)calloc(n * L, sizeof(ramx_col_pileup));
+  ramx_plane *planes = (ramx_plane *)calloc(n * 2 * (size_t)(g_linkage_max > 0 ? g_linkage_max : 1), sizeof(ramx_plane));
+  int32_t *co = NULL;
+  for (int b = 0; b < nb; b++) nrows[b] = ret[b] > 0 ? ret[b] : 0;
+  int rc = ramx_dev_planes(d, fl, npad, first, count, nb, p, cons, nrows, cols, NULL, NULL);
+  if (rc == RAMX_OK)
+  {
+    int32_t at = 0;
+    int64_t cells = 0;
+    for (int b = 0; b < nb; b++)
+    {
+      pfirst[b] = at;
+      /* a family without a flank has no tile to take a plane from */
+      pcount[b] = count[b] > 0 ? ramx_select_planes(cons + (size_t)b * p->L, nrows[b], cols + (size_t)b * L, g_linkage_count, g_linkage_permille, g_linkage_max, planes + at) : 0;
+      cfirst[b] = cells;
+      at += pcount[b]; cells += (int64_t)pcount[b] * pcount[b];
+    }
+    co = (int32_t *)calloc((size_t)(cells > 0 ? cells : 1), sizeof(int32_t));
+    rc = ramx_dev_plane_gram(d, nb, planes, pfirst, pcount, co, cfirst, NULL, NULL);
+  }
+  for (int b = 0; b < nb && rc == RAMX_OK; b++)
+  {
+    ramx_linkage lk;
+    memset(&lk, 0, sizeof(lk));
+    lk.direction = direction; lk.family = fidx ? fidx[b] : 0; lk.rows = nrows[b]; lk.n_planes = pcount[b];
+    lk.cons = cons + (size_t)b * p->L; lk.cols = cols + (size_t)b * L; lk.planes = planes + pfirst[b]; lk.co = co + cfirst[b];
+    g_linkage_cb(&lk, g_linkage_user);
+  }
+  free(nrows); free(pfirst); free(pcount); free(cfirst); free(cols); free(planes); free(co);
+  return rc;
+}
+
 /* nx flanks padded to whole tiles of 64 with empty flanks (no base: t_lo > t_hi): a malloc'ed copy, for nx = 0 too; *npad its length */
 static ramx_flank empty_flank(void) { ramx_flank x; memset(&x, 0, sizeof(x)); x.t_lo = 1; x.t_hi = 0; x.step = 1; return x; }
 static ramx_flank *pad_to_tiles(const ramx_flank *fl, int nx, int *npad)
@@ -542,6 +595,18 @@ static int copies_direction(ramx_dev *d, int direction, int family, const ramx_f
   int8_t *c1 = (int8_t *)calloc((size_t)(p->L > 0 ? p->L : 1), 1);
   if (ret > 0) memcpy(c1, cons, (size_t)ret);
   const int rc = copies_families(d, direction, &family, 1, pf, map, npad, &first, &count, p, c1, &r, NULL);
+  free(pf); free(c1);
+  return rc;
+}
+
+/* one direction of one family, as refine_direction */
+static int linkage_direction(ramx_dev *d, int direction, int family, const ramx_flank *fl, int nx, const ramx_params *p, const int8_t *cons, int ret)
+{
+  int npad; ramx_flank *pf = pad_to_tiles(fl, nx, &npad);
+  const int32_t first = 0, count = nx, r = ret;
+  int8_t *c1 = (int8_t *)calloc((size_t)(p->L > 0 ? p->L : 1), 1);
+  if (ret > 0) memcpy(c1, cons, (size_t)ret);
+  const int rc = linkage_families(d, direction, &family, 1, pf, npad, &first, &count, p, c1, &r);
   free(pf); free(c1);
   return rc;
 }
@@ -806,6 +871,11 @@ run_again:
   {
     rc = copies_direction(d, direction, family, fl, map, nx, p, cons, info->ret);
     SEAM1_PHASE("per-copy statistics");
+  }
+  if (rc == RAMX_OK && g_linkage_cb != NULL)
+  {
+    rc = linkage_direction(d, direction, family, fl, nx, p, cons, info->ret);
+    SEAM1_PHASE("linkage");
   }
 #undef SEAM1_PHASE
 #undef FP_JOIN
@@ -1138,6 +1208,14 @@ int ramx_extend_batch(int direction, ramx_family *fam, int32_t F, const ramx_par
       rc = copies_families(d, direction, fidx, nb, fl, map, (int32_t)fpos, first, count, p, cons, rets, at_of);
       free(rets);
       BATCH_PHASE("per-copy statistics");
+    }
+    if (rc == RAMX_OK && g_linkage_cb != NULL)
+    {
+      int32_t *rets = (int32_t *)malloc(sizeof(int32_t) * (size_t)nb);
+      for (int b = 0; b < nb; b++) rets[b] = binfo[b].ret;
+      rc = linkage_families(d, direction, fidx, nb, fl, (int32_t)fpos, first, count, p, cons, rets);
+      free(rets);
+      BATCH_PHASE("linkage");
     }
     free(binfo); free(cons); free(th); free(tp);
     BATCH_PHASE("write-back");

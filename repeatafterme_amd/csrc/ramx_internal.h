@@ -20,6 +20,9 @@ int ramx_runtime_l(void);
 /* seam 1's routing: families up to this many extendable cores run as a batch of one (csrc/ramx_device.hip) */
 int ramx_dev_family_route_max(ramx_dev *d, const ramx_params *p);
 
+/* a communicator or mailbox route is active on this device: counts of one rank are not the family's (csrc/ramx_device.hip) */
+int ramx_dev_is_multi(ramx_dev *d);
+
 /* the packed twin of a library made by ramx_load_sequence_subset_packed (NULL for any other library) */
 const ramx_packed_library *ramx_packed_of(const struct sequenceLibrary *lib);
 /* a library is about to be freed: the device copy it may own is forgotten (csrc/ramx_extend.c) */

@@ -139,6 +139,26 @@ COPY_STATS_DTYPE = np.dtype([(k, np.int32) for k in COPY_STATS_FIELDS])
 assert COPY_STATS_DTYPE.itemsize == 48
 
 
+# co-segregation of variants: C-ABI ramx_plane (8 bytes) and ramx_link (40 bytes), include/ramx.h
+PLANE_DTYPE = np.dtype([("row", np.int32), ("cls", np.int32)])
+LINK_DTYPE = np.dtype([(k, np.int32) for k in ("p", "q", "n", "n_p", "n_q", "n_pq")] + [("expected", np.float64), ("mlog10p", np.float64)])
+assert PLANE_DTYPE.itemsize == 8 and LINK_DTYPE.itemsize == 40
+PLANE_COVER = 6                      # RAMX_PLANE_COVER
+LINKAGE_MAX_PLANES = 2048            # RAMX_LINKAGE_MAX_PLANES
+PLANE_NAMES = ("A", "C", "G", "T", "N", "del", "cover", "ins")
+
+
+@dataclass
+class Linkage:
+    """Variants of one direction of one family along its kept consensus and their Gram matrix (C-ABI ramx_linkage)."""
+    direction: int
+    family: int                      # index in a batch, else 0
+    cons: np.ndarray                 # int8 [rows]: the kept consensus (rows = ret)
+    cols: np.ndarray                 # PILEUP_DTYPE [rows]
+    planes: np.ndarray               # PLANE_DTYPE [P]: the selected variants and their rows' cover planes
+    co: np.ndarray                   # int32 [P][P]
+
+
 @dataclass
 class Copies:
     """Per-copy statistics of one direction of one family along its kept consensus (C-ABI ramx_copies / ramx_dev_copy_stats)."""

@@ -10,7 +10,8 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .datamodel import ALN_END_DTYPE, ALN_NONE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, PILEUP_DTYPE, CoreSet, ExtendParams
+from .datamodel import (ALN_END_DTYPE, ALN_NONE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, LINK_DTYPE, PILEUP_DTYPE, PLANE_DTYPE, CoreSet,
+                        ExtendParams)
 from .extend import RunInfo, _info, _params
 
 
@@ -71,6 +72,38 @@ class CopyStatsResult:
     stats: np.ndarray                      # COPY_STATS_DTYPE [n_padded]
     ends: np.ndarray                       # ALN_END_DTYPE [n_padded]
     kernel_ms: tuple                       # HIP-event times of the forward kernels, the walk kernels, the statistics kernel
+
+
+@dataclass
+class PlanesResult:
+    cols: np.ndarray                       # PILEUP_DTYPE [n_families][L], as PileupResult
+    ends: np.ndarray                       # ALN_END_DTYPE [n_padded]
+    kernel_ms: tuple                       # HIP-event times: forward, walk, pileup + sum, planes
+    fam_count: np.ndarray                  # int32 [n_families]: what plane_gram sizes `bits` with
+
+
+def select_planes(cons, cols, min_count: int = 4, min_permille: int = 100, max_variants: int = 1024) -> np.ndarray:
+    """The variants of a pileup and their rows' cover planes (C-ABI ramx_select_planes, host C): -> PLANE_DTYPE [P]."""
+    c = np.ascontiguousarray(cons, np.int8)
+    pl = np.ascontiguousarray(cols, PILEUP_DTYPE).reshape(-1)
+    assert len(pl) >= len(c)
+    out = np.zeros(max(2 * max(int(max_variants), 0), 1), PLANE_DTYPE)
+    n = _lib.lib().ramx_select_planes(c.ctypes.data, len(c), pl.ctypes.data, int(min_count), int(min_permille), int(max_variants),
+                                      out.ctypes.data)
+    return out[:n].copy()
+
+
+def link_pairs(planes, co, min_mlog10p: float = 0.0, cap: Optional[int] = None):
+    """The pair statistic on a Gram matrix (C-ABI ramx_link_pairs, host C): -> (LINK_DTYPE [min(found, cap)], found)."""
+    pl = np.ascontiguousarray(planes, PLANE_DTYPE).reshape(-1)
+    P = len(pl)
+    m = np.ascontiguousarray(co, np.int32)
+    assert m.size == P * P
+    if cap is None:
+        cap = P * (P - 1) // 2
+    out = np.zeros(max(cap, 1), LINK_DTYPE)
+    n = _lib.lib().ramx_link_pairs(pl.ctypes.data, P, m.ctypes.data, float(min_mlog10p), out.ctypes.data, int(cap))
+    return out[:min(n, cap)].copy(), int(n)
 
 
 def copy_kimura(stats) -> float:
@@ -264,6 +297,51 @@ class Device:
                                                cons.ctypes.data, rows_a.ctypes.data, int(bool(rows_reversed)), stats.ctypes.data,
                                                ends.ctypes.data, ms), "ramx_dev_copy_stats")
         return CopyStatsResult(stats, ends, (ms[0], ms[1], ms[2]))
+
+    def planes(self, flanks, p: ExtendParams, cons, rows=None, fam_first=None, fam_count=None) -> PlanesResult:
+        """The pileup of every family along a given consensus, and its bit planes left resident on the device for plane_gram()
+        (C-ABI ramx_dev_planes): arguments as profile()."""
+        cp, keep = _params(p)
+        arr, npad, first, count, cons, rows_a = self._families(flanks, p, cons, rows, fam_first, fam_count)
+        nf = len(first)
+        cols = np.zeros((nf, max(p.L, 1)), PILEUP_DTYPE)
+        ends = self._no_ends(npad)
+        ms = (C.c_double * 4)()
+        _lib.check(self._L.ramx_dev_planes(self._h, arr, npad, first.ctypes.data, count.ctypes.data, nf, C.byref(cp),
+                                           cons.ctypes.data, rows_a.ctypes.data, cols.ctypes.data, ends.ctypes.data, ms),
+                   "ramx_dev_planes")
+        self._plane_tiles = (count + 63) // 64
+        return PlanesResult(cols, ends, tuple(ms), count)
+
+    def plane_gram(self, planes, bits: bool = False):
+        """The Gram matrix of chosen planes of the resident replay (C-ABI ramx_dev_plane_gram).  `planes`: one PLANE_DTYPE
+        array (one family), or a list of them, one per family of the planes() call.  -> co (int32 [P][P]), or (co, bits) with
+        bits uint64 [P][T]; lists of them for a list."""
+        one = not isinstance(planes, (list, tuple))
+        lists = [np.ascontiguousarray(x, PLANE_DTYPE).reshape(-1) for x in ([planes] if one else planes)]
+        nf = len(lists)
+        tiles = getattr(self, "_plane_tiles", np.zeros(nf, np.int64))
+        tiles = [int(tiles[f]) if f < len(tiles) else 0 for f in range(nf)]
+        cnt = np.array([len(x) for x in lists], np.int32)
+        first = np.concatenate([[0], np.cumsum(cnt)[:-1]]).astype(np.int32) if nf else np.zeros(0, np.int32)
+        allp = np.concatenate(lists) if nf and cnt.sum() else np.zeros(1, PLANE_DTYPE)
+        co_first = np.concatenate([[0], np.cumsum(cnt.astype(np.int64) ** 2)[:-1]]).astype(np.int64) if nf else np.zeros(0, np.int64)
+        co = np.full(max(int((cnt.astype(np.int64) ** 2).sum()), 1), -1, np.int32)
+        bsz = np.array([int(cnt[f]) * tiles[f] for f in range(nf)], np.int64)
+        b_first = np.concatenate([[0], np.cumsum(bsz)[:-1]]).astype(np.int64) if nf else np.zeros(0, np.int64)
+        bw = np.zeros(max(int(bsz.sum()), 1), np.uint64) if bits else None
+        _lib.check(self._L.ramx_dev_plane_gram(self._h, nf, allp.ctypes.data, first.ctypes.data, cnt.ctypes.data, co.ctypes.data,
+                                               co_first.ctypes.data, bw.ctypes.data if bits else None,
+                                               b_first.ctypes.data if bits else None), "ramx_dev_plane_gram")
+        cos = [co[co_first[f]:co_first[f] + int(cnt[f]) ** 2].reshape(int(cnt[f]), int(cnt[f])) for f in range(nf)]
+        if not bits:
+            return cos[0] if one else cos
+        bws = [bw[b_first[f]:b_first[f] + bsz[f]].reshape(int(cnt[f]), tiles[f]) for f in range(nf)]
+        return (cos[0], bws[0]) if one else (cos, bws)
+
+    def plane_gram_ms(self) -> float:
+        """HIP-event time of the Gram kernel of the last plane_gram() (C-ABI ramx_dev_plane_gram_ms)."""
+        return float(self._L.ramx_dev_plane_gram_ms(self._h))
 
     def refine(self, flanks, p: ExtendParams, cons, rows=None, fam_first=None, fam_count=None,
                max_replays: int = 10) -> RefineResult:

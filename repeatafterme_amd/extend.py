@@ -13,8 +13,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .datamodel import (ALN_END_DTYPE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, FLANK_DTYPE, PILEUP_DTYPE, Alignment, Copies, CoreSet,
-                        ExtendParams, Profile, Refinement)
+from .datamodel import (ALN_END_DTYPE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, FLANK_DTYPE, PILEUP_DTYPE, PLANE_DTYPE, Alignment, Copies,
+                        CoreSet, ExtendParams, Linkage, Profile, Refinement)
 
 
 @dataclass
@@ -170,14 +170,52 @@ class _CopiesSink:
         return False
 
 
+class _LinkageSink:
+    """Collects what seam 1 hands to the linkage sink (ramx_set_linkage_sink) while the block runs.  select: (min_count,
+    min_permille, max_variants)."""
+
+    def __init__(self, select=(4, 100, 1024)):
+        self.got = []
+        self.select = tuple(int(x) for x in select)
+
+        def _cb(ptr, _user):
+            lk = ptr.contents
+
+            def grab(src, count, dtype):
+                out = np.zeros(count, dtype)
+                if count and src:
+                    C.memmove(out.ctypes.data, src, count * out.dtype.itemsize)
+                return out
+            P = lk.n_planes
+            self.got.append(Linkage(lk.direction, lk.family, grab(lk.cons, lk.rows, np.int8), grab(lk.cols, lk.rows, PILEUP_DTYPE),
+                                    grab(lk.planes, P, PLANE_DTYPE), grab(lk.co, P * P, np.int32).reshape(P, P)))
+        self._cb = _lib.LINKAGE_CB(_cb)
+
+    def __enter__(self):
+        _lib.lib().ramx_set_linkage_sink(self._cb, None, *self.select)
+        return self
+
+    def __exit__(self, *exc):
+        _lib.lib().ramx_set_linkage_sink(_lib.LINKAGE_CB(), None, 4, 100, 1024)
+        return False
+
+
 def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, master: np.ndarray,
-                     p: ExtendParams, profile: bool = False, align: bool = False, refine: int = 0, copies: bool = False):
+                     p: ExtendParams, profile: bool = False, align: bool = False, refine: int = 0, copies: bool = False,
+                     linkage=None):
     """direction: 1 = right, 0 = left (reference ram_extend.c:424,506).  profile=True: returns (RunInfo, Profile) -- the
     direction is replayed along the consensus it chose (C-ABI ramx_dev_profile) after the loop.  align=True: returns
     (RunInfo, Alignment), or (RunInfo, Profile, Alignment) with both -- every flank aligned to the kept consensus (C-ABI
     ramx_dev_align).  refine=n > 0: a Refinement comes last in the tuple -- the kept consensus' pileup and its refinement over at
     most n replays (C-ABI ramx_dev_pileup / ramx_dev_refine).  copies=True: a Copies comes last of all -- every copy's
-    statistics along the kept consensus (C-ABI ramx_dev_copy_stats)."""
+    statistics along the kept consensus (C-ABI ramx_dev_copy_stats).  linkage=True or (min_count, min_permille, max_variants): a
+    Linkage comes behind everything else -- the variants of the kept consensus and their Gram matrix (C-ABI ramx_dev_planes,
+    ramx_select_planes, ramx_dev_plane_gram)."""
+    if linkage:
+        with _LinkageSink((4, 100, 1024) if linkage is True else linkage) as lsink:
+            res = extend_alignment(direction, cores, sequence, master, p, profile=profile, align=align, refine=refine, copies=copies)
+        assert len(lsink.got) == 1
+        return (res + (lsink.got[0],)) if isinstance(res, tuple) else (res, lsink.got[0])
     if copies:
         with _CopiesSink() as csink:
             res = extend_alignment(direction, cores, sequence, master, p, profile=profile, align=align, refine=refine)
@@ -212,11 +250,20 @@ def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, maste
     return _info(ci)
 
 
-def extend_batch(direction: int, families, p: ExtendParams, profile: bool = False, align: bool = False, copies: bool = False):
+def extend_batch(direction: int, families, p: ExtendParams, profile: bool = False, align: bool = False, copies: bool = False,
+                 linkage=None):
     """Many families in one launch (C-ABI ramx_extend_batch).  `families` is a list of (cores, sequence, master);
     every family is updated in place exactly like extend_alignment does for one.  Returns one RunInfo per family;
     profile=True: (RunInfos, Profiles), one Profile per family in the order of `families`; align=True: (RunInfos,
-    Alignments), or (RunInfos, Profiles, Alignments) with both.  copies=True: the families' Copies come last in the tuple."""
+    Alignments), or (RunInfos, Profiles, Alignments) with both.  copies=True: the families' Copies come last in the tuple.
+    linkage (as extend_alignment): the families' Linkages come behind everything else."""
+    if linkage:
+        with _LinkageSink((4, 100, 1024) if linkage is True else linkage) as lsink:
+            res = extend_batch(direction, families, p, profile=profile, align=align, copies=copies)
+        by_family = {lk.family: lk for lk in lsink.got}
+        assert len(by_family) == len(lsink.got) == len(families)
+        lks = [by_family[i] for i in range(len(families))]
+        return (res + (lks,)) if isinstance(res, tuple) else (res, lks)
     if copies:
         with _CopiesSink() as csink:
             res = extend_batch(direction, families, p, profile=profile, align=align)

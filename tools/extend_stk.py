@@ -16,7 +16,9 @@ rebuilds with an external aligner from -cons and -outfa (extend-stk.pl:553-556);
 replays (RAMExtend -outpileup / -outrefined / -refine), the wrapper's `alignAndCallConsensus.pl -refine 10` step (:553-555);
 with -copies, <id>-copies.tsv: every copy's divergence from the kept consensus of both extensions (RAMExtend -outcopies), and
 per direction the family's mean Kimura divergence over the extension beside the matrix the wrapper's ladder would pick for it
--- the check that the matrix chosen from the seed alignment was the right one for the extended part.
+-- the check that the matrix chosen from the seed alignment was the right one for the extended part; with -linkage,
+<id>-linkage.tsv: the pairs of variant columns of both extensions whose variants travel together in the copies (RAMExtend
+-outlinkage) -- the sign that the family is two subfamilies under one consensus.
 
 (the re-alignment and Stockholm rewriting that follow in the wrapper belong to RepeatModeler and are out of scope).
 """
@@ -48,6 +50,7 @@ def main(argv=None):
                     help="also write <id>-pileup.tsv and <id>-refined-cons.fa per family (RAMExtend -outpileup / -outrefined / -refine N)")
     ap.add_argument("-copies", action="store_true", help="also write <id>-copies.tsv per family (RAMExtend -outcopies) and print "
                     "each extension's divergence with the matrix it would call for")
+    ap.add_argument("-linkage", action="store_true", help="also write <id>-linkage.tsv per family (RAMExtend -outlinkage)")
     ap.add_argument("-one_by_one", action="store_true", help="start one RAMExtend per family, as the wrapper does")
     a = ap.parse_args(argv)
 
@@ -88,7 +91,8 @@ def main(argv=None):
                                        (["-outaln", base + "-aln.a2m"] if a.aln else []) +
                                        (["-outpileup", base + "-pileup.tsv", "-outrefined", base + "-refined-cons.fa", "-refine",
                                          str(a.refine)] if a.refine > 0 else []) +
-                                       (["-outcopies", base + "-copies.tsv"] if a.copies else []),
+                                       (["-outcopies", base + "-copies.tsv"] if a.copies else []) +
+                                       (["-outlinkage", base + "-linkage.tsv"] if a.linkage else []),
                                        stdout=log, stderr=subprocess.STDOUT).returncode
                 if rc:
                     sys.exit(f"  RAMExtend failed! [{rc}] see {base}-repam.log")
@@ -96,10 +100,10 @@ def main(argv=None):
             lst = os.path.join(a.outdir, f"batch-{matrix}-{minimp}.list")
             with open(lst, "w") as fh:
                 for seed, base in fams:
-                    # fields six to ten are optional: "-" holds the place of one that is not asked for before one that is
+                    # fields six to eleven are optional: "-" holds the place of one that is not asked for before one that is
                     opt = [base + "-profile.tsv" if a.profile else "-", base + "-aln.a2m" if a.aln else "-",
                            base + "-pileup.tsv" if a.refine > 0 else "-", base + "-refined-cons.fa" if a.refine > 0 else "-",
-                           base + "-copies.tsv" if a.copies else "-"]
+                           base + "-copies.tsv" if a.copies else "-", base + "-linkage.tsv" if a.linkage else "-"]
                     while opt and opt[-1] == "-":
                         opt.pop()
                     fh.write("\t".join([base + "-linup.tsv", base + "-repam.log", base + "-ext-cons.fa",
@@ -135,6 +139,12 @@ def main(argv=None):
                     would = stk.choose_scoring(div, a.min_aligning_seqs)[0]
                     print(f"  - Extension divergence [{tag}]: {div:.2f} % over {used.split('=')[1]} of {copies.split('=')[1]} copies: "
                           f"matrix {would} (used: {matrix})" + ("" if would == matrix or used.endswith("=0") else "  **differs**"))
+            if a.linkage and os.path.exists(base + "-linkage.tsv"):
+                for line in open(base + "-linkage.tsv"):                # the summary line of each direction
+                    if line.startswith("#"):
+                        tag, variants, pairs, linked = line[1:].rstrip("\n").split("\t")
+                        print(f"  - Linked variants [{tag}]: {linked.split('=')[1]} of {pairs.split('=')[1]} pairs among "
+                              f"{variants.split('=')[1]} variants")
     return 0
 
 

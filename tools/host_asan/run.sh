@@ -1,7 +1,7 @@
 #!/bin/bash
 # Host code of the replays under AddressSanitizer + UBSan, as stand-alone programs on the CPU (no GPU is opened, nothing is
 # loaded into python): replay_plan of ramx_device.hip and pad_to_tiles of ramx_extend.c, both static, so each program includes
-# its source file and takes the rest of the library from the built libramx.so.
+# its source file and takes the rest of the library from the built libramx.so; and ramx_linkage.c, which stands alone.
 # usage: tools/host_asan/run.sh        (after the library has been built)
 set -euo pipefail
 here=$(cd "$(dirname "$0")" && pwd)
@@ -14,6 +14,9 @@ lib="-L$root/repeatafterme_amd -lramx -Wl,-rpath,$root/repeatafterme_amd -Wl,-rp
 san="-fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g"
 gcc -std=gnu11 -O1 -Wno-alloc-size-larger-than $san $inc -o "$out/pad_to_tiles" "$here/pad_to_tiles_main.c" $lib -lm -lpthread
 "$out/pad_to_tiles"
+# the selection and the pair statistic of the linkage (ramx_linkage.c is compiled into the program, under the sanitizers too)
+gcc -std=gnu11 -O1 $san $inc -o "$out/linkage" "$here/linkage_main.c" -lm
+"$out/linkage"
 # (the device side of ramx_device.hip is compiled too, which takes a minute or two: the host object refers to its code object)
 "$rocm/bin/hipcc" --offload-arch=gfx950 -x hip -std=c++17 -O1 -g -fno-omit-frame-pointer $inc -Xarch_host -fsanitize=address,undefined \
   -Xarch_host -fno-sanitize-recover=undefined -o "$out/replay_plan" "$here/replay_plan_main.cpp" $lib -L"$rocm/lib" -lrccl -lpthread
