@@ -432,6 +432,121 @@ int ramx_resolve_flanks(int direction, const ramx_flat_cores *c, int bandwidth, 
   return nx;
 }
 
+/* What every sink is fed from: nb families laid out in tiles, with what the loop returned for each.  ramx_extend_batch fills it
+ * from the arrays of its launch, extend_flat_impl builds one of a single family (one_family_view); neither does unless a sink
+ * is set. */
+struct sink_view
+{
+  ramx_dev *d;
+  int direction;
+  const ramx_params *p;
+  int nb;
+  const int32_t *fidx;               /* [nb]: the family index a sink is told */
+  const ramx_flank *fl;              /* [npad]: every family's flanks padded to whole tiles of 64 */
+  const int32_t *map;                /* [npad]: the flanks' positions in their core lists */
+  int32_t npad;
+  const int32_t *first, *count;      /* [nb]: where a family's flanks begin in fl, and how many they are */
+  const int8_t *cons;                /* [nb][L]: the bases the loop chose */
+  const int32_t *rows_executed;      /* [nb] */
+  const int32_t *ret;                /* [nb]: the kept columns, clamped at 0 */
+  const uint64_t *lib_at;            /* by family index: where a family's own library begins in the one fl addresses (NULL: all 0) */
+};
+
+/* nx flanks padded to whole tiles of 64 with empty flanks (no base: t_lo > t_hi): a malloc'ed copy, for nx = 0 too; *npad its length */
+static ramx_flank empty_flank(void) { ramx_flank x; memset(&x, 0, sizeof(x)); x.t_lo = 1; x.t_hi = 0; x.step = 1; return x; }
+static ramx_flank *pad_to_tiles(const ramx_flank *fl, int nx, int *npad)
+{
+  const int n = *npad = (nx + 63) & ~63;
+  ramx_flank *pf = (ramx_flank *)malloc(sizeof(ramx_flank) * (size_t)(n > 0 ? n : 1));
+  if (nx > 0) memcpy(pf, fl, sizeof(ramx_flank) * (size_t)nx);
+  for (int i = nx; i < n; i++) pf[i] = empty_flank();
+  return pf;
+}
+
+/* The view of one direction of one family: its flanks padded once, and the rows_executed bases of the direction's own buffer
+ * copied once into an [1][L] block with zeros behind them.  free_one_family_view releases what this allocated. */
+static void one_family_view(struct sink_view *v, ramx_dev *d, int direction, const ramx_params *p, int family, const ramx_flank *fl,
+                            const int32_t *map, int nx, const int8_t *cons, int rows_executed, int ret)
+{
+  int npad;
+  int8_t *c1 = (int8_t *)calloc((size_t)(p->L > 0 ? p->L : 1), 1);
+  int32_t *one = (int32_t *)malloc(sizeof(int32_t) * 5);
+  if (rows_executed > 0) memcpy(c1, cons, (size_t)(rows_executed < p->L ? rows_executed : p->L));
+  one[0] = family; one[1] = 0; one[2] = nx; one[3] = rows_executed; one[4] = ret > 0 ? ret : 0;
+  memset(v, 0, sizeof(*v));
+  v->d = d; v->direction = direction; v->p = p; v->nb = 1;
+  v->fl = pad_to_tiles(fl, nx, &npad); v->map = map; v->npad = npad;
+  v->fidx = one; v->first = one + 1; v->count = one + 2; v->rows_executed = one + 3; v->ret = one + 4;
+  v->cons = c1;
+}
+static void free_one_family_view(struct sink_view *v)
+{
+  free((void *)v->fl); free((void *)v->cons); free((void *)v->fidx);
+}
+
+/* family b's flanks in the coordinates of its own library: a malloc'ed copy */
+static ramx_flank *own_flanks(const struct sink_view *v, int b)
+{
+  const int n = v->count[b];
+  ramx_flank *own = (ramx_flank *)malloc(sizeof(ramx_flank) * (size_t)(n > 0 ? n : 1));
+  for (int i = 0; i < n; i++) { own[i] = v->fl[v->first[b] + i]; if (v->lib_at) own[i].start -= (int64_t)v->lib_at[v->fidx[b]]; }
+  return own;
+}
+
+/* With a profile sink set: every family replayed in one call along the consensus the loop chose, over its rows_executed columns,
+ * handed over family by family.  A view without any flank is answered here (the device may hold no library then): every
+ * candidate total of every column is 0 and the vote gives the loop's base, A. */
+static int profile_families(const struct sink_view *v)
+{
+  const ramx_params *p = v->p;
+  ramx_col_profile *cols = (ramx_col_profile *)calloc((size_t)v->nb * (size_t)(p->L > 0 ? p->L : 1), sizeof(ramx_col_profile));
+  int32_t *last = (int32_t *)malloc(sizeof(int32_t) * (size_t)(v->npad > 0 ? v->npad : 1));
+  int rc = RAMX_OK;
+  if (v->npad == 0)
+  {
+    for (int b = 0; b < v->nb; b++)
+      for (int r = 0; r < v->rows_executed[b]; r++) cols[(size_t)b * p->L + r].base = v->cons[(size_t)b * p->L + r];
+  }
+  else
+    rc = ramx_dev_profile(v->d, v->fl, v->npad, v->first, v->count, v->nb, p, v->cons, v->rows_executed, cols, last, NULL, NULL, NULL);
+  for (int b = 0; b < v->nb && rc == RAMX_OK; b++)
+  {
+    ramx_profile pr;
+    pr.direction = v->direction; pr.family = v->fidx[b]; pr.n_cols = v->rows_executed[b]; pr.ret = v->ret[b]; pr.n_flanks = v->count[b];
+    pr.cols = cols + (size_t)b * p->L; pr.core_index = v->map + v->first[b]; pr.last_uncapped_row = last + v->first[b];
+    g_profile_cb(&pr, g_profile_user);
+  }
+  free(cols); free(last);
+  return rc;
+}
+
+/* With an alignment sink set: every family replayed in one call along its kept consensus (rows = ret), every flank walked back,
+ * handed over family by family.  ramx_dev_align answers the families without a flank or a kept column over the prefilled ends. */
+static int align_families(const struct sink_view *v)
+{
+  const size_t n = (size_t)(v->npad > 0 ? v->npad : 1);
+  int maxret = 0;
+  for (int b = 0; b < v->nb; b++) if (v->ret[b] > maxret) maxret = v->ret[b];
+  ramx_aln_end *ends = (ramx_aln_end *)malloc(sizeof(ramx_aln_end) * n);
+  int32_t *idx = (int32_t *)malloc(sizeof(int32_t) * n * (size_t)(maxret > 0 ? maxret : 1));
+  int32_t *ins = (int32_t *)malloc(sizeof(int32_t) * n * (size_t)(maxret > 0 ? maxret : 1));
+  for (int32_t i = 0; i < v->npad; i++) { ends[i].end_row = -1; ends[i].end_idx = -1; ends[i].score = 0; ends[i].start_idx = 0; ends[i].tail_ins = 0; }
+  const int rc = ramx_dev_align(v->d, v->fl, v->npad, v->first, v->count, v->nb, v->p, v->cons, v->ret, ends, idx, ins, NULL);
+  for (int b = 0; b < v->nb && rc == RAMX_OK; b++)
+  {
+    ramx_flank *own_fl = own_flanks(v, b);
+    ramx_alignment al;
+    memset(&al, 0, sizeof(al));
+    al.direction = v->direction; al.family = v->fidx[b]; al.rows = v->ret[b]; al.n_flanks = v->count[b]; al.stride = v->npad;
+    al.cons = v->cons + (size_t)b * v->p->L; al.flanks = own_fl; al.core_index = v->map + v->first[b]; al.ends = ends + v->first[b];
+    if (v->ret[b] > 0 && v->count[b] > 0) { al.col_idx = idx + v->first[b]; al.col_ins = ins + v->first[b]; }
+    g_align_cb(&al, g_align_user);
+    free(own_fl);
+  }
+  free(ends); free(idx); free(ins);
+  return rc;
+}
+
 static ramx_refine_cb g_refine_cb = NULL;
 static void *g_refine_user = NULL;
 static int g_refine_replays = 10;
@@ -442,33 +557,33 @@ void ramx_set_refine_sink(ramx_refine_cb cb, void *user, int32_t max_replays)
   g_refine_replays = max_replays >= 1 ? max_replays : 1;
 }
 
-/* With a refinement sink set: the pileup of nb families' kept consensus (rows = ret) and their refinement, handed over family
+/* With a refinement sink set: the pileup of the families' kept consensus (rows = ret) and their refinement, handed over family
  * by family.  The refinement's first replay IS the kept consensus' pileup: only when some family's consensus moved is the kept
- * one piled up in a call of its own.  fl is laid out in tiles (npad flanks); cons is [nb][L]. */
-static int refine_families(ramx_dev *d, int direction, const int *fidx, int nb, const ramx_flank *fl, int32_t npad,
-                           const int32_t *first, const int32_t *count, const ramx_params *p, const int8_t *cons, const int32_t *ret)
+ * one piled up in a call of its own. */
+static int refine_families(const struct sink_view *v)
 {
+  const ramx_params *p = v->p;
+  const int nb = v->nb;
   const size_t L = (size_t)(p->L > 0 ? p->L : 1);
-  int32_t *nrows = (int32_t *)calloc((size_t)(nb > 0 ? nb : 1) * 4, sizeof(int32_t)), *rrows = nrows + nb, *replays = rrows + nb, *conv = replays + nb;
+  int32_t *rrows = (int32_t *)calloc((size_t)(nb > 0 ? nb : 1) * 3, sizeof(int32_t)), *replays = rrows + nb, *conv = replays + nb;
   ramx_col_pileup *kept = (ramx_col_pileup *)calloc((size_t)nb * L, sizeof(ramx_col_pileup));
   ramx_col_pileup *refd = (ramx_col_pileup *)calloc((size_t)nb * L, sizeof(ramx_col_pileup));
   int8_t *rcons = (int8_t *)calloc((size_t)nb * L, 1);
   int moved = 0;
-  for (int b = 0; b < nb; b++) nrows[b] = ret[b] > 0 ? ret[b] : 0;
-  int rc = ramx_dev_refine(d, fl, npad, first, count, nb, p, cons, nrows, g_refine_replays, rcons, rrows, replays, conv, refd, NULL, NULL);
+  int rc = ramx_dev_refine(v->d, v->fl, v->npad, v->first, v->count, nb, p, v->cons, v->ret, g_refine_replays, rcons, rrows, replays, conv, refd, NULL, NULL);
   for (int b = 0; b < nb && rc == RAMX_OK; b++) moved |= replays[b] > 1;
-  if (rc == RAMX_OK && moved) rc = ramx_dev_pileup(d, fl, npad, first, count, nb, p, cons, nrows, kept, NULL, NULL);
+  if (rc == RAMX_OK && moved) rc = ramx_dev_pileup(v->d, v->fl, v->npad, v->first, v->count, nb, p, v->cons, v->ret, kept, NULL, NULL);
   for (int b = 0; b < nb && rc == RAMX_OK; b++)
   {
     ramx_refinement rf;
     memset(&rf, 0, sizeof(rf));
-    rf.direction = direction; rf.family = fidx ? fidx[b] : 0; rf.rows = nrows[b]; rf.refined_rows = rrows[b];
-    rf.replays = replays[b]; rf.converged = conv[b]; rf.n_flanks = count[b];
-    rf.cons = cons + (size_t)b * p->L; rf.cols = (moved ? kept : refd) + (size_t)b * p->L;
+    rf.direction = v->direction; rf.family = v->fidx[b]; rf.rows = v->ret[b]; rf.refined_rows = rrows[b];
+    rf.replays = replays[b]; rf.converged = conv[b]; rf.n_flanks = v->count[b];
+    rf.cons = v->cons + (size_t)b * p->L; rf.cols = (moved ? kept : refd) + (size_t)b * p->L;
     rf.refined_cons = rcons + (size_t)b * p->L; rf.refined_cols = refd + (size_t)b * p->L;
     g_refine_cb(&rf, g_refine_user);
   }
-  free(nrows); free(kept); free(refd); free(rcons);
+  free(rrows); free(kept); free(refd); free(rcons);
   return rc;
 }
 
@@ -480,31 +595,26 @@ void ramx_set_copies_sink(ramx_copies_cb cb, void *user)
   g_copies_user = user;
 }
 
-/* With a copies sink set: the per-copy statistics of nb families along their kept consensus (rows = ret), handed over family by
- * family.  fl is laid out in tiles (npad flanks); cons is [nb][L]; map the flanks' positions in their core lists; lib_at (NULL:
- * all 0) where a family's own library begins in the one the flanks address. */
-static int copies_families(ramx_dev *d, int direction, const int *fidx, int nb, const ramx_flank *fl, const int32_t *map, int32_t npad,
-                           const int32_t *first, const int32_t *count, const ramx_params *p, const int8_t *cons, const int32_t *ret,
-                           const uint64_t *lib_at)
+/* With a copies sink set: the per-copy statistics of the families along their kept consensus (rows = ret), handed over family by
+ * family. */
+static int copies_families(const struct sink_view *v)
 {
-  int32_t *nrows = (int32_t *)calloc((size_t)(nb > 0 ? nb : 1), sizeof(int32_t));
-  ramx_copy_stats *stats = (ramx_copy_stats *)calloc((size_t)(npad > 0 ? npad : 1), sizeof(ramx_copy_stats));
-  ramx_aln_end *ends = (ramx_aln_end *)malloc(sizeof(ramx_aln_end) * (size_t)(npad > 0 ? npad : 1));
-  for (int b = 0; b < nb; b++) nrows[b] = ret[b] > 0 ? ret[b] : 0;
-  const int rc = ramx_dev_copy_stats(d, fl, npad, first, count, nb, p, cons, nrows, !direction, stats, ends, NULL);
-  for (int b = 0; b < nb && rc == RAMX_OK; b++)
+  const size_t n = (size_t)(v->npad > 0 ? v->npad : 1);
+  ramx_copy_stats *stats = (ramx_copy_stats *)calloc(n, sizeof(ramx_copy_stats));
+  ramx_aln_end *ends = (ramx_aln_end *)malloc(sizeof(ramx_aln_end) * n);
+  const int rc = ramx_dev_copy_stats(v->d, v->fl, v->npad, v->first, v->count, v->nb, v->p, v->cons, v->ret, !v->direction, stats, ends, NULL);
+  for (int b = 0; b < v->nb && rc == RAMX_OK; b++)
   {
-    ramx_flank *own_fl = (ramx_flank *)malloc(sizeof(ramx_flank) * (size_t)(count[b] > 0 ? count[b] : 1));
-    for (int i = 0; i < count[b]; i++) { own_fl[i] = fl[first[b] + i]; if (lib_at) own_fl[i].start -= (int64_t)lib_at[fidx[b]]; }
+    ramx_flank *own_fl = own_flanks(v, b);
     ramx_copies cp;
     memset(&cp, 0, sizeof(cp));
-    cp.direction = direction; cp.family = fidx ? fidx[b] : 0; cp.rows = nrows[b]; cp.n_flanks = count[b];
-    cp.cons = cons + (size_t)b * p->L; cp.flanks = own_fl; cp.core_index = map + first[b];
-    cp.ends = ends + first[b]; cp.stats = stats + first[b];
+    cp.direction = v->direction; cp.family = v->fidx[b]; cp.rows = v->ret[b]; cp.n_flanks = v->count[b];
+    cp.cons = v->cons + (size_t)b * v->p->L; cp.flanks = own_fl; cp.core_index = v->map + v->first[b];
+    cp.ends = ends + v->first[b]; cp.stats = stats + v->first[b];
     g_copies_cb(&cp, g_copies_user);
     free(own_fl);
   }
-  free(nrows); free(stats); free(ends);
+  free(stats); free(ends);
   return rc;
 }
 
@@ -519,21 +629,21 @@ void ramx_set_linkage_sink(ramx_linkage_cb cb, void *user, int32_t min_count, in
   g_linkage_max = max_variants < 0 ? 0 : max_variants > RAMX_LINKAGE_MAX_PLANES / 2 ? RAMX_LINKAGE_MAX_PLANES / 2 : max_variants;
 }
 
-/* With a linkage sink set: the bit planes of nb families along their kept consensus (rows = ret), the variants selected from the
- * pileup of that replay and their Gram matrix, handed over family by family.  Layout as copies_families. */
-static int linkage_families(ramx_dev *d, int direction, const int *fidx, int nb, const ramx_flank *fl, int32_t npad,
-                            const int32_t *first, const int32_t *count, const ramx_params *p, const int8_t *cons, const int32_t *ret)
+/* With a linkage sink set: the bit planes of the families along their kept consensus (rows = ret), the variants selected from the
+ * pileup of that replay and their Gram matrix, handed over family by family. */
+static int linkage_families(const struct sink_view *v)
 {
-  if (ramx_dev_is_multi(d))
+  if (ramx_dev_is_multi(v->d))
   { ramx_set_error("linkage sink: not with a communicator or mailbox route active (the selection needs the counts of every rank)"); return RAMX_ERR_UNSUPPORTED; }
+  const ramx_params *p = v->p;
+  const int nb = v->nb;
   const size_t L = (size_t)(p->L > 0 ? p->L : 1), n = (size_t)(nb > 0 ? nb : 1);
-  int32_t *nrows = (int32_t *)calloc(n, sizeof(int32_t)), *pfirst = (int32_t *)calloc(n, sizeof(int32_t)), *pcount = (int32_t *)calloc(n, sizeof(int32_t));
+  int32_t *pfirst = (int32_t *)calloc(n, sizeof(int32_t)), *pcount = (int32_t *)calloc(n, sizeof(int32_t));
   int64_t *cfirst = (int64_t *)calloc(n, sizeof(int64_t));
   ramx_col_pileup *cols = (ramx_col_pileup *)calloc(n * L, sizeof(ramx_col_pileup));
   ramx_plane *planes = (ramx_plane *)calloc(n * 2 * (size_t)(g_linkage_max > 0 ? g_linkage_max : 1), sizeof(ramx_plane));
   int32_t *co = NULL;
-  for (int b = 0; b < nb; b++) nrows[b] = ret[b] > 0 ? ret[b] : 0;
-  int rc = ramx_dev_planes(d, fl, npad, first, count, nb, p, cons, nrows, cols, NULL, NULL);
+  int rc = ramx_dev_planes(v->d, v->fl, v->npad, v->first, v->count, nb, p, v->cons, v->ret, cols, NULL, NULL);
   if (rc == RAMX_OK)
   {
     int32_t at = 0;
@@ -542,143 +652,79 @@ static int linkage_families(ramx_dev *d, int direction, const int *fidx, int nb,
     {
       pfirst[b] = at;
       /* a family without a flank has no tile to take a plane from */
-      pcount[b] = count[b] > 0 ? ramx_select_planes(cons + (size_t)b * p->L, nrows[b], cols + (size_t)b * L, g_linkage_count, g_linkage_permille, g_linkage_max, planes + at) : 0;
+      pcount[b] = v->count[b] > 0 ? ramx_select_planes(v->cons + (size_t)b * p->L, v->ret[b], cols + (size_t)b * L, g_linkage_count, g_linkage_permille, g_linkage_max, planes + at) : 0;
       cfirst[b] = cells;
       at += pcount[b]; cells += (int64_t)pcount[b] * pcount[b];
     }
     co = (int32_t *)calloc((size_t)(cells > 0 ? cells : 1), sizeof(int32_t));
-    rc = ramx_dev_plane_gram(d, nb, planes, pfirst, pcount, co, cfirst, NULL, NULL);
+    rc = ramx_dev_plane_gram(v->d, nb, planes, pfirst, pcount, co, cfirst, NULL, NULL);
   }
   for (int b = 0; b < nb && rc == RAMX_OK; b++)
   {
     ramx_linkage lk;
     memset(&lk, 0, sizeof(lk));
-    lk.direction = direction; lk.family = fidx ? fidx[b] : 0; lk.rows = nrows[b]; lk.n_planes = pcount[b];
-    lk.cons = cons + (size_t)b * p->L; lk.cols = cols + (size_t)b * L; lk.planes = planes + pfirst[b]; lk.co = co + cfirst[b];
+    lk.direction = v->direction; lk.family = v->fidx[b]; lk.rows = v->ret[b]; lk.n_planes = pcount[b];
+    lk.cons = v->cons + (size_t)b * p->L; lk.cols = cols + (size_t)b * L; lk.planes = planes + pfirst[b]; lk.co = co + cfirst[b];
     g_linkage_cb(&lk, g_linkage_user);
   }
-  free(nrows); free(pfirst); free(pcount); free(cfirst); free(cols); free(planes); free(co);
+  free(pfirst); free(pcount); free(cfirst); free(cols); free(planes); free(co);
   return rc;
 }
 
-/* nx flanks padded to whole tiles of 64 with empty flanks (no base: t_lo > t_hi): a malloc'ed copy, for nx = 0 too; *npad its length */
-static ramx_flank empty_flank(void) { ramx_flank x; memset(&x, 0, sizeof(x)); x.t_lo = 1; x.t_hi = 0; x.step = 1; return x; }
-static ramx_flank *pad_to_tiles(const ramx_flank *fl, int nx, int *npad)
+static int any_sink(void) { return g_profile_cb || g_align_cb || g_refine_cb || g_copies_cb || g_linkage_cb; }
+
+/* one RAMX_TIMING line: the time since the phase before, under the caller's name */
+static void phase_line(const char *who, int width, const char *name, double *since)
 {
-  const int n = *npad = (nx + 63) & ~63;
-  ramx_flank *pf = (ramx_flank *)malloc(sizeof(ramx_flank) * (size_t)(n > 0 ? n : 1));
-  if (nx > 0) memcpy(pf, fl, sizeof(ramx_flank) * (size_t)nx);
-  for (int i = nx; i < n; i++) pf[i] = empty_flank();
-  return pf;
+  const double t = wall_ms();
+  fprintf(stderr, "RAMX_TIMING     %s %-*s %8.3f ms\n", who, width, name, t - *since);
+  *since = t;
 }
 
-/* one direction of one family: its flanks padded to whole tiles (no extendable core or ret = 0: answered by the calls on the host) */
-static int refine_direction(ramx_dev *d, int direction, int family, const ramx_flank *fl, int nx, const ramx_params *p,
-                            const int8_t *cons, int ret)
+/* every sink that is set, in this order, families ascending within a sink; stops at the first error */
+static int run_sinks(const struct sink_view *v, const char *who, int width, int timing, double *since)
 {
-  int npad; ramx_flank *pf = pad_to_tiles(fl, nx, &npad);
-  const int32_t first = 0, count = nx, r = ret;
-  /* cons holds at least L entries only in the batch; here it is the direction's own buffer, copied into an [1][L] block */
-  int8_t *c1 = (int8_t *)calloc((size_t)(p->L > 0 ? p->L : 1), 1);
-  if (ret > 0) memcpy(c1, cons, (size_t)ret);
-  const int rc = refine_families(d, direction, &family, 1, pf, npad, &first, &count, p, c1, &r);
-  free(pf); free(c1);
-  return rc;
-}
-
-/* one direction of one family, as refine_direction */
-static int copies_direction(ramx_dev *d, int direction, int family, const ramx_flank *fl, const int32_t *map, int nx,
-                            const ramx_params *p, const int8_t *cons, int ret)
-{
-  int npad; ramx_flank *pf = pad_to_tiles(fl, nx, &npad);
-  const int32_t first = 0, count = nx, r = ret;
-  int8_t *c1 = (int8_t *)calloc((size_t)(p->L > 0 ? p->L : 1), 1);
-  if (ret > 0) memcpy(c1, cons, (size_t)ret);
-  const int rc = copies_families(d, direction, &family, 1, pf, map, npad, &first, &count, p, c1, &r, NULL);
-  free(pf); free(c1);
-  return rc;
-}
-
-/* one direction of one family, as refine_direction */
-static int linkage_direction(ramx_dev *d, int direction, int family, const ramx_flank *fl, int nx, const ramx_params *p, const int8_t *cons, int ret)
-{
-  int npad; ramx_flank *pf = pad_to_tiles(fl, nx, &npad);
-  const int32_t first = 0, count = nx, r = ret;
-  int8_t *c1 = (int8_t *)calloc((size_t)(p->L > 0 ? p->L : 1), 1);
-  if (ret > 0) memcpy(c1, cons, (size_t)ret);
-  const int rc = linkage_families(d, direction, &family, 1, pf, npad, &first, &count, p, c1, &r);
-  free(pf); free(c1);
-  return rc;
-}
-
-/* With a profile sink set: replay one direction of one family along the consensus the loop chose and hand it over. */
-static int profile_direction(ramx_dev *d, int direction, int family, const ramx_flank *fl, const int32_t *map, int nx,
-                             const ramx_params *p, const int8_t *cons, int rows, int ret)
-{
-  const int L = p->L;
-  ramx_col_profile *cols = (ramx_col_profile *)calloc((size_t)(L > 0 ? L : 1), sizeof(ramx_col_profile));
-  int32_t *last = NULL;
+  const struct { int on; int (*feed)(const struct sink_view *); const char *phase; } sinks[] = {
+    { g_profile_cb != NULL, profile_families, "profile replay" },
+    { g_align_cb != NULL, align_families, "alignment replay" },
+    { g_refine_cb != NULL, refine_families, "pileup + refinement" },
+    { g_copies_cb != NULL, copies_families, "per-copy statistics" },
+    { g_linkage_cb != NULL, linkage_families, "linkage" },
+  };
   int rc = RAMX_OK;
-  if (nx == 0)
+  for (size_t i = 0; i < sizeof(sinks) / sizeof(sinks[0]) && rc == RAMX_OK; i++)
   {
-    /* no extendable core: every candidate total of every column is 0 and the vote gives A (answered on the host) */
-    for (int r = 0; r < rows; r++) cols[r].base = cons[r];
+    if (!sinks[i].on) continue;
+    rc = sinks[i].feed(v);
+    if (timing) phase_line(who, width, sinks[i].phase, since);
   }
-  else
-  {
-    int npad; ramx_flank *pf = pad_to_tiles(fl, nx, &npad);
-    last = (int32_t *)malloc(sizeof(int32_t) * (size_t)npad);
-    const int32_t first = 0, count = nx, nrows = rows;
-    rc = ramx_dev_profile(d, pf, npad, &first, &count, 1, p, cons, &nrows, cols, last, NULL, NULL, NULL);
-    free(pf);
-  }
-  if (rc == RAMX_OK)
-  {
-    ramx_profile pr;
-    pr.direction = direction; pr.family = family; pr.n_cols = rows; pr.ret = ret; pr.n_flanks = nx;
-    pr.cols = cols; pr.core_index = map; pr.last_uncapped_row = last;
-    g_profile_cb(&pr, g_profile_user);
-  }
-  free(cols); free(last);
   return rc;
 }
 
-/* With an alignment sink set: replay one direction of one family along the kept consensus (rows = ret), walk every flank
- * back and hand the alignments over. */
-static int align_direction(ramx_dev *d, int direction, int family, const ramx_flank *fl, const int32_t *map, int nx,
-                           const ramx_params *p, const int8_t *cons, int ret)
+/* what a finished direction leaves with the caller: the executed columns in master (ram_extend.c:1092-1095), and per flank with
+ * a positive trimmed score the extension length and score of its core (ram_extend.c:1234-1247) */
+static void write_back(int direction, const ramx_params *p, int8_t *master, ramx_flat_cores *c, const int8_t *cons, int rows_executed,
+                       const int32_t *map, const int32_t *th, const int32_t *tp, int nx)
 {
-  ramx_alignment al;
-  memset(&al, 0, sizeof(al));
-  al.direction = direction; al.family = family; al.rows = ret > 0 ? ret : 0; al.n_flanks = nx;
-  al.cons = cons; al.flanks = fl; al.core_index = map;
-  if (nx == 0 || ret <= 0)
+  for (int r = 0; r < rows_executed; r++)
   {
-    /* no extendable core, or no kept column: no flank has an alignment (answered on the host) */
-    ramx_aln_end *ends = (ramx_aln_end *)malloc(sizeof(ramx_aln_end) * (size_t)(nx > 0 ? nx : 1));
-    for (int i = 0; i < nx; i++) { ends[i].end_row = -1; ends[i].end_idx = -1; ends[i].score = 0; ends[i].start_idx = 0; ends[i].tail_ins = 0; }
-    al.ends = ends;
-    g_align_cb(&al, g_align_user);
-    free(ends);
-    return RAMX_OK;
+    if (direction) master[(size_t)p->L + p->l + r] = cons[r];
+    else master[(size_t)p->L - r - 1] = cons[r];
   }
-  int npad; ramx_flank *pf = pad_to_tiles(fl, nx, &npad);
-  ramx_aln_end *ends = (ramx_aln_end *)malloc(sizeof(ramx_aln_end) * (size_t)npad);
-  int32_t *idx = (int32_t *)malloc(sizeof(int32_t) * (size_t)npad * (size_t)ret);
-  int32_t *ins = (int32_t *)malloc(sizeof(int32_t) * (size_t)npad * (size_t)ret);
-  const int32_t first = 0, count = nx, nrows = ret;
-  const int rc = ramx_dev_align(d, pf, npad, &first, &count, 1, p, cons, &nrows, ends, idx, ins, NULL);
-  if (rc == RAMX_OK)
+  for (int i = 0; i < nx; i++)
   {
-    al.stride = npad; al.ends = ends; al.col_idx = idx; al.col_ins = ins;
-    g_align_cb(&al, g_align_user);
+    if (th[i] > 0 && tp[i] >= 0)
+    {
+      const int n = map[i];
+      if (direction) c->right_len[n] = tp[i] + 1;
+      else c->left_len[n] = tp[i] + 1;
+      c->score[n] += th[i];
+    }
   }
-  free(pf); free(ends); free(idx); free(ins);
-  return rc;
 }
 
 /* packed != NULL: the device already holds the library (ramx_preload_library_packed); `sequence` is not looked at;
-   family: the index a profile sink is told (ramx_extend_batch running a family on its own, else 0) */
+   family: the index the sinks are told (ramx_extend_batch running a family on its own, else 0) */
 static int extend_flat_impl(int direction, ramx_flat_cores *c, const int8_t *sequence, uint64_t seq_len,
                             int8_t *master, const ramx_params *p, ramx_run_info *info, const ramx_packed_library *packed, int family)
 {
@@ -691,7 +737,7 @@ static int extend_flat_impl(int direction, ramx_flat_cores *c, const int8_t *seq
   const double t0 = wall_ms();
   const int timing = getenv("RAMX_TIMING") != NULL;
   double tph = t0;
-#define SEAM1_PHASE(name) do { if (timing) { const double t_ = wall_ms(); fprintf(stderr, "RAMX_TIMING     seam1 %-22s %8.3f ms\n", name, t_ - tph); tph = t_; } } while (0)
+#define SEAM1_PHASE(name) do { if (timing) phase_line("seam1", 22, name, &tph); } while (0)
   const int N = c->n, W = p->bandwidth, L = p->L;
   int rc;
   int *map = (int *)malloc(sizeof(int) * (N > 0 ? N : 1));
@@ -831,51 +877,14 @@ run_again:
     }
     SEAM1_PHASE("fingerprint joined");
   }
-  if (rc == RAMX_OK)
-  {
-    /* ram_extend.c:1092-1095 */
-    for (int r = 0; r < info->rows_executed; r++)
-    {
-      if (direction) master[(size_t)L + p->l + r] = cons[r];
-      else master[(size_t)L - r - 1] = cons[r];
-    }
-    /* ram_extend.c:1234-1247 */
-    for (int i = 0; i < nx; i++)
-    {
-      if (th[i] > 0 && tp[i] >= 0)
-      {
-        const int n = map[i];
-        if (direction) c->right_len[n] = tp[i] + 1;
-        else c->left_len[n] = tp[i] + 1;
-        c->score[n] += th[i];
-      }
-    }
-  }
+  if (rc == RAMX_OK) write_back(direction, p, master, c, cons, info->rows_executed, map, th, tp, nx);
   SEAM1_PHASE("download + write-back");
-  if (rc == RAMX_OK && g_profile_cb != NULL)
+  if (rc == RAMX_OK && any_sink())
   {
-    rc = profile_direction(d, direction, family, fl, map, nx, p, cons, info->rows_executed, info->ret);
-    SEAM1_PHASE("profile replay");
-  }
-  if (rc == RAMX_OK && g_align_cb != NULL)
-  {
-    rc = align_direction(d, direction, family, fl, map, nx, p, cons, info->ret);
-    SEAM1_PHASE("alignment replay");
-  }
-  if (rc == RAMX_OK && g_refine_cb != NULL)
-  {
-    rc = refine_direction(d, direction, family, fl, nx, p, cons, info->ret);
-    SEAM1_PHASE("pileup + refinement");
-  }
-  if (rc == RAMX_OK && g_copies_cb != NULL)
-  {
-    rc = copies_direction(d, direction, family, fl, map, nx, p, cons, info->ret);
-    SEAM1_PHASE("per-copy statistics");
-  }
-  if (rc == RAMX_OK && g_linkage_cb != NULL)
-  {
-    rc = linkage_direction(d, direction, family, fl, nx, p, cons, info->ret);
-    SEAM1_PHASE("linkage");
+    struct sink_view v;
+    one_family_view(&v, d, direction, p, family, fl, map, nx, cons, info->rows_executed, info->ret);
+    rc = run_sinks(&v, "seam1", 22, timing, &tph);
+    free_one_family_view(&v);
   }
 #undef SEAM1_PHASE
 #undef FP_JOIN
@@ -1041,7 +1050,7 @@ int ramx_extend_batch(int direction, ramx_family *fam, int32_t F, const ramx_par
   int rc = RAMX_OK;
   const int timing = getenv("RAMX_TIMING") != NULL;
   double tph = timing ? wall_ms() : 0;
-#define BATCH_PHASE(name) do { if (timing) { const double t_ = wall_ms(); fprintf(stderr, "RAMX_TIMING     batch %-26s %8.3f ms\n", name, t_ - tph); tph = t_; } } while (0)
+#define BATCH_PHASE(name) do { if (timing) phase_line("batch", 26, name, &tph); } while (0)
   /* which families can the batch kernel take? */
   /* every band width and gap sign has a family kernel (register-resident for W = 14/20/40 with non-positive
    * penalties, streaming otherwise); only families above one workgroup (512 flanks) go one by one */
@@ -1123,99 +1132,22 @@ int ramx_extend_batch(int direction, ramx_family *fam, int32_t F, const ramx_par
     BATCH_PHASE("library upload");
     if (rc == RAMX_OK) rc = ramx_dev_run_families(d, fl, (int32_t)fpos, first, count, nb, p, binfo, cons, th, tp);
     BATCH_PHASE("run families (device)");
-    if (rc == RAMX_OK)
+    for (int b = 0; b < nb && rc == RAMX_OK; b++)
     {
-      for (int b = 0; b < nb; b++)
-      {
-        const int f = fidx[b];
-        ramx_flat_cores *c = &fam[f].cores;
-        infos[f] = binfo[b];
-        for (int r = 0; r < binfo[b].rows_executed; r++)
-        {
-          if (direction) fam[f].master[(size_t)L + p->l + r] = cons[(size_t)b * L + r];
-          else fam[f].master[(size_t)L - r - 1] = cons[(size_t)b * L + r];
-        }
-        for (int i = 0; i < count[b]; i++)
-        {
-          const size_t g = (size_t)first[b] + i;
-          if (th[g] > 0 && tp[g] >= 0)
-          {
-            const int n = map[g];
-            if (direction) c->right_len[n] = tp[g] + 1;
-            else c->left_len[n] = tp[g] + 1;
-            c->score[n] += th[g];
-          }
-        }
-      }
+      const int f = fidx[b];
+      infos[f] = binfo[b];
+      write_back(direction, p, fam[f].master, &fam[f].cores, cons + (size_t)b * L, binfo[b].rows_executed, map + first[b], th + first[b],
+                 tp + first[b], count[b]);
     }
-    if (rc == RAMX_OK && g_profile_cb != NULL)
+    if (rc == RAMX_OK && any_sink())
     {
-      /* every family of the launch replayed in one call, along its own consensus and over its own number of columns */
-      ramx_col_profile *cols = (ramx_col_profile *)calloc((size_t)nb * (size_t)(L > 0 ? L : 1), sizeof(ramx_col_profile));
-      int32_t *last = (int32_t *)malloc(sizeof(int32_t) * (fpos ? fpos : 1));
-      int32_t *nrows = (int32_t *)malloc(sizeof(int32_t) * (size_t)nb);
-      for (int b = 0; b < nb; b++) nrows[b] = binfo[b].rows_executed;
-      rc = ramx_dev_profile(d, fl, (int32_t)fpos, first, count, nb, p, cons, nrows, cols, last, NULL, NULL, NULL);
-      for (int b = 0; b < nb && rc == RAMX_OK; b++)
-      {
-        ramx_profile pr;
-        pr.direction = direction; pr.family = fidx[b]; pr.n_cols = nrows[b]; pr.ret = binfo[b].ret; pr.n_flanks = count[b];
-        pr.cols = cols + (size_t)b * L; pr.core_index = map + first[b]; pr.last_uncapped_row = last + first[b];
-        g_profile_cb(&pr, g_profile_user);
-      }
-      free(cols); free(last); free(nrows);
-      BATCH_PHASE("profile replay");
-    }
-    if (rc == RAMX_OK && g_align_cb != NULL)
-    {
-      /* every family of the launch in one call, along its own kept consensus; the sink sees a family's flanks in the
-       * coordinates of the family's own library */
-      int32_t *nrows = (int32_t *)malloc(sizeof(int32_t) * (size_t)nb);
-      int maxret = 0;
-      for (int b = 0; b < nb; b++) { nrows[b] = binfo[b].ret > 0 ? binfo[b].ret : 0; if (nrows[b] > maxret) maxret = nrows[b]; }
-      ramx_aln_end *ends = (ramx_aln_end *)malloc(sizeof(ramx_aln_end) * (fpos ? fpos : 1));
-      int32_t *idx = (int32_t *)malloc(sizeof(int32_t) * (fpos ? fpos : 1) * (size_t)(maxret > 0 ? maxret : 1));
-      int32_t *ins = (int32_t *)malloc(sizeof(int32_t) * (fpos ? fpos : 1) * (size_t)(maxret > 0 ? maxret : 1));
-      for (size_t i = 0; i < fpos; i++) { ends[i].end_row = -1; ends[i].end_idx = -1; ends[i].score = 0; ends[i].start_idx = 0; ends[i].tail_ins = 0; }
-      rc = ramx_dev_align(d, fl, (int32_t)fpos, first, count, nb, p, cons, nrows, ends, idx, ins, NULL);
-      for (int b = 0; b < nb && rc == RAMX_OK; b++)
-      {
-        ramx_flank *own_fl = (ramx_flank *)malloc(sizeof(ramx_flank) * (size_t)(count[b] > 0 ? count[b] : 1));
-        for (int i = 0; i < count[b]; i++) { own_fl[i] = fl[first[b] + i]; own_fl[i].start -= (int64_t)at_of[fidx[b]]; }
-        ramx_alignment al;
-        memset(&al, 0, sizeof(al));
-        al.direction = direction; al.family = fidx[b]; al.rows = nrows[b]; al.n_flanks = count[b]; al.stride = (int32_t)fpos;
-        al.cons = cons + (size_t)b * L; al.flanks = own_fl; al.core_index = map + first[b]; al.ends = ends + first[b];
-        if (nrows[b] > 0 && count[b] > 0) { al.col_idx = idx + first[b]; al.col_ins = ins + first[b]; }
-        g_align_cb(&al, g_align_user);
-        free(own_fl);
-      }
-      free(nrows); free(ends); free(idx); free(ins);
-      BATCH_PHASE("alignment replay");
-    }
-    if (rc == RAMX_OK && g_refine_cb != NULL)
-    {
-      int32_t *rets = (int32_t *)malloc(sizeof(int32_t) * (size_t)nb);
-      for (int b = 0; b < nb; b++) rets[b] = binfo[b].ret;
-      rc = refine_families(d, direction, fidx, nb, fl, (int32_t)fpos, first, count, p, cons, rets);
-      free(rets);
-      BATCH_PHASE("pileup + refinement");
-    }
-    if (rc == RAMX_OK && g_copies_cb != NULL)
-    {
-      int32_t *rets = (int32_t *)malloc(sizeof(int32_t) * (size_t)nb);
-      for (int b = 0; b < nb; b++) rets[b] = binfo[b].ret;
-      rc = copies_families(d, direction, fidx, nb, fl, map, (int32_t)fpos, first, count, p, cons, rets, at_of);
-      free(rets);
-      BATCH_PHASE("per-copy statistics");
-    }
-    if (rc == RAMX_OK && g_linkage_cb != NULL)
-    {
-      int32_t *rets = (int32_t *)malloc(sizeof(int32_t) * (size_t)nb);
-      for (int b = 0; b < nb; b++) rets[b] = binfo[b].ret;
-      rc = linkage_families(d, direction, fidx, nb, fl, (int32_t)fpos, first, count, p, cons, rets);
-      free(rets);
-      BATCH_PHASE("linkage");
+      /* every family of the launch in one view: each sink replays them in one call, along their own consensus and over their
+       * own number of columns, and sees a family's flanks in the coordinates of the family's own library */
+      int32_t *rows = (int32_t *)malloc(sizeof(int32_t) * 2 * (size_t)nb), *ret = rows + nb;
+      for (int b = 0; b < nb; b++) { rows[b] = binfo[b].rows_executed; ret[b] = binfo[b].ret > 0 ? binfo[b].ret : 0; }
+      const struct sink_view v = { d, direction, p, nb, fidx, fl, map, (int32_t)fpos, first, count, cons, rows, ret, at_of };
+      rc = run_sinks(&v, "batch", 26, timing, &tph);
+      free(rows);
     }
     free(binfo); free(cons); free(th); free(tp);
     BATCH_PHASE("write-back");

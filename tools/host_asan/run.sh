@@ -1,6 +1,6 @@
 #!/bin/bash
 # Host code of the replays under AddressSanitizer + UBSan, as stand-alone programs on the CPU (no GPU is opened, nothing is
-# loaded into python): replay_plan of ramx_device.hip and pad_to_tiles of ramx_extend.c, both static, so each program includes
+# loaded into python): replay_plan of ramx_device.hip, pad_to_tiles and the sinks' one-family view of ramx_extend.c, all static, so each program includes
 # its source file and takes the rest of the library from the built libramx.so; and ramx_linkage.c, which stands alone.
 # usage: tools/host_asan/run.sh        (after the library has been built)
 set -euo pipefail
