@@ -295,6 +295,51 @@ __device__ __forceinline__ long long wave_sum_nonneg31(int v)
   return ((long long)hi << 16) + (long long)lo;
 }
 
+// FOUR values reduced together as a reduce-scatter: every step halves the lanes a value is spread over AND the values a lane
+// carries, so the four reductions share their steps instead of running 6 DPP steps each.
+//   v_permlane32_swap a, b   lanes 32..63 of a <-> lanes 0..31 of b; a + b then holds a's total over the two halves in lanes
+//                            0..31 and b's in lanes 32..63: one swap and one add take a step for two values
+//   v_permlane16_swap a, b   rows (16 lanes) 1 and 3 of a <-> rows 0 and 2 of b: a + b holds a's in rows 0 and 2, b's in 1 and 3
+// After both, row 0 carries v0, row 1 v2, row 2 v1 and row 3 v3; four DPP steps inside the rows finish all four at once.
+// (The compiler pads the "VALU write -> v_permlane*_swap read" hazard of the builtin itself.)
+#define RAMX_ROW_STEPS(STEP) do { STEP(0xB1); STEP(0x4E); STEP(0x124); STEP(0x128); } while (0)   // quad_perm [1,0,3,2], [2,3,0,1], row_ror:4, row_ror:8
+// Sums of four values in [0, 2^31) per lane (results as wave_sum_nonneg31's, identical for every such input).  The first step
+// runs on the values themselves (two of them fit 32 bits); the remaining 32 additions on their 16-bit halves.
+__device__ __forceinline__ void wave_sum4_nonneg31(const int (&v)[4], long long (&t)[4])
+{
+  const auto s01 = __builtin_amdgcn_permlane32_swap((unsigned)v[0], (unsigned)v[1], false, false);
+  const auto s23 = __builtin_amdgcn_permlane32_swap((unsigned)v[2], (unsigned)v[3], false, false);
+  const unsigned x = s01[0] + s01[1];             // rows 0, 1: v0   rows 2, 3: v1
+  const unsigned y = s23[0] + s23[1];             // rows 0, 1: v2   rows 2, 3: v3
+  const auto sl = __builtin_amdgcn_permlane16_swap(x & 0xffffu, y & 0xffffu, false, false);
+  const auto sh = __builtin_amdgcn_permlane16_swap(x >> 16, y >> 16, false, false);
+  unsigned lo = sl[0] + sl[1], hi = sh[0] + sh[1];      // row 0: v0   row 1: v2   row 2: v1   row 3: v3
+#define RAMX_SUM_STEP(ctrl) do { lo += (unsigned)__builtin_amdgcn_update_dpp(0, (int)lo, ctrl, 0xf, 0xf, false); \
+                                 hi += (unsigned)__builtin_amdgcn_update_dpp(0, (int)hi, ctrl, 0xf, 0xf, false); } while (0)
+  RAMX_ROW_STEPS(RAMX_SUM_STEP);
+#undef RAMX_SUM_STEP
+#define RAMX_SUM_ROW(row) (((long long)(unsigned)__builtin_amdgcn_readlane((int)hi, 16 * (row)) << 16) + (long long)(unsigned)__builtin_amdgcn_readlane((int)lo, 16 * (row)))
+  t[0] = RAMX_SUM_ROW(0); t[1] = RAMX_SUM_ROW(2); t[2] = RAMX_SUM_ROW(1); t[3] = RAMX_SUM_ROW(3);
+#undef RAMX_SUM_ROW
+}
+// maxima of four values (any int), returned to every lane through the scalar unit
+__device__ __forceinline__ void wave_max4_i32(const int (&v)[4], int (&m)[4])
+{
+  const auto s01 = __builtin_amdgcn_permlane32_swap((unsigned)v[0], (unsigned)v[1], false, false);
+  const auto s23 = __builtin_amdgcn_permlane32_swap((unsigned)v[2], (unsigned)v[3], false, false);
+  const int x = (int)s01[0] > (int)s01[1] ? (int)s01[0] : (int)s01[1];
+  const int y = (int)s23[0] > (int)s23[1] ? (int)s23[0] : (int)s23[1];
+  const auto s = __builtin_amdgcn_permlane16_swap((unsigned)x, (unsigned)y, false, false);
+  int z = (int)s[0] > (int)s[1] ? (int)s[0] : (int)s[1];
+  const int lowest = -2147483647 - 1;
+#define RAMX_MAX_STEP(ctrl) do { const int o_ = __builtin_amdgcn_update_dpp(lowest, z, ctrl, 0xf, 0xf, false); z = z > o_ ? z : o_; } while (0)
+  RAMX_ROW_STEPS(RAMX_MAX_STEP);
+#undef RAMX_MAX_STEP
+  m[0] = __builtin_amdgcn_readlane(z, 0); m[1] = __builtin_amdgcn_readlane(z, 32);
+  m[2] = __builtin_amdgcn_readlane(z, 16); m[3] = __builtin_amdgcn_readlane(z, 48);
+}
+#undef RAMX_ROW_STEPS
+
 // The DP rows are written once per column and read once by the next launch.  Plain (cacheable) accesses are the
 // measured choice: the 131 MB ping-pong working set of the N = 100,000 workload stays largely resident in the
 // 256 MB Infinity Cache between launches; non-temporal accesses (-DRAMX_NT_LDST) were 25 % slower

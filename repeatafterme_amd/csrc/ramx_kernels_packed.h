@@ -276,10 +276,17 @@ __device__ __forceinline__ void pkb_leader_rows(const PkTabs &pt, int *scr /* [2
     }
     hit[h] = __ballot(ok && m == bf);
   }
-  const int mx = wave_max_i32_dpp(me);
   int best[4];
+#ifndef PKB_PROBE_OLD_REDUCE     // A/B: five / eight independent DPP chains, as before wave_max4_i32 / wave_sum4_nonneg31
+  // the deletion term is every candidate's: folded in per lane, four maxima reduced together remain
+#pragma unroll
+  for (int c = 0; c < 4; c++) ta[c] = imax(ta[c], me);
+  wave_max4_i32(ta, best);
+#else
+  const int mx = wave_max_i32_dpp(me);
 #pragma unroll
   for (int c = 0; c < 4; c++) best[c] = imax(wave_max_i32_dpp(ta[c]), mx);
+#endif
   int jb = 0;                                            // lowest cell on ties (bnw_extend.c:1020-1024)
 #pragma unroll
   for (int h = NH - 1; h >= 0; h--)
@@ -807,8 +814,14 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void ramx_packed_kernel(const P
       if (!early && send)
       {
 #ifndef PKB_PROBE_NO_REDUCE      // timing probe (wrong results)
-        const long long t0 = wave_sum_nonneg31(contrib[0]), t1 = wave_sum_nonneg31(contrib[1]);
-        const long long t2 = wave_sum_nonneg31(contrib[2]), t3 = wave_sum_nonneg31(contrib[3]);
+        long long t[4];
+#ifndef PKB_PROBE_OLD_REDUCE
+        wave_sum4_nonneg31(contrib, t);           // the four sums share their steps (ramx_kernels_common.h)
+#else
+#pragma unroll
+        for (int c = 0; c < 4; c++) t[c] = wave_sum_nonneg31(contrib[c]);
+#endif
+        const long long t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3];
 #else
         const long long t0 = __builtin_amdgcn_readfirstlane(contrib[0]), t1 = __builtin_amdgcn_readfirstlane(contrib[1]);
         const long long t2 = __builtin_amdgcn_readfirstlane(contrib[2]), t3 = __builtin_amdgcn_readfirstlane(contrib[3]);
