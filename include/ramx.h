@@ -576,6 +576,89 @@ typedef struct ramx_linkage
 typedef void (*ramx_linkage_cb)(const ramx_linkage *lk, void *user);
 void ramx_set_linkage_sink(ramx_linkage_cb cb, void *user, int32_t min_count, int32_t min_permille, int32_t max_variants);
 
+/* Subfamilies of an extension: the copies of a family split by the variants they carry, the step after the linkage.  For one
+ * family and one consensus, planes[0..P) is a list as ramx_select_planes returns it: variants (cls != 6) and the cover plane
+ * (row, 6) of every row that has a variant.  The variants in list order are v = 0..V-1, cov(v) is the cover plane of v's row;
+ * for copy i, x_i[v] is its bit in plane v and c_i[v] its bit in cov(v).
+ *   Pattern: a bit per variant, pat_k[v]; K patterns, 1 <= K <= RAMX_SUBFAM_MAX.  Pattern 0 starts empty: the consensus itself.
+ *   Distance: d(i, k) = the number of variants v with c_i[v] = 1 and x_i[v] != pat_k[v]; rows the copy does not cover count
+ *   nothing.
+ *   Assignment: label_i = argmin_k d(i, k), ties to the lowest k.  A non-padding copy without an alignment has d = 0 everywhere
+ *   and label 0; padding flanks get label -1 and belong to no group.
+ *   Counts: for every plane p of the list (variants AND covers) and every k, cnt[k][p] is the number of copies with label k
+ *   whose bit in p is set; size[k] the number of copies with label k.
+ *   Update: pat_k[v] = 1 iff 2 * cnt[k][v] > cnt[k][cov(v)] -- exactly half is not a majority, as in ramx_recall_consensus; a
+ *   group with size[k] = 0 keeps its pattern.
+ *   Iteration: assign, count; then update, assign, count again ... until an assignment after the first changes no label
+ *   (converged = 1) or max_iter assignments have been made (converged = 0).  With K = 1 no assignment can change a label: the
+ *   first one ends the family, converged = 1.  iterations is the number of assignments made; labels, counts and sizes are those
+ *   of the last assignment and patterns_out the patterns it used (for a converged family also their own update).  Families
+ *   proceed independently. */
+#define RAMX_SUBFAM_MAX 8
+
+/* The initial patterns (plain host C) from the output of ramx_link_pairs at the caller's threshold: links[0..n_links) with p, q
+ * indices into planes[0..P).  The connected components of the graph whose edges are those pairs, the components with at least
+ * two variants kept, ordered by decreasing size with ties to the lowest member, the first K - 1 of them kept: pattern j + 1
+ * carries exactly the variants of component j, pattern 0 none.  Returns the number of patterns K' = 1 + kept components (<= K)
+ * and writes init as [V][K'] bytes (0 / 1; room for V * K), V the variants of the list in list order; component (may be NULL)
+ * receives, per variant, the pattern that carries it or 0.  0 for K outside 1..RAMX_SUBFAM_MAX or a link outside the list. */
+int32_t ramx_link_components(const ramx_plane *planes, int32_t P, const ramx_link *links, int32_t n_links, int32_t K,
+                             uint8_t *init, int32_t *component);
+
+/* The iteration on the resident planes of the last ramx_dev_planes (n_families as in that call); plane lists as
+ * ramx_dev_plane_gram, with the same checks -- RAMX_ERR_STATE without resident planes, RAMX_ERR_ARG for a bad list -- and
+ * RAMX_ERR_ARG for a variant whose row's cover plane is not in the list, for K outside 1..RAMX_SUBFAM_MAX and for max_iter < 1.
+ * Everything is checked before anything is launched or written.  With V_f variants and P_f planes in family f's list, and
+ * v0(f) = sum of V_g, p0(f) = sum of P_g over g < f: init and patterns_out hold family f at K * v0(f) as [V_f][K] bytes
+ * (0 / 1), cnt_out at K * p0(f) as [K][P_f], size_out is [n_families][K], iterations / converged [n_families], labels
+ * [n_padded] of that ramx_dev_planes call (-1 for padding flanks and outside every family).  One wave per tile assigns (one lane
+ * per flank, the distances in registers, the group masks as ballots); one wave per listed plane counts popcount(plane & mask)
+ * over the family's tiles; between two assignments only the per-tile change counts and the counts come to the host, where the
+ * update rule runs.  Exact integers, no atomics.  The planes stay resident and untouched.  Rank-local under a communicator. */
+int ramx_dev_subfamilies(ramx_dev *d, int32_t n_families, const ramx_plane *planes, const int32_t *plane_first,
+                         const int32_t *plane_count, const uint8_t *init, int32_t K, int32_t max_iter, int32_t *labels,
+                         uint8_t *patterns_out, int32_t *cnt_out, int32_t *size_out, int32_t *iterations, int32_t *converged);
+/* The group masks of the last ramx_dev_subfamilies (a diagnostic): mask receives [K][T_f] words, bit i % 64 of word i / 64 of
+ * plane k set iff flank i of the family has label k.  RAMX_ERR_STATE without such a result. */
+int ramx_dev_subfam_masks(ramx_dev *d, int32_t family, uint64_t *mask);
+/* HIP-event times (ms) of the assign and of the count kernels of the last ramx_dev_subfamilies, each summed over its
+ * iterations; 0 if none was launched. */
+void ramx_dev_subfam_ms(ramx_dev *d, double ms[2]);
+
+/* Subfamily sink of seam 1, as the other sinks (the sixth, after the linkage sink): with a sink set, per direction and family
+ * that has run, along the kept consensus (rows = ret): ramx_dev_planes, ramx_select_planes(min_count, min_permille,
+ * max_variants), ramx_dev_plane_gram, ramx_link_pairs at min_mlog10p, ramx_link_components with K and ramx_dev_subfamilies with
+ * the K' it returned and max_iter.  The flanks of every group with size[k] >= min_members are then gathered into a family of
+ * its own and ONE ramx_dev_refine call over all of them, starting from the kept consensus with max_replays, gives every kept
+ * group its own consensus and pileup.  dist is [n_flanks][K]: d(i, k) to the patterns handed over.  A direction without an
+ * extendable core or with ret = 0 is answered on the host: K = 1, every copy in group 0, no variant, no kept group.  With a
+ * communicator or mailbox route active the direction fails with RAMX_ERR_UNSUPPORTED, as the linkage sink.  If the linkage
+ * sink is set too, the planes and the Gram matrix are computed once for each.  cb == NULL (the default): off. */
+typedef struct ramx_subfam_group
+{
+  int32_t group, size, refined_rows, replays, converged;
+  const int8_t *refined_cons;             /* [refined_rows] */
+  const ramx_col_pileup *refined_cols;    /* [refined_rows] */
+} ramx_subfam_group;
+typedef struct ramx_subfamilies
+{
+  int32_t direction, family /* index in a batch, else 0 */, rows /* = ret */, n_flanks, n_planes, n_variants, K, iterations, converged,
+          n_groups /* kept: size >= min_members */;
+  const int8_t *cons;                 /* [rows] */
+  const ramx_flank *flanks;           /* [n_flanks], in the coordinates of the family's own library */
+  const int32_t *core_index;          /* [n_flanks] */
+  const ramx_plane *planes;           /* [n_planes] */
+  const int32_t *labels;              /* [n_flanks] */
+  const uint8_t *patterns;            /* [n_variants][K] */
+  const int32_t *cnt;                 /* [K][n_planes] */
+  const int32_t *size;                /* [K] */
+  const int32_t *dist;                /* [n_flanks][K] */
+  const ramx_subfam_group *groups;    /* [n_groups], ascending in group */
+} ramx_subfamilies;
+typedef void (*ramx_subfam_cb)(const ramx_subfamilies *sf, void *user);
+void ramx_set_subfam_sink(ramx_subfam_cb cb, void *user, int32_t min_count, int32_t min_permille, int32_t max_variants,
+                          double min_mlog10p, int32_t K, int32_t max_iter, int32_t min_members, int32_t max_replays);
+
 /* multi-GPU: flanks are sharded over ranks; each column's 4 candidate sums are all-reduced
  * (4 x int64, RCCL over xGMI).  unique_id is the 128-byte ncclUniqueId made by rank 0
  * (ramx_comm_unique_id) and handed to the other ranks by the launcher (e.g. torch.distributed). */

@@ -24,6 +24,7 @@ EXPORTS = [
     "ramx_dev_pileup", "ramx_recall_consensus", "ramx_dev_refine", "ramx_set_refine_sink",
     "ramx_dev_copy_stats", "ramx_copy_kimura", "ramx_family_divergence", "ramx_set_copies_sink",
     "ramx_dev_planes", "ramx_dev_plane_gram", "ramx_dev_plane_gram_ms", "ramx_select_planes", "ramx_link_pairs", "ramx_set_linkage_sink",
+    "ramx_link_components", "ramx_dev_subfamilies", "ramx_dev_subfam_masks", "ramx_dev_subfam_ms", "ramx_set_subfam_sink",
 ]
 
 
@@ -113,6 +114,21 @@ class LinkageRec(C.Structure):      # ramx_linkage
 
 
 LINKAGE_CB = C.CFUNCTYPE(None, C.POINTER(LinkageRec), C.c_void_p)
+
+
+class SubfamGroup(C.Structure):     # ramx_subfam_group
+    _fields_ = [(k, C.c_int32) for k in ("group", "size", "refined_rows", "replays", "converged")] + \
+               [(k, C.c_void_p) for k in ("refined_cons", "refined_cols")]
+
+
+class SubfamRec(C.Structure):       # ramx_subfamilies
+    _fields_ = [(k, C.c_int32) for k in ("direction", "family", "rows", "n_flanks", "n_planes", "n_variants", "K", "iterations",
+                                         "converged", "n_groups")] + \
+               [(k, C.c_void_p) for k in ("cons", "flanks", "core_index", "planes", "labels", "patterns", "cnt", "size", "dist")] + \
+               [("groups", C.POINTER(SubfamGroup))]
+
+
+SUBFAM_CB = C.CFUNCTYPE(None, C.POINTER(SubfamRec), C.c_void_p)
 
 
 def build(force: bool = False) -> None:
@@ -207,6 +223,18 @@ def lib() -> C.CDLL:
         L.ramx_link_pairs.restype = C.c_int32
         L.ramx_set_linkage_sink.argtypes = [LINKAGE_CB, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
         L.ramx_set_linkage_sink.restype = None
+        L.ramx_set_subfam_sink.argtypes = [SUBFAM_CB, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32]
+        L.ramx_set_subfam_sink.restype = None
+        L.ramx_link_components.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        L.ramx_link_components.restype = C.c_int32
+        L.ramx_dev_subfamilies.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ramx_dev_subfamilies.restype = C.c_int
+        L.ramx_dev_subfam_masks.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.ramx_dev_subfam_masks.restype = C.c_int
+        L.ramx_dev_subfam_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        L.ramx_dev_subfam_ms.restype = None
         if hasattr(L, "ramx_cli_main"):
             L.ramx_cli_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
         _lib = L

@@ -97,6 +97,12 @@ static void usage(void)
     "     -linkcount <num>      # ... a variant needs this many copies (4),\n"
     "     -linkfrac <num>       # ... and this many per thousand of the copies that cover its column (100).\n"
     "     -linkscore <num>      # ... a pair is written from this -log10 p of its hypergeometric test (3).\n"
+    "     -outsubfam <file>     # Save the split of the copies into subfamilies by the linked variants they carry\n"
+    "                           #   (selection and threshold: -linkcount, -linkfrac, -linkscore), every group\n"
+    "                           #   with its own refined consensus (-refine replays), as a TSV.\n"
+    "     -subfamk <num>        # ... at most this many groups, 1..8 (4),\n"
+    "     -subfammin <num>      # ... a group gets a consensus of its own from this many copies (4),\n"
+    "     -subfamiter <num>     # ... at most this many assignments (8).\n"
     "     -version              # Print out one-line version information\n"
     "     -v[v[v[v]]]           # How verbose do you want it to be?  -vvvv is super-verbose.\n"
     "\n"
@@ -248,8 +254,8 @@ static void warm_start(void)
 /* everything the command line decides */
 struct cli_opts
 {
-  const char *ranges_file, *outtsv, *outfa, *outmat, *cons_file, *seq_file, *matrix_name, *batch_file, *outprofile, *outaln, *outpileup, *outrefined, *outcopies, *outlinkage;
-  int refine, linkcount, linkfrac, linkscore;
+  const char *ranges_file, *outtsv, *outfa, *outmat, *cons_file, *seq_file, *matrix_name, *batch_file, *outprofile, *outaln, *outpileup, *outrefined, *outcopies, *outlinkage, *outsubfam;
+  int refine, linkcount, linkfrac, linkscore, subfamk, subfammin, subfamiter;
   int flanking, L, bandwidth, maxn, when_to_stop, num_threads, verbose;
   int gap_ext, gap_open, match, mismatch, cappenalty, minimprovement, is_rs;
   struct scoringSystem *sp;
@@ -472,7 +478,7 @@ static void write_results(const struct cli_opts *o, struct coreAlignment *cores,
  */
 struct batch_item
 {
-  char *ranges, *log, *cons, *tsv, *fa, *profile, *aln, *pileup, *refined, *copies, *linkage;
+  char *ranges, *log, *cons, *tsv, *fa, *profile, *aln, *pileup, *refined, *copies, *linkage, *subfam;
   struct coreAlignment *cores;
   struct sequenceLibrary *lib;
   int N, rightbp, leftbp;
@@ -852,6 +858,103 @@ static void linkage_write(struct linkage_family *lf, int min_score)
   fclose(fp);
 }
 
+/*
+ * -outsubfam <file>: the copies of both extensions split into subfamilies (include/ramx.h, ramx_set_subfam_sink) as a TSV, the
+ * right block first.  Per group a line "group": direction, group, size, the assignments made and whether they converged, the
+ * group's pattern as a list of row:variant ("-": none), and -- for a group of at least -subfammin copies -- the length of its
+ * refined consensus, the replays, whether those converged, and the consensus in reading order (else NA NA NA -).  After it one
+ * line "copy" per copy of the group in flank order: the -outfa record name, its label and its distance to every pattern.  The
+ * names need both directions' lengths, so the sink keeps the records and the file is written with the other results.
+ */
+struct subfam_block { int have, n, K, iterations, converged; int32_t *core, *labels, *dist, *size; char **pattern, **cons; int *rows, *replays, *conv; };
+struct subfam_family { const char *path; struct sequenceLibrary *lib; struct subfam_block blk[2]; };
+struct subfam_out { struct subfam_family *fam; };
+static const char k_subfam_header[] =
+  "#group\tdir\tgroup\tsize\titerations\tconverged\tpattern\trefined_bp\treplays\trefined_converged\tconsensus\n"
+  "#copy\tdir\tcopy\tlabel\tdistances\n";
+
+static void subfam_sink(const ramx_subfamilies *sf, void *user)
+{
+  static const char *const var_name[8] = { "A", "C", "G", "T", "N", "del", "cover", "ins" };
+  struct subfam_family *f = &((const struct subfam_out *)user)->fam[sf->family];
+  if (!f->path) return;
+  struct subfam_block *b = &f->blk[sf->direction ? 1 : 0];
+  const size_t n = (size_t)(sf->n_flanks > 0 ? sf->n_flanks : 1), K = (size_t)sf->K;
+  b->have = 1; b->n = sf->n_flanks; b->K = sf->K; b->iterations = sf->iterations; b->converged = sf->converged;
+  b->core = (int32_t *)malloc(sizeof(int32_t) * n); b->labels = (int32_t *)malloc(sizeof(int32_t) * n);
+  b->dist = (int32_t *)malloc(sizeof(int32_t) * n * K); b->size = (int32_t *)malloc(sizeof(int32_t) * K);
+  b->pattern = (char **)calloc(K, sizeof(char *)); b->cons = (char **)calloc(K, sizeof(char *));
+  b->rows = (int *)calloc(K * 3, sizeof(int)); b->replays = b->rows + K; b->conv = b->replays + K;
+  memcpy(b->core, sf->core_index, sizeof(int32_t) * (size_t)sf->n_flanks);
+  memcpy(b->labels, sf->labels, sizeof(int32_t) * (size_t)sf->n_flanks);
+  memcpy(b->dist, sf->dist, sizeof(int32_t) * (size_t)sf->n_flanks * K);
+  memcpy(b->size, sf->size, sizeof(int32_t) * K);
+  for (int k = 0; k < sf->K; k++)
+  {
+    char *txt = (char *)malloc((size_t)sf->n_variants * 24 + 2), *w = txt;
+    int v = 0;
+    for (int i = 0; i < sf->n_planes; i++)
+    {
+      if (sf->planes[i].cls == RAMX_PLANE_COVER) continue;
+      if (sf->patterns[(size_t)v * K + (size_t)k]) w += sprintf(w, "%s%d:%s", w == txt ? "" : ",", sf->planes[i].row, var_name[sf->planes[i].cls & 7]);
+      v++;
+    }
+    if (w == txt) *w++ = '-';
+    *w = 0;
+    b->pattern[k] = txt;
+  }
+  for (int g = 0; g < sf->n_groups; g++)
+  {
+    const ramx_subfam_group *gr = &sf->groups[g];
+    const int rn = gr->refined_rows, d = sf->direction ? 1 : 0;
+    char *seq = (char *)malloc((size_t)rn + 2);
+    for (int r = 0; r < rn; r++) seq[r] = code_to_char(gr->refined_cons[d ? r : rn - 1 - r]);
+    if (rn == 0) { seq[0] = '-'; seq[1] = 0; } else seq[rn] = 0;
+    b->cons[gr->group] = seq; b->rows[gr->group] = rn; b->replays[gr->group] = gr->replays; b->conv[gr->group] = gr->converged;
+  }
+}
+
+/* after both directions: the file, then the buffers are released */
+static void subfam_write(struct subfam_family *f, struct coreAlignment *cores, int flanking)
+{
+  if (!f->path) return;
+  FILE *fp = fopen(f->path, "w");
+  if (!fp) { fprintf(stderr, "Could not create the subfamily file %s\n", f->path); exit(1); }
+  fputs(k_subfam_header, fp);
+  int cnt = 0;
+  for (struct coreAlignment *s = cores; s != NULL; s = s->next) cnt++;
+  struct coreAlignment **arr = (struct coreAlignment **)malloc(sizeof(*arr) * (size_t)(cnt ? cnt : 1));
+  cnt = 0;
+  for (struct coreAlignment *s = cores; s != NULL; s = s->next) arr[cnt++] = s;
+  for (int dir = 1; dir >= 0; dir--)
+  {
+    struct subfam_block *b = &f->blk[dir];
+    if (!b->have) continue;
+    const char *tag = dir ? "right" : "left";
+    for (int k = 0; k < b->K; k++)
+    {
+      fprintf(fp, "group\t%s\t%d\t%d\t%d\t%d\t%s\t", tag, k, b->size[k], b->iterations, b->converged, b->pattern[k]);
+      if (b->cons[k]) fprintf(fp, "%d\t%d\t%d\t%s\n", b->rows[k], b->replays[k], b->conv[k], b->cons[k]);
+      else fputs("NA\tNA\tNA\t-\n", fp);
+      for (int i = 0; i < b->n; i++)
+      {
+        if (b->labels[i] != k) continue;
+        char id[1024];
+        if (b->core[i] < 0 || b->core[i] >= cnt) { fprintf(stderr, "RAMExtend(ramx): subfamily record of an unknown core %d\n", b->core[i]); exit(1); }
+        aln_record_id(id, sizeof(id), arr[b->core[i]], f->lib, flanking);
+        fprintf(fp, "copy\t%s\t%s\t%d", tag, id, b->labels[i]);
+        for (int j = 0; j < b->K; j++) fprintf(fp, "\t%d", b->dist[(size_t)i * b->K + j]);
+        fputc('\n', fp);
+      }
+      free(b->pattern[k]); free(b->cons[k]);
+    }
+    free(b->core); free(b->labels); free(b->dist); free(b->size); free(b->pattern); free(b->cons); free(b->rows);
+    memset(b, 0, sizeof(*b));
+  }
+  free(arr);
+  fclose(fp);
+}
+
 /* flat view of a core list for ramx_extend_batch (arrays owned by the caller's arena) */
 static void flatten_cores(struct coreAlignment *cores, int N, ramx_flat_cores *fc)
 {
@@ -909,6 +1012,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   { fprintf(stderr, "RAMExtend(ramx): with -batch every family's pileup file is the eighth field of its line in the list and its refined consensus the ninth\n"); exit(1); }
   if (o->outcopies != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's copies file is the tenth field of its line in the list\n"); exit(1); }
   if (o->outlinkage != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's linkage file is the eleventh field of its line in the list\n"); exit(1); }
+  if (o->outsubfam != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's subfamily file is the twelfth field of its line in the list\n"); exit(1); }
   FILE *lf = fopen(o->batch_file, "r");
   if (!lf) { fprintf(stderr, "Could not open batch list %s\n", o->batch_file); exit(1); }
   size_t cap = 64, F = 0;
@@ -920,9 +1024,9 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   {
     while (len > 0 && (line[len - 1] == '\n' || line[len - 1] == '\r')) line[--len] = 0;
     if (line[0] == '#' || line[0] == 0) continue;
-    char *f[11] = { NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL };
+    char *f[12] = { NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL };
     char *p = line;
-    for (int k = 0; k < 11 && p; k++) { f[k] = p; char *t = strchr(p, '\t'); if (t) { *t = 0; p = t + 1; } else p = NULL; }
+    for (int k = 0; k < 12 && p; k++) { f[k] = p; char *t = strchr(p, '\t'); if (t) { *t = 0; p = t + 1; } else p = NULL; }
     if (!f[0] || !f[1]) { fprintf(stderr, "batch list: every line needs at least <ranges><TAB><log>\n"); exit(1); }
     if (F == cap) { cap *= 2; it = (struct batch_item *)realloc(it, cap * sizeof(*it)); memset(it + F, 0, (cap - F) * sizeof(*it)); }
     it[F].ranges = strdup(f[0]); it[F].log = strdup(f[1]);
@@ -935,6 +1039,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
     it[F].refined = field_or_null(f[8]) ? strdup(f[8]) : NULL;       /* optional ninth field: the family's -outrefined file */
     it[F].copies = field_or_null(f[9]) ? strdup(f[9]) : NULL;        /* optional tenth field: the family's -outcopies file */
     it[F].linkage = field_or_null(f[10]) ? strdup(f[10]) : NULL;     /* optional eleventh field: the family's -outlinkage file */
+    it[F].subfam = field_or_null(f[11]) ? strdup(f[11]) : NULL;      /* optional twelfth field: the family's -outsubfam file */
     F++;
   }
   free(line);
@@ -1000,6 +1105,11 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   for (size_t i = 0; i < F; i++)
     if ((lout.fam[i].path = it[i].linkage) != NULL) any_linkage = 1;
   if (any_linkage) ramx_set_linkage_sink(linkage_sink, &lout, o->linkcount, o->linkfrac, 1024);
+  struct subfam_out sout = { (struct subfam_family *)calloc(F ? F : 1, sizeof(struct subfam_family)) };
+  int any_subfam = 0;
+  for (size_t i = 0; i < F; i++)
+    if ((sout.fam[i].path = it[i].subfam) != NULL) { sout.fam[i].lib = it[i].lib; any_subfam = 1; }
+  if (any_subfam) ramx_set_subfam_sink(subfam_sink, &sout, o->linkcount, o->linkfrac, 1024, (double)o->linkscore, o->subfamk, o->subfamiter, o->subfammin, o->refine);
   /* phase 2: right extension of all families in one launch; phase 3: per family, overlap avoidance */
   for (size_t i = 0; i < F; i++) flatten_cores(it[i].cores, it[i].N, &fam[i].cores);
   if (ramx_extend_batch(1, fam, (int32_t)F, &p, ir) < 0) { fprintf(stderr, "RAMExtend(ramx): batch extension failed: %s\n", ramx_last_error()); exit(1); }
@@ -1034,6 +1144,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
     refined_write(&rout.fam[i]);
     copies_write(&cout.fam[i], it[i].cores, o->flanking);
     linkage_write(&lout.fam[i], o->linkscore);
+    subfam_write(&sout.fam[i], it[i].cores, o->flanking);
     const double duration = difftime(time(0), t_start);
     printf("Program duration is %.1f sec = %.1f min = %.1f hr\n", duration, duration / 60.0, duration / 3600.0);
   }
@@ -1045,14 +1156,15 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   {
     ramx_free_library(it[i].lib, it[i].cores);
     free(it[i].master); free(it[i].ranges); free(it[i].log); free(it[i].cons); free(it[i].tsv); free(it[i].fa); free(it[i].profile); free(it[i].aln);
-    free(it[i].pileup); free(it[i].refined); free(it[i].copies); free(it[i].linkage);
+    free(it[i].pileup); free(it[i].refined); free(it[i].copies); free(it[i].linkage); free(it[i].subfam);
   }
   ramx_set_profile_sink(NULL, NULL);
   ramx_set_align_sink(NULL, NULL);
   ramx_set_refine_sink(NULL, NULL, 1);
   ramx_set_copies_sink(NULL, NULL);
   ramx_set_linkage_sink(NULL, NULL, 4, 100, 1024);
-  free(aout.fam); free(rout.fam); free(cout.fam); free(lout.fam);
+  ramx_set_subfam_sink(NULL, NULL, 4, 100, 1024, 3.0, 4, 8, 4, 10);
+  free(aout.fam); free(rout.fam); free(cout.fam); free(lout.fam); free(sout.fam);
   free(profile_paths);
   free(it); free(fam); free(ir); free(il); free(mflat);
   ramx_free_scoring_system(o->sp);
@@ -1089,6 +1201,12 @@ int ramx_cli_main(int argc, char **argv)
   if (!opt_int(argc, argv, "-linkcount", &o.linkcount)) o.linkcount = 4;
   if (!opt_int(argc, argv, "-linkfrac", &o.linkfrac)) o.linkfrac = 100;
   if (!opt_int(argc, argv, "-linkscore", &o.linkscore)) o.linkscore = 3;
+  opt_string(argc, argv, "-outsubfam", &o.outsubfam);
+  if (!opt_int(argc, argv, "-subfamk", &o.subfamk)) o.subfamk = 4;
+  if (!opt_int(argc, argv, "-subfammin", &o.subfammin)) o.subfammin = 4;
+  if (!opt_int(argc, argv, "-subfamiter", &o.subfamiter)) o.subfamiter = 8;
+  if (o.subfamk < 1 || o.subfamk > RAMX_SUBFAM_MAX || o.subfamiter < 1)
+  { fprintf(stderr, "RAMExtend(ramx): -subfamk takes 1..%d groups, -subfamiter at least 1 assignment\n", RAMX_SUBFAM_MAX); exit(1); }
   if (!opt_int(argc, argv, "-refine", &o.refine)) o.refine = 10;
   if (o.refine < 1) { fprintf(stderr, "RAMExtend(ramx): -refine takes the largest number of replays, at least 1\n"); exit(1); }
   if (!opt_int(argc, argv, "-L", &o.L)) o.L = 10000;
@@ -1200,6 +1318,11 @@ int ramx_cli_main(int argc, char **argv)
   lfam.path = o.outlinkage;
   struct linkage_out lout = { &lfam };
   if (o.outlinkage != NULL) ramx_set_linkage_sink(linkage_sink, &lout, o.linkcount, o.linkfrac, 1024);
+  struct subfam_family sfam;
+  memset(&sfam, 0, sizeof(sfam));
+  sfam.path = o.outsubfam; sfam.lib = lib;
+  struct subfam_out sout = { &sfam };
+  if (o.outsubfam != NULL) ramx_set_subfam_sink(subfam_sink, &sout, o.linkcount, o.linkfrac, 1024, (double)o.linkscore, o.subfamk, o.subfamiter, o.subfammin, o.refine);
   fflush(stdout);
   warm_join();
   phase_done("device ready");
@@ -1216,11 +1339,13 @@ int ramx_cli_main(int argc, char **argv)
   ramx_set_refine_sink(NULL, NULL, 1);
   ramx_set_copies_sink(NULL, NULL);
   ramx_set_linkage_sink(NULL, NULL, 4, 100, 1024);
+  ramx_set_subfam_sink(NULL, NULL, 4, 100, 1024, 3.0, 4, 8, 4, 10);
   write_results(&o, cores, lib, master, rightbp, leftbp, o.cons_file, o.outtsv, o.outfa);
   aln_write(&afam, cores, o.flanking);
   refined_write(&rfam);
   copies_write(&cfam, cores, o.flanking);
   linkage_write(&lfam, o.linkscore);
+  subfam_write(&sfam, cores, o.flanking);
   if (fp_mat != NULL) fclose(fp_mat);     /* ram_extend.c:778-779 */
   phase_done("report + outputs");
 

@@ -55,6 +55,7 @@
 #include "ramx_pileup_api.h"
 #include "ramx_copystats_api.h"
 #include "ramx_linkage_api.h"
+#include "ramx_subfam_api.h"
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
@@ -173,6 +174,15 @@ struct ramx_dev
   size_t cap_lk_planes, cap_lk_base, cap_lk_at, cap_lk_coat, cap_lk_block, cap_lk_gfam, cap_lk_co;
   int planes_ready, lk_families; long long *lk_fam;
   double lk_gram_ms;        // HIP-event time of the last Gram kernel (ramx_dev_plane_gram_ms)
+  // ramx_dev_subfamilies (allocated on its first call): the lists it uploads, the labels, the mask planes and the counts; the
+  // host keeps where the resident families' flanks lie (lk_place: first and count per family) and the replay's n_padded
+  SubfamFam *d_sf_fam; long long *d_sf_at; longlong2 *d_sf_var; unsigned char *d_sf_pat; int2 *d_sf_tile, *d_sf_item;
+  int *d_sf_count, *d_sf_labels, *d_sf_changed, *d_sf_cnt; unsigned long long *d_sf_mask;
+  size_t cap_sf_fam, cap_sf_at, cap_sf_var, cap_sf_pat, cap_sf_tile, cap_sf_item, cap_sf_count, cap_sf_labels, cap_sf_changed,
+         cap_sf_cnt, cap_sf_mask;
+  int *lk_place, lk_npadded;
+  long long *sf_lay; int sf_families, sf_K;       // the last result's mask planes: (first word, tiles) per family
+  double sf_ms[2];          // HIP-event times of the assign and the count kernels of the last ramx_dev_subfamilies, summed
 };
 
 extern "C" int ramx_device_count(void)
@@ -263,6 +273,10 @@ extern "C" void ramx_dev_destroy(ramx_dev *d)
   (void)hipFree(d->d_lk_planes); (void)hipFree(d->d_lk_base); (void)hipFree(d->d_lk_at); (void)hipFree(d->d_lk_coat);
   (void)hipFree(d->d_lk_block); (void)hipFree(d->d_lk_gfam); (void)hipFree(d->d_lk_co);
   free(d->lk_fam);
+  (void)hipFree(d->d_sf_fam); (void)hipFree(d->d_sf_at); (void)hipFree(d->d_sf_var); (void)hipFree(d->d_sf_pat);
+  (void)hipFree(d->d_sf_tile); (void)hipFree(d->d_sf_item); (void)hipFree(d->d_sf_count); (void)hipFree(d->d_sf_labels);
+  (void)hipFree(d->d_sf_changed); (void)hipFree(d->d_sf_cnt); (void)hipFree(d->d_sf_mask);
+  free(d->lk_place); free(d->sf_lay);
   if (d->hostbox_mirror) (void)hipFree(d->hostbox_mirror);
   if (d->d_peer) (void)hipFree(d->d_peer);
   for (int i = 0; i < 2; i++) if (d->ev_chk[i]) (void)hipEventDestroy(d->ev_chk[i]);
@@ -2151,6 +2165,10 @@ extern "C" int ramx_dev_planes(ramx_dev *d, const ramx_flank *flanks, int32_t n_
   if (!keep) { ramx_set_error("ramx_dev_planes: out of memory"); return RAMX_ERR_ARG; }
   memcpy(keep, lay.data(), lay.size() * sizeof(long long));
   d->lk_fam = keep; d->lk_families = n_families;
+  int *place = (int *)realloc(d->lk_place, (size_t)(n_families > 0 ? n_families : 1) * 2 * sizeof(int));
+  if (!place) { ramx_set_error("ramx_dev_planes: out of memory"); return RAMX_ERR_ARG; }
+  for (int f = 0; f < n_families; f++) { place[2 * f] = fam_first[f]; place[2 * f + 1] = fam_count[f]; }
+  d->lk_place = place; d->lk_npadded = n_padded;
   d->planes_ready = 1;
   return RAMX_OK;
 }
@@ -2237,6 +2255,217 @@ extern "C" int ramx_dev_plane_gram(ramx_dev *d, int32_t n_families, const ramx_p
 }
 
 extern "C" double ramx_dev_plane_gram_ms(ramx_dev *d) { return d ? d->lk_gram_ms : 0; }
+
+// one timed launch on d->stream: ms is added to *sum
+template <typename F>
+static int timed_launch(ramx_dev *d, F launch, double *sum)
+{
+  hipEvent_t ev[2] = { NULL, NULL };
+  const bool timed = hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
+  if (timed) (void)hipEventRecord(ev[0], d->stream);
+  const int rc = launch();
+  if (timed && rc == RAMX_OK) (void)hipEventRecord(ev[1], d->stream);
+  const hipError_t se = hipStreamSynchronize(d->stream);
+  float ms = 0;
+  if (timed && rc == RAMX_OK && se == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) *sum += ms;
+  for (int i = 0; i < 2; i++) if (ev[i]) (void)hipEventDestroy(ev[i]);
+  if (rc != RAMX_OK) return rc;
+  HIPCHK(se);
+  return RAMX_OK;
+}
+
+extern "C" int ramx_dev_subfamilies(ramx_dev *d, int32_t n_families, const ramx_plane *planes, const int32_t *plane_first,
+                                    const int32_t *plane_count, const uint8_t *init, int32_t K, int32_t max_iter, int32_t *labels,
+                                    uint8_t *patterns_out, int32_t *cnt_out, int32_t *size_out, int32_t *iterations, int32_t *converged)
+{
+  if (!d || n_families < 0 || (n_families && (!plane_first || !plane_count || !size_out || !iterations || !converged)))
+  { ramx_set_error("ramx_dev_subfamilies: bad argument"); return RAMX_ERR_ARG; }
+  if (K < 1 || K > RAMX_SUBFAM_K) { ramx_set_error("ramx_dev_subfamilies: K = %d outside [1, %d]", K, RAMX_SUBFAM_K); return RAMX_ERR_ARG; }
+  if (max_iter < 1) { ramx_set_error("ramx_dev_subfamilies: max_iter = %d below 1", max_iter); return RAMX_ERR_ARG; }
+  if (!d->planes_ready)
+  { ramx_set_error("ramx_dev_subfamilies: no resident bit planes (ramx_dev_planes has not run on this device, or a later call dropped them)"); return RAMX_ERR_STATE; }
+  if (n_families != d->lk_families)
+  { ramx_set_error("ramx_dev_subfamilies: %d families, the resident replay has %d", n_families, d->lk_families); return RAMX_ERR_ARG; }
+  if (d->lk_npadded > 0 && !labels) { ramx_set_error("ramx_dev_subfamilies: labels missing"); return RAMX_ERR_ARG; }
+  // everything is checked before anything is launched or written
+  const size_t nf1 = (size_t)(n_families > 0 ? n_families : 1);
+  std::vector<SubfamFam> fam(nf1);
+  std::vector<long long> at;
+  std::vector<longlong2> var;
+  std::vector<int> cov;                               // per variant: its cover plane's index in the family's list
+  std::vector<int> vidx;                              // per variant: its own index in the family's list
+  std::vector<unsigned char> pat;
+  std::vector<int> count(nf1, 0);
+  size_t mask_words = 0, cnt_words = 0;
+  int max_tiles = 0;
+  for (int f = 0; f < n_families; f++)
+  {
+    const int P = plane_count[f];
+    const long long frows = d->lk_fam[3 * (size_t)f], T = d->lk_fam[3 * (size_t)f + 1], base = d->lk_fam[3 * (size_t)f + 2];
+    if (P < 0 || P > RAMX_LINKAGE_MAX_PLANES)
+    { ramx_set_error("ramx_dev_subfamilies: family %d: %d planes outside [0, %d]", f, P, RAMX_LINKAGE_MAX_PLANES); return RAMX_ERR_ARG; }
+    if (P > 0 && (plane_first[f] < 0 || !planes || !cnt_out))
+    { ramx_set_error("ramx_dev_subfamilies: family %d: bad argument", f); return RAMX_ERR_ARG; }
+    const ramx_plane *pp = P > 0 ? planes + plane_first[f] : NULL;
+    SubfamFam &fd = fam[f];
+    fd.var0 = (int)var.size(); fd.at0 = (int)at.size(); fd.P = P; fd.T = (int)T; fd.flank0 = d->lk_place[2 * f];
+    fd.mask0 = (long long)mask_words; fd.cnt0 = (long long)cnt_words;
+    count[f] = d->lk_place[2 * f + 1];
+    for (int i = 0; i < P; i++)
+    {
+      if (pp[i].row < 0 || pp[i].row >= frows || pp[i].cls < 0 || pp[i].cls >= RAMX_PLANE_CLASSES)
+      { ramx_set_error("ramx_dev_subfamilies: family %d, plane %d: (row %d, class %d) outside the resident replay (%lld rows, classes 0..7)", f, i, pp[i].row, pp[i].cls, frows); return RAMX_ERR_ARG; }
+      if (i > 0 && (pp[i].row < pp[i - 1].row || (pp[i].row == pp[i - 1].row && pp[i].cls <= pp[i - 1].cls)))
+      { ramx_set_error("ramx_dev_subfamilies: family %d, plane %d: the planes are not strictly increasing in (row, class)", f, i); return RAMX_ERR_ARG; }
+      at.push_back(base + ((long long)pp[i].row * RAMX_PLANE_CLASSES + pp[i].cls) * T);
+    }
+    for (int i = 0; i < P; i++)
+    {
+      if (pp[i].cls == RAMX_PLANE_COVER) continue;
+      int c = -1;
+      for (int j = i; j >= 0 && pp[j].row == pp[i].row; j--) if (pp[j].cls == RAMX_PLANE_COVER) c = j;
+      for (int j = i + 1; j < P && pp[j].row == pp[i].row; j++) if (pp[j].cls == RAMX_PLANE_COVER) c = j;
+      if (c < 0)
+      { ramx_set_error("ramx_dev_subfamilies: family %d, plane %d: the cover plane (%d, %d) of the variant (%d, %d) is not in the list", f, i, pp[i].row, RAMX_PLANE_COVER, pp[i].row, pp[i].cls); return RAMX_ERR_ARG; }
+      longlong2 vr; vr.x = at[(size_t)fd.at0 + i]; vr.y = at[(size_t)fd.at0 + c];
+      var.push_back(vr); cov.push_back(c); vidx.push_back(i);
+    }
+    fd.V = (int)var.size() - fd.var0;
+    if (fd.V > 0 && (!init || !patterns_out)) { ramx_set_error("ramx_dev_subfamilies: family %d: init / patterns_out missing", f); return RAMX_ERR_ARG; }
+    for (int v = 0; v < fd.V; v++)
+    {
+      unsigned char b = 0;
+      for (int k = 0; k < K; k++) if (init[((size_t)fd.var0 + v) * K + k]) b |= (unsigned char)(1u << k);
+      pat.push_back(b);
+    }
+    mask_words += (size_t)K * T;
+    cnt_words += (size_t)K * (P + 1);
+    if (T > max_tiles) max_tiles = (int)T;
+  }
+  {
+    long long *lay = (long long *)realloc(d->sf_lay, nf1 * 2 * sizeof(long long));
+    if (!lay) { ramx_set_error("ramx_dev_subfamilies: out of memory"); return RAMX_ERR_ARG; }
+    for (int f = 0; f < n_families; f++) { lay[2 * f] = fam[f].mask0; lay[2 * f + 1] = fam[f].T; }
+    d->sf_lay = lay; d->sf_families = 0; d->sf_K = K;       // no result until the call has succeeded
+  }
+  // the answers of a family that never reaches the device (no tile): one assignment of nobody
+  for (int i = 0; i < d->lk_npadded; i++) labels[i] = -1;
+  std::vector<char> active(nf1, 0);
+  int n_active = 0;
+  size_t total_tiles = 0, total_items = 0;
+  for (int f = 0; f < n_families; f++)
+  {
+    iterations[f] = 1; converged[f] = 1;
+    for (int k = 0; k < K; k++) size_out[(size_t)f * K + k] = 0;
+    for (size_t i = 0; i < (size_t)K * fam[f].P; i++) cnt_out[(size_t)K * fam[f].at0 + i] = 0;
+    for (size_t i = 0; i < (size_t)K * fam[f].V; i++) patterns_out[(size_t)K * fam[f].var0 + i] = init[(size_t)K * fam[f].var0 + i] ? 1 : 0;
+    if (fam[f].T == 0) continue;
+    active[f] = 1; n_active++;
+    total_tiles += (size_t)fam[f].T; total_items += (size_t)fam[f].P + 1;
+  }
+  d->sf_ms[0] = d->sf_ms[1] = 0;
+  if (n_active == 0) { d->sf_families = n_families; return RAMX_OK; }
+  HIPCHK(hipSetDevice(d->ordinal));
+  int rc;
+  if ((rc = ensure(&d->d_sf_fam, &d->cap_sf_fam, nf1 * sizeof(SubfamFam)))) return rc;
+  if ((rc = ensure(&d->d_sf_at, &d->cap_sf_at, (at.size() + 1) * sizeof(long long)))) return rc;
+  if ((rc = ensure(&d->d_sf_var, &d->cap_sf_var, (var.size() + 1) * sizeof(longlong2)))) return rc;
+  if ((rc = ensure(&d->d_sf_pat, &d->cap_sf_pat, pat.size() + 1))) return rc;
+  if ((rc = ensure(&d->d_sf_tile, &d->cap_sf_tile, total_tiles * sizeof(int2)))) return rc;
+  if ((rc = ensure(&d->d_sf_item, &d->cap_sf_item, total_items * sizeof(int2)))) return rc;
+  if ((rc = ensure(&d->d_sf_count, &d->cap_sf_count, nf1 * sizeof(int)))) return rc;
+  if ((rc = ensure(&d->d_sf_labels, &d->cap_sf_labels, (size_t)d->lk_npadded * sizeof(int)))) return rc;
+  if ((rc = ensure(&d->d_sf_changed, &d->cap_sf_changed, total_tiles * sizeof(int)))) return rc;
+  if ((rc = ensure(&d->d_sf_cnt, &d->cap_sf_cnt, cnt_words * sizeof(int)))) return rc;
+  if ((rc = ensure(&d->d_sf_mask, &d->cap_sf_mask, mask_words * sizeof(unsigned long long)))) return rc;
+  HIPCHK(hipMemcpyAsync(d->d_sf_fam, fam.data(), nf1 * sizeof(SubfamFam), hipMemcpyHostToDevice, d->stream));
+  if (!at.empty()) HIPCHK(hipMemcpyAsync(d->d_sf_at, at.data(), at.size() * sizeof(long long), hipMemcpyHostToDevice, d->stream));
+  if (!var.empty()) HIPCHK(hipMemcpyAsync(d->d_sf_var, var.data(), var.size() * sizeof(longlong2), hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemcpyAsync(d->d_sf_count, count.data(), nf1 * sizeof(int), hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemsetAsync(d->d_sf_labels, 0xff, (size_t)d->lk_npadded * sizeof(int), d->stream));      // no label yet: -1
+  HIPCHK(hipMemsetAsync(d->d_sf_cnt, 0, cnt_words * sizeof(int), d->stream));
+  SubfamArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  sa.planes = d->d_lk_planes; sa.fam = d->d_sf_fam; sa.at = d->d_sf_at; sa.var = d->d_sf_var; sa.pat = d->d_sf_pat;
+  sa.tile = d->d_sf_tile; sa.item = d->d_sf_item; sa.count = d->d_sf_count; sa.labels = d->d_sf_labels; sa.mask = d->d_sf_mask;
+  sa.changed = d->d_sf_changed; sa.cnt = d->d_sf_cnt; sa.K = K;
+  std::vector<int2> tile, item;
+  std::vector<int> changed, cnt(cnt_words, 0);
+  // between two assignments only the per-tile change counts and the counts come to the host: the update rule runs here
+  for (int it = 1; n_active > 0; it++)
+  {
+    tile.clear(); item.clear();
+    for (int f = 0; f < n_families; f++)
+    {
+      if (!active[f]) continue;
+      for (int t = 0; t < fam[f].T; t++) tile.push_back(make_int2(f, t));
+      for (int i = 0; i <= fam[f].P; i++) item.push_back(make_int2(f, i));
+    }
+    changed.assign(tile.size(), 0);
+    if (!pat.empty()) HIPCHK(hipMemcpyAsync(d->d_sf_pat, pat.data(), pat.size(), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(d->d_sf_tile, tile.data(), tile.size() * sizeof(int2), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(d->d_sf_item, item.data(), item.size() * sizeof(int2), hipMemcpyHostToDevice, d->stream));
+    if ((rc = timed_launch(d, [&] { return ramx_subfam_assign_launch(d->stream, (int)tile.size(), sa); }, &d->sf_ms[0])) != RAMX_OK)
+    { if (rc == RAMX_ERR_HIP) ramx_set_error("ramx_dev_subfamilies: the assign launch of %d waves failed", (int)tile.size()); return rc; }
+    if ((rc = timed_launch(d, [&] { return ramx_subfam_count_launch(d->stream, (int)item.size(), sa); }, &d->sf_ms[1])) != RAMX_OK)
+    { if (rc == RAMX_ERR_HIP) ramx_set_error("ramx_dev_subfamilies: the count launch of %d waves failed", (int)item.size()); return rc; }
+    HIPCHK(hipMemcpy(changed.data(), d->d_sf_changed, tile.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cnt.data(), d->d_sf_cnt, cnt_words * sizeof(int), hipMemcpyDeviceToHost));
+    size_t w = 0;
+    for (int f = 0; f < n_families; f++)
+    {
+      if (!active[f]) continue;
+      const SubfamFam &fd = fam[f];
+      long long nchanged = 0;
+      for (int t = 0; t < fd.T; t++) nchanged += changed[w++];
+      iterations[f] = it;
+      // the first assignment has no label to agree with; with one pattern no later one could differ from it
+      const bool stable = K == 1 || (it > 1 && nchanged == 0);
+      if (stable || it == max_iter)
+      {
+        converged[f] = stable ? 1 : 0;
+        active[f] = 0; n_active--;
+        for (int k = 0; k < K; k++)
+        {
+          const int *row = cnt.data() + fd.cnt0 + (size_t)k * (fd.P + 1);
+          size_out[(size_t)f * K + k] = row[fd.P];
+          for (int i = 0; i < fd.P; i++) cnt_out[(size_t)K * fd.at0 + (size_t)k * fd.P + i] = row[i];
+        }
+        for (int v = 0; v < fd.V; v++)
+          for (int k = 0; k < K; k++) patterns_out[((size_t)fd.var0 + v) * K + k] = (pat[(size_t)fd.var0 + v] >> k) & 1;
+        continue;
+      }
+      for (int k = 0; k < K; k++)
+      {
+        const int *row = cnt.data() + fd.cnt0 + (size_t)k * (fd.P + 1);
+        if (row[fd.P] == 0) continue;                 // an empty group keeps its pattern
+        for (int v = 0; v < fd.V; v++)
+        {
+          const size_t g = (size_t)fd.var0 + v;
+          const bool on = 2LL * row[vidx[g]] > (long long)row[cov[g]];          // exactly half is not a majority
+          pat[g] = (unsigned char)(on ? pat[g] | (1u << k) : pat[g] & ~(1u << k));
+        }
+      }
+    }
+  }
+  for (int f = 0; f < n_families; f++)
+    if (fam[f].T > 0 && count[f] > 0)
+      HIPCHK(hipMemcpy(labels + fam[f].flank0, d->d_sf_labels + fam[f].flank0, (size_t)count[f] * sizeof(int), hipMemcpyDeviceToHost));
+  d->sf_families = n_families;
+  return RAMX_OK;
+}
+
+extern "C" int ramx_dev_subfam_masks(ramx_dev *d, int32_t family, uint64_t *mask)
+{
+  if (!d || !mask || family < 0) { ramx_set_error("ramx_dev_subfam_masks: bad argument"); return RAMX_ERR_ARG; }
+  if (!d->planes_ready || !d->sf_lay || family >= d->sf_families)
+  { ramx_set_error("ramx_dev_subfam_masks: no ramx_dev_subfamilies result of family %d on the resident planes", family); return RAMX_ERR_STATE; }
+  const long long mask0 = d->sf_lay[2 * (size_t)family], T = d->sf_lay[2 * (size_t)family + 1];
+  if (T > 0) HIPCHK(hipMemcpy(mask, d->d_sf_mask + mask0, (size_t)d->sf_K * T * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  return RAMX_OK;
+}
+
+extern "C" void ramx_dev_subfam_ms(ramx_dev *d, double ms[2]) { ms[0] = d ? d->sf_ms[0] : 0; ms[1] = d ? d->sf_ms[1] : 0; }
 
 extern "C" int ramx_dev_refine(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
                                const int32_t *fam_count, int32_t n_families, const ramx_params *p,

@@ -671,7 +671,233 @@ static int linkage_families(const struct sink_view *v)
   return rc;
 }
 
-static int any_sink(void) { return g_profile_cb || g_align_cb || g_refine_cb || g_copies_cb || g_linkage_cb; }
+static ramx_subfam_cb g_subfam_cb = NULL;
+static void *g_subfam_user = NULL;
+static int32_t g_subfam_count = 4, g_subfam_permille = 100, g_subfam_max = 1024, g_subfam_K = 4, g_subfam_iter = 8, g_subfam_members = 4,
+               g_subfam_replays = 10;
+static double g_subfam_score = 3.0;
+void ramx_set_subfam_sink(ramx_subfam_cb cb, void *user, int32_t min_count, int32_t min_permille, int32_t max_variants,
+                          double min_mlog10p, int32_t K, int32_t max_iter, int32_t min_members, int32_t max_replays)
+{
+  g_subfam_cb = cb;
+  g_subfam_user = user;
+  g_subfam_count = min_count; g_subfam_permille = min_permille;
+  g_subfam_max = max_variants < 0 ? 0 : max_variants > RAMX_LINKAGE_MAX_PLANES / 2 ? RAMX_LINKAGE_MAX_PLANES / 2 : max_variants;
+  g_subfam_score = min_mlog10p;
+  g_subfam_K = K < 1 ? 1 : K > RAMX_SUBFAM_MAX ? RAMX_SUBFAM_MAX : K;
+  g_subfam_iter = max_iter >= 1 ? max_iter : 1;
+  g_subfam_members = min_members;
+  g_subfam_replays = max_replays >= 1 ? max_replays : 1;
+}
+
+/* With a subfamily sink set: the linkage sink's planes, selection and Gram matrix; the linked pairs' components as initial
+ * patterns; the split on the device, the families with the same number of patterns in one call (the others with an empty list:
+ * their labels of that call are not used); the distances to the final patterns from the planes' words; and one refinement over
+ * the flanks of every kept group as a family of its own. */
+static int subfam_families(const struct sink_view *v)
+{
+  if (ramx_dev_is_multi(v->d))
+  { ramx_set_error("subfamily sink: not with a communicator or mailbox route active (the selection needs the counts of every rank)"); return RAMX_ERR_UNSUPPORTED; }
+  const ramx_params *p = v->p;
+  const int nb = v->nb, KM = RAMX_SUBFAM_MAX;
+  const size_t L = (size_t)(p->L > 0 ? p->L : 1), n = (size_t)(nb > 0 ? nb : 1), np1 = (size_t)(v->npad > 0 ? v->npad : 1);
+  const size_t pcap = 2 * (size_t)(g_subfam_max > 0 ? g_subfam_max : 1);
+  int32_t *pfirst = (int32_t *)calloc(n * 8, sizeof(int32_t)), *pcount = pfirst + n, *Kb = pcount + n, *vfirst = Kb + n, *vcount = vfirst + n,
+          *iters = vcount + n, *conv = iters + n, *qcount = conv + n;
+  int64_t *cfirst = (int64_t *)calloc(n * 2, sizeof(int64_t)), *bfirst = cfirst + n;
+  ramx_col_pileup *cols = (ramx_col_pileup *)calloc(n * L, sizeof(ramx_col_pileup));
+  ramx_plane *planes = (ramx_plane *)calloc(n * pcap, sizeof(ramx_plane));
+  int32_t *labels = (int32_t *)malloc(sizeof(int32_t) * np1), *lab1 = (int32_t *)malloc(sizeof(int32_t) * np1);
+  int32_t *size = (int32_t *)calloc(n * KM, sizeof(int32_t)), *size1 = (int32_t *)calloc(n * KM, sizeof(int32_t));
+  int32_t *dist = (int32_t *)calloc(np1 * KM, sizeof(int32_t));
+  int32_t *co = NULL, *cnt = NULL, *cnt1 = NULL, *it1 = (int32_t *)calloc(n * 2, sizeof(int32_t)), *cv1 = it1 + n;
+  uint64_t *bits = NULL;
+  uint8_t *init = NULL, *pats = NULL, *init1 = NULL, *pats1 = NULL;
+  /* the kept groups as families of their own */
+  ramx_flank *gfl = NULL;
+  int32_t *gfirst = NULL, *gcount = NULL, *grows = NULL, *gout = NULL, *gof = NULL, *ggroup = NULL;
+  int8_t *gcons = NULL, *gref = NULL;
+  ramx_col_pileup *gcols = NULL;
+  ramx_subfam_group *groups = NULL;
+  int ng = 0;
+  int32_t planes_total = 0, var_total = 0;
+  for (int32_t i = 0; i < v->npad; i++) labels[i] = -1;
+  int rc = ramx_dev_planes(v->d, v->fl, v->npad, v->first, v->count, nb, p, v->cons, v->ret, cols, NULL, NULL);
+  if (rc == RAMX_OK)
+  {
+    int64_t cells = 0, words = 0;
+    for (int b = 0; b < nb; b++)
+    {
+      pfirst[b] = planes_total;
+      pcount[b] = v->count[b] > 0 ? ramx_select_planes(v->cons + (size_t)b * p->L, v->ret[b], cols + (size_t)b * L, g_subfam_count, g_subfam_permille, g_subfam_max, planes + planes_total) : 0;
+      cfirst[b] = cells; bfirst[b] = words;
+      vfirst[b] = var_total;
+      for (int i = 0; i < pcount[b]; i++) vcount[b] += planes[planes_total + i].cls != RAMX_PLANE_COVER;
+      planes_total += pcount[b]; var_total += vcount[b];
+      cells += (int64_t)pcount[b] * pcount[b]; words += (int64_t)pcount[b] * ((v->count[b] + 63) / 64);
+    }
+    co = (int32_t *)calloc((size_t)(cells > 0 ? cells : 1), sizeof(int32_t));
+    bits = (uint64_t *)calloc((size_t)(words > 0 ? words : 1), sizeof(uint64_t));
+    rc = ramx_dev_plane_gram(v->d, nb, planes, pfirst, pcount, co, cfirst, bits, bfirst);
+  }
+  const size_t pt = (size_t)(planes_total > 0 ? planes_total : 1), vt = (size_t)(var_total > 0 ? var_total : 1);
+  init = (uint8_t *)calloc(vt * KM, 1); pats = (uint8_t *)calloc(vt * KM, 1); init1 = (uint8_t *)calloc(vt * KM, 1); pats1 = (uint8_t *)calloc(vt * KM, 1);
+  cnt = (int32_t *)calloc(pt * KM, sizeof(int32_t)); cnt1 = (int32_t *)calloc(pt * KM, sizeof(int32_t));
+  if (rc == RAMX_OK)
+  {
+    /* family b's initial patterns at KM * vfirst[b] as [V][Kb[b]] */
+    for (int b = 0; b < nb; b++)
+    {
+      const int32_t P = pcount[b];
+      /* room for 4096 linked pairs; a family with more is asked again with room for all it has */
+      int32_t cap = 4096;
+      ramx_link *links = (ramx_link *)malloc(sizeof(ramx_link) * (size_t)cap);
+      int32_t nl = P > 0 ? ramx_link_pairs(planes + pfirst[b], P, co + cfirst[b], g_subfam_score, links, cap) : 0;
+      if (nl > cap)
+      {
+        cap = nl;
+        free(links);
+        links = (ramx_link *)malloc(sizeof(ramx_link) * (size_t)cap);
+        nl = ramx_link_pairs(planes + pfirst[b], P, co + cfirst[b], g_subfam_score, links, cap);
+      }
+      Kb[b] = ramx_link_components(planes + pfirst[b], P, links, nl, g_subfam_K, init + (size_t)KM * vfirst[b], NULL);
+      free(links);
+      iters[b] = 1; conv[b] = 1;
+      for (int32_t i = 0; i < v->count[b]; i++) labels[v->first[b] + i] = 0;
+      size[(size_t)b * KM] = v->count[b];
+    }
+    /* one call per number of patterns: the families that have it with their lists, the others with none */
+    for (int K = 1; K <= g_subfam_K && rc == RAMX_OK; K++)
+    {
+      int any = 0;
+      int32_t at = 0, vat = 0;
+      for (int b = 0; b < nb; b++)
+      {
+        const int on = Kb[b] == K && v->count[b] > 0 && v->ret[b] > 0;
+        qcount[b] = on ? pcount[b] : 0;
+        if (!on) continue;
+        any = 1;
+        memcpy(init1 + (size_t)K * vat, init + (size_t)KM * vfirst[b], (size_t)K * vcount[b]);
+        at += pcount[b]; vat += vcount[b];
+      }
+      if (!any) continue;
+      /* the lists of this call are those families' lists one after the other: their places are the running sums */
+      int32_t *qfirst = (int32_t *)calloc(n, sizeof(int32_t));
+      ramx_plane *qplanes = (ramx_plane *)calloc(pt, sizeof(ramx_plane));
+      at = 0;
+      for (int b = 0; b < nb; b++)
+      {
+        qfirst[b] = at;
+        if (qcount[b]) memcpy(qplanes + at, planes + pfirst[b], sizeof(ramx_plane) * (size_t)qcount[b]);
+        at += qcount[b];
+      }
+      rc = ramx_dev_subfamilies(v->d, nb, qplanes, qfirst, qcount, init1, K, g_subfam_iter, lab1, pats1, cnt1, size1, it1, cv1);
+      vat = 0;
+      for (int b = 0; b < nb && rc == RAMX_OK; b++)
+      {
+        if (!(Kb[b] == K && v->count[b] > 0 && v->ret[b] > 0)) continue;
+        memcpy(labels + v->first[b], lab1 + v->first[b], sizeof(int32_t) * (size_t)v->count[b]);
+        memcpy(pats + (size_t)KM * vfirst[b], pats1 + (size_t)K * vat, (size_t)K * vcount[b]);
+        memcpy(cnt + (size_t)KM * pfirst[b], cnt1 + (size_t)K * qfirst[b], sizeof(int32_t) * (size_t)K * pcount[b]);
+        memcpy(size + (size_t)b * KM, size1 + (size_t)b * K, sizeof(int32_t) * (size_t)K);
+        iters[b] = it1[b]; conv[b] = cv1[b];
+        vat += vcount[b];
+      }
+      free(qfirst); free(qplanes);
+    }
+  }
+  if (rc == RAMX_OK)
+  {
+    /* the distances to the patterns handed over, from the words of the selected planes */
+    for (int b = 0; b < nb; b++)
+    {
+      const int32_t P = pcount[b], T = (v->count[b] + 63) / 64, K = Kb[b];
+      const ramx_plane *pp = planes + pfirst[b];
+      const uint64_t *w = bits + bfirst[b];
+      const uint8_t *pt_b = pats + (size_t)KM * vfirst[b];
+      if (!(v->count[b] > 0 && v->ret[b] > 0)) continue;
+      int32_t vn = 0;
+      for (int32_t i = 0; i < P; i++)
+      {
+        if (pp[i].cls == RAMX_PLANE_COVER) continue;
+        int32_t c = -1;
+        for (int32_t j = 0; j < P; j++) if (pp[j].row == pp[i].row && pp[j].cls == RAMX_PLANE_COVER) c = j;
+        for (int32_t f = 0; f < v->count[b]; f++)
+        {
+          const int x = (int)((w[(size_t)i * T + f / 64] >> (f % 64)) & 1), cv = (int)((w[(size_t)c * T + f / 64] >> (f % 64)) & 1);
+          for (int k = 0; k < K; k++) dist[((size_t)v->first[b] + f) * KM + k] += cv & (x ^ pt_b[(size_t)vn * K + k]);
+        }
+        vn++;
+      }
+    }
+    /* the kept groups */
+    for (int b = 0; b < nb; b++)
+      for (int k = 0; k < Kb[b]; k++) if (v->count[b] > 0 && v->ret[b] > 0 && size[(size_t)b * KM + k] >= g_subfam_members && size[(size_t)b * KM + k] > 0) ng++;
+    const size_t g1 = (size_t)(ng > 0 ? ng : 1);
+    gfirst = (int32_t *)calloc(g1 * 6, sizeof(int32_t)); gcount = gfirst + g1; grows = gcount + g1; gout = grows + g1; gof = gout + g1; ggroup = gof + g1;
+    int32_t *greplays = (int32_t *)calloc(g1 * 2, sizeof(int32_t)), *gconv = greplays + g1;
+    gcons = (int8_t *)calloc(g1 * L, 1); gref = (int8_t *)calloc(g1 * L, 1);
+    gcols = (ramx_col_pileup *)calloc(g1 * L, sizeof(ramx_col_pileup));
+    groups = (ramx_subfam_group *)calloc(g1, sizeof(ramx_subfam_group));
+    int32_t gpad = 0;
+    int g = 0;
+    for (int b = 0; b < nb; b++)
+      for (int k = 0; k < Kb[b]; k++)
+      {
+        const int32_t sz = size[(size_t)b * KM + k];
+        if (!(v->count[b] > 0 && v->ret[b] > 0 && sz >= g_subfam_members && sz > 0)) continue;
+        gfirst[g] = gpad; gcount[g] = sz; grows[g] = v->ret[b]; gof[g] = b; ggroup[g] = k;
+        memcpy(gcons + (size_t)g * L, v->cons + (size_t)b * p->L, (size_t)v->ret[b]);
+        gpad += (sz + 63) & ~63;
+        g++;
+      }
+    gfl = (ramx_flank *)malloc(sizeof(ramx_flank) * (size_t)(gpad > 0 ? gpad : 1));
+    for (int32_t i = 0; i < gpad; i++) gfl[i] = empty_flank();
+    for (g = 0; g < ng; g++)
+    {
+      const int b = gof[g];
+      int32_t at = gfirst[g];
+      for (int32_t f = 0; f < v->count[b]; f++) if (labels[v->first[b] + f] == ggroup[g]) gfl[at++] = v->fl[v->first[b] + f];
+    }
+    if (ng > 0)
+      rc = ramx_dev_refine(v->d, gfl, gpad, gfirst, gcount, ng, p, gcons, grows, g_subfam_replays, gref, gout, greplays, gconv, gcols, NULL, NULL);
+    for (g = 0; g < ng; g++)
+    {
+      groups[g].group = ggroup[g]; groups[g].size = gcount[g]; groups[g].refined_rows = gout[g]; groups[g].replays = greplays[g];
+      groups[g].converged = gconv[g]; groups[g].refined_cons = gref + (size_t)g * L; groups[g].refined_cols = gcols + (size_t)g * L;
+    }
+    free(greplays);
+  }
+  int g0 = 0;
+  for (int b = 0; b < nb && rc == RAMX_OK; b++)
+  {
+    ramx_flank *own_fl = own_flanks(v, b);
+    ramx_subfamilies sf;
+    memset(&sf, 0, sizeof(sf));
+    const int on = v->count[b] > 0 && v->ret[b] > 0;
+    sf.direction = v->direction; sf.family = v->fidx[b]; sf.rows = v->ret[b]; sf.n_flanks = v->count[b];
+    sf.n_planes = on ? pcount[b] : 0; sf.n_variants = on ? vcount[b] : 0; sf.K = on ? Kb[b] : 1;
+    sf.iterations = iters[b]; sf.converged = conv[b];
+    while (g0 + sf.n_groups < ng && gof[g0 + sf.n_groups] == b) sf.n_groups++;
+    sf.cons = v->cons + (size_t)b * p->L; sf.flanks = own_fl; sf.core_index = v->map + v->first[b];
+    sf.planes = planes + pfirst[b]; sf.labels = labels + v->first[b];
+    /* the callback's tables are [.][K], the work tables [.][RAMX_SUBFAM_MAX]: the distances are repacked, the others are [.][K] already */
+    int32_t *d1 = (int32_t *)calloc((size_t)(v->count[b] > 0 ? v->count[b] : 1) * (size_t)sf.K, sizeof(int32_t));
+    for (int32_t f = 0; f < v->count[b]; f++)
+      for (int k = 0; k < sf.K; k++) d1[(size_t)f * sf.K + k] = dist[((size_t)v->first[b] + f) * KM + k];
+    sf.patterns = pats + (size_t)KM * vfirst[b]; sf.cnt = cnt + (size_t)KM * pfirst[b]; sf.size = size + (size_t)b * KM; sf.dist = d1;
+    sf.groups = groups ? groups + g0 : NULL;
+    g_subfam_cb(&sf, g_subfam_user);
+    g0 += sf.n_groups;
+    free(d1); free(own_fl);
+  }
+  free(pfirst); free(cfirst); free(cols); free(planes); free(labels); free(lab1); free(size); free(size1); free(dist); free(co);
+  free(cnt); free(cnt1); free(it1); free(bits); free(init); free(pats); free(init1); free(pats1);
+  free(gfl); free(gfirst); free(gcons); free(gref); free(gcols); free(groups);
+  return rc;
+}
+
+static int any_sink(void) { return g_profile_cb || g_align_cb || g_refine_cb || g_copies_cb || g_linkage_cb || g_subfam_cb; }
 
 /* one RAMX_TIMING line: the time since the phase before, under the caller's name */
 static void phase_line(const char *who, int width, const char *name, double *since)
@@ -690,6 +916,7 @@ static int run_sinks(const struct sink_view *v, const char *who, int width, int 
     { g_refine_cb != NULL, refine_families, "pileup + refinement" },
     { g_copies_cb != NULL, copies_families, "per-copy statistics" },
     { g_linkage_cb != NULL, linkage_families, "linkage" },
+    { g_subfam_cb != NULL, subfam_families, "subfamilies" },
   };
   int rc = RAMX_OK;
   for (size_t i = 0; i < sizeof(sinks) / sizeof(sinks[0]) && rc == RAMX_OK; i++)

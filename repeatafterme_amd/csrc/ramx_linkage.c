@@ -1,6 +1,6 @@
-/* ramx_linkage.c -- co-segregation of an extension's variants, the host side (include/ramx.h, ramx_select_planes and
- * ramx_link_pairs): which bit planes to ask the device for, and the pair statistic on their Gram matrix.  Plain host C, usable
- * without a device.
+/* ramx_linkage.c -- co-segregation of an extension's variants, the host side (include/ramx.h, ramx_select_planes,
+ * ramx_link_pairs and ramx_link_components): which bit planes to ask the device for, the pair statistic on their Gram matrix,
+ * and the linked variants as the initial patterns of a split into subfamilies.  Plain host C, usable without a device.
  *
  * The statistic is a one-sided hypergeometric test per pair, and every pair of variants on different rows is tested: there is
  * NO multiple-testing correction here.  The caller sets the threshold with the number of pairs in mind. */
@@ -121,4 +121,53 @@ int32_t ramx_link_pairs(const ramx_plane *planes, int32_t P, const int32_t *co, 
   }
   free(cover);
   return found;
+}
+
+struct comp { int32_t size, low; };
+
+static int by_size(const void *a, const void *b)
+{
+  const struct comp *x = (const struct comp *)a, *y = (const struct comp *)b;
+  if (x->size != y->size) return x->size > y->size ? -1 : 1;
+  return (x->low > y->low) - (x->low < y->low);
+}
+
+static int32_t root_of(int32_t *up, int32_t i)
+{
+  while (up[i] != i) { up[i] = up[up[i]]; i = up[i]; }
+  return i;
+}
+
+int32_t ramx_link_components(const ramx_plane *planes, int32_t P, const ramx_link *links, int32_t n_links, int32_t K,
+                             uint8_t *init, int32_t *component)
+{
+  if (K < 1 || K > RAMX_SUBFAM_MAX || P < 0 || n_links < 0 || (P && !planes) || (n_links && !links)) return 0;
+  /* variant number of every listed plane (-1: a cover plane); the smaller root wins a union, so a root is its lowest member */
+  int32_t *vnum = (int32_t *)malloc(sizeof(int32_t) * (size_t)(P + 1) * 3);
+  struct comp *c = (struct comp *)malloc(sizeof(struct comp) * (size_t)(P + 1));
+  if (!vnum || !c) { free(vnum); free(c); return 0; }
+  int32_t *up = vnum + (P + 1), *size = up + (P + 1), V = 0, nc = 0, Kp = 0;
+  for (int32_t i = 0; i < P; i++) vnum[i] = planes[i].cls == RAMX_PLANE_COVER ? -1 : V++;
+  for (int32_t v = 0; v < V; v++) { up[v] = v; size[v] = 0; }
+  for (int32_t l = 0; l < n_links; l++)
+  {
+    if (links[l].p < 0 || links[l].p >= P || links[l].q < 0 || links[l].q >= P || vnum[links[l].p] < 0 || vnum[links[l].q] < 0) goto done;
+    const int32_t a = root_of(up, vnum[links[l].p]), b = root_of(up, vnum[links[l].q]);
+    if (a != b) up[a > b ? a : b] = a < b ? a : b;
+  }
+  for (int32_t v = 0; v < V; v++) size[root_of(up, v)]++;
+  for (int32_t v = 0; v < V; v++) if (up[v] == v && size[v] >= 2) { c[nc].size = size[v]; c[nc].low = v; nc++; }
+  qsort(c, (size_t)nc, sizeof(*c), by_size);
+  if (nc > K - 1) nc = K - 1;
+  Kp = nc + 1;
+  for (int32_t v = 0; v < V; v++)
+  {
+    int32_t k = 0;
+    for (int32_t j = 0; j < nc; j++) if (c[j].low == root_of(up, v)) k = j + 1;
+    if (component) component[v] = k;
+    if (init) for (int32_t j = 0; j < Kp; j++) init[(size_t)v * Kp + j] = j > 0 && j == k;
+  }
+done:
+  free(vnum); free(c);
+  return Kp;
 }

@@ -159,6 +159,39 @@ class Linkage:
     co: np.ndarray                   # int32 [P][P]
 
 
+SUBFAM_MAX = 8                       # RAMX_SUBFAM_MAX
+
+
+@dataclass
+class SubfamGroup:
+    """One kept group of a split: its own refined consensus and pileup (C-ABI ramx_subfam_group)."""
+    group: int
+    size: int
+    refined_cons: np.ndarray         # int8 [refined rows]
+    refined_cols: np.ndarray         # PILEUP_DTYPE [refined rows]
+    replays: int
+    converged: int
+
+
+@dataclass
+class Subfamilies:
+    """The copies of one direction of one family split by the linked variants they carry (C-ABI ramx_subfamilies)."""
+    direction: int
+    family: int                      # index in a batch, else 0
+    cons: np.ndarray                 # int8 [rows]: the kept consensus (rows = ret)
+    flanks: np.ndarray               # FLANK_DTYPE [n_flanks]
+    core_index: np.ndarray           # position in the core list of every flank
+    planes: np.ndarray               # PLANE_DTYPE [P]
+    labels: np.ndarray               # int32 [n_flanks]
+    patterns: np.ndarray             # uint8 [V][K]
+    cnt: np.ndarray                  # int32 [K][P]
+    size: np.ndarray                 # int32 [K]
+    dist: np.ndarray                 # int32 [n_flanks][K]
+    iterations: int
+    converged: int
+    groups: list                     # SubfamGroup, ascending in group: those of at least min_members copies
+
+
 @dataclass
 class Copies:
     """Per-copy statistics of one direction of one family along its kept consensus (C-ABI ramx_copies / ramx_dev_copy_stats)."""

@@ -106,6 +106,32 @@ def link_pairs(planes, co, min_mlog10p: float = 0.0, cap: Optional[int] = None):
     return out[:min(n, cap)].copy(), int(n)
 
 
+def link_components(planes, links, K: int = 4):
+    """The initial patterns of a split into subfamilies from the linked pairs (C-ABI ramx_link_components, host C).  links:
+    LINK_DTYPE records as link_pairs returns them at the caller's threshold.  -> (init uint8 [V][K'], component int32 [V]), K' = 1 +
+    the components kept."""
+    pl = np.ascontiguousarray(planes, PLANE_DTYPE).reshape(-1)
+    lk = np.ascontiguousarray(links, LINK_DTYPE).reshape(-1)
+    V = int((pl["cls"] != 6).sum())
+    init = np.zeros(max(V * max(int(K), 1), 1), np.uint8)
+    comp = np.zeros(max(V, 1), np.int32)
+    kp = _lib.lib().ramx_link_components(pl.ctypes.data, len(pl), lk.ctypes.data, len(lk), int(K), init.ctypes.data, comp.ctypes.data)
+    if kp < 1:
+        raise _lib.RamxError(f"ramx_link_components: K = {K} outside 1..8, or a link outside the list")
+    return init[:V * kp].reshape(V, kp).copy(), comp[:V].copy()
+
+
+@dataclass
+class SubfamResult:
+    labels: np.ndarray                     # int32 [flanks of the family]: the group of every copy
+    patterns: np.ndarray                   # uint8 [V][K]: the patterns of the last assignment
+    cnt: np.ndarray                        # int32 [K][P]: copies of group k with the listed plane's bit set
+    size: np.ndarray                       # int32 [K]
+    iterations: int                        # assignments made
+    converged: int
+    masks: Optional[np.ndarray]            # uint64 [K][T]: the groups as bit planes, or None
+
+
 def copy_kimura(stats) -> float:
     """Kimura two-parameter divergence (percent) of one COPY_STATS_DTYPE record (C-ABI ramx_copy_kimura); < 0: undefined."""
     s = np.ascontiguousarray(stats, COPY_STATS_DTYPE).reshape(-1)
@@ -311,6 +337,7 @@ class Device:
                                            cons.ctypes.data, rows_a.ctypes.data, cols.ctypes.data, ends.ctypes.data, ms),
                    "ramx_dev_planes")
         self._plane_tiles = (count + 63) // 64
+        self._plane_place = (first.copy(), count.copy(), npad)
         return PlanesResult(cols, ends, tuple(ms), count)
 
     def plane_gram(self, planes, bits: bool = False):
@@ -338,6 +365,55 @@ class Device:
             return cos[0] if one else cos
         bws = [bw[b_first[f]:b_first[f] + bsz[f]].reshape(int(cnt[f]), tiles[f]) for f in range(nf)]
         return (cos[0], bws[0]) if one else (cos, bws)
+
+    def subfamilies(self, planes, init, max_iter: int = 8, masks: bool = False, K: Optional[int] = None):
+        """The copies of every family of the resident replay split by the variants they carry (C-ABI ramx_dev_subfamilies).
+        `planes` as plane_gram(); `init`: uint8 [V][K] per family (link_components), the same K for all.  -> SubfamResult, or a
+        list of them for a list."""
+        one = not isinstance(planes, (list, tuple))
+        lists = [np.ascontiguousarray(x, PLANE_DTYPE).reshape(-1) for x in ([planes] if one else planes)]
+        inits = [np.ascontiguousarray(x, np.uint8) for x in ([init] if one else init)]
+        nf = len(lists)
+        V = [int((x["cls"] != 6).sum()) for x in lists]
+        if K is None:
+            K = next((int(x.shape[1]) for x in inits if x.ndim == 2), 1)
+        for f in range(nf):
+            assert not 1 <= K <= 8 or inits[f].size == V[f] * K, (f, inits[f].shape, V[f], K)     # another K: the library refuses it
+        first_f, count_f, npad = getattr(self, "_plane_place", (np.zeros(nf, np.int32), np.zeros(nf, np.int32), 0))
+        cnt = np.array([len(x) for x in lists], np.int32)
+        first = np.concatenate([[0], np.cumsum(cnt)[:-1]]).astype(np.int32) if nf else np.zeros(0, np.int32)
+        allp = np.concatenate(lists) if nf and cnt.sum() else np.zeros(1, PLANE_DTYPE)
+        alli = np.concatenate([x.reshape(-1) for x in inits] + [np.zeros(1, np.uint8)])
+        labels = np.full(max(npad, 1), -2, np.int32)
+        pats = np.full(max(sum(V) * max(K, 1), 1), 255, np.uint8)
+        counts = np.full(max(int(cnt.sum()) * max(K, 1), 1), -1, np.int32)
+        size = np.full(max(nf * max(K, 1), 1), -1, np.int32)
+        its, conv = np.full(max(nf, 1), -1, np.int32), np.full(max(nf, 1), -1, np.int32)
+        _lib.check(self._L.ramx_dev_subfamilies(self._h, nf, allp.ctypes.data, first.ctypes.data, cnt.ctypes.data, alli.ctypes.data,
+                                                int(K), int(max_iter), labels.ctypes.data, pats.ctypes.data, counts.ctypes.data,
+                                                size.ctypes.data, its.ctypes.data, conv.ctypes.data), "ramx_dev_subfamilies")
+        out, v0 = [], 0
+        for f in range(nf):
+            P, T = int(cnt[f]), int(self._plane_tiles[f]) if f < len(self._plane_tiles) else 0
+            mk = None
+            if masks:
+                mk = np.zeros((K, T), np.uint64)
+                buf = np.zeros(max(K * T, 1), np.uint64)
+                _lib.check(self._L.ramx_dev_subfam_masks(self._h, f, buf.ctypes.data), "ramx_dev_subfam_masks")
+                mk = buf[:K * T].reshape(K, T)
+            out.append(SubfamResult(labels[int(first_f[f]):int(first_f[f]) + int(count_f[f])].copy(),
+                                    pats[K * v0:K * (v0 + V[f])].reshape(V[f], K).copy(),
+                                    counts[K * int(first[f]):K * (int(first[f]) + P)].reshape(K, P).copy(),
+                                    size[f * K:(f + 1) * K].copy(), int(its[f]), int(conv[f]), mk))
+            v0 += V[f]
+        self._subfam_labels = labels[:npad]
+        return out[0] if one else out
+
+    def subfam_ms(self):
+        """HIP-event times of the assign and the count kernels of the last subfamilies(), summed over its iterations."""
+        ms = (C.c_double * 2)()
+        self._L.ramx_dev_subfam_ms(self._h, ms)
+        return float(ms[0]), float(ms[1])
 
     def plane_gram_ms(self) -> float:
         """HIP-event time of the Gram kernel of the last plane_gram() (C-ABI ramx_dev_plane_gram_ms)."""

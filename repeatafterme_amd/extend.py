@@ -13,7 +13,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .datamodel import (ALN_END_DTYPE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, FLANK_DTYPE, PILEUP_DTYPE, PLANE_DTYPE, Alignment, Copies,
+from .datamodel import (ALN_END_DTYPE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, FLANK_DTYPE, PILEUP_DTYPE, PLANE_DTYPE, Alignment, Copies, SubfamGroup, Subfamilies,
                         CoreSet, ExtendParams, Linkage, Profile, Refinement)
 
 
@@ -200,9 +200,50 @@ class _LinkageSink:
         return False
 
 
+class _SubfamSink:
+    """Collects what seam 1 hands to the subfamily sink (ramx_set_subfam_sink) while the block runs.  args: (min_count,
+    min_permille, max_variants, min_mlog10p, K, max_iter, min_members, max_replays)."""
+    DEFAULT = (4, 100, 1024, 3.0, 4, 8, 4, 10)
+
+    def __init__(self, args=DEFAULT):
+        self.got = []
+        a = tuple(args)
+        self.args = tuple(int(x) for x in a[:3]) + (float(a[3]),) + tuple(int(x) for x in a[4:])
+        assert len(self.args) == 8
+
+        def _cb(ptr, _user):
+            sf = ptr.contents
+
+            def grab(src, count, dtype):
+                out = np.zeros(count, dtype)
+                if count and src:
+                    C.memmove(out.ctypes.data, src, count * out.dtype.itemsize)
+                return out
+            n, P, V, K = sf.n_flanks, sf.n_planes, sf.n_variants, sf.K
+            groups = []
+            for g in range(sf.n_groups):
+                gr = sf.groups[g]
+                groups.append(SubfamGroup(gr.group, gr.size, grab(gr.refined_cons, gr.refined_rows, np.int8),
+                                          grab(gr.refined_cols, gr.refined_rows, PILEUP_DTYPE), gr.replays, gr.converged))
+            self.got.append(Subfamilies(sf.direction, sf.family, grab(sf.cons, sf.rows, np.int8), grab(sf.flanks, n, FLANK_DTYPE),
+                                        grab(sf.core_index, n, np.int32), grab(sf.planes, P, PLANE_DTYPE), grab(sf.labels, n, np.int32),
+                                        grab(sf.patterns, V * K, np.uint8).reshape(V, K), grab(sf.cnt, K * P, np.int32).reshape(K, P),
+                                        grab(sf.size, K, np.int32), grab(sf.dist, n * K, np.int32).reshape(n, K), sf.iterations,
+                                        sf.converged, groups))
+        self._cb = _lib.SUBFAM_CB(_cb)
+
+    def __enter__(self):
+        _lib.lib().ramx_set_subfam_sink(self._cb, None, *self.args)
+        return self
+
+    def __exit__(self, *exc):
+        _lib.lib().ramx_set_subfam_sink(_lib.SUBFAM_CB(), None, *self.DEFAULT)
+        return False
+
+
 def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, master: np.ndarray,
                      p: ExtendParams, profile: bool = False, align: bool = False, refine: int = 0, copies: bool = False,
-                     linkage=None):
+                     linkage=None, subfam=None):
     """direction: 1 = right, 0 = left (reference ram_extend.c:424,506).  profile=True: returns (RunInfo, Profile) -- the
     direction is replayed along the consensus it chose (C-ABI ramx_dev_profile) after the loop.  align=True: returns
     (RunInfo, Alignment), or (RunInfo, Profile, Alignment) with both -- every flank aligned to the kept consensus (C-ABI
@@ -210,7 +251,14 @@ def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, maste
     most n replays (C-ABI ramx_dev_pileup / ramx_dev_refine).  copies=True: a Copies comes last of all -- every copy's
     statistics along the kept consensus (C-ABI ramx_dev_copy_stats).  linkage=True or (min_count, min_permille, max_variants): a
     Linkage comes behind everything else -- the variants of the kept consensus and their Gram matrix (C-ABI ramx_dev_planes,
-    ramx_select_planes, ramx_dev_plane_gram)."""
+    ramx_select_planes, ramx_dev_plane_gram).  subfam=True or the eight arguments of ramx_set_subfam_sink behind its callback: a
+    Subfamilies comes last of all -- the copies split by their linked variants, every kept group with its own consensus."""
+    if subfam:
+        with _SubfamSink(_SubfamSink.DEFAULT if subfam is True else subfam) as ssink:
+            res = extend_alignment(direction, cores, sequence, master, p, profile=profile, align=align, refine=refine, copies=copies,
+                                   linkage=linkage)
+        assert len(ssink.got) == 1
+        return (res + (ssink.got[0],)) if isinstance(res, tuple) else (res, ssink.got[0])
     if linkage:
         with _LinkageSink((4, 100, 1024) if linkage is True else linkage) as lsink:
             res = extend_alignment(direction, cores, sequence, master, p, profile=profile, align=align, refine=refine, copies=copies)
@@ -251,12 +299,20 @@ def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, maste
 
 
 def extend_batch(direction: int, families, p: ExtendParams, profile: bool = False, align: bool = False, copies: bool = False,
-                 linkage=None):
+                 linkage=None, subfam=None):
     """Many families in one launch (C-ABI ramx_extend_batch).  `families` is a list of (cores, sequence, master);
     every family is updated in place exactly like extend_alignment does for one.  Returns one RunInfo per family;
     profile=True: (RunInfos, Profiles), one Profile per family in the order of `families`; align=True: (RunInfos,
     Alignments), or (RunInfos, Profiles, Alignments) with both.  copies=True: the families' Copies come last in the tuple.
-    linkage (as extend_alignment): the families' Linkages come behind everything else."""
+    linkage (as extend_alignment): the families' Linkages come behind everything else; subfam (as extend_alignment): their
+    Subfamilies last of all."""
+    if subfam:
+        with _SubfamSink(_SubfamSink.DEFAULT if subfam is True else subfam) as ssink:
+            res = extend_batch(direction, families, p, profile=profile, align=align, copies=copies, linkage=linkage)
+        by_family = {sf.family: sf for sf in ssink.got}
+        assert len(by_family) == len(ssink.got) == len(families)
+        sfs = [by_family[i] for i in range(len(families))]
+        return (res + (sfs,)) if isinstance(res, tuple) else (res, sfs)
     if linkage:
         with _LinkageSink((4, 100, 1024) if linkage is True else linkage) as lsink:
             res = extend_batch(direction, families, p, profile=profile, align=align, copies=copies)

@@ -1,5 +1,6 @@
-/* ramx_select_planes and ramx_link_pairs (csrc/ramx_linkage.c, compiled into this program) at the corners of their layouts:
- * rows = 0, columns without cover, max_variants = 1, cap = 0, and 2048 planes.  CPU only. */
+/* ramx_select_planes, ramx_link_pairs and ramx_link_components (csrc/ramx_linkage.c, compiled into this program) at the corners
+ * of their layouts: rows = 0, columns without cover, max_variants = 1, cap = 0, and 2048 planes; no plane, no link, every link of
+ * the 2048-plane list, K = 1 and 8.  CPU only. */
 #include <assert.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -60,6 +61,33 @@ int main(void)
   assert(ramx_link_pairs(pl, P2, co, 3.0, ln, linked) == linked);
   for (int i = 0; i < linked; i++) assert(ln[i].n == 300 && ln[i].n_pq == 30 && ln[i].mlog10p >= 3.0 && ln[i].p < ln[i].q);
   assert(ramx_link_pairs(pl, 0, co, 0.0, ln, linked) == 0 && ramx_link_pairs(NULL, 5, co, 0.0, ln, linked) == 0);
+  /* the components of those links: 1024 variants, init sized for exactly V * K' bytes */
+  {
+    int32_t *comp = (int32_t *)malloc(sizeof(int32_t) * 1024);
+    for (int K = 1; K <= RAMX_SUBFAM_MAX; K += 7)
+    {
+      const int32_t Kp = ramx_link_components(pl, P2, ln, linked, K, NULL, comp);
+      assert(Kp >= 1 && Kp <= K);
+      uint8_t *init = (uint8_t *)malloc((size_t)1024 * (size_t)Kp);
+      assert(ramx_link_components(pl, P2, ln, linked, K, init, comp) == Kp);
+      for (int v = 0; v < 1024; v++)
+      {
+        assert(comp[v] >= 0 && comp[v] < Kp && init[(size_t)v * Kp] == 0);
+        for (int k = 1; k < Kp; k++) assert(init[(size_t)v * Kp + k] == (comp[v] == k));
+      }
+      free(init);
+    }
+    uint8_t b1[1];
+    assert(ramx_link_components(pl, P2, NULL, 0, 4, NULL, comp) == 1 && comp[1023] == 0);
+    assert(ramx_link_components(NULL, 0, NULL, 0, 4, b1, NULL) == 1);
+    assert(ramx_link_components(pl, P2, ln, linked, 0, NULL, NULL) == 0 && ramx_link_components(pl, P2, ln, linked, 9, NULL, NULL) == 0);
+    ramx_link bad = ln[0];
+    bad.q = 1;                                                               /* a cover plane is no variant */
+    assert(ramx_link_components(pl, P2, &bad, 1, 4, NULL, comp) == 0);
+    bad.q = P2;
+    assert(ramx_link_components(pl, P2, &bad, 1, 4, NULL, comp) == 0);
+    free(comp);
+  }
   /* a list without cover planes tests nothing; empty tables score 0 */
   for (int i = 0; i < 8; i++) { pl[i].row = i; pl[i].cls = 5; }
   assert(ramx_link_pairs(pl, 8, co, 0.0, ln, linked) == 0);

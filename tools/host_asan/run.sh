@@ -14,7 +14,7 @@ lib="-L$root/repeatafterme_amd -lramx -Wl,-rpath,$root/repeatafterme_amd -Wl,-rp
 san="-fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g"
 gcc -std=gnu11 -O1 -Wno-alloc-size-larger-than $san $inc -o "$out/pad_to_tiles" "$here/pad_to_tiles_main.c" $lib -lm -lpthread
 "$out/pad_to_tiles"
-# the selection and the pair statistic of the linkage (ramx_linkage.c is compiled into the program, under the sanitizers too)
+# the selection, the pair statistic and the components of the linkage (ramx_linkage.c is compiled into the program, under the sanitizers too)
 gcc -std=gnu11 -O1 $san $inc -o "$out/linkage" "$here/linkage_main.c" -lm
 "$out/linkage"
 # (the device side of ramx_device.hip is compiled too, which takes a minute or two: the host object refers to its code object)
