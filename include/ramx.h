@@ -659,6 +659,67 @@ typedef void (*ramx_subfam_cb)(const ramx_subfamilies *sf, void *user);
 void ramx_set_subfam_sink(ramx_subfam_cb cb, void *user, int32_t min_count, int32_t min_permille, int32_t max_variants,
                           double min_mlog10p, int32_t K, int32_t max_iter, int32_t min_members, int32_t max_replays);
 
+/* Target-site duplications of the extended copies: the short direct repeat an insertion leaves immediately outside both termini
+ * of the element.  Everything above looks at one direction of an extension; this looks at an extended copy as a whole element
+ * with two ends, after both directions.  Exact integer arithmetic, every copy on its own.
+ *   Site: the element occupies library positions lo..hi inclusive on the forward strand of the library; an empty element has
+ *   lo == hi + 1.  seq_lo <= lo, lo <= hi + 1, hi <= seq_hi, else RAMX_ERR_ARG.
+ *   Class of position p: library codes 0..3 are classes 0..3, codes 4..7 are code - 4, everything else is class 4: any other
+ *   code, a position outside [seq_lo, seq_hi], a position outside the library.  Two positions AGREE iff both classes are below 4
+ *   and equal.
+ *   Candidate (dl, dr, k), |dl|, |dr| <= slack, kmin <= k <= kmax: the left word is positions lo + dl - k + j, the right word
+ *   positions hi + 1 + dr + j, j = 0..k-1; mm is the number of j that do not agree.  With m(k) = mm_div ? k / mm_div : 0 the
+ *   candidate is admissible iff (i) lo + dl <= hi + 1 + dr, (ii) j = 0 and j = k - 1 agree, (iii) mm <= m(k).  Its quality is
+ *   q = 2 (k - 2 mm) - |dl| - |dr|.
+ *   Best candidate: the largest q; ties to the smallest |dl| + |dr|, then the largest k, then the smallest dl, then the smallest
+ *   dr -- a total order, so the record is unique.  All zeros when no candidate is admissible.
+ * Parameters: slack 0..7, kmin 1..32, kmax kmin..32, mm_div 0 or >= 4; anything else is RAMX_ERR_ARG, raised before anything is
+ * launched or written.  Defaults: 3, 4, 20, 10. */
+typedef struct ramx_tsd_params { int32_t slack, kmin, kmax, mm_div; } ramx_tsd_params;
+typedef struct ramx_tsd_site { int64_t lo, hi, seq_lo, seq_hi; } ramx_tsd_site;       /* 32 bytes */
+typedef struct ramx_tsd { int32_t k, mm, dl, dr; } ramx_tsd;                          /* 16 bytes */
+
+/* The records on the device, from the library it holds (ramx_dev_load_library*, either form): the two outside windows of every
+ * site are packed as flanks by the pack kernels of the extension loop, then one lane per site scores every candidate in
+ * registers and writes its record.  Self-contained like the replays (a following ramx_dev_run_direction needs a new
+ * ramx_dev_begin_direction; resident bit planes are dropped); rank-local under a communicator, which is all there is to it: the
+ * records are per site.  n_sites == 0 returns RAMX_OK and launches nothing.  kernel_ms (may be NULL): two values, the HIP-event
+ * times of the pack of the 2 * n_sites windows and of the TSD kernel. */
+int ramx_dev_tsd(ramx_dev *d, const ramx_tsd_site *sites, int32_t n_sites, const ramx_tsd_params *params, ramx_tsd *out,
+                 double *kernel_ms);
+
+/* One site per core, in list order, from cores that both directions have extended (plain host C): orient == 0: lo = left_pos -
+ * left_len, hi = right_pos + right_len; otherwise lo = right_pos - right_len, hi = left_pos + left_len -- the extents the
+ * reference prints (ram_extend.c:721-727); seq_lo / seq_hi are the core's lower / upper, the bounds the loop never reads past.
+ * out holds cores->n sites; returns their number. */
+int32_t ramx_tsd_sites(const ramx_flat_cores *cores, ramx_tsd_site *out);
+
+/* What a family's records say together (plain host C): hist[k] counts the records by k, 0..32; mode is the k >= 1 with the
+ * largest count, ties to the larger k, 0 if there is none, and mode_count that count; null[k] = n * min(1, (2 slack + 1)^2 *
+ * sum_{j <= m(k)} C(k, j) 3^j / 4^k), the number of copies expected to show a word of that length by chance (null[0] = 0).
+ * RAMX_ERR_ARG for bad parameters, n < 0 or a record with k outside 0..32. */
+typedef struct ramx_tsd_hist { int32_t hist[33]; int32_t mode, mode_count, pad_; double null[33]; } ramx_tsd_hist;
+int ramx_tsd_summary(const ramx_tsd *records, int32_t n, const ramx_tsd_params *params, ramx_tsd_hist *out);
+
+/* The termini of the extended consensus (plain host C).  cons_left / cons_right are the kept columns of the two directions as
+ * the loop hands them over (codes 0..3), ret_left / ret_right their numbers; the left rows run outward from the core.  five
+ * receives the first min(T, ret_left) bases of the extended consensus in reading order, three the last min(T, ret_right), both
+ * as upper-case characters with a terminating 0 (room for T + 1 each).  tir_len: the number of leading j < min(ret_left,
+ * ret_right, 32) with cons_left[ret_left - 1 - j] == 3 - cons_right[ret_right - 1 - j], stopping at the first failure -- the
+ * length of a terminal inverted repeat.  RAMX_ERR_ARG for T < 0, a negative length or a missing pointer. */
+int ramx_termini(const int8_t *cons_left, int32_t ret_left, const int8_t *cons_right, int32_t ret_right, int32_t T,
+                 char *five, char *three, int32_t *tir_len);
+
+/* Seam 1, called after both extension calls: ramx_tsd_sites of the cores and ramx_dev_tsd on the session's device.  out holds
+ * one record per core in list order.  The library the device holds is used when the cache key of seam 1 matches (the same
+ * buffer the two directions ran on; the packed twin of seqLib; for the batch the concatenated library ramx_extend_batch leaves
+ * there, with the families' offsets), otherwise it is uploaded -- and is then the resident one for the calls that follow.
+ * ramx_tsd_alignment walks the whole core list; ramx_tsd_batch writes family f's records behind those of the families before it
+ * (sum of their cores.n).  Return RAMX_OK or a negative error code. */
+int ramx_tsd_flat(const ramx_flat_cores *cores, const int8_t *sequence, uint64_t seq_len, const ramx_tsd_params *params, ramx_tsd *out);
+int ramx_tsd_alignment(struct coreAlignment *coreAlign, struct sequenceLibrary *seqLib, const ramx_tsd_params *params, ramx_tsd *out);
+int ramx_tsd_batch(const ramx_family *families, int32_t n_families, const ramx_tsd_params *params, ramx_tsd *out);
+
 /* multi-GPU: flanks are sharded over ranks; each column's 4 candidate sums are all-reduced
  * (4 x int64, RCCL over xGMI).  unique_id is the 128-byte ncclUniqueId made by rank 0
  * (ramx_comm_unique_id) and handed to the other ranks by the launcher (e.g. torch.distributed). */

@@ -25,6 +25,7 @@ EXPORTS = [
     "ramx_dev_copy_stats", "ramx_copy_kimura", "ramx_family_divergence", "ramx_set_copies_sink",
     "ramx_dev_planes", "ramx_dev_plane_gram", "ramx_dev_plane_gram_ms", "ramx_select_planes", "ramx_link_pairs", "ramx_set_linkage_sink",
     "ramx_link_components", "ramx_dev_subfamilies", "ramx_dev_subfam_masks", "ramx_dev_subfam_ms", "ramx_set_subfam_sink",
+    "ramx_dev_tsd", "ramx_tsd_sites", "ramx_tsd_summary", "ramx_termini", "ramx_tsd_flat", "ramx_tsd_alignment", "ramx_tsd_batch",
 ]
 
 
@@ -131,6 +132,14 @@ class SubfamRec(C.Structure):       # ramx_subfamilies
 SUBFAM_CB = C.CFUNCTYPE(None, C.POINTER(SubfamRec), C.c_void_p)
 
 
+class TsdParams(C.Structure):       # ramx_tsd_params
+    _fields_ = [(k, C.c_int32) for k in ("slack", "kmin", "kmax", "mm_div")]
+
+
+class TsdHist(C.Structure):         # ramx_tsd_hist
+    _fields_ = [("hist", C.c_int32 * 33), ("mode", C.c_int32), ("mode_count", C.c_int32), ("pad_", C.c_int32), ("null", C.c_double * 33)]
+
+
 def build(force: bool = False) -> None:
     """Compile libramx.so + RAMExtend in-tree (hipcc --offload-arch=gfx950, gcc)."""
     if force or not os.path.exists(LIB_PATH) or not os.path.exists(CLI_PATH):
@@ -235,6 +244,20 @@ def lib() -> C.CDLL:
         L.ramx_dev_subfam_masks.restype = C.c_int
         L.ramx_dev_subfam_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.ramx_dev_subfam_ms.restype = None
+        L.ramx_dev_tsd.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(TsdParams), C.c_void_p, C.POINTER(C.c_double)]
+        L.ramx_dev_tsd.restype = C.c_int
+        L.ramx_tsd_sites.argtypes = [C.POINTER(FlatCores), C.c_void_p]
+        L.ramx_tsd_sites.restype = C.c_int32
+        L.ramx_tsd_summary.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TsdParams), C.POINTER(TsdHist)]
+        L.ramx_tsd_summary.restype = C.c_int
+        L.ramx_termini.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_char_p, C.c_char_p, C.POINTER(C.c_int32)]
+        L.ramx_termini.restype = C.c_int
+        L.ramx_tsd_flat.argtypes = [C.POINTER(FlatCores), C.c_void_p, C.c_uint64, C.POINTER(TsdParams), C.c_void_p]
+        L.ramx_tsd_flat.restype = C.c_int
+        L.ramx_tsd_alignment.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TsdParams), C.c_void_p]
+        L.ramx_tsd_alignment.restype = C.c_int
+        L.ramx_tsd_batch.argtypes = [C.POINTER(Family), C.c_int32, C.POINTER(TsdParams), C.c_void_p]
+        L.ramx_tsd_batch.restype = C.c_int
         if hasattr(L, "ramx_cli_main"):
             L.ramx_cli_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
         _lib = L

@@ -103,6 +103,12 @@ static void usage(void)
     "     -subfamk <num>        # ... at most this many groups, 1..8 (4),\n"
     "     -subfammin <num>      # ... a group gets a consensus of its own from this many copies (4),\n"
     "     -subfamiter <num>     # ... at most this many assignments (8).\n"
+    "     -outtsd <file>        # Save the target-site duplication of every extended copy ( the direct repeat\n"
+    "                           #   just outside its two ends ) and the family's modal length to a TSV file.\n"
+    "     -tsdslack <num>       # ... either end may lie this many bases off the reported one, 0..7 (3),\n"
+    "     -tsdmin <num>         # ... shortest and\n"
+    "     -tsdmax <num>         # ... longest duplication looked for, 1..32 (4, 20),\n"
+    "     -tsdmm <num>          # ... one mismatch allowed per this many bases, 0 = none (10).\n"
     "     -version              # Print out one-line version information\n"
     "     -v[v[v[v]]]           # How verbose do you want it to be?  -vvvv is super-verbose.\n"
     "\n"
@@ -254,7 +260,8 @@ static void warm_start(void)
 /* everything the command line decides */
 struct cli_opts
 {
-  const char *ranges_file, *outtsv, *outfa, *outmat, *cons_file, *seq_file, *matrix_name, *batch_file, *outprofile, *outaln, *outpileup, *outrefined, *outcopies, *outlinkage, *outsubfam;
+  const char *ranges_file, *outtsv, *outfa, *outmat, *cons_file, *seq_file, *matrix_name, *batch_file, *outprofile, *outaln, *outpileup, *outrefined, *outcopies, *outlinkage, *outsubfam, *outtsd;
+  ramx_tsd_params tsd;
   int refine, linkcount, linkfrac, linkscore, subfamk, subfammin, subfamiter;
   int flanking, L, bandwidth, maxn, when_to_stop, num_threads, verbose;
   int gap_ext, gap_open, match, mismatch, cappenalty, minimprovement, is_rs;
@@ -478,7 +485,7 @@ static void write_results(const struct cli_opts *o, struct coreAlignment *cores,
  */
 struct batch_item
 {
-  char *ranges, *log, *cons, *tsv, *fa, *profile, *aln, *pileup, *refined, *copies, *linkage, *subfam;
+  char *ranges, *log, *cons, *tsv, *fa, *profile, *aln, *pileup, *refined, *copies, *linkage, *subfam, *tsd;
   struct coreAlignment *cores;
   struct sequenceLibrary *lib;
   int N, rightbp, leftbp;
@@ -955,6 +962,73 @@ static void subfam_write(struct subfam_family *f, struct coreAlignment *cores, i
   fclose(fp);
 }
 
+/*
+ * -outtsd <file>: the target-site duplication of every extended copy (include/ramx.h, ramx_tsd) as a TSV.  "#" lines carry the
+ * parameters, the kept columns of both directions, the two termini of the extended consensus with the length of their inverted
+ * repeat, the histogram of the lengths found, and the modal length with its count and the count expected by chance.  Then one
+ * line per core in list order: named and placed as -outtsv places it, the record, and the two words as the library has them on
+ * its forward strand ("N" for a position outside the core's bounds, "-" without a duplication).  Unlike the files above this
+ * one is no sink: it needs both directions, and is computed when they are done.
+ */
+#define TSD_TERMINUS 32
+static const char k_tsd_header[] = "core\tseqid\tstart\tend\tstrand\text_left\text_right\ttsd_len\tmismatches\tshift_left\tshift_right\tleft_word\tright_word\n";
+
+static void tsd_word(char *buf, const struct sequenceLibrary *lib, const struct coreAlignment *s, int64_t from, int k)
+{
+  for (int j = 0; j < k; j++)
+  {
+    const int64_t p = from + j;
+    const int in = p >= 0 && (uint64_t)p < lib->length && p >= (int64_t)s->lowerSeqBound && p <= (int64_t)s->upperSeqBound;
+    buf[j] = in ? code_to_char(ramx_lib_code(lib, (uint64_t)p)) : 'N';
+  }
+  buf[k] = 0;
+}
+
+static void tsd_write(const char *path, const ramx_tsd_params *tp, struct coreAlignment *cores, struct sequenceLibrary *lib, const char *master,
+                      int L, int rightbp, int leftbp, const ramx_tsd *rec, int n)
+{
+  FILE *fp = fopen(path, "w");
+  if (!fp) { fprintf(stderr, "Could not create the target-site duplication file %s\n", path); exit(1); }
+  const int l = 1, nl = leftbp > 0 ? leftbp : 0, nr = rightbp > 0 ? rightbp : 0;
+  int8_t *cl = (int8_t *)malloc((size_t)(nl > 0 ? nl : 1));
+  for (int r = 0; r < nl; r++) cl[r] = (int8_t)master[(size_t)L - r - 1];        /* the left rows run outward from the core */
+  char five[TSD_TERMINUS + 1], three[TSD_TERMINUS + 1];
+  int32_t tir = 0;
+  ramx_tsd_hist h;
+  if (ramx_termini(cl, nl, (const int8_t *)master + L + l, nr, TSD_TERMINUS, five, three, &tir) != RAMX_OK || ramx_tsd_summary(rec, n, tp, &h) != RAMX_OK)
+  { fprintf(stderr, "RAMExtend(ramx): target-site duplications: %s\n", ramx_last_error()); exit(1); }
+  free(cl);
+  fprintf(fp, "#tsd\tslack=%d\tkmin=%d\tkmax=%d\tmm_div=%d\n", tp->slack, tp->kmin, tp->kmax, tp->mm_div);
+  fprintf(fp, "#rows\tleft_rows=%d\tright_rows=%d\n", nl, nr);
+  fprintf(fp, "#termini\tfive=%s\tthree=%s\ttir=%d\n", five[0] ? five : "-", three[0] ? three : "-", (int)tir);
+  fprintf(fp, "#hist");
+  for (int k = 0; k <= 32; k++) if (h.hist[k] > 0) fprintf(fp, "\t%d:%d", k, h.hist[k]);
+  fprintf(fp, "\n#mode\tmode=%d\tmode_count=%d\tnull=%.4f\n", h.mode, h.mode_count, h.null[h.mode]);
+  fputs(k_tsd_header, fp);
+  int x = 0;
+  for (struct coreAlignment *s = cores; s != NULL && x < n; s = s->next, x++)
+  {
+    const int si = s->seqIdx;
+    const uint64_t lo = si > 0 ? lib->boundaries[si - 1] : 0;
+    const uint64_t off = (lib->offsets != NULL && lib->offsets[si] > 0) ? lib->offsets[si] : 0;
+    /* the copy's ends in the library, and as -outtsv prints them */
+    const int64_t e_lo = s->orient ? (int64_t)s->rightSeqPos - s->rightExtensionLen : (int64_t)s->leftSeqPos - s->leftExtensionLen;
+    const int64_t e_hi = s->orient ? (int64_t)s->leftSeqPos + s->leftExtensionLen : (int64_t)s->rightSeqPos + s->rightExtensionLen;
+    char lbuf[32], rbuf[32], lw[33] = "-", rw[33] = "-";
+    if (s->leftExtendable) snprintf(lbuf, sizeof(lbuf), "%d", s->leftExtensionLen); else strcpy(lbuf, "*");
+    if (s->rightExtendable) snprintf(rbuf, sizeof(rbuf), "%d", s->rightExtensionLen); else strcpy(rbuf, "*");
+    const ramx_tsd *t = &rec[x];
+    if (t->k > 0)
+    {
+      tsd_word(lw, lib, s, e_lo + t->dl - t->k, t->k);
+      tsd_word(rw, lib, s, e_hi + 1 + t->dr, t->k);
+    }
+    fprintf(fp, "%d\t%s\t%ld\t%ld\t%c\t%s\t%s\t%d\t%d\t%d\t%d\t%s\t%s\n", x, lib->identifiers[si], (long)((int64_t)off + e_lo - (int64_t)lo + 1),
+            (long)((int64_t)off + e_hi - (int64_t)lo + 1), s->orient ? '-' : '+', lbuf, rbuf, t->k, t->mm, t->dl, t->dr, lw, rw);
+  }
+  fclose(fp);
+}
+
 /* flat view of a core list for ramx_extend_batch (arrays owned by the caller's arena) */
 static void flatten_cores(struct coreAlignment *cores, int N, ramx_flat_cores *fc)
 {
@@ -1013,6 +1087,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   if (o->outcopies != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's copies file is the tenth field of its line in the list\n"); exit(1); }
   if (o->outlinkage != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's linkage file is the eleventh field of its line in the list\n"); exit(1); }
   if (o->outsubfam != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's subfamily file is the twelfth field of its line in the list\n"); exit(1); }
+  if (o->outtsd != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's target-site duplication file is the thirteenth field of its line in the list\n"); exit(1); }
   FILE *lf = fopen(o->batch_file, "r");
   if (!lf) { fprintf(stderr, "Could not open batch list %s\n", o->batch_file); exit(1); }
   size_t cap = 64, F = 0;
@@ -1024,9 +1099,9 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   {
     while (len > 0 && (line[len - 1] == '\n' || line[len - 1] == '\r')) line[--len] = 0;
     if (line[0] == '#' || line[0] == 0) continue;
-    char *f[12] = { NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL };
+    char *f[13] = { NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL };
     char *p = line;
-    for (int k = 0; k < 12 && p; k++) { f[k] = p; char *t = strchr(p, '\t'); if (t) { *t = 0; p = t + 1; } else p = NULL; }
+    for (int k = 0; k < 13 && p; k++) { f[k] = p; char *t = strchr(p, '\t'); if (t) { *t = 0; p = t + 1; } else p = NULL; }
     if (!f[0] || !f[1]) { fprintf(stderr, "batch list: every line needs at least <ranges><TAB><log>\n"); exit(1); }
     if (F == cap) { cap *= 2; it = (struct batch_item *)realloc(it, cap * sizeof(*it)); memset(it + F, 0, (cap - F) * sizeof(*it)); }
     it[F].ranges = strdup(f[0]); it[F].log = strdup(f[1]);
@@ -1040,6 +1115,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
     it[F].copies = field_or_null(f[9]) ? strdup(f[9]) : NULL;        /* optional tenth field: the family's -outcopies file */
     it[F].linkage = field_or_null(f[10]) ? strdup(f[10]) : NULL;     /* optional eleventh field: the family's -outlinkage file */
     it[F].subfam = field_or_null(f[11]) ? strdup(f[11]) : NULL;      /* optional twelfth field: the family's -outsubfam file */
+    it[F].tsd = field_or_null(f[12]) ? strdup(f[12]) : NULL;         /* optional thirteenth field: the family's -outtsd file */
     F++;
   }
   free(line);
@@ -1151,12 +1227,31 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   fflush(stdout);
   dup2(saved, 1);
   close(saved);
+  /* phase 6, only where a family asks for it: the target-site duplications of all families in one launch, on the library the two
+   * launches left on the device */
+  int any_tsd = 0;
+  for (size_t i = 0; i < F; i++) any_tsd |= it[i].tsd != NULL;
+  if (any_tsd)
+  {
+    size_t total = 0;
+    for (size_t i = 0; i < F; i++) { flatten_cores(it[i].cores, it[i].N, &fam[i].cores); total += (size_t)it[i].N; }
+    ramx_tsd *rec = (ramx_tsd *)calloc(total ? total : 1, sizeof(ramx_tsd));
+    if (ramx_tsd_batch(fam, (int32_t)F, &o->tsd, rec) < 0) { fprintf(stderr, "RAMExtend(ramx): target-site duplications failed: %s\n", ramx_last_error()); exit(1); }
+    size_t at = 0;
+    for (size_t i = 0; i < F; i++)
+    {
+      if (it[i].tsd != NULL) tsd_write(it[i].tsd, &o->tsd, it[i].cores, it[i].lib, it[i].master, L, it[i].rightbp, it[i].leftbp, rec + at, it[i].N);
+      at += (size_t)it[i].N;
+      free_flat(&fam[i].cores);
+    }
+    free(rec);
+  }
   printf("RAMExtend(ramx) batch: %zu families done\n", F);
   for (size_t i = 0; i < F; i++)
   {
     ramx_free_library(it[i].lib, it[i].cores);
     free(it[i].master); free(it[i].ranges); free(it[i].log); free(it[i].cons); free(it[i].tsv); free(it[i].fa); free(it[i].profile); free(it[i].aln);
-    free(it[i].pileup); free(it[i].refined); free(it[i].copies); free(it[i].linkage); free(it[i].subfam);
+    free(it[i].pileup); free(it[i].refined); free(it[i].copies); free(it[i].linkage); free(it[i].subfam); free(it[i].tsd);
   }
   ramx_set_profile_sink(NULL, NULL);
   ramx_set_align_sink(NULL, NULL);
@@ -1207,6 +1302,12 @@ int ramx_cli_main(int argc, char **argv)
   if (!opt_int(argc, argv, "-subfamiter", &o.subfamiter)) o.subfamiter = 8;
   if (o.subfamk < 1 || o.subfamk > RAMX_SUBFAM_MAX || o.subfamiter < 1)
   { fprintf(stderr, "RAMExtend(ramx): -subfamk takes 1..%d groups, -subfamiter at least 1 assignment\n", RAMX_SUBFAM_MAX); exit(1); }
+  opt_string(argc, argv, "-outtsd", &o.outtsd);
+  if (!opt_int(argc, argv, "-tsdslack", &o.tsd.slack)) o.tsd.slack = 3;
+  if (!opt_int(argc, argv, "-tsdmin", &o.tsd.kmin)) o.tsd.kmin = 4;
+  if (!opt_int(argc, argv, "-tsdmax", &o.tsd.kmax)) o.tsd.kmax = 20;
+  if (!opt_int(argc, argv, "-tsdmm", &o.tsd.mm_div)) o.tsd.mm_div = 10;
+  if (ramx_tsd_check_params(&o.tsd) != RAMX_OK) { fprintf(stderr, "RAMExtend(ramx): %s\n", ramx_last_error()); exit(1); }
   if (!opt_int(argc, argv, "-refine", &o.refine)) o.refine = 10;
   if (o.refine < 1) { fprintf(stderr, "RAMExtend(ramx): -refine takes the largest number of replays, at least 1\n"); exit(1); }
   if (!opt_int(argc, argv, "-L", &o.L)) o.L = 10000;
@@ -1346,6 +1447,16 @@ int ramx_cli_main(int argc, char **argv)
   copies_write(&cfam, cores, o.flanking);
   linkage_write(&lfam, o.linkscore);
   subfam_write(&sfam, cores, o.flanking);
+  if (o.outtsd != NULL)
+  {
+    /* after both directions, on the library they left on the device */
+    int cnt = 0;
+    for (struct coreAlignment *s = cores; s != NULL; s = s->next) cnt++;
+    ramx_tsd *rec = (ramx_tsd *)calloc((size_t)(cnt ? cnt : 1), sizeof(ramx_tsd));
+    if (ramx_tsd_alignment(cores, lib, &o.tsd, rec) != RAMX_OK) { fprintf(stderr, "RAMExtend(ramx): target-site duplications failed: %s\n", ramx_last_error()); exit(1); }
+    tsd_write(o.outtsd, &o.tsd, cores, lib, master, L, rightbp, leftbp, rec, cnt);
+    free(rec);
+  }
   if (fp_mat != NULL) fclose(fp_mat);     /* ram_extend.c:778-779 */
   phase_done("report + outputs");
 

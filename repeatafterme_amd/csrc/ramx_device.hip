@@ -56,6 +56,7 @@
 #include "ramx_copystats_api.h"
 #include "ramx_linkage_api.h"
 #include "ramx_subfam_api.h"
+#include "ramx_tsd_api.h"
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
@@ -183,6 +184,8 @@ struct ramx_dev
   int *lk_place, lk_npadded;
   long long *sf_lay; int sf_families, sf_K;       // the last result's mask planes: (first word, tiles) per family
   double sf_ms[2];          // HIP-event times of the assign and the count kernels of the last ramx_dev_subfamilies, summed
+  // ramx_dev_tsd (allocated on its first call): per site the room between the two words, and its record
+  int *d_tsd_room; ramx_tsd *d_tsd_out; size_t cap_tsd_room, cap_tsd_out;
 };
 
 extern "C" int ramx_device_count(void)
@@ -277,6 +280,7 @@ extern "C" void ramx_dev_destroy(ramx_dev *d)
   (void)hipFree(d->d_sf_tile); (void)hipFree(d->d_sf_item); (void)hipFree(d->d_sf_count); (void)hipFree(d->d_sf_labels);
   (void)hipFree(d->d_sf_changed); (void)hipFree(d->d_sf_cnt); (void)hipFree(d->d_sf_mask);
   free(d->lk_place); free(d->sf_lay);
+  (void)hipFree(d->d_tsd_room); (void)hipFree(d->d_tsd_out);
   if (d->hostbox_mirror) (void)hipFree(d->hostbox_mirror);
   if (d->d_peer) (void)hipFree(d->d_peer);
   for (int i = 0; i < 2; i++) if (d->ev_chk[i]) (void)hipEventDestroy(d->ev_chk[i]);
@@ -2098,6 +2102,79 @@ extern "C" int ramx_dev_copy_stats(ramx_dev *d, const ramx_flank *flanks, int32_
     }
     HIPCHK(hipMemcpy(stats + (size_t)t0 * 64, d->d_cs_stats + (size_t)t0 * 64, (size_t)nt * 64 * sizeof(ramx_copy_stats), hipMemcpyDeviceToHost));
     if (ends) HIPCHK(hipMemcpy(ends + (size_t)t0 * 64, d->d_al_ends + (size_t)t0 * 64, (size_t)nt * 64 * sizeof(ramx_aln_end), hipMemcpyDeviceToHost));
+  }
+  return RAMX_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// target-site duplications: the two outside windows of every site packed as flanks, then one lane per site (ramx_kernels_tsd.h)
+// ------------------------------------------------------------------------------------------
+extern "C" int ramx_dev_tsd(ramx_dev *d, const ramx_tsd_site *sites, int32_t n_sites, const ramx_tsd_params *params, ramx_tsd *out,
+                            double *kernel_ms)
+{
+  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0;
+  if (!d || n_sites < 0 || (n_sites && (!sites || !out))) { ramx_set_error("ramx_dev_tsd: bad argument"); return RAMX_ERR_ARG; }
+  int rc;
+  if ((rc = ramx_tsd_check_params(params)) != RAMX_OK) return rc;
+  for (int i = 0; i < n_sites; i++)
+    if (sites[i].seq_lo < -RAMX_TSD_POS_MAX || sites[i].seq_hi > RAMX_TSD_POS_MAX ||       // (so that no difference below overflows)
+        sites[i].seq_lo > sites[i].lo || sites[i].lo > sites[i].hi + 1 || sites[i].hi > sites[i].seq_hi)
+    { ramx_set_error("ramx_dev_tsd: site %d: lo %lld hi %lld outside its bounds %lld..%lld, or lo > hi + 1", i, (long long)sites[i].lo,
+                     (long long)sites[i].hi, (long long)sites[i].seq_lo, (long long)sites[i].seq_hi); return RAMX_ERR_ARG; }
+  if (n_sites == 0) return RAMX_OK;
+  if (n_sites > (1 << 29)) { ramx_set_error("ramx_dev_tsd: more than 2^29 sites in one call"); return RAMX_ERR_UNSUPPORTED; }
+  HIPCHK(hipSetDevice(d->ordinal));
+  // the windows: the left one runs down from lo - 1, the right one up from hi + 1, t = -slack .. kmax + slack - 1 cut by the
+  // site's bounds; the left windows of all (padded) sites first, then the right ones
+  const int n = n_sites, Np = (n + 63) & ~63, S = params->slack, t_last = params->kmax + S - 1;
+  std::vector<ramx_flank> fl((size_t)2 * Np);
+  std::vector<int> room((size_t)Np, 0);
+  auto cut = [&](ramx_flank &f, long long lo_t, long long hi_t) {
+    const long long a = lo_t > -S ? lo_t : -S, b = hi_t < t_last ? hi_t : t_last;
+    if (a > b) { f.t_lo = 1; f.t_hi = 0; } else { f.t_lo = (int32_t)a; f.t_hi = (int32_t)b; }
+  };
+  for (int i = 0; i < Np; i++)
+  {
+    ramx_flank &l = fl[(size_t)i], &r = fl[(size_t)Np + i];
+    memset(&l, 0, sizeof(l)); memset(&r, 0, sizeof(r));
+    l.step = -1; r.step = 1; l.t_lo = r.t_lo = 1;             // (padding: no base)
+    if (i >= n) continue;
+    const ramx_tsd_site &s = sites[i];
+    l.start = s.lo - 1; r.start = s.hi + 1;
+    cut(l, s.lo - 1 - s.seq_hi, s.lo - 1 - s.seq_lo);         // position lo - 1 - t inside seq_lo..seq_hi
+    cut(r, s.seq_lo - s.hi - 1, s.seq_hi - s.hi - 1);         // position hi + 1 + t
+    room[(size_t)i] = s.hi + 1 - s.lo < 64 ? (int)(s.hi + 1 - s.lo) : 64;
+  }
+  // the flank and window buffers of the direction are reused, as by the replays
+  if (d->pack_busy) { HIPCHK(hipEventSynchronize(d->pack_done)); d->pack_busy = 0; }
+  if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)2 * Np * sizeof(ramx_flank)))) return rc;
+  if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)RAMX_TSD_KW * 2 * Np * sizeof(unsigned)))) return rc;
+  if ((rc = ensure(&d->d_bounds, &d->cap_bounds, (size_t)2 * Np * sizeof(int2)))) return rc;
+  if ((rc = ensure(&d->d_tsd_room, &d->cap_tsd_room, (size_t)Np * sizeof(int)))) return rc;
+  if ((rc = ensure(&d->d_tsd_out, &d->cap_tsd_out, (size_t)Np * sizeof(ramx_tsd)))) return rc;
+  d->ready = 0;
+  d->planes_ready = 0;
+  hipEvent_t ev[3] = { NULL, NULL, NULL };
+  if (kernel_ms) for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+  HIPCHK(hipMemcpyAsync(d->d_flanks, fl.data(), fl.size() * sizeof(ramx_flank), hipMemcpyHostToDevice, d->stream));
+  HIPCHK(hipMemcpyAsync(d->d_tsd_room, room.data(), room.size() * sizeof(int), hipMemcpyHostToDevice, d->stream));
+  if (kernel_ms) HIPCHK(hipEventRecord(ev[0], d->stream));
+  if ((rc = launch_pack(d, 2 * Np, 2 * Np, RAMX_TSD_W, 0, RAMX_TSD_KW, d->stream)) != RAMX_OK) return rc;
+  d->packed_kw = RAMX_TSD_KW;
+  if (kernel_ms) HIPCHK(hipEventRecord(ev[1], d->stream));
+  TsdArgs ta;
+  ta.bases = d->d_bases; ta.room = d->d_tsd_room; ta.out = d->d_tsd_out; ta.n = n; ta.Np = Np;
+  ta.slack = S; ta.kmin = params->kmin; ta.kmax = params->kmax; ta.mm_div = params->mm_div;
+  if ((rc = ramx_tsd_launch(d->stream, ta)) != RAMX_OK) { ramx_set_error("ramx_dev_tsd: launch failed (%s)", hipGetErrorString(hipGetLastError())); return rc; }
+  if (kernel_ms) HIPCHK(hipEventRecord(ev[2], d->stream));
+  HIPCHK(hipMemcpyAsync(out, d->d_tsd_out, (size_t)n * sizeof(ramx_tsd), hipMemcpyDeviceToHost, d->stream));
+  HIPCHK(hipStreamSynchronize(d->stream));
+  if (kernel_ms)
+  {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1])); kernel_ms[0] = ms;
+    HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2])); kernel_ms[1] = ms;
+    for (auto &e : ev) (void)hipEventDestroy(e);
   }
   return RAMX_OK;
 }

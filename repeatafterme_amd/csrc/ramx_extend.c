@@ -1261,6 +1261,34 @@ static void batch_lib_range(int lo, int hi, void *user)
   }
 }
 
+/* Does the device hold the concatenation of these families' libraries (family f at at_of[f], total_len bases in all)?  fps
+ * receives every family's fingerprint (0 beyond RAMX_FP_MAX in all: such a batch is always sent again). */
+static int batch_lib_cached(const ramx_family *fam, int F, const uint64_t *at_of, uint64_t total_len, uint64_t *fps)
+{
+  int cached = (g_lib_ptr == (const int8_t *)&g_bl_n) && g_bl_n == F && g_lib_len == total_len && total_len <= RAMX_FP_MAX;
+  struct batch_lib_ctx bc = { fam, fps, at_of, NULL, total_len <= RAMX_FP_MAX };
+  ramx_parallel_for(F, 8, batch_lib_range, &bc);       /* ~10 GB/s per thread: 100 MB of families cost 10 ms on one */
+  for (int f = 0; f < F && cached; f++)
+    if (g_bl_ptr[f] != fam[f].sequence || g_bl_len[f] != fam[f].seq_len || g_bl_fp[f] != fps[f]) cached = 0;
+  return cached;
+}
+
+/* the concatenated library goes to the device and becomes the one the cache key describes */
+static int batch_lib_upload(ramx_dev *d, const ramx_family *fam, int F, const int8_t *lib, uint64_t total_len, const uint64_t *fps)
+{
+  g_lib_ptr = NULL; g_lib_len = 0; g_lib_fp = 0; g_lib_trusted = 0; g_packed_owner = NULL; /* whatever library the device held is replaced */
+  const int rc = ramx_dev_load_library(d, lib, total_len);
+  if (rc != RAMX_OK) return rc;
+  g_bl_ptr = (const int8_t **)realloc((void *)g_bl_ptr, sizeof(*g_bl_ptr) * (size_t)(F ? F : 1));
+  g_bl_len = (uint64_t *)realloc(g_bl_len, sizeof(*g_bl_len) * (size_t)(F ? F : 1));
+  g_bl_fp = (uint64_t *)realloc(g_bl_fp, sizeof(*g_bl_fp) * (size_t)(F ? F : 1));
+  for (int f = 0; f < F; f++) { g_bl_ptr[f] = fam[f].sequence; g_bl_len[f] = fam[f].seq_len; g_bl_fp[f] = fps[f]; }
+  g_bl_n = F;
+  g_lib_ptr = (const int8_t *)&g_bl_n;         /* sentinel: the device holds the batch library described by g_bl_* */
+  g_lib_len = total_len;
+  return RAMX_OK;
+}
+
 /*
  * Batch mode: many families, one launch (include/ramx.h).  Libraries are concatenated into one device buffer,
  * every family's flanks are padded to a multiple of 64 with empty flanks, results are written back per family
@@ -1298,14 +1326,8 @@ int ramx_extend_batch(int direction, ramx_family *fam, int32_t F, const ramx_par
   uint64_t *at_of = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(F ? F : 1));
   total_len = 0;
   for (int f = 0; f < F; f++) { at_of[f] = total_len; total_len += fam[f].seq_len; }
-  int lib_cached = (g_lib_ptr == (const int8_t *)&g_bl_n) && g_bl_n == F && g_lib_len == total_len && total_len <= RAMX_FP_MAX;
   uint64_t *fps = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(F ? F : 1));
-  {
-    struct batch_lib_ctx bc = { fam, fps, at_of, NULL, total_len <= RAMX_FP_MAX };
-    ramx_parallel_for(F, 8, batch_lib_range, &bc);       /* ~10 GB/s per thread: 100 MB of families cost 10 ms on one */
-  }
-  for (int f = 0; f < F && lib_cached; f++)
-    if (g_bl_ptr[f] != fam[f].sequence || g_bl_len[f] != fam[f].seq_len || g_bl_fp[f] != fps[f]) lib_cached = 0;
+  const int lib_cached = batch_lib_cached(fam, F, at_of, total_len, fps);
   BATCH_PHASE("library fingerprints");
   int8_t *lib = lib_cached ? NULL : (int8_t *)malloc(total_len ? total_len : 1);
   ramx_flank *fl = (ramx_flank *)malloc(sizeof(ramx_flank) * (total_pad ? total_pad : 1));
@@ -1341,21 +1363,7 @@ int ramx_extend_batch(int direction, ramx_family *fam, int32_t F, const ramx_par
     int8_t *cons = (int8_t *)malloc((size_t)nb * (size_t)(L > 0 ? L : 1));
     int32_t *th = (int32_t *)malloc(sizeof(int32_t) * (fpos ? fpos : 1));
     int32_t *tp = (int32_t *)malloc(sizeof(int32_t) * (fpos ? fpos : 1));
-    if (!lib_cached)
-    {
-      g_lib_ptr = NULL; g_lib_len = 0; g_lib_fp = 0; g_lib_trusted = 0; g_packed_owner = NULL; /* whatever library the device held is replaced */
-      rc = ramx_dev_load_library(d, lib, total_len);
-      if (rc == RAMX_OK)
-      {
-        g_bl_ptr = (const int8_t **)realloc((void *)g_bl_ptr, sizeof(*g_bl_ptr) * (size_t)(F ? F : 1));
-        g_bl_len = (uint64_t *)realloc(g_bl_len, sizeof(*g_bl_len) * (size_t)(F ? F : 1));
-        g_bl_fp = (uint64_t *)realloc(g_bl_fp, sizeof(*g_bl_fp) * (size_t)(F ? F : 1));
-        for (int f = 0; f < F; f++) { g_bl_ptr[f] = fam[f].sequence; g_bl_len[f] = fam[f].seq_len; g_bl_fp[f] = fps[f]; }
-        g_bl_n = F;
-        g_lib_ptr = (const int8_t *)&g_bl_n;         /* sentinel: the device holds the batch library described by g_bl_* */
-        g_lib_len = total_len;
-      }
-    }
+    if (!lib_cached) rc = batch_lib_upload(d, fam, F, lib, total_len, fps);
     BATCH_PHASE("library upload");
     if (rc == RAMX_OK) rc = ramx_dev_run_families(d, fl, (int32_t)fpos, first, count, nb, p, binfo, cons, th, tp);
     BATCH_PHASE("run families (device)");
@@ -1387,6 +1395,119 @@ int ramx_extend_batch(int direction, ramx_family *fam, int32_t F, const ramx_par
     if (r1 < 0) rc = r1;
   }
   free(lib); free(at_of); free(fl); free(map); free(first); free(count); free(fidx); free(take); free(own); free(fps);
+  return rc;
+}
+
+/* ---- target-site duplications (include/ramx.h): called after both extension calls, on whatever library they left resident ---- */
+
+/* the one-byte library on the device, by seam 1's cache key: the check extend_flat_impl makes, without its helper thread */
+static int library_resident(ramx_dev *d, const int8_t *sequence, uint64_t seq_len)
+{
+  if (g_lib_trusted && sequence == g_lib_ptr && seq_len == g_lib_len) return RAMX_OK;
+  const uint64_t fp = fingerprint_large(sequence, seq_len);
+  if (sequence == g_lib_ptr && seq_len == g_lib_len && fp != 0 && fp == g_lib_fp) return RAMX_OK;
+  ramx_invalidate_library();
+  const int rc = ramx_dev_load_library(d, sequence, seq_len);
+  if (rc != RAMX_OK) return rc;
+  g_lib_ptr = sequence; g_lib_len = seq_len; g_lib_fp = fp;
+  return RAMX_OK;
+}
+
+int ramx_tsd_flat(const ramx_flat_cores *cores, const int8_t *sequence, uint64_t seq_len, const ramx_tsd_params *params, ramx_tsd *out)
+{
+  int rc;
+  if ((rc = ramx_tsd_check_params(params)) != RAMX_OK) return rc;
+  if (!cores || cores->n < 0 || (cores->n > 0 && (!sequence || !out))) { ramx_set_error("ramx_tsd_flat: bad argument"); return RAMX_ERR_ARG; }
+  if (cores->n == 0) return RAMX_OK;
+  ramx_dev *d = ramx_default_device();
+  if (!d) return RAMX_ERR_NO_DEVICE;
+  ramx_tsd_site *sites = (ramx_tsd_site *)malloc(sizeof(ramx_tsd_site) * (size_t)cores->n);
+  ramx_tsd_sites(cores, sites);
+  if ((rc = library_resident(d, sequence, seq_len)) == RAMX_OK) rc = ramx_dev_tsd(d, sites, cores->n, params, out, NULL);
+  free(sites);
+  return rc;
+}
+
+int ramx_tsd_alignment(struct coreAlignment *coreAlign, struct sequenceLibrary *seqLib, const ramx_tsd_params *params, ramx_tsd *out)
+{
+  int rc;
+  if ((rc = ramx_tsd_check_params(params)) != RAMX_OK) return rc;
+  if (!seqLib) { ramx_set_error("ramx_tsd_alignment: bad argument"); return RAMX_ERR_ARG; }
+  int n = 0;
+  for (struct coreAlignment *cc = coreAlign; cc != NULL; cc = cc->next) n++;
+  if (n == 0) return RAMX_OK;
+  if (!out) { ramx_set_error("ramx_tsd_alignment: bad argument"); return RAMX_ERR_ARG; }
+  ramx_dev *d = ramx_default_device();
+  if (!d) return RAMX_ERR_NO_DEVICE;
+  ramx_tsd_site *sites = (ramx_tsd_site *)malloc(sizeof(ramx_tsd_site) * (size_t)n);
+  int k = 0;
+  for (struct coreAlignment *cc = coreAlign; cc != NULL; cc = cc->next, k++)
+  {
+    /* ramx_tsd_sites on the list's own fields */
+    const int64_t lp = (int64_t)cc->leftSeqPos, rp = (int64_t)cc->rightSeqPos;
+    sites[k].lo = cc->orient ? rp - cc->rightExtensionLen : lp - cc->leftExtensionLen;
+    sites[k].hi = cc->orient ? lp + cc->leftExtensionLen : rp + cc->rightExtensionLen;
+    sites[k].seq_lo = (int64_t)cc->lowerSeqBound;
+    sites[k].seq_hi = (int64_t)cc->upperSeqBound;
+  }
+  if (seqLib->sequence == NULL)
+  {
+    /* loaded packed: the twin goes to the device unless it is the library there already */
+    const ramx_packed_library *packed = ramx_packed_of(seqLib);
+    if (!packed) { ramx_set_error("ramx_tsd_alignment: the sequence library holds no bases (sequence == NULL and no packed twin)"); rc = RAMX_ERR_ARG; }
+    else if (g_packed_owner != seqLib) rc = ramx_preload_library_packed(seqLib, packed);
+  }
+  else
+    rc = library_resident(d, (const int8_t *)seqLib->sequence, seqLib->length);
+  if (rc == RAMX_OK) rc = ramx_dev_tsd(d, sites, n, params, out, NULL);
+  free(sites);
+  return rc;
+}
+
+int ramx_tsd_batch(const ramx_family *fam, int32_t F, const ramx_tsd_params *params, ramx_tsd *out)
+{
+  int rc;
+  if ((rc = ramx_tsd_check_params(params)) != RAMX_OK) return rc;
+  if (F < 0 || (F && !fam)) { ramx_set_error("ramx_tsd_batch: bad argument"); return RAMX_ERR_ARG; }
+  int64_t total = 0;
+  for (int f = 0; f < F; f++)
+  {
+    if (fam[f].cores.n < 0 || (fam[f].cores.n > 0 && !fam[f].sequence)) { ramx_set_error("ramx_tsd_batch: bad family %d", f); return RAMX_ERR_ARG; }
+    total += fam[f].cores.n;
+  }
+  if (total == 0) return RAMX_OK;
+  if (!out || total > 0x7fffffff) { ramx_set_error("ramx_tsd_batch: bad argument"); return RAMX_ERR_ARG; }
+  ramx_dev *d = ramx_default_device();
+  if (!d) return RAMX_ERR_NO_DEVICE;
+  /* every family at the offset ramx_extend_batch gives it in the concatenated library */
+  uint64_t *at_of = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)F), *fps = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)F);
+  uint64_t total_len = 0;
+  for (int f = 0; f < F; f++) { at_of[f] = total_len; total_len += fam[f].seq_len; }
+  if (!batch_lib_cached(fam, F, at_of, total_len, fps))
+  {
+    int8_t *lib = (int8_t *)malloc(total_len ? total_len : 1);
+    struct batch_lib_ctx bc = { fam, NULL, at_of, lib, 0 };
+    ramx_parallel_for(F, 8, batch_lib_range, &bc);
+    rc = batch_lib_upload(d, fam, F, lib, total_len, fps);
+    free(lib);
+  }
+  ramx_tsd_site *sites = (ramx_tsd_site *)malloc(sizeof(ramx_tsd_site) * (size_t)total);
+  int64_t at = 0;
+  for (int f = 0; f < F; f++)
+  {
+    ramx_tsd_sites(&fam[f].cores, sites + at);
+    for (int i = 0; i < fam[f].cores.n; i++)
+    {
+      ramx_tsd_site *s = &sites[at + i];
+      /* outside the family's own library is outside the library: its neighbours in the concatenation are never read */
+      if (s->seq_lo < 0) s->seq_lo = 0;
+      if (s->seq_hi > (int64_t)fam[f].seq_len - 1) s->seq_hi = (int64_t)fam[f].seq_len - 1;
+      s->lo += (int64_t)at_of[f]; s->hi += (int64_t)at_of[f]; s->seq_lo += (int64_t)at_of[f]; s->seq_hi += (int64_t)at_of[f];
+    }
+    at += fam[f].cores.n;
+  }
+  if (rc == RAMX_OK) rc = ramx_dev_tsd(d, sites, (int32_t)total, params, out, NULL);
+  free(sites); free(at_of); free(fps);
   return rc;
 }
 

@@ -30,6 +30,10 @@ void ramx_forget_library_owner(const struct sequenceLibrary *lib);
 /* one base of a library of either kind (1 byte per base, or packed) */
 int ramx_lib_code(const struct sequenceLibrary *lib, uint64_t at);
 
+/* the checks of ramx_tsd_params (csrc/ramx_tsd.c): RAMX_OK, or RAMX_ERR_ARG with the error text set */
+int ramx_tsd_check_params(const ramx_tsd_params *tp);
+#define RAMX_TSD_POS_MAX ((int64_t)1 << 61)  /* positions of a ramx_tsd_site lie within +- this */
+
 /* host threads for a loop over `items` (at most 16, at most one per min_items_per_thread; RAMX_HOST_THREADS overrides) */
 int ramx_host_threads(long items, long min_items_per_thread);
 /* fn formats items [lo, hi) into outs[0..n_outs) (memory streams; an entry is NULL where the real stream is); the chunks'

@@ -217,6 +217,29 @@ class Refinement:
     converged: int
 
 
+# target-site duplications: C-ABI ramx_tsd_site (32 bytes), ramx_tsd (16 bytes), ramx_tsd_params
+TSD_SITE_DTYPE = np.dtype([("lo", np.int64), ("hi", np.int64), ("seq_lo", np.int64), ("seq_hi", np.int64)])
+TSD_DTYPE = np.dtype([("k", np.int32), ("mm", np.int32), ("dl", np.int32), ("dr", np.int32)])
+assert TSD_SITE_DTYPE.itemsize == 32 and TSD_DTYPE.itemsize == 16
+
+
+@dataclass
+class TsdParams:
+    slack: int = 3
+    kmin: int = 4
+    kmax: int = 20
+    mm_div: int = 10
+
+
+@dataclass
+class TsdSummary:
+    """What a family's records say together (C-ABI ramx_tsd_hist)."""
+    hist: np.ndarray                 # int32 [33]: records by k
+    mode: int                        # the k >= 1 with the largest count, ties to the larger k; 0: none
+    mode_count: int
+    null: np.ndarray                 # float64 [33]: copies expected to show a word of that length by chance
+
+
 FLANK_DTYPE = np.dtype([("start", np.int64), ("t_lo", np.int32), ("t_hi", np.int32), ("step", np.int8), ("compl_", np.int8),
                         ("pad_", np.int8, (6,))])
 assert FLANK_DTYPE.itemsize == 24

@@ -10,8 +10,8 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .datamodel import (ALN_END_DTYPE, ALN_NONE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, LINK_DTYPE, PILEUP_DTYPE, PLANE_DTYPE, CoreSet,
-                        ExtendParams)
+from .datamodel import (ALN_END_DTYPE, ALN_NONE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, LINK_DTYPE, PILEUP_DTYPE, PLANE_DTYPE, TSD_DTYPE, TSD_SITE_DTYPE,
+                        CoreSet, ExtendParams, TsdParams)
 from .extend import RunInfo, _info, _params
 
 
@@ -195,6 +195,31 @@ class Device:
     def load_library(self, sequence: np.ndarray):
         assert sequence.dtype == np.int8 and sequence.flags.c_contiguous
         _lib.check(self._L.ramx_dev_load_library(self._h, sequence.ctypes.data, len(sequence)), "ramx_dev_load_library")
+
+    def load_library_packed(self, tables: dict):
+        """The packed form of a library (C-ABI ramx_dev_load_library_packed); tables as loader.pack_library makes them."""
+        from .loader import _Packed
+        keep = {k: np.ascontiguousarray(tables[k], dt) for k, dt in
+                (("win_start", np.uint64), ("win_byte", np.uint64), ("win_phase", np.uint8), ("bytes", np.uint8),
+                 ("n_start", np.uint64), ("n_len", np.uint32))}
+        ptr = lambda k, ct: keep[k].ctypes.data_as(C.POINTER(ct))       # noqa: E731
+        pk = _Packed(int(tables["length"]), len(keep["win_phase"]), ptr("win_start", C.c_uint64), ptr("win_byte", C.c_uint64),
+                     ptr("win_phase", C.c_uint8), ptr("bytes", C.c_uint8), len(keep["bytes"]), ptr("n_start", C.c_uint64),
+                     ptr("n_len", C.c_uint32), len(keep["n_len"]))
+        self._L.ramx_dev_load_library_packed.argtypes = [C.c_void_p, C.POINTER(_Packed)]
+        _lib.check(self._L.ramx_dev_load_library_packed(self._h, C.byref(pk)), "ramx_dev_load_library_packed")
+
+    def tsd(self, sites, tp: Optional[TsdParams] = None, timing: bool = False):
+        """The target-site duplication of every site on the library this device holds (C-ABI ramx_dev_tsd): -> TSD_DTYPE
+        [n_sites]; timing=True: (records, [pack ms, kernel ms])."""
+        s = np.ascontiguousarray(sites, TSD_SITE_DTYPE).reshape(-1)
+        tp = TsdParams() if tp is None else tp
+        cp = _lib.TsdParams(int(tp.slack), int(tp.kmin), int(tp.kmax), int(tp.mm_div))
+        out = np.zeros(len(s), TSD_DTYPE)
+        ms = (C.c_double * 2)()
+        _lib.check(self._L.ramx_dev_tsd(self._h, s.ctypes.data if len(s) else None, len(s), C.byref(cp),
+                                        out.ctypes.data if len(s) else None, ms), "ramx_dev_tsd")
+        return (out, [ms[0], ms[1]]) if timing else out
 
     def begin_direction(self, flanks, p: ExtendParams):
         arr, nx = flanks

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from .datamodel import (ALN_END_DTYPE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, FLANK_DTYPE, PILEUP_DTYPE, PLANE_DTYPE, Alignment, Copies, SubfamGroup, Subfamilies,
-                        CoreSet, ExtendParams, Linkage, Profile, Refinement)
+                        CoreSet, ExtendParams, Linkage, Profile, Refinement, TSD_DTYPE, TSD_SITE_DTYPE, TsdParams, TsdSummary)
 
 
 @dataclass
@@ -357,3 +357,85 @@ def extend_batch(direction: int, families, p: ExtendParams, profile: bool = Fals
     infos = (_lib.RunInfo * max(n, 1))()
     _lib.check(L.ramx_extend_batch(int(direction), arr, n, C.byref(cp), infos), "ramx_extend_batch")
     return [_info(infos[i]) for i in range(n)]
+
+
+# ---- target-site duplications (include/ramx.h, ramx_tsd): after both extension calls ----
+
+def _tsd_params(tp):
+    tp = TsdParams() if tp is None else tp
+    return _lib.TsdParams(int(tp.slack), int(tp.kmin), int(tp.kmax), int(tp.mm_div))
+
+
+def _flat_cores(cores: CoreSet):
+    return _lib.FlatCores(cores.n, *[getattr(cores, k).ctypes.data for k in
+                                     ("left_pos", "right_pos", "lower", "upper", "orient", "left_ext",
+                                      "right_ext", "left_len", "right_len", "score")])
+
+
+def tsd_sites(cores: CoreSet) -> np.ndarray:
+    """One site per core from the extents both directions left in the cores (C-ABI ramx_tsd_sites, host C)."""
+    out = np.zeros(cores.n, TSD_SITE_DTYPE)
+    fc = _flat_cores(cores)
+    _lib.check(_lib.lib().ramx_tsd_sites(C.byref(fc), out.ctypes.data if cores.n else None), "ramx_tsd_sites")
+    return out
+
+
+def tsd_summary(records, tp: TsdParams = None) -> TsdSummary:
+    """Histogram, modal length and chance expectation of a family's records (C-ABI ramx_tsd_summary, host C)."""
+    r = np.ascontiguousarray(records, TSD_DTYPE).reshape(-1)
+    h = _lib.TsdHist()
+    cp = _tsd_params(tp)
+    _lib.check(_lib.lib().ramx_tsd_summary(r.ctypes.data if len(r) else None, len(r), C.byref(cp), C.byref(h)), "ramx_tsd_summary")
+    return TsdSummary(np.array(h.hist[:], np.int32), int(h.mode), int(h.mode_count), np.array(h.null[:], np.float64))
+
+
+def termini(cons_left, cons_right, T: int = 32):
+    """-> (first bases, last bases, terminal-inverted-repeat length) of the extended consensus, from the kept columns of the two
+    directions as the loop hands them over -- the left rows run outward from the core (C-ABI ramx_termini, host C)."""
+    cl, cr = np.ascontiguousarray(cons_left, np.int8), np.ascontiguousarray(cons_right, np.int8)
+    five, three = C.create_string_buffer(max(T, 0) + 1), C.create_string_buffer(max(T, 0) + 1)
+    tir = C.c_int32()
+    _lib.check(_lib.lib().ramx_termini(cl.ctypes.data if len(cl) else None, len(cl), cr.ctypes.data if len(cr) else None, len(cr),
+                                       int(T), five, three, C.byref(tir)), "ramx_termini")
+    return five.value.decode(), three.value.decode(), int(tir.value)
+
+
+def tsd_flat(cores: CoreSet, sequence: np.ndarray, tp: TsdParams = None) -> np.ndarray:
+    """The target-site duplication of every core after both extension calls, on the library they left on the session's device
+    (C-ABI ramx_tsd_flat): -> TSD_DTYPE [cores.n]."""
+    assert sequence.dtype == np.int8 and sequence.flags.c_contiguous
+    out = np.zeros(cores.n, TSD_DTYPE)
+    fc = _flat_cores(cores)
+    cp = _tsd_params(tp)
+    _lib.check(_lib.lib().ramx_tsd_flat(C.byref(fc), sequence.ctypes.data, len(sequence), C.byref(cp), out.ctypes.data if cores.n else None),
+               "ramx_tsd_flat")
+    return out
+
+
+def tsd_alignment(core_list, seq_lib, n: int, tp: TsdParams = None) -> np.ndarray:
+    """The same on the reference's data model: core_list / seq_lib are pointers to a struct coreAlignment list of n nodes and its
+    struct sequenceLibrary, as the loader returns them -- packed twin included (C-ABI ramx_tsd_alignment)."""
+    out = np.zeros(n, TSD_DTYPE)
+    cp = _tsd_params(tp)
+    _lib.check(_lib.lib().ramx_tsd_alignment(C.cast(core_list, C.c_void_p), C.cast(seq_lib, C.c_void_p), C.byref(cp),
+                                             out.ctypes.data if n else None), "ramx_tsd_alignment")
+    return out
+
+
+def tsd_batch(families, tp: TsdParams = None):
+    """The same for the families of an extend_batch, in one launch on the concatenated library it leaves on the device (C-ABI
+    ramx_tsd_batch).  `families` as extend_batch takes them; -> one TSD_DTYPE array per family."""
+    n = len(families)
+    arr = (_lib.Family * max(n, 1))()
+    for i, (cores, sequence, master) in enumerate(families):
+        assert sequence.dtype == np.int8 and sequence.flags.c_contiguous
+        arr[i].cores = _flat_cores(cores)
+        arr[i].sequence = sequence.ctypes.data
+        arr[i].seq_len = len(sequence)
+        arr[i].master = master.ctypes.data if master is not None else None
+    total = sum(f[0].n for f in families)
+    out = np.zeros(total, TSD_DTYPE)
+    cp = _tsd_params(tp)
+    _lib.check(_lib.lib().ramx_tsd_batch(arr, n, C.byref(cp), out.ctypes.data if total else None), "ramx_tsd_batch")
+    ends = np.cumsum([0] + [f[0].n for f in families])
+    return [out[ends[i]:ends[i + 1]].copy() for i in range(n)]

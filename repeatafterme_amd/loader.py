@@ -161,6 +161,32 @@ def write_twobit(path: str, records: Sequence[Tuple[str, np.ndarray]]) -> None:
             f.write(b)
 
 
+def pack_library(codes, win_starts=(0,), win_phases=None) -> dict:
+    """The packed form (include/ramx.h, ramx_packed_library) of a one-byte-per-base library: windows beginning at win_starts
+    (the first at 0), each stored from a byte of its own at the given phase (position 0..3 of its first base in that byte);
+    codes 0..3 are packed, anything else becomes a run of N.  -> the tables Device.load_library_packed takes."""
+    codes = np.asarray(codes, np.int8)
+    n = len(codes)
+    starts = [int(s) for s in win_starts]
+    assert starts and starts[0] == 0 and all(a < b for a, b in zip(starts, starts[1:])) and starts[-1] < max(n, 1)
+    phases = [0] * len(starts) if win_phases is None else [int(p) for p in win_phases]
+    isn = (codes < 0) | (codes > 3)
+    d = np.diff(np.concatenate(([0], isn.view(np.int8), [0])))
+    n_start = np.nonzero(d == 1)[0].astype(np.uint64)
+    n_len = (np.nonzero(d == -1)[0] - n_start.astype(np.int64)).astype(np.uint32)
+    vals = _CODE_TO_2BIT[np.where(isn, 3, codes).astype(np.int64)]
+    out, win_byte = [], []
+    for i, s in enumerate(starts):
+        e = starts[i + 1] if i + 1 < len(starts) else n
+        win_byte.append(sum(len(b) for b in out))
+        v = np.concatenate((np.zeros(phases[i], np.uint8), vals[s:e]))
+        v = np.concatenate((v, np.zeros((-len(v)) % 4, np.uint8))).reshape(-1, 4)
+        out.append(((v[:, 0] << 6) | (v[:, 1] << 4) | (v[:, 2] << 2) | v[:, 3]).astype(np.uint8))
+    win_byte.append(sum(len(b) for b in out))
+    return dict(length=n, win_start=np.array(starts + [n], np.uint64), win_byte=np.array(win_byte, np.uint64),
+                win_phase=np.array(phases, np.uint8), bytes=np.concatenate(out + [np.zeros(4, np.uint8)]), n_start=n_start, n_len=n_len)
+
+
 def write_ranges(path: str, rows: Sequence[Tuple[str, int, int, int, int, str]]) -> None:
     with open(path, "w") as f:
         for name, start, end, le, re_, strand in rows:

@@ -1,0 +1,276 @@
+"""ramx_dev_tsd and the three seam-1 calls against the brute-force restatement (tests/tsd_ref.py), record for record: site
+counts round the wave of 64, every slack / length range / mismatch rule, both library forms, sites at both ends of the library,
+bounds that cut a word, N runs and window boundaries of the packed form; then the seam-1 calls after real extension calls."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from oracle import pyoracle as po
+from repeatafterme_amd import _lib
+from repeatafterme_amd.datamodel import TSD_DTYPE, TSD_SITE_DTYPE, CoreSet, TsdParams, new_master
+from repeatafterme_amd.loader import pack_library
+
+import tsd_ref as tr
+from helpers import to_extend_params
+
+pytestmark = pytest.mark.gpu
+ERR_ARG = -103
+N_SITES = 130
+
+
+def make_sites(seed=3):
+    """A library with N_SITES planted sites: element i sits between two copies of a word of 1..32 bases, sometimes with a
+    mismatch, an N run across the word's beginning, lower-case bases; the reported ends are off by up to three bases and the
+    bounds sometimes cut a word.  Site 0 begins at position 0, the last site ends at the last position, some elements are empty."""
+    rng = np.random.default_rng(seed)
+    parts, sites, at = [], [], 0
+    for i in range(N_SITES):
+        k = int(rng.choice([1, 2, 4, 5, 6, 8, 9, 12, 15, 20, 26, 32, 32, 32]))
+        word = rng.integers(0, 4, k).astype(np.int8)
+        right = word.copy()
+        if k >= 4 and rng.random() < 0.3:
+            j = int(rng.integers(1, k - 1))
+            right[j] = (right[j] + 1) % 4
+        left = word.copy()
+        if k >= 8 and rng.random() < 0.15:
+            left[:2] = 99                                   # an N run that begins in the filler and crosses into the word
+        elem = rng.integers(0, 4, int(rng.choice([0, 3, 17, 25, 33, 40, 61]))).astype(np.int8)
+        filler = rng.integers(0, 4, 70).astype(np.int8)
+        if k >= 8 and (left[:2] == 99).all():
+            filler[-3:] = 99
+        first, last = i == 0, i == N_SITES - 1
+        pre = [] if first else [filler, left]
+        post = [] if last else [right]
+        if first or last:
+            elem = rng.integers(0, 4, 40).astype(np.int8)
+        lo = at + sum(len(x) for x in pre)
+        hi = lo + len(elem) - 1
+        for x in pre + [elem] + post:
+            parts.append(x)
+            at += len(x)
+        # what the caller reports: ends off by up to three bases (never crossing), bounds wide or cutting into a word
+        sl, sr = (0, 0) if len(elem) < 7 or first or last else (int(rng.integers(-3, 4)), int(rng.integers(-3, 4)))
+        rlo, rhi = lo - sl, hi + sr
+        seq_lo = rlo - int(rng.choice([200, 200, 200, 35, max(k - 2, 0), 0]))
+        seq_hi = rhi + int(rng.choice([200, 200, 200, 35, max(k - 2, 0), 0]))
+        sites.append((rlo, rhi, seq_lo, seq_hi))
+    lib = np.concatenate(parts).astype(np.int8)
+    lower = (rng.random(len(lib)) < 0.1) & (lib < 4)
+    lib[lower] += 4
+    s = np.array(sites, np.int64).view(TSD_SITE_DTYPE).reshape(-1)
+    assert s["lo"][0] == 0 and s["hi"][-1] == len(lib) - 1 and (s["lo"] == s["hi"] + 1).any()
+    return lib, s
+
+
+_cache = {}
+
+
+def library(form):
+    """The library of the seam-2 tests, its sites, and for the packed form the tables: windows that begin at a site's first base
+    (the left word ends in the window before), in the middle of a word, at odd phases."""
+    if not _cache:
+        lib, sites = make_sites()
+        # the packed form knows A C G T and N only: lower case is not part of it
+        plain = np.where((lib >= 4) & (lib <= 7), lib - 4, lib).astype(np.int8)
+        starts = [0, int(sites["lo"][40]), int(sites["hi"][77]) + 3, int(sites["lo"][100]) - 2]
+        _cache.update(byte=(lib, sites, None), packed=(plain, sites, pack_library(plain, starts, [0, 3, 1, 2])))
+        _cache["expected"] = {}
+    return _cache[form]
+
+
+def expected(form, n, tp):
+    key = (form, n, tp.slack, tp.kmin, tp.kmax, tp.mm_div)
+    lib, sites, _ = library(form)
+    if key not in _cache["expected"]:
+        _cache["expected"][key] = tr.tsd_all(lib, [tuple(int(v) for v in s) for s in sites[:n]], slack=tp.slack, kmin=tp.kmin,
+                                             kmax=tp.kmax, mm_div=tp.mm_div)
+    return _cache["expected"][key]
+
+
+@pytest.fixture(scope="module")
+def devices():
+    from repeatafterme_amd.device import Device
+    out = {}
+    for form in ("byte", "packed"):
+        lib, _, tables = library(form)
+        d = Device(0)
+        if tables is None:
+            d.load_library(np.ascontiguousarray(lib))
+        else:
+            d.load_library_packed(tables)
+        out[form] = d
+    yield out
+    for d in out.values():
+        d.close()
+
+
+# every n round the wave, every slack, every length range and every mismatch rule at least once on each form; the widest search
+# (slack 7, lengths 1..32) on the sites of one wave and a bit
+SHAPES = [
+    ("byte", 130, TsdParams(3, 4, 20, 10)),
+    ("packed", 130, TsdParams(3, 4, 20, 10)),
+    ("byte", 65, TsdParams(0, 1, 32, 4)),
+    ("packed", 64, TsdParams(7, 4, 20, 0)),
+    ("byte", 130, TsdParams(3, 32, 32, 10)),
+    ("packed", 130, TsdParams(0, 32, 32, 4)),
+    ("packed", 1, TsdParams(7, 1, 32, 4)),
+    ("byte", 1, TsdParams(3, 1, 32, 0)),
+    ("byte", 63, TsdParams(3, 1, 32, 0)),
+    ("byte", 65, TsdParams(7, 1, 32, 10)),
+    ("packed", 63, TsdParams(7, 1, 32, 10)),
+]
+
+
+@pytest.mark.parametrize("form,n,tp", SHAPES, ids=lambda v: v if isinstance(v, str) else (str(v) if isinstance(v, int) else
+                                                                                         f"S{v.slack}k{v.kmin}-{v.kmax}m{v.mm_div}"))
+def test_records_equal_the_restatement(devices, form, n, tp):
+    _, sites, _ = library(form)
+    got = devices[form].tsd(sites[:n], tp)
+    want = expected(form, n, tp)
+    bad = [(i, tuple(int(v) for v in got[i]), want[i]) for i in range(n) if tuple(int(v) for v in got[i]) != want[i]]
+    assert not bad, bad[:5]
+    # a second call with the same arguments gives the same bytes
+    assert devices[form].tsd(sites[:n], tp).tobytes() == got.tobytes()
+
+
+def test_the_shapes_are_not_empty_ground():
+    """The restatement's own records on these sites: duplications found, with and without mismatches, at every shift, none at
+    the two ends of the library, and the bounds and the N runs change what is found."""
+    for form in ("byte", "packed"):
+        lib, sites, _ = library(form)
+        want = np.array(expected(form, 130, TsdParams(3, 4, 20, 10)))
+        assert (want[:, 0] > 0).sum() > 40 and (want[:, 1] > 0).sum() > 5 and (want[:, 0] == 0).sum() > 5
+        assert set(want[:, 2]) >= set(range(-3, 4)) and set(want[:, 3]) >= set(range(-3, 4))
+        assert tuple(want[0]) == (0, 0, 0, 0) and tuple(want[-1]) == (0, 0, 0, 0)
+        wide = [(int(s["lo"]), int(s["hi"]), -10 ** 6, 10 ** 6) for s in sites]
+        assert sum(a != tuple(b) for a, b in zip(tr.tsd_all(lib, wide), want)) > 3
+        nofold = np.where(lib == 99, 0, lib)
+        assert sum(a != tuple(b) for a, b in zip(tr.tsd_all(nofold, [tuple(int(v) for v in s) for s in sites]), want)) > 0
+    assert (np.array(expected("byte", 130, TsdParams(3, 32, 32, 10)))[:, 0] == 32).sum() >= 5
+    assert (np.array(expected("packed", 130, TsdParams(0, 32, 32, 4)))[:, 0] == 32).sum() >= 2
+
+
+def test_no_site_and_bad_arguments(devices):
+    d = devices["byte"]
+    _, sites, _ = library("byte")
+    assert len(d.tsd(sites[:0])) == 0
+    L, ok = _lib.lib(), _lib.TsdParams(3, 4, 20, 10)
+    out = np.full(4, 7, np.int32).repeat(4).view(TSD_DTYPE)
+    keep = out.copy()
+    for bad in [(-1, 4, 20, 10), (8, 4, 20, 10), (3, 0, 20, 10), (3, 6, 5, 10), (3, 4, 33, 10), (3, 4, 20, 3)]:
+        assert L.ramx_dev_tsd(d._h, sites.ctypes.data, 4, C.byref(_lib.TsdParams(*bad)), out.ctypes.data, None) == ERR_ARG, bad
+    assert L.ramx_dev_tsd(d._h, sites.ctypes.data, 4, None, out.ctypes.data, None) == ERR_ARG
+    assert L.ramx_dev_tsd(d._h, sites.ctypes.data, -1, C.byref(ok), out.ctypes.data, None) == ERR_ARG
+    assert L.ramx_dev_tsd(d._h, None, 4, C.byref(ok), out.ctypes.data, None) == ERR_ARG
+    assert L.ramx_dev_tsd(d._h, sites.ctypes.data, 4, C.byref(ok), None, None) == ERR_ARG
+    assert L.ramx_dev_tsd(None, sites.ctypes.data, 4, C.byref(ok), out.ctypes.data, None) == ERR_ARG
+    for field, delta in (("seq_lo", +1), ("seq_hi", -1), ("lo", None)):
+        s = sites[:4].copy()
+        if delta is None:
+            s["lo"][2] = s["hi"][2] + 2
+        else:
+            s[field][2] = (s["lo"][2] if field == "seq_lo" else s["hi"][2]) + delta
+        assert L.ramx_dev_tsd(d._h, s.ctypes.data, 4, C.byref(ok), out.ctypes.data, None) == ERR_ARG, field
+    # raised before anything is written
+    assert out.tobytes() == keep.tobytes()
+    assert L.ramx_dev_tsd(d._h, sites.ctypes.data, 0, C.byref(ok), None, None) == 0
+
+
+# ---- seam 1 ----
+
+def gpu_both_directions(cores, seq, p):
+    from repeatafterme_amd.extend import extend_alignment
+    c, m = cores.copy(), new_master(p.L)
+    rets = {d: extend_alignment(d, c, seq, m, to_extend_params(p)).ret for d in (1, 0)}
+    return c, m, rets
+
+
+def test_tsd_flat_on_the_planted_family():
+    """Two extend_alignment calls, then ramx_tsd_flat on the library they left on the device: the CPU expectation (the loop is
+    bit-exact against the oracle, so the sites are the same)."""
+    from repeatafterme_amd.extend import tsd_flat, tsd_summary
+    e = tr.planted_expectation()
+    c, m, rets = gpu_both_directions(e["cores"], e["seq"], e["p"])
+    assert rets == e["rets"] and np.array_equal(c.left_len, e["after"].left_len) and np.array_equal(c.right_len, e["after"].right_len)
+    got = tsd_flat(c, e["seq"])
+    assert [tuple(int(v) for v in r) for r in got] == e["records"]
+    s = tsd_summary(got)
+    assert s.mode == tr.PLANTED["k"] and 2 * s.mode_count >= tr.PLANTED["M"]
+    # on a library the device does not hold (a copy at another address): uploaded, the same records
+    assert tsd_flat(c, e["seq"].copy()).tobytes() == got.tobytes()
+    assert tsd_flat(c.subset(slice(0, 0)), e["seq"]).shape == (0,)
+
+
+def test_tsd_alignment_on_the_list():
+    """The same through the reference's data model: a linked list of cores and a sequence library."""
+    from repeatafterme_amd.extend import tsd_alignment
+    from repeatafterme_amd.loader import _Core, _SeqLib
+    e = tr.planted_expectation()
+    c, n = e["after"], e["after"].n
+    arr = (_Core * n)()
+    for i in range(n):
+        a = arr[i]
+        a.next = C.pointer(arr[i + 1]) if i + 1 < n else None
+        a.leftSeqPos, a.rightSeqPos, a.lowerSeqBound, a.upperSeqBound = int(c.left_pos[i]), int(c.right_pos[i]), int(c.lower[i]), int(c.upper[i])
+        a.orient = bytes([int(c.orient[i])])
+        a.leftExtensionLen, a.rightExtensionLen = int(c.left_len[i]), int(c.right_len[i])
+    seq = np.ascontiguousarray(e["seq"])
+    sl = _SeqLib(seq.ctypes.data_as(C.POINTER(C.c_int8)), None, None, None, len(seq), 0, 0, None)
+    got = tsd_alignment(arr, C.pointer(sl), n)
+    assert [tuple(int(v) for v in r) for r in got] == e["records"]
+
+
+def test_tsd_batch_with_an_empty_family_between():
+    from repeatafterme_amd.extend import extend_batch, tsd_batch
+    p = tr.planted_expectation()["p"]
+    fams = []
+    for kw in (dict(M=14, k=5, seed=21, div=0.05), None, dict(M=9, k=8, seed=22, div=0.05)):
+        if kw is None:
+            seq = np.random.default_rng(5).integers(0, 4, 333).astype(np.int8)
+            cores = CoreSet(left_pos=[], right_pos=[], lower=[], upper=[], orient=[], left_ext=[], right_ext=[])
+        else:
+            seq, cores, _ = tr.planted_family(**kw)
+        fams.append((cores, seq))
+    batch = [(c.copy(), s, new_master(p.L)) for c, s in fams]
+    for d in (1, 0):
+        extend_batch(d, batch, to_extend_params(p))
+    got = tsd_batch(batch)
+    assert [len(g) for g in got] == [14, 0, 9]
+    modes = []
+    for (c0, s), (c, _, m), g in zip(fams, batch, got):
+        if c0.n == 0:
+            continue
+        oc, om = c0.copy(), new_master(p.L)
+        for d in (1, 0):
+            po.oracle_extend(d, oc, s, om, p)
+        assert np.array_equal(c.left_len, oc.left_len) and np.array_equal(c.right_len, oc.right_len)
+        want = tr.tsd_all(s, tr.sites_of(oc))
+        assert [tuple(int(v) for v in r) for r in g] == want
+        modes.append(tr.summary(want)[1])
+    assert modes == [5, 8]
+    # once more on copies of the libraries: the concatenation is built and sent again, the records are the same
+    again = tsd_batch([(c, s.copy(), m) for c, s, m in batch])
+    assert all(a.tobytes() == g.tobytes() for a, g in zip(again, got))
+
+
+def test_an_extension_after_a_tsd_call_is_unchanged():
+    """The TSD call reuses the device's flank and window buffers and may replace the library: an extension between and after TSD
+    calls still gives the oracle's result."""
+    from repeatafterme_amd.extend import extend_alignment, tsd_flat
+    from repeatafterme_amd.synth import synth_family
+    e = tr.planted_expectation()
+    p = e["p"]
+    ep = to_extend_params(p)
+    fs = synth_family(200, 300, 14, K=200, seed=3, both_sides=True, minus_frac=0.3, n_run_frac=0.1)
+    oc, om = fs.cores.copy(), new_master(p.L)
+    orets = [po.oracle_extend(d, oc, fs.sequence, om, p).ret for d in (1, 0)]
+    c, m = fs.cores.copy(), new_master(p.L)
+    r1 = extend_alignment(1, c, fs.sequence, m, ep).ret
+    mid = tsd_flat(c, fs.sequence)                        # on the resident library, between the two directions
+    tsd_flat(e["after"], e["seq"])                        # ... and on another one, which replaces it
+    r0 = extend_alignment(0, c, fs.sequence, m, ep).ret
+    assert [r1, r0] == orets and np.array_equal(m, om)
+    for key in ("left_len", "right_len", "score"):
+        assert np.array_equal(getattr(c, key), getattr(oc, key)), key
+    assert len(mid) == 200

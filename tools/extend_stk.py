@@ -19,6 +19,7 @@ per direction the family's mean Kimura divergence over the extension beside the 
 -- the check that the matrix chosen from the seed alignment was the right one for the extended part; with -linkage,
 <id>-linkage.tsv: the pairs of variant columns of both extensions whose variants travel together in the copies (RAMExtend
 -outlinkage) -- the sign that the family is two subfamilies under one consensus.
+<id>-tsd.tsv: with -tsd, the target-site duplication of every extended copy and the family's modal length (RAMExtend -outtsd).
 
 (the re-alignment and Stockholm rewriting that follow in the wrapper belong to RepeatModeler and are out of scope).
 """
@@ -51,6 +52,8 @@ def main(argv=None):
     ap.add_argument("-copies", action="store_true", help="also write <id>-copies.tsv per family (RAMExtend -outcopies) and print "
                     "each extension's divergence with the matrix it would call for")
     ap.add_argument("-linkage", action="store_true", help="also write <id>-linkage.tsv per family (RAMExtend -outlinkage)")
+    ap.add_argument("-tsd", action="store_true", help="also write <id>-tsd.tsv per family (RAMExtend -outtsd) and print the modal "
+                    "target-site duplication of the extended copies")
     ap.add_argument("-one_by_one", action="store_true", help="start one RAMExtend per family, as the wrapper does")
     a = ap.parse_args(argv)
 
@@ -92,7 +95,8 @@ def main(argv=None):
                                        (["-outpileup", base + "-pileup.tsv", "-outrefined", base + "-refined-cons.fa", "-refine",
                                          str(a.refine)] if a.refine > 0 else []) +
                                        (["-outcopies", base + "-copies.tsv"] if a.copies else []) +
-                                       (["-outlinkage", base + "-linkage.tsv"] if a.linkage else []),
+                                       (["-outlinkage", base + "-linkage.tsv"] if a.linkage else []) +
+                                       (["-outtsd", base + "-tsd.tsv"] if a.tsd else []),
                                        stdout=log, stderr=subprocess.STDOUT).returncode
                 if rc:
                     sys.exit(f"  RAMExtend failed! [{rc}] see {base}-repam.log")
@@ -100,10 +104,11 @@ def main(argv=None):
             lst = os.path.join(a.outdir, f"batch-{matrix}-{minimp}.list")
             with open(lst, "w") as fh:
                 for seed, base in fams:
-                    # fields six to eleven are optional: "-" holds the place of one that is not asked for before one that is
+                    # fields six to thirteen are optional (the twelfth, the subfamily file, is never asked for here): "-" holds the place of one that is not asked for before one that is
                     opt = [base + "-profile.tsv" if a.profile else "-", base + "-aln.a2m" if a.aln else "-",
                            base + "-pileup.tsv" if a.refine > 0 else "-", base + "-refined-cons.fa" if a.refine > 0 else "-",
-                           base + "-copies.tsv" if a.copies else "-", base + "-linkage.tsv" if a.linkage else "-"]
+                           base + "-copies.tsv" if a.copies else "-", base + "-linkage.tsv" if a.linkage else "-", "-",
+                           base + "-tsd.tsv" if a.tsd else "-"]
                     while opt and opt[-1] == "-":
                         opt.pop()
                     fh.write("\t".join([base + "-linup.tsv", base + "-repam.log", base + "-ext-cons.fa",
@@ -145,6 +150,11 @@ def main(argv=None):
                         tag, variants, pairs, linked = line[1:].rstrip("\n").split("\t")
                         print(f"  - Linked variants [{tag}]: {linked.split('=')[1]} of {pairs.split('=')[1]} pairs among "
                               f"{variants.split('=')[1]} variants")
+            if a.tsd and os.path.exists(base + "-tsd.tsv"):
+                for line in open(base + "-tsd.tsv"):                    # the summary line
+                    if line.startswith("#mode"):
+                        mode, count, null = (kv.split("=")[1] for kv in line.rstrip("\n").split("\t")[1:])
+                        print(f"  - Target-site duplication: {mode} bp in {count} copies ({null} expected by chance)")
     return 0
 
 
