@@ -290,6 +290,17 @@ int ramx_dev_download(ramx_dev *d, int8_t *cons, int32_t cons_cap, int32_t *trim
  * cell transformed: (m, e) = (max(sub,gap), max(sub+gapopen,gap)+gapextn) -- see csrc/ramx_kernels_common.h. */
 int ramx_dev_peek_state(ramx_dev *d, int32_t flank, int32_t *cells, int32_t *high, int32_t *pos);
 
+/* debug / test hook: the transposed 4-bit flank windows and the bounds as the last pack call on this device left them -- a
+ * direction's (begin_direction and the pieces packed while it ran), a replay's or ramx_dev_tsd's.  Nothing is packed here: how
+ * many words a run chose to pack is part of what is read.  A piece still being packed on the second stream is waited for.
+ * *packed_words = K and *lanes = Np are written first; words receives [K][Np] uint32 (nibble i of word k of lane n is flank
+ * position t = 8k + i - W - 8, class 8 where there is no base), bounds [Np][2] int32 (t_lo + W, t_hi + W; (1, 0) for a lane
+ * without a flank).  words_cap / lanes_cap are the buffers' capacities in words / lanes: RAMX_ERR_ARG, with the two counts
+ * written, when they are too small or a buffer is NULL (a first call with capacity 0 sizes the buffers); RAMX_ERR_ARG also for
+ * a device on which nothing has been packed yet. */
+int ramx_dev_peek_windows(ramx_dev *d, uint32_t *words, int64_t words_cap, int32_t *bounds, int64_t lanes_cap,
+                          int32_t *packed_words, int32_t *lanes);
+
 /* debug / test hook: with RAMX_CP_PEEK=1 in the environment the cell-parallel family kernel keeps the final DP row of
  * every flank of the last ramx_dev_run_families call; cells receives [2W+1][2] int32 in the (m, e) encoding of
  * ramx_dev_peek_state.  `flank` indexes the (padded) flank array of that call; d == NULL means the process-wide

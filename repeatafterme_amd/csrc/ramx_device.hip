@@ -149,6 +149,7 @@ struct ramx_dev
   CpDevDesc *d_devdesc; size_t cap_devdesc;       // device-wide cell-parallel launches: one descriptor per workgroup
   PShard *d_vote_sets; size_t cap_vote_sets; unsigned *d_err_sets; size_t cap_err_sets;   // batch mode: per-set vote / error words
   int packed_kw;       // words of every window packed so far (begin_direction packs the first piece, see pack_rest)
+  int pk_last_lanes, pk_last_words;   // what launch_pack was last called with: lanes of d_bases, words packed (ramx_dev_peek_windows)
   hipStream_t pack_stream; hipEvent_t pack_done; int pack_busy;      // the following pieces are packed beside the running one
   int pk_r0;           // begin_direction: first row from which no flank has a low out-of-bounds cell (the packed-row kernel starts there); -1: none
   int last_packed_r0;  // last direction: first row of the packed-row kernel, -1 if it did not run
@@ -362,6 +363,7 @@ static int window_words(int L, int W) { return (L + 2 * W + 2) / 8 + 12; }
 static int launch_pack(ramx_dev *d, int Nx, int Np, int W, int k_lo, int k_hi, hipStream_t st)
 {
   if (k_hi <= k_lo) return RAMX_OK;
+  d->pk_last_lanes = Np; d->pk_last_words = k_hi;      // (a piece continues where the piece before ended: words [0, k_hi) are packed)
   if (!d->lib_packed)
   {
     dim3 grid((Np + 255) / 256, k_hi - k_lo);
@@ -3119,6 +3121,23 @@ extern "C" int ramx_dev_peek_state(ramx_dev *d, int32_t flank, int32_t *cells, i
     if (2 * q + 1 < B) { cells[4 * q + 2] = v.z; cells[4 * q + 3] = v.w; }
     else { if (high) *high = v.z; if (pos) *pos = v.w; }
   }
+  return RAMX_OK;
+}
+
+extern "C" int ramx_dev_peek_windows(ramx_dev *d, uint32_t *words, int64_t words_cap, int32_t *bounds, int64_t lanes_cap,
+                                     int32_t *packed_words, int32_t *lanes)
+{
+  if (!d || !packed_words || !lanes || words_cap < 0 || lanes_cap < 0 || d->pk_last_words <= 0 || d->pk_last_lanes <= 0 || !d->d_bases || !d->d_bounds)
+  { ramx_set_error("ramx_dev_peek_windows: bad argument, or nothing has been packed on this device"); return RAMX_ERR_ARG; }
+  const int KW = d->pk_last_words, Np = d->pk_last_lanes;
+  *packed_words = KW; *lanes = Np;
+  if (!words || !bounds || words_cap < (int64_t)KW * Np || lanes_cap < Np)
+  { ramx_set_error("ramx_dev_peek_windows: %d words of %d lanes do not fit the caller's buffers", KW, Np); return RAMX_ERR_ARG; }
+  HIPCHK(hipSetDevice(d->ordinal));
+  if (d->pack_busy) { HIPCHK(hipEventSynchronize(d->pack_done)); d->pack_busy = 0; }     // a piece still being packed on the second stream
+  HIPCHK(hipStreamSynchronize(d->stream));
+  HIPCHK(hipMemcpy(words, d->d_bases, (size_t)KW * Np * sizeof(unsigned), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(bounds, d->d_bounds, (size_t)Np * sizeof(int2), hipMemcpyDeviceToHost));
   return RAMX_OK;
 }
 

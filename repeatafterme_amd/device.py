@@ -470,6 +470,20 @@ class Device:
                    "ramx_dev_peek_state")
         return cells[:2 * B].reshape(B, 2).copy(), hi.value, po.value
 
+    def peek_windows(self):
+        """Debug / test hook (C-ABI ramx_dev_peek_windows): what the last pack call on this device left -- a direction's, a
+        replay's or tsd()'s.  -> (words uint32 [packed_words][lanes], bounds int32 [lanes][2]); nothing is packed here."""
+        kw, lanes = C.c_int32(), C.c_int32()
+        rc = self._L.ramx_dev_peek_windows(self._h, None, 0, None, 0, C.byref(kw), C.byref(lanes))     # sizes the buffers
+        if kw.value <= 0 or lanes.value <= 0:
+            _lib.check(rc, "ramx_dev_peek_windows")
+        words = np.zeros((kw.value, lanes.value), np.uint32)
+        bounds = np.zeros((lanes.value, 2), np.int32)
+        _lib.check(self._L.ramx_dev_peek_windows(self._h, words.ctypes.data, words.size, bounds.ctypes.data, lanes.value,
+                                                 C.byref(kw), C.byref(lanes)), "ramx_dev_peek_windows")
+        assert words.shape == (kw.value, lanes.value)
+        return words, bounds
+
     def unique_id(self) -> np.ndarray:
         uid = np.zeros(128, np.uint8)
         _lib.check(self._L.ramx_comm_unique_id(uid.ctypes.data), "ramx_comm_unique_id")

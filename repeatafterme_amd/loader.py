@@ -96,6 +96,7 @@ def load_sequence_subset_packed(twobit: str, ranges: str, max_flanking_bp: int):
                   win_start=np.array([p.win_start[i] for i in range(nw + 1)], np.uint64),
                   win_byte=np.array([p.win_byte[i] for i in range(nw + 1)], np.uint64),
                   win_phase=np.array([p.win_phase[i] for i in range(nw)], np.uint8),
+                  bytes=np.ctypeslib.as_array(p.bytes, (int(p.n_bytes),)).copy() if p.n_bytes else np.zeros(0, np.uint8),
                   n_start=np.array([p.n_start[i] for i in range(nb)], np.uint64),
                   n_len=np.array([p.n_len[i] for i in range(nb)], np.uint32))
     seq = np.zeros(int(sl.length), np.int8)
