@@ -35,6 +35,7 @@
 #include <rccl/rccl.h>
 #include <errno.h>
 #include <fcntl.h>
+#include <limits.h>
 #include <sys/mman.h>
 #include <unistd.h>
 #include <stdarg.h>
@@ -43,7 +44,6 @@
 #include <string.h>
 #include <time.h>
 #include <vector>
-
 
 #include "ramx_kernels_common.h"
 #include "ramx_kernels_stream.h"
@@ -107,7 +107,7 @@ static double now_ms(void)
 
 struct ramx_dev
 {
-  int ordinal;
+  int ordinal, cus;   // cus: compute units (what every co-resident launch is planned against)
   hipStream_t stream;
   signed char *d_lib; unsigned long long lib_len; unsigned long long lib_cap;
   // packed library (ramx_dev_load_library_packed): the .2bit payload of the windows + window / N-run tables; lib_packed = 1
@@ -211,7 +211,7 @@ extern "C" int ramx_dev_create(int ordinal, ramx_dev **out)
     return RAMX_ERR_NO_DEVICE;
   }
   ramx_dev *d = (ramx_dev *)calloc(1, sizeof(ramx_dev));
-  d->ordinal = ordinal;
+  d->ordinal = ordinal; d->cus = prop.multiProcessorCount;
   // any failure below releases what has been created so far (ramx_dev_destroy copes with a partly built session)
 #define CRCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
     ramx_set_error("HIP error %s at %s:%d (%s)", hipGetErrorString(e_), __FILE__, __LINE__, #call); ramx_dev_destroy(d); return RAMX_ERR_HIP; } } while (0)
@@ -725,13 +725,11 @@ static int lean_p_of(const int (&tab)[RAMX_NCLASS][4], int go, int ge)
 //   <= 4 tiles per CU (N <= 65,536): 256-thread blocks, one wave per SIMD, up to 256 blocks;
 //   otherwise 512-thread blocks (two waves per SIMD), up to 256 blocks = 131,072 flanks.
 template <int W, int BLOCK>
-static int prk_capacity_blocks(int *out)
+static int prk_capacity_blocks(int cus, int *out)
 {
   static int cached = -1;              // (one device per process; the query is a runtime call per direction otherwise)
   if (cached >= 0) { *out = cached; return RAMX_OK; }
-  int per_cu = 0, dev = 0, cus = 0;
-  HIPCHK(hipGetDevice(&dev));
-  HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  int per_cu = 0;
   HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ramx_persistent_kernel<W, BLOCK>, BLOCK, 0));
   if (per_cu > 1) per_cu = 1;          // one block per CU by design; never trust the API for more
   *out = per_cu * cus;
@@ -772,11 +770,11 @@ static int prk_launch(ramx_dev *d, PArgs &pa, int blocks)
 
 // block shape that keeps the whole flank set resident, or 0
 template <int W>
-static int prk_plan(int tiles, int *block, int *blocks)
+static int prk_plan(int tiles, int cus, int *block, int *blocks)
 {
   int cap = 0, rc;
   *block = 0; *blocks = 0;
-  if ((rc = prk_capacity_blocks<W, 256>(&cap)) != RAMX_OK) return rc;
+  if ((rc = prk_capacity_blocks<W, 256>(cus, &cap)) != RAMX_OK) return rc;
   if ((tiles + 3) / 4 <= cap)
   {
     *block = 256; *blocks = (tiles + 3) / 4;
@@ -784,7 +782,7 @@ static int prk_plan(int tiles, int *block, int *blocks)
   }
   if constexpr (W <= 40)     // wider bands have no two-waves-per-SIMD shape: the row needs more than 256 registers
   {
-    if ((rc = prk_capacity_blocks<W, 512>(&cap)) != RAMX_OK) return rc;
+    if ((rc = prk_capacity_blocks<W, 512>(cus, &cap)) != RAMX_OK) return rc;
     if ((tiles + 7) / 8 <= cap) { *block = 512; *blocks = (tiles + 7) / 8; }
   }
   return RAMX_OK;
@@ -795,7 +793,6 @@ static bool prk_has_width(int W) { return W == 14 || W == 20 || W == 40 || W == 
 // ... and which have a one-workgroup-per-family instantiation (ramx_family_kernel: two waves per SIMD, 256 registers)
 static bool fam_has_width(int W) { return W == 14 || W == 20 || W == 40; }
 
-// this rank's own answer to "can the lane-per-flank persistent kernel run this direction", and its launch shape
 // A few words from device memory to the host at the end of a launch (control blocks, the error word, the consensus): written by
 // a kernel into the session's pinned buffer.  hipMemcpy would do, but the first device-to-host copy of a process costs
 // milliseconds of DMA set-up on this stack (6-10 ms of a 33 ms direction at N = 100,000), a store over the bus none.
@@ -821,64 +818,218 @@ static int d2h_small(ramx_dev *d, void *dst, const void *src, size_t bytes)
 }
 
 #define RAMX_CP_MIN_K_OVER_PACKED 4      // the cell-parallel kernel goes first with at least this many lanes per flank
-static int prk_local_can(ramx_dev *d, const KArgs &a, int L, bool multi, bool *can_out, int *block, int *blocks)
+// ---- the route of a direction -------------------------------------------------------------------
+// Decided once, at the top of ramx_dev_run_direction, and read by every later step.
+struct DirRoute
 {
-  const int W = a.W;
-  const int tiles = d->Np / 64;
-  int rc;
-  *block = 0; *blocks = 0;
-  bool can = !(getenv("RAMX_NO_PERSISTENT") != NULL || d->force_chain || a.go > 0 || a.ge > 0 || a.go + a.ge < -32768 ||
-               !prk_has_width(W) || L <= 0);
-  if (multi && (!d->peer_ready || d->nranks < 2 || L >= 65536 || getenv("RAMX_NO_PEER") != NULL)) can = false;
-  if (can)
+  bool tracing, multi;
+  bool mailbox_ok;                  // multi-rank: the vote can cross the devices through the mailboxes (true on one GPU)
+  bool int32_can; int block, blocks;                          // the int32 persistent rows can run here, and their launch shape
+  bool pk; int pk_r0, spread, rebase, pk_block, pk_blocks;    // the packed rows take the direction from row pk_r0 on
+  bool cp_try;                      // the cell-parallel attempt is made (multi-rank: its agreement is held even with k == 0 here)
+  int k, th, nb, vwf;               // its plan: lanes per flank (0: not on this rank), threads, workgroups, vote wave
+  bool pack_now;                    // the kernel that goes first reads the whole window: pack the rest before anything else
+};
+
+// The switches that move a direction from one kernel to another.  Read once per direction and never kept: the tests flip them
+// between two directions of one device.  (RAMX_NO_PK, RAMX_NO_CP and the value of RAMX_CP_K are read by the plans themselves.)
+struct RouteEnv { bool no_persistent, no_peer, no_pk_multi, no_cp_device, cp_k; int cp_maxn; };      // cp_maxn: RAMX_CP_DEVICE_MAXN, most flanks of a device-wide launch
+static RouteEnv route_env(void)
+{
+  const char *mx = getenv("RAMX_CP_DEVICE_MAXN");
+  return { getenv("RAMX_NO_PERSISTENT") != NULL, getenv("RAMX_NO_PEER") != NULL, getenv("RAMX_NO_PK_MULTI") != NULL,
+           getenv("RAMX_NO_CP_DEVICE") != NULL, getenv("RAMX_CP_K") != NULL, mx ? atoi(mx) : INT_MAX };
+}
+
+// Which kernels are admissible for this scoring system, band width, flank set, rank layout and these switches -- everything
+// that can be said without asking the device (no HIP call, no session): int32_can / pk still await their occupancy answers,
+// the cell-parallel plan the rule of RAMX_CP_MIN_K_OVER_PACKED (route_settle).
+static DirRoute route_gates(const RouteEnv &e, int W, int go, int ge, const int (&tab)[RAMX_NCLASS][4], int L, int Nx, int pk_r0,
+                            bool cp_flanks_ok, bool tracing, bool multi, bool peer_ready, int nranks, bool force_chain, int cus)
+{
+  DirRoute rt = {};
+  rt.tracing = tracing; rt.multi = multi;
+  rt.mailbox_ok = !multi || (peer_ready && nranks >= 2 && L < 65536 && !e.no_peer);
+  // any kernel that runs the whole direction in one launch (a trace wants a launch per row)
+  const bool single_launch = !tracing && !e.no_persistent && !force_chain && L > 0;
+  rt.int32_can = single_launch && rt.mailbox_ok && go <= 0 && ge <= 0 && go + ge >= -32768 && prk_has_width(W);
+  // The packed rows (ramx_kernels_packed.h): a scoring system whose rows fit int16 relative to a per-flank base.  (Multi-rank:
+  // the packed kernel speaks the same mailbox protocol as the int32 one, ramx_kernels_vote.h; which of the two a rank runs, from
+  // which row on and in how many pieces is that rank's own business.)
+  rt.pk_r0 = single_launch ? pk_r0 : -1;
+  rt.pk = rt.pk_r0 >= 0 && rt.pk_r0 < L && rt.mailbox_ok && !(multi && e.no_pk_multi) && ramx_pk_plan(W, go, ge, tab, &rt.spread, &rt.rebase) != 0;
+  // The cell-parallel kernel in device-wide mode: at most one workgroup per CU.  Multi-rank: every rank takes this route or none,
+  // so a rank with no flank of its own plans for one.
+  rt.cp_try = single_launch && rt.mailbox_ok && !e.no_cp_device && (multi || Nx > 0);
+  if (rt.cp_try && cp_flanks_ok && Nx <= e.cp_maxn && ramx_cp_max_family(W, go, ge, tab, L) > 0)
+    ramx_cp_device_plan(W, Nx > 0 ? Nx : 1, cus, 0, &rt.k, &rt.th, &rt.nb, &rt.vwf);
+  return rt;
+}
+
+// The rules that need the occupancy answers (rt.block / rt.pk_block of an admissible kernel; 0: its flank set is not co-resident).
+static void route_settle(DirRoute &rt, const RouteEnv &e, int Nx)
+{
+  rt.int32_can = rt.int32_can && rt.block != 0;          // not co-resident: keep the streaming kernel
+  // resident, and -- where flanks have low out-of-bounds cells in the first rows -- the int32 kernel for those rows
+  rt.pk = rt.pk && rt.pk_block != 0 && (rt.pk_r0 == 0 || rt.int32_can);
+  // Two lanes per flank (33,000-65,536 flanks at W = 40) against the packed-row kernel with one wave per SIMD, whole bench launch
+  // at 50,000 / 65,000 flanks: 5.44 / 5.55 against 4.76 / 4.66 us per column (aligned phase alike, the capped tail is the packed
+  // kernel's; profiles/r04_route_ab.log) -- where the packed rows can run they take those sets.
+  if (rt.k > 0 && rt.k < RAMX_CP_MIN_K_OVER_PACKED && !e.cp_k && rt.pk) rt.k = 0;
+  // Every route but the packed-row one reads base words of the whole window: it packs what begin_direction left (pack_rest).
+  // Multi-rank the route is agreed later; whichever kernel then needs the whole window packs the rest first.
+  rt.pack_now = rt.tracing || Nx <= 0 || !rt.pk || (!rt.multi && rt.k > 0);
+}
+
+// The route of the direction begun on d: the gates, then the occupancy questions of the admissible lane-per-flank kernels (each
+// asked once per process), and the rules that need their answers.
+static int direction_route(ramx_dev *d, const KArgs &a, int L, DirRoute *out)
+{
+  const RouteEnv e = route_env();
+  DirRoute rt = route_gates(e, a.W, a.go, a.ge, a.tab, L, d->Nx, d->pk_r0, d->cp_flanks_ok != 0, d->trace_cb != NULL || d->verbose_cb != NULL,
+                            dev_is_multi(d), d->peer_ready != 0, d->nranks, d->force_chain != 0, d->cus);
+  const int W = a.W, tiles = d->Np / 64;
+  if (rt.int32_can)
   {
-    rc = (W == 14) ? prk_plan<14>(tiles, block, blocks) : (W == 20) ? prk_plan<20>(tiles, block, blocks) :
-         (W == 40) ? prk_plan<40>(tiles, block, blocks) : prk_plan<80>(tiles, block, blocks);
+    const int rc = (W == 14) ? prk_plan<14>(tiles, d->cus, &rt.block, &rt.blocks) : (W == 20) ? prk_plan<20>(tiles, d->cus, &rt.block, &rt.blocks) :
+                   (W == 40) ? prk_plan<40>(tiles, d->cus, &rt.block, &rt.blocks) : prk_plan<80>(tiles, d->cus, &rt.block, &rt.blocks);
     if (rc != RAMX_OK) return rc;
-    if (*block == 0) can = false;          // not co-resident: keep the streaming kernel
   }
-  *can_out = can;
+  if (rt.pk && ramx_pk_shape(W, tiles, &rt.pk_block, &rt.pk_blocks) != RAMX_OK) { ramx_set_error("packed-row kernel: occupancy query failed"); return RAMX_ERR_HIP; }
+  route_settle(rt, e, d->Nx);
+  *out = rt;
   return RAMX_OK;
 }
 
-// Will the packed-row kernel (ramx_kernels_packed.h) take this direction (from row d->pk_r0 on)?  Single GPU, a scoring system whose
-// rows fit int16 relative to a per-flank base, the flank set resident, and -- where flanks have low out-of-bounds cells in the
-// first rows -- the int32 kernel for those rows.
-static int pk_route(ramx_dev *d, const KArgs &a, int L, bool multi, bool int32_can, bool *pk_out, int *spread, int *rebase, int *pk_block, int *pk_blocks)
+// ---- multi-rank: this rank's mailbox before a launch ----------------------------------------------
+// My box is cleared BEFORE the agreement that precedes the launch, which no remote launch can get past without my taking part:
+// nobody writes a word of this run into it too early, and nothing of the last run survives.  Complete, not just enqueued: the
+// agreement may be a host-only collective, and a peer that gets past it launches and writes into this box at once.
+static int mailbox_clear(ramx_dev *d)
 {
-  *pk_out = false; *pk_block = 0; *pk_blocks = 0;
-  const int pk_r0 = (getenv("RAMX_NO_PERSISTENT") != NULL || d->force_chain || L <= 0) ? -1 : d->pk_r0;
-  // (multi-rank: the packed kernel speaks the same mailbox protocol as the int32 one, ramx_kernels_vote.h; which of the two a rank
-  // runs, from which row on and in how many pieces is that rank's own business)
-  bool pk = pk_r0 >= 0 && pk_r0 < L && ramx_pk_plan(a.W, a.go, a.ge, a.tab, spread, rebase) != 0;
-  if (multi && (!d->peer_ready || d->nranks < 2 || L >= 65536 || getenv("RAMX_NO_PEER") != NULL || getenv("RAMX_NO_PK_MULTI") != NULL)) pk = false;
-  if (pk)
-  {
-    if (ramx_pk_shape(a.W, d->Np / 64, pk_block, pk_blocks) != RAMX_OK) { ramx_set_error("packed-row kernel: occupancy query failed"); return RAMX_ERR_HIP; }
-    if (*pk_block == 0 || (pk_r0 > 0 && !int32_can)) pk = false;
-  }
-  *pk_out = pk;
+  if (!d->hostbox_host) HIPCHK(hipMemsetAsync(d->xbox, 0, sizeof(PeerBox), d->stream));
+  HIPCHK(hipStreamSynchronize(d->stream));
+  if (d->hostbox_host) { memset((void *)d->hostbox_host, 0, sizeof(PeerBox)); __sync_synchronize(); }
   return RAMX_OK;
 }
 
-static int prk_run(ramx_dev *d, const KArgs &a, int L, bool *used)
+// host-memory boxes: the zeroed device copy of my box (kept current by block 0, polled by the others); NULL with device boxes
+static int mailbox_mirror(ramx_dev *d, PeerBox **mirror)
+{
+  *mirror = NULL;
+  if (!d->hostbox_host) return RAMX_OK;
+  if (!d->hostbox_mirror) HIPCHK(hipMalloc((void **)&d->hostbox_mirror, sizeof(PeerBox)));
+  HIPCHK(hipMemsetAsync(d->hostbox_mirror, 0, sizeof(PeerBox), d->stream));
+  *mirror = d->hostbox_mirror;
+  return RAMX_OK;
+}
+
+// both control blocks (a direction that ran in pieces leaves its last one in either) and the error word (a refused entry check,
+// a bounded spin that gave up) after a single-launch kernel
+static int read_launch_state(ramx_dev *d, RamxCtl c[2], unsigned *errw)
+{
+  unsigned long long ew = 0;
+  HIPCHK(hipStreamSynchronize(d->stream));
+  int rc = d2h_small(d, c, d->d_ctl, 2 * sizeof(RamxCtl));
+  if (rc == RAMX_OK) rc = d2h_small(d, &ew, d->d_err, sizeof(ew));
+  *errw = (unsigned)ew;
+  return rc;
+}
+
+#ifdef RAMX_PRK_TIMING
+// -DRAMX_PRK_TIMING builds: phase breakdown per column of the launch that has just run, in ns (wall_clock64 ticks are 10 ns)
+static int prk_timing_report(ramx_dev *d, unsigned long long *dbgbuf, size_t nw, bool pk, int block, int blocks, int L, int pk_r0)
+{
+  HIPCHK(hipStreamSynchronize(d->stream));
+  unsigned long long *h = (unsigned long long *)malloc(nw * 8 * sizeof(unsigned long long));
+  HIPCHK(hipMemcpy(h, dbgbuf, nw * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  static const char *nm[6] = { "wait vote", "block barrier 1", "band", pk ? "early arrival" : "reduce+barrier 2", pk ? "late arrival" : "issue atomics", "loop top" };
+  const int wpb = block / 64;
+  fprintf(stderr, "PRK_TIMING %s blocks %d x %d threads, L %d, first row %d (ns per column)\n", pk ? "packed rows" : "int32 rows", blocks, block, L, pk ? pk_r0 : 0);
+  for (int k = 0; k < 6; k++)
+  {
+    double s0 = 0, sO = 0, mx = 0, mn = 1e30;
+    for (size_t i = 0; i < nw; i++)
+    {
+      const double v = 10.0 * (double)h[i * 8 + k] / L;
+      if ((int)(i % wpb) == 0) s0 += v; else sO += v;
+      if (v > mx) mx = v;
+      if (v < mn) mn = v;
+    }
+    fprintf(stderr, "PRK_TIMING %-18s wave0 avg %8.1f  other waves avg %8.1f  min %8.1f  max %8.1f\n", nm[k], s0 / blocks,
+            wpb > 1 ? sO / (double)(nw - blocks) : 0.0, mn, mx);
+  }
+  fprintf(stderr, "PRK_TIMING band by wave index:");
+  for (int wv = 0; wv < wpb; wv++)
+  {
+    double sw = 0;
+    for (int b = 0; b < blocks - 1; b++) sw += 10.0 * (double)h[((size_t)b * wpb + wv) * 8 + 2] / L;
+    fprintf(stderr, " w%d %.0f", wv, sw / (blocks > 1 ? blocks - 1 : 1));
+  }
+  fprintf(stderr, "\n");
+  {
+    // the workgroup everybody waits for: the one whose vote wave waits least for the vote
+    int gb = 0;
+    for (int b = 1; b < blocks; b++) if (h[(size_t)b * wpb * 8 + 0] < h[(size_t)gb * wpb * 8 + 0]) gb = b;
+    fprintf(stderr, "PRK_TIMING workgroup %d (shortest vote wait), per wave: wait vote | barrier | band | early | late | top\n", gb);
+    for (int wv = 0; wv < wpb; wv++)
+    {
+      const unsigned long long *q = h + ((size_t)gb * wpb + wv) * 8;
+      fprintf(stderr, "PRK_TIMING   w%d %7.0f %7.0f %7.0f %7.0f %7.0f %7.0f   rows full %llu lean %llu\n", wv, 10.0 * q[0] / L, 10.0 * q[1] / L, 10.0 * q[2] / L,
+              10.0 * q[3] / L, 10.0 * q[4] / L, 10.0 * q[5] / L, q[6], q[7]);
+    }
+  }
+  {
+    // second half of the run: waves that were kept from the LEAN band, and by how many lanes
+    const double half = L - L / 2;
+    size_t never = 0, always = 0, wg_any = 0;
+    double lanes = 0, cols = 0;
+    int hist[6] = { 0, 0, 0, 0, 0, 0 };       // waves by average number of such lanes in their non-lean columns: <=1, <=2, <=4, <=8, <=16, more
+    for (int b = 0; b < blocks; b++)
+    {
+      bool any = false;
+      for (int wv = 0; wv < wpb; wv++)
+      {
+        const size_t i = (size_t)b * wpb + wv;
+        const double c = (double)h[i * 8 + 6], l = (double)h[i * 8 + 7];
+        if (c == 0) { never++; continue; }
+        any = any || c > 0.5 * half;
+        if (c > 0.9 * half) always++;
+        lanes += l; cols += c;
+        const double avg = l / c;
+        hist[avg <= 1 ? 0 : avg <= 2 ? 1 : avg <= 4 ? 2 : avg <= 8 ? 3 : avg <= 16 ? 4 : 5]++;
+      }
+      if (any) wg_any++;
+    }
+    fprintf(stderr, "PRK_LEANSTAT second half (%.0f columns): %zu of %zu waves always LEAN, %zu non-LEAN in > 90 %% of the columns; workgroups with a wave "
+            "non-LEAN in > 50 %%: %zu of %d; lanes per non-LEAN wave-column %.2f; waves by that average <=1: %d <=2: %d <=4: %d <=8: %d <=16: %d more: %d\n",
+            half, never, nw, always, wg_any, blocks, cols > 0 ? lanes / cols : 0.0, hist[0], hist[1], hist[2], hist[3], hist[4], hist[5]);
+  }
+  free(h);
+  (void)hipFree(dbgbuf);
+  return RAMX_OK;
+}
+#endif
+
+// The lane-per-flank persistent kernels on the route rt: the int32 rows, the packed rows, or the packed rows behind first rows
+// on the int32 kernel.  Multi-rank only the agreement here can still turn the int32 rows off.
+static int prk_run(ramx_dev *d, const KArgs &a, int L, DirRoute &rt, bool *used)
 {
   *used = false;
   const int W = a.W;
-  const bool multi = dev_is_multi(d);
-  int block = 0, blocks = 0, rc;
-  bool can = false;
-  if ((rc = prk_local_can(d, a, L, multi, &can, &block, &blocks)) != RAMX_OK) return rc;
+  const bool multi = rt.multi;
+  int rc;
   if (multi)
   {
     // every rank must take the same path: agree (max over ranks of "cannot")
-    int cannot = can ? 0 : 1;
+    int cannot = rt.int32_can ? 0 : 1;
     if ((rc = host_allreduce_flag(d, &cannot)) != RAMX_OK) return rc;
-    can = !cannot;
+    rt.int32_can = !cannot;
   }
-  const bool int32_can = can;
-  const int pk_r0 = (getenv("RAMX_NO_PERSISTENT") != NULL || d->force_chain || L <= 0) ? -1 : d->pk_r0;
-  if (!can && (multi || pk_r0 < 0)) return RAMX_OK;
+  const bool pk = rt.pk;
+  const int pk_r0 = rt.pk_r0, pk_block = rt.pk_block, pk_blocks = rt.pk_blocks;
+  int block = rt.block, blocks = rt.blocks;
+  if (!rt.int32_can && (multi || !pk)) return RAMX_OK;
   *used = true;        // agreed (multi-rank: by all ranks): from here on the caller handles a local failure collectively
   PArgs pa;
   memset(&pa, 0, sizeof(pa));
@@ -890,35 +1041,10 @@ static int prk_run(ramx_dev *d, const KArgs &a, int L, bool *used)
   if (multi)
   {
     pa.nranks = d->nranks; pa.rank = d->rank; pa.peers = (PeerBox *const *)d->d_peer; pa.box = d->xbox;
-    pa.mirror = NULL;
     // Rank-local steps first, WITHOUT leaving on an error: the collective below is executed by every rank in any case
     // (a rank that skipped it would pair its next collective with this one on the other ranks).
-    auto local_prep = [&]() -> int
-    {
-      if (d->hostbox_host)
-      {
-        if (!d->hostbox_mirror) HIPCHK(hipMalloc((void **)&d->hostbox_mirror, sizeof(PeerBox)));
-        HIPCHK(hipMemsetAsync(d->hostbox_mirror, 0, sizeof(PeerBox), d->stream));
-        pa.mirror = d->hostbox_mirror;
-      }
-      // my box is cleared BEFORE the collective below, which no remote launch can get past without my taking part:
-      // nobody writes a word of this run into it too early, and nothing of the last run survives
-      if (d->hostbox_host)
-      {
-        HIPCHK(hipStreamSynchronize(d->stream));
-        memset((void *)d->hostbox_host, 0, sizeof(PeerBox));
-        __sync_synchronize();
-      }
-      else
-      {
-        // complete, not just enqueued: the agreement below may be a host-only collective, and a peer that gets past it
-        // launches and writes into this box at once
-        HIPCHK(hipMemsetAsync(d->xbox, 0, sizeof(PeerBox), d->stream));
-        HIPCHK(hipStreamSynchronize(d->stream));
-      }
-      return RAMX_OK;
-    };
-    const int lrc = local_prep();
+    int lrc = mailbox_mirror(d, &pa.mirror);
+    if (lrc == RAMX_OK) lrc = mailbox_clear(d);
     if ((rc = host_allreduce_shards(d, d->d_sums)) != RAMX_OK) return rc;     // vote of row 0 (from K(-1)) over ranks
     if (lrc != RAMX_OK) return lrc;
     // test hook: RAMX_TEST_FAIL_PRK_RANK=<rank> makes that rank fail where a launch error would
@@ -937,10 +1063,7 @@ static int prk_run(ramx_dev *d, const KArgs &a, int L, bool *used)
   // out-of-bounds cells at the LOW end of the band there) stay on this kernel, which hands over the sums of row r0 --------
   PKArgs ka;
   memset(&ka, 0, sizeof(ka));
-  int pk_block = 0, pk_blocks = 0;
-  bool pk = false;
-  if ((rc = pk_route(d, a, L, multi, int32_can, &pk, &ka.spread, &ka.rebase, &pk_block, &pk_blocks)) != RAMX_OK) return rc;
-  if (!pk && !int32_can) { *used = false; return RAMX_OK; }
+  ka.spread = rt.spread; ka.rebase = rt.rebase;
   if (!pk && (rc = pack_rest(d)) != RAMX_OK) return rc;        // the int32 kernel reads the whole window
   HIPCHK(hipMemsetAsync(d->d_vote, 0, PRK_NSETS * NSHARD * sizeof(PShard), d->stream));
   HIPCHK(hipMemsetAsync(d->d_err, 0, 64, d->stream));
@@ -1033,17 +1156,13 @@ static int prk_run(ramx_dev *d, const KArgs &a, int L, bool *used)
         d->packed_kw = words_for(r2);
       }
       // did this piece end the direction?  (one synchronisation per piece: 2,048 columns)
-      RamxCtl hc;
+      RamxCtl c2[2];
       unsigned errw = 0;
       HIPCHK(hipStreamSynchronize(d->stream));
       if (tmarks) fprintf(stderr, "RAMX_TIMING       run: piece %d complete %.3f ms after the first launch\n", s_i, now_ms() - tm0);
-      {
-        unsigned long long ew = 0;
-        if ((rc = d2h_small(d, &hc, d->d_ctl + out_i, sizeof(hc))) != RAMX_OK) break;
-        if ((rc = d2h_small(d, &ew, d->d_err, sizeof(ew))) != RAMX_OK) break;
-        errw = (unsigned)ew;
-      }
+      if ((rc = read_launch_state(d, c2, &errw)) != RAMX_OK) break;
       rt_mark("piece: control block and error word read");
+      const RamxCtl &hc = c2[out_i];
       if (hc.stopped || hc.pad != 0 || errw != 0 || hc.rows_done < r1) break;
       sums_in = sbuf[nextbuf]; nextbuf ^= 1; ctl_i = out_i; r = r1;
     }
@@ -1052,77 +1171,7 @@ static int prk_run(ramx_dev *d, const KArgs &a, int L, bool *used)
   }
   else d->last_packed_r0 = -1;
 #ifdef RAMX_PRK_TIMING
-  if (rc == RAMX_OK)
-  {
-    // debug build: phase breakdown per column, in ns (wall_clock64 ticks are 10 ns)
-    HIPCHK(hipStreamSynchronize(d->stream));
-    unsigned long long *h = (unsigned long long *)malloc(nw * 8 * sizeof(unsigned long long));
-    HIPCHK(hipMemcpy(h, dbgbuf, nw * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    static const char *nm[6] = { "wait vote", "block barrier 1", "band", pk ? "early arrival" : "reduce+barrier 2", pk ? "late arrival" : "issue atomics", "loop top" };
-    const int wpb = block / 64;
-    fprintf(stderr, "PRK_TIMING %s blocks %d x %d threads, L %d, first row %d (ns per column)\n", pk ? "packed rows" : "int32 rows", blocks, block, L, pk ? pk_r0 : 0);
-    for (int k = 0; k < 6; k++)
-    {
-      double s0 = 0, sO = 0, mx = 0, mn = 1e30;
-      for (size_t i = 0; i < nw; i++)
-      {
-        const double v = 10.0 * (double)h[i * 8 + k] / L;
-        if ((int)(i % wpb) == 0) s0 += v; else sO += v;
-        if (v > mx) mx = v;
-        if (v < mn) mn = v;
-      }
-      fprintf(stderr, "PRK_TIMING %-18s wave0 avg %8.1f  other waves avg %8.1f  min %8.1f  max %8.1f\n", nm[k], s0 / blocks,
-              wpb > 1 ? sO / (double)(nw - blocks) : 0.0, mn, mx);
-    }
-    fprintf(stderr, "PRK_TIMING band by wave index:");
-    for (int wv = 0; wv < wpb; wv++)
-    {
-      double sw = 0;
-      for (int b = 0; b < blocks - 1; b++) sw += 10.0 * (double)h[((size_t)b * wpb + wv) * 8 + 2] / L;
-      fprintf(stderr, " w%d %.0f", wv, sw / (blocks > 1 ? blocks - 1 : 1));
-    }
-    fprintf(stderr, "\n");
-    {
-      // the workgroup everybody waits for: the one whose vote wave waits least for the vote
-      int gb = 0;
-      for (int b = 1; b < blocks; b++) if (h[(size_t)b * wpb * 8 + 0] < h[(size_t)gb * wpb * 8 + 0]) gb = b;
-      fprintf(stderr, "PRK_TIMING workgroup %d (shortest vote wait), per wave: wait vote | barrier | band | early | late | top\n", gb);
-      for (int wv = 0; wv < wpb; wv++)
-      {
-        const unsigned long long *q = h + ((size_t)gb * wpb + wv) * 8;
-        fprintf(stderr, "PRK_TIMING   w%d %7.0f %7.0f %7.0f %7.0f %7.0f %7.0f   rows full %llu lean %llu\n", wv, 10.0 * q[0] / L, 10.0 * q[1] / L, 10.0 * q[2] / L,
-                10.0 * q[3] / L, 10.0 * q[4] / L, 10.0 * q[5] / L, q[6], q[7]);
-      }
-    }
-    {
-      // second half of the run: waves that were kept from the LEAN band, and by how many lanes
-      const double half = L - L / 2;
-      size_t never = 0, always = 0, wg_any = 0;
-      double lanes = 0, cols = 0;
-      int hist[6] = { 0, 0, 0, 0, 0, 0 };       // waves by average number of such lanes in their non-lean columns: <=1, <=2, <=4, <=8, <=16, more
-      for (int b = 0; b < blocks; b++)
-      {
-        bool any = false;
-        for (int wv = 0; wv < wpb; wv++)
-        {
-          const size_t i = (size_t)b * wpb + wv;
-          const double c = (double)h[i * 8 + 6], l = (double)h[i * 8 + 7];
-          if (c == 0) { never++; continue; }
-          any = any || c > 0.5 * half;
-          if (c > 0.9 * half) always++;
-          lanes += l; cols += c;
-          const double avg = l / c;
-          hist[avg <= 1 ? 0 : avg <= 2 ? 1 : avg <= 4 ? 2 : avg <= 8 ? 3 : avg <= 16 ? 4 : 5]++;
-        }
-        if (any) wg_any++;
-      }
-      fprintf(stderr, "PRK_LEANSTAT second half (%.0f columns): %zu of %zu waves always LEAN, %zu non-LEAN in > 90 %% of the columns; workgroups with a wave "
-              "non-LEAN in > 50 %%: %zu of %d; lanes per non-LEAN wave-column %.2f; waves by that average <=1: %d <=2: %d <=4: %d <=8: %d <=16: %d more: %d\n",
-              half, never, nw, always, wg_any, blocks, cols > 0 ? lanes / cols : 0.0, hist[0], hist[1], hist[2], hist[3], hist[4], hist[5]);
-    }
-    free(h);
-    (void)hipFree(dbgbuf);
-  }
+  if (rc == RAMX_OK) rc = prk_timing_report(d, dbgbuf, nw, pk, block, blocks, L, pk_r0);
 #endif
   return rc;
 }
@@ -1198,13 +1247,10 @@ static int run_families_pass(ramx_dev *d, const ramx_flank *flanks, int32_t n_pa
   // Families above one cell-parallel workgroup (group -1): several workgroups per family, the family's vote through its
   // own ticket words -- the device-wide mode of the same kernel, all such families in ONE launch of at most one
   // workgroup per CU (every workgroup must be resident).
-  int n_cp = 0, n_dev = 0, dev_k = 0, dev_threads = 0, dev_vw = 0, cus = 0;
+  int n_cp = 0, n_dev = 0, dev_k = 0, dev_threads = 0, dev_vw = 0;
+  const int cus = d->cus;
   std::vector<CpDevDesc> hdev;
   std::vector<int> dev_round_first, dev_round_blocks;   // rounds of at most `cus` workgroups, launched one after the other
-  {
-    int devo = 0;
-    if (hipGetDevice(&devo) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, devo) != hipSuccess) cus = 0;
-  }
   const bool dev_route = allow_dev && cp_max > 0 && cus > 0 && getenv("RAMX_NO_CP_DEVICE") == NULL && getenv("RAMX_NO_PERSISTENT") == NULL;
   // small workgroups (four band waves, lowest latency) when all the multi-workgroup families then fit the CUs together
   int dev_wide = 0;
@@ -2607,403 +2653,312 @@ extern "C" int ramx_dev_refine(ramx_dev *d, const ramx_flank *flanks, int32_t n_
   return RAMX_OK;
 }
 
-extern "C" int ramx_dev_run_direction(ramx_dev *d, ramx_run_info *info)
-{
-  if (!d || !d->ready) { ramx_set_error("ramx_dev_run_direction: begin_direction has not been called"); return RAMX_ERR_STATE; }
-  HIPCHK(hipSetDevice(d->ordinal));
-  const ramx_params &p = d->p;
-  const int L = p.L;
-  KArgs a;
-  memset(&a, 0, sizeof(a));
-  a.bases = d->d_bases; a.bounds = d->d_bounds; a.trim = d->d_trim; a.cons_out = d->d_cons;
-  a.Np = d->Np; a.Nx = d->Nx; a.W = p.bandwidth; a.go = p.gapopen; a.ge = p.gapextn; a.cap = p.cappenalty;
-  a.minimp = p.minimprovement; a.when_to_stop = p.when_to_stop;
-  memcpy(a.tab, d->tab, sizeof(a.tab));
-  const bool multi = dev_is_multi(d);
+// ---- ramx_dev_run_direction and its steps -----------------------------------------------------------
+static long long *sums_slot(ramx_dev *d, int r) { return d->d_sums + (size_t)(((r % 3) + 3) % 3) * NSHARD * 4; }
 
-  auto slot = [&](int r) { return d->d_sums + (size_t)(((r % 3) + 3) % 3) * NSHARD * 4; };
-  int launches = 0, nsamp = 0, pending = -1, chk = 0, lanes = 1, prk_local_rc = RAMX_OK;
-  bool persistent = false;
-  // ---- cell-parallel route (single GPU): K lanes per flank, the whole direction in one cooperative launch of at most one
-  // workgroup per CU; boundary row and every column inside the kernel ---------------------------------------------------
-  const bool tracing = d->trace_cb != NULL || d->verbose_cb != NULL;
-  const bool verbose_trace = d->verbose_cb != NULL;
-  const int Bt = 2 * p.bandwidth + 1;
-  // hands the DBG buffers of the launch that has just completed to the callbacks
-  auto deliver_trace = [&](int r, int besta) -> int
+// -outmat / -vvvv: the DBG buffers a traced column launch writes
+static int trace_buffers(ramx_dev *d, KArgs &ka)
+{
+  const int Bt = 2 * d->p.bandwidth + 1;
+  int trc;
+  if ((trc = ensure(&d->d_dbg_best, &d->cap_dbg_best, (size_t)d->Np * sizeof(int2))) != RAMX_OK) return trc;
+  ka.dbg_best = d->d_dbg_best;
+  ka.dbg_codes = NULL; ka.dbg_cand = NULL; ka.dbg_gap = NULL; ka.dbg_band = NULL;
+  if (d->trace_cb)
   {
-    std::vector<int8_t> codes;
-    std::vector<int2> best((size_t)d->Nx + 1), gaps((size_t)d->Nx + 1);
-    std::vector<int32_t> bs((size_t)d->Nx + 1), bi((size_t)d->Nx + 1), gfl(2 * (size_t)d->Nx + 2), cand(16 * (size_t)d->Nx + 16);
-    if (d->Nx && r >= 0) HIPCHK(hipMemcpy(best.data(), d->d_dbg_best, (size_t)d->Nx * sizeof(int2), hipMemcpyDeviceToHost));
-    for (int i = 0; i < d->Nx; i++) { bs[i] = best[i].x; bi[i] = best[i].y; }
-    if (d->trace_cb && r >= 0)
-    {
-      codes.resize((size_t)d->Nx * Bt + 1);
-      if (d->Nx) HIPCHK(hipMemcpy(codes.data(), d->d_dbg_codes, (size_t)d->Nx * Bt, hipMemcpyDeviceToHost));
-      d->trace_cb(r, besta, codes.data(), bs.data(), bi.data(), d->trace_user);
-    }
-    if (d->verbose_cb)
-    {
-      if (d->Nx)
-      {
-        HIPCHK(hipMemcpy(cand.data(), d->d_dbg_cand, (size_t)d->Nx * 16 * sizeof(int), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(gaps.data(), d->d_dbg_gap, (size_t)d->Nx * sizeof(int2), hipMemcpyDeviceToHost));
-      }
-      for (int i = 0; i < d->Nx; i++) { gfl[2 * i] = gaps[i].x; gfl[2 * i + 1] = gaps[i].y; }
-      std::vector<int32_t> band;
-      if (d->verbose_band && d->Nx)
-      {
-        band.resize((size_t)d->Nx * 8 * Bt);
-        HIPCHK(hipMemcpy(band.data(), d->d_dbg_band, band.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-      }
-      d->verbose_cb(r, besta, d->Nx, bs.data(), bi.data(), gfl.data(), cand.data(), band.empty() ? NULL : band.data(), d->verbose_user);
-    }
-    return RAMX_OK;
-  };
-  auto trace_buffers = [&](KArgs &ka) -> int
-  {
-    int trc;
-    if ((trc = ensure(&d->d_dbg_best, &d->cap_dbg_best, (size_t)d->Np * sizeof(int2))) != RAMX_OK) return trc;
-    ka.dbg_best = d->d_dbg_best;
-    ka.dbg_codes = NULL; ka.dbg_cand = NULL; ka.dbg_gap = NULL; ka.dbg_band = NULL;
-    if (d->trace_cb)
-    {
-      if ((trc = ensure(&d->d_dbg_codes, &d->cap_dbg_codes, (size_t)d->Np * Bt)) != RAMX_OK) return trc;
-      ka.dbg_codes = d->d_dbg_codes;
-    }
-    if (verbose_trace)
-    {
-      if ((trc = ensure(&d->d_dbg_cand, &d->cap_dbg_cand, (size_t)d->Np * 16 * sizeof(int))) != RAMX_OK) return trc;
-      if ((trc = ensure(&d->d_dbg_gap, &d->cap_dbg_gap, (size_t)d->Np * sizeof(int2))) != RAMX_OK) return trc;
-      ka.dbg_cand = d->d_dbg_cand; ka.dbg_gap = d->d_dbg_gap;
-      if (d->verbose_band)
-      {
-        if ((trc = ensure(&d->d_dbg_band, &d->cap_dbg_band, (size_t)d->Np * 8 * Bt * sizeof(int))) != RAMX_OK) return trc;
-        ka.dbg_band = d->d_dbg_band;
-      }
-    }
-    return RAMX_OK;
-  };
-  // Multi-rank: the vote crosses the devices through the mailboxes (ramx_dev_peer_* set-up), exactly as in the
-  // lane-per-flank persistent kernel; every rank must take this route or none (one agreement before, one after).
-  // every route but the packed-row one reads base words of the whole window: pack what begin_direction left (pack_rest)
-  rt_mark(NULL);
-  {
-    bool lazy = false;
-    if (!tracing && d->Nx > 0)
-    {
-      int blk = 0, blks = 0, sp = 0, rb = 0, pb = 0, pbs = 0;
-      bool can32 = false;
-      int lrc = prk_local_can(d, a, L, multi, &can32, &blk, &blks);
-      if (lrc != RAMX_OK) return lrc;
-      if ((lrc = pk_route(d, a, L, multi, can32, &lazy, &sp, &rb, &pb, &pbs)) != RAMX_OK) return lrc;
-      // (the device-wide cell-parallel kernel goes first where it applies: it takes the whole window)
-      // (multi-rank: the route is agreed below; whichever kernel then needs the whole window packs the rest first)
-      if (lazy && !multi && d->cp_flanks_ok && getenv("RAMX_NO_CP_DEVICE") == NULL && ramx_cp_max_family(a.W, a.go, a.ge, d->tab, L) > 0)
-      {
-        int dev = 0, cus = 0, k = 0, th = 0, nb = 0, vwf = 0;
-        HIPCHK(hipGetDevice(&dev));
-        HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        const char *mx = getenv("RAMX_CP_DEVICE_MAXN");
-        if (mx == NULL || d->Nx <= atoi(mx)) ramx_cp_device_plan(a.W, d->Nx, cus, 0, &k, &th, &nb, &vwf);
-        if (k > 0 && k < RAMX_CP_MIN_K_OVER_PACKED && getenv("RAMX_CP_K") == NULL) k = 0;      // (the packed-row kernel is the faster one there, see below)
-        if (k > 0) lazy = false;
-      }
-    }
-    if (!lazy) { const int prc = pack_rest(d); if (prc != RAMX_OK) return prc; }
+    if ((trc = ensure(&d->d_dbg_codes, &d->cap_dbg_codes, (size_t)d->Np * Bt)) != RAMX_OK) return trc;
+    ka.dbg_codes = d->d_dbg_codes;
   }
-  rt_mark("route (occupancy answers)");
-  const bool cp_multi_ok = !multi || (d->peer_ready && d->nranks >= 2 && L < 65536 && getenv("RAMX_NO_PEER") == NULL);
-  if (!tracing && cp_multi_ok && !d->force_chain && L > 0 && getenv("RAMX_NO_PERSISTENT") == NULL && getenv("RAMX_NO_CP_DEVICE") == NULL &&
-      (multi || d->Nx > 0))
+  if (d->verbose_cb)
   {
-    int dev = 0, cus = 0, k = 0, th = 0, nb = 0, vwf = 0;
-    HIPCHK(hipGetDevice(&dev));
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const char *mx = getenv("RAMX_CP_DEVICE_MAXN");
-    if (d->cp_flanks_ok && ramx_cp_max_family(a.W, a.go, a.ge, d->tab, L) > 0 && (mx == NULL || d->Nx <= atoi(mx)))
-      ramx_cp_device_plan(a.W, d->Nx > 0 ? d->Nx : 1, cus, 0, &k, &th, &nb, &vwf);
-    if (k > 0 && k < RAMX_CP_MIN_K_OVER_PACKED && getenv("RAMX_CP_K") == NULL)
+    if ((trc = ensure(&d->d_dbg_cand, &d->cap_dbg_cand, (size_t)d->Np * 16 * sizeof(int))) != RAMX_OK) return trc;
+    if ((trc = ensure(&d->d_dbg_gap, &d->cap_dbg_gap, (size_t)d->Np * sizeof(int2))) != RAMX_OK) return trc;
+    ka.dbg_cand = d->d_dbg_cand; ka.dbg_gap = d->d_dbg_gap;
+    if (d->verbose_band)
     {
-      // Two lanes per flank (33,000-65,536 flanks at W = 40) against the packed-row kernel with one wave per SIMD, whole bench launch
-      // at 50,000 / 65,000 flanks: 5.44 / 5.55 against 4.76 / 4.66 us per column (aligned phase alike, the capped tail is the packed
-      // kernel's; profiles/r04_route_ab.log) -- where the packed rows can run they take those sets.
-      int blk = 0, blks = 0, sp = 0, rb = 0, pb = 0, pbs = 0;
-      bool can32 = false, pkq = false;
-      int lrc = prk_local_can(d, a, L, multi, &can32, &blk, &blks);
-      if (lrc != RAMX_OK) return lrc;
-      if ((lrc = pk_route(d, a, L, multi, can32, &pkq, &sp, &rb, &pb, &pbs)) != RAMX_OK) return lrc;
-      if (pkq) k = 0;
-    }
-    if (multi)
-    {
-      // my mailbox is cleared BEFORE the agreement, which no remote launch can get past without my taking part
-      if (d->hostbox_host)
-      {
-        HIPCHK(hipStreamSynchronize(d->stream));
-        memset((void *)d->hostbox_host, 0, sizeof(PeerBox));
-        __sync_synchronize();
-      }
-      else
-      {
-        // complete, not just enqueued: the agreement below may be a host-only collective, and a peer that gets past it
-        // launches and writes into this box at once
-        HIPCHK(hipMemsetAsync(d->xbox, 0, sizeof(PeerBox), d->stream));
-        HIPCHK(hipStreamSynchronize(d->stream));
-      }
-      int cannot = k > 0 ? 0 : 1;
-      int arc = host_allreduce_flag(d, &cannot);
-      if (arc != RAMX_OK) return arc;
-      if (cannot) k = 0;
-    }
-    if (k > 0)
-    {
-      // from here on a multi-rank run never leaves before the second agreement (a rank that did would leave the others'
-      // kernels spinning to their limit and then waiting in a collective it never joins)
-      int lrc = RAMX_OK;
-      bool accepted = false;      // the launch call went through
-      auto launch = [&]() -> int
-      {
-        { const int prc = pack_rest(d); if (prc != RAMX_OK) return prc; }      // this kernel reads the whole window
-        CPArgs ca;
-        memset(&ca, 0, sizeof(ca));
-        ca.bases = d->d_bases; ca.bounds = d->d_bounds; ca.trim = d->d_trim; ca.ctl_out = d->d_ctl; ca.cons_out = d->d_cons;
-        ca.Np = d->Np; ca.KW = d->KW; ca.L = L; ca.go = a.go; ca.ge = a.ge; ca.cap = a.cap; ca.minimp = a.minimp; ca.when_to_stop = a.when_to_stop;
-        memcpy(ca.tab, d->tab, sizeof(ca.tab));
-        {
-          std::vector<CpDevDesc> hd((size_t)nb);
-          for (int i = 0; i < nb; i++) { memset(&hd[i], 0, sizeof(CpDevDesc)); hd[i].first = 0; hd[i].nx = d->Nx; hd[i].b = i; hd[i].nb = nb; hd[i].id = 0; }
-          int drc = ensure(&d->d_devdesc, &d->cap_devdesc, sizeof(CpDevDesc) * (size_t)nb);
-          if (drc != RAMX_OK) return drc;
-          HIPCHK(hipMemcpyAsync(d->d_devdesc, hd.data(), sizeof(CpDevDesc) * (size_t)nb, hipMemcpyHostToDevice, d->stream));
-          HIPCHK(hipStreamSynchronize(d->stream));       // hd goes out of scope
-        }
-        ca.dev = d->d_devdesc; ca.vote = d->d_vote; ca.err = d->d_err; ca.S = d->d_state[0]; ca.vote_wave = vwf;
-        { const char *td = getenv("RAMX_TEST_CP_DROP_TICKET"); ca.test_drop_row = td ? atoi(td) : 0; ca.test_drop_id = -1; }
-        cp_test_hooks(ca);
-        ca.nranks = 1; ca.rank = 0;
-        if (multi)
-        {
-          ca.nranks = d->nranks; ca.rank = d->rank; ca.peers = (PeerBox *const *)d->d_peer; ca.box = d->xbox; ca.mirror = NULL;
-          if (d->hostbox_host)
-          {
-            if (!d->hostbox_mirror) HIPCHK(hipMalloc((void **)&d->hostbox_mirror, sizeof(PeerBox)));
-            HIPCHK(hipMemsetAsync(d->hostbox_mirror, 0, sizeof(PeerBox), d->stream));
-            ca.mirror = d->hostbox_mirror;
-          }
-          const char *tf = getenv("RAMX_TEST_FAIL_PRK_RANK");      // test hook: this rank fails where a launch error would
-          if (tf && atoi(tf) == d->rank) { ramx_set_error("test hook: forced failure of the cell-parallel launch on rank %d", d->rank); return RAMX_ERR_HIP; }
-        }
-        HIPCHK(hipMemsetAsync(d->d_vote, 0, RAMX_CP_NSETS * NSHARD * sizeof(PShard), d->stream));
-        HIPCHK(hipMemsetAsync(d->d_err, 0, 64, d->stream));
-        HIPCHK(hipMemsetAsync(d->d_ctl, 0, 2 * sizeof(RamxCtl), d->stream));
-#ifdef RAMX_CP_TIMING
-        HIPCHK(hipMalloc((void **)&ca.dbg, (16 * 16 + 8) * sizeof(unsigned long long)));
-        HIPCHK(hipMemset(ca.dbg, 0, (16 * 16 + 8) * sizeof(unsigned long long)));
-#endif
-        HIPCHK(hipEventRecord(d->ev_begin, d->stream));
-        if (multi) test_delay_rank(d);
-        int crc = ramx_cp_launch_device(d->stream, a.W, k, th, nb, ca);
-        if (crc != RAMX_OK)
-        {
-#ifdef RAMX_CP_TIMING
-          (void)hipFree(ca.dbg);
-#endif
-          ramx_set_error("cell-parallel device launch failed (W %d, %d lanes per flank, %d workgroups)", a.W, k, nb);
-          return crc;
-        }
-        accepted = true;          // from here on an error is the kernel's (an execution error: not something another route can serve)
-        HIPCHK(hipEventRecord(d->ev_end, d->stream));
-        HIPCHK(hipStreamSynchronize(d->stream));
-#ifdef RAMX_CP_TIMING
-        if (vwf)
-        {
-          unsigned long long h[16 * 16 + 8];
-          HIPCHK(hipMemcpy(h, ca.dbg, sizeof(h), hipMemcpyDeviceToHost));
-          const double cols = h[16 * 16] ? (double)h[16 * 16] : 1.0;
-          fprintf(stderr, "SP_TIMING workgroup 0, %d workgroups x %d threads, K %d, %.0f rows; shader clocks (100 MHz) per row\n", nb, th, k, cols);
-          fprintf(stderr, "SP_TIMING vote wave: tickets wait+fold %.1f | winner+forward %.1f | stop rule, decision %.1f | loop %.1f | waiting for band sums %.1f | forwarded at once %.0f %%\n",
-                  h[0] / cols, h[1] / cols, h[2] / cols, h[3] / cols, h[4] / cols, 100.0 * h[5] / cols);
-          for (int wv = 1; wv < th / 64; wv++)
-            fprintf(stderr, "SP_TIMING band wave %d: idle %.1f | planning %.1f | rows %.1f\n", wv, h[wv * 16 + 0] / cols, h[wv * 16 + 1] / cols, h[wv * 16 + 2] / cols);
-        }
-        (void)hipFree(ca.dbg);
-#endif
-        return RAMX_OK;
-      };
-      lrc = launch();
-      RamxCtl c0;
-      memset(&c0, 0, sizeof(c0));
-      int bad = lrc != RAMX_OK;
-      if (!bad && hipMemcpy(&c0, d->d_ctl, sizeof(c0), hipMemcpyDeviceToHost) != hipSuccess) bad = 1;
-      bad = bad || c0.pad != 0;
-      if (multi)
-      {
-        if (lrc != RAMX_OK) (void)hipStreamSynchronize(d->stream);
-        int frc = host_allreduce_flag(d, &bad);
-        if (frc != RAMX_OK) return frc;
-        if (bad)
-        {
-          fprintf(stderr, "ramx: cross-device cell-parallel launch gave up or failed on some rank; repeating the direction with per-column "
-                          "launches and leaving the mailbox path off for the rest of this process\n");
-          d->peer_ready = 0;        // agreed by all ranks (the flag above is reduced)
-        }
-      }
-      else if (lrc != RAMX_OK && accepted)
-        return lrc;               // the kernel ran and failed (a fault is sticky: the context is gone): the error as it was reported
-      else if (lrc != RAMX_OK)
-      {
-        // single GPU: the other routes can serve the same flank set -- an occupancy query that says no, a launch configuration
-        // this one instantiation refuses -- so a refusal here is not the direction's failure
-        (void)hipStreamSynchronize(d->stream);
-        (void)hipGetLastError();
-        fprintf(stderr, "ramx: cell-parallel device launch not possible (%s); continuing on the lane-per-flank route\n", ramx_last_error());
-      }
-      else if (bad)
-        fprintf(stderr, "ramx: device-wide vote of the cell-parallel launch timed out (bounded spin); repeating the direction with "
-                        "per-column launches\n");
-      if (!bad) { persistent = true; lanes = k; launches = 1; }
+      if ((trc = ensure(&d->d_dbg_band, &d->cap_dbg_band, (size_t)d->Np * 8 * Bt * sizeof(int))) != RAMX_OK) return trc;
+      ka.dbg_band = d->d_dbg_band;
     }
   }
-  const bool cp_done = persistent;
-  rt_mark("cell-parallel plan / launch");
-  if (!cp_done)
+  return RAMX_OK;
+}
+
+// hands the DBG buffers of the launch that has just completed to the callbacks
+static int deliver_trace(ramx_dev *d, int r, int besta)
+{
+  const int Bt = 2 * d->p.bandwidth + 1;
+  std::vector<int8_t> codes;
+  std::vector<int2> best((size_t)d->Nx + 1), gaps((size_t)d->Nx + 1);
+  std::vector<int32_t> bs((size_t)d->Nx + 1), bi((size_t)d->Nx + 1), gfl(2 * (size_t)d->Nx + 2), cand(16 * (size_t)d->Nx + 16);
+  if (d->Nx && r >= 0) HIPCHK(hipMemcpy(best.data(), d->d_dbg_best, (size_t)d->Nx * sizeof(int2), hipMemcpyDeviceToHost));
+  for (int i = 0; i < d->Nx; i++) { bs[i] = best[i].x; bi[i] = best[i].y; }
+  if (d->trace_cb && r >= 0)
   {
+    codes.resize((size_t)d->Nx * Bt + 1);
+    if (d->Nx) HIPCHK(hipMemcpy(codes.data(), d->d_dbg_codes, (size_t)d->Nx * Bt, hipMemcpyDeviceToHost));
+    d->trace_cb(r, besta, codes.data(), bs.data(), bi.data(), d->trace_user);
+  }
+  if (d->verbose_cb)
+  {
+    if (d->Nx)
+    {
+      HIPCHK(hipMemcpy(cand.data(), d->d_dbg_cand, (size_t)d->Nx * 16 * sizeof(int), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(gaps.data(), d->d_dbg_gap, (size_t)d->Nx * sizeof(int2), hipMemcpyDeviceToHost));
+    }
+    for (int i = 0; i < d->Nx; i++) { gfl[2 * i] = gaps[i].x; gfl[2 * i + 1] = gaps[i].y; }
+    std::vector<int32_t> band;
+    if (d->verbose_band && d->Nx)
+    {
+      band.resize((size_t)d->Nx * 8 * Bt);
+      HIPCHK(hipMemcpy(band.data(), d->d_dbg_band, band.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    d->verbose_cb(r, besta, d->Nx, bs.data(), bi.data(), gfl.data(), cand.data(), band.empty() ? NULL : band.data(), d->verbose_user);
+  }
+  return RAMX_OK;
+}
+
+// K(-1): the boundary row and the candidates of row 0 -- how every direction but a cell-parallel one begins, and (again) how a
+// direction starts over on the per-column route after a single-launch kernel gave up: d_ctl[1] then holds the initial control
+// block again, and d_ctl[0], where that kernel left its last one, is cleared.
+static int boundary_row(ramx_dev *d, KArgs &a, bool again)
+{
   HIPCHK(hipMemsetAsync(d->d_sums, 0, 3 * NSHARD * 4 * sizeof(long long), d->stream));
-  HIPCHK(hipEventRecord(d->ev_begin, d->stream));
-  // K(-1): boundary row + candidates of row 0
+  if (!again) HIPCHK(hipEventRecord(d->ev_begin, d->stream));
   a.r = -1; a.S_in = d->d_state[0]; a.S_out = d->d_state[1]; a.ctl_in = d->d_ctl; a.ctl_out = d->d_ctl + 1;
-  a.sums_in = slot(0); a.sums_out = slot(0); a.sums_zero = slot(1); a.nshards_in = NSHARD;
-  if (verbose_trace)
+  a.sums_in = sums_slot(d, 0); a.sums_out = sums_slot(d, 0); a.sums_zero = sums_slot(d, 1); a.nshards_in = NSHARD;
+  if (!again && d->verbose_cb != NULL)
   {
-    int trc = trace_buffers(a);
+    int trc = trace_buffers(d, a);
     if (trc != RAMX_OK) return trc;
     launch_column_trace(d, a, true);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(d->stream));
-    if ((trc = deliver_trace(-1, 0)) != RAMX_OK) return trc;
+    if ((trc = deliver_trace(d, -1, 0)) != RAMX_OK) return trc;
   }
   else launch_column<true>(d, a);
-  HIPCHK(hipGetLastError());
-  rt_mark("boundary row launched");
+  if (again) HIPCHK(hipMemsetAsync(d->d_ctl, 0, sizeof(RamxCtl), d->stream));
+  else HIPCHK(hipGetLastError());
+  return RAMX_OK;
+}
+
+#ifdef RAMX_CP_TIMING
+static int cp_timing_report(const CPArgs &ca, const DirRoute &rt)
+{
+  unsigned long long h[16 * 16 + 8];
+  HIPCHK(hipMemcpy(h, ca.dbg, sizeof(h), hipMemcpyDeviceToHost));
+  const double cols = h[16 * 16] ? (double)h[16 * 16] : 1.0;
+  fprintf(stderr, "SP_TIMING workgroup 0, %d workgroups x %d threads, K %d, %.0f rows; shader clocks (100 MHz) per row\n", rt.nb, rt.th, rt.k, cols);
+  fprintf(stderr, "SP_TIMING vote wave: tickets wait+fold %.1f | winner+forward %.1f | stop rule, decision %.1f | loop %.1f | waiting for band sums %.1f | forwarded at once %.0f %%\n",
+          h[0] / cols, h[1] / cols, h[2] / cols, h[3] / cols, h[4] / cols, 100.0 * h[5] / cols);
+  for (int wv = 1; wv < rt.th / 64; wv++)
+    fprintf(stderr, "SP_TIMING band wave %d: idle %.1f | planning %.1f | rows %.1f\n", wv, h[wv * 16 + 0] / cols, h[wv * 16 + 1] / cols, h[wv * 16 + 2] / cols);
+  return RAMX_OK;
+}
+#endif
+
+// The device-wide cell-parallel launch of the plan in rt: boundary row and every column inside the kernel.  *accepted: the launch
+// call went through -- from there on an error is the kernel's (an execution error: not something another route can serve).
+static int cp_device_launch(ramx_dev *d, const KArgs &a, int L, const DirRoute &rt, bool *accepted)
+{
+  const int nb = rt.nb;
+  { const int prc = pack_rest(d); if (prc != RAMX_OK) return prc; }      // this kernel reads the whole window
+  CPArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  ca.bases = d->d_bases; ca.bounds = d->d_bounds; ca.trim = d->d_trim; ca.ctl_out = d->d_ctl; ca.cons_out = d->d_cons;
+  ca.Np = d->Np; ca.KW = d->KW; ca.L = L; ca.go = a.go; ca.ge = a.ge; ca.cap = a.cap; ca.minimp = a.minimp; ca.when_to_stop = a.when_to_stop;
+  memcpy(ca.tab, d->tab, sizeof(ca.tab));
   {
-    // the in-place row buffer holds S(-1) after K(-1); d_ctl[1] holds the initial control block, the persistent
-    // kernel writes its final one to d_ctl[0]
-    if (d->d_state[0] != d->d_state[1]) { ramx_set_error("persistent path needs the in-place row buffer"); }
-    else if (!tracing)
-    {
-      prk_local_rc = prk_run(d, a, L, &persistent);
-      // Single GPU: a failure is simply returned.  Multi-rank: once the ranks have agreed on the persistent path
-      // (prk_run sets `persistent` after that agreement) a rank-local failure -- an allocation, a memset, the launch
-      // itself -- must NOT leave before the agreement below, or the other ranks' kernels spin to their limit and then
-      // wait in a collective this rank never joins.
-      if (prk_local_rc != RAMX_OK && !(multi && persistent)) return prk_local_rc;
-    }
+    std::vector<CpDevDesc> hd((size_t)nb);
+    for (int i = 0; i < nb; i++) { memset(&hd[i], 0, sizeof(CpDevDesc)); hd[i].first = 0; hd[i].nx = d->Nx; hd[i].b = i; hd[i].nb = nb; hd[i].id = 0; }
+    int drc = ensure(&d->d_devdesc, &d->cap_devdesc, sizeof(CpDevDesc) * (size_t)nb);
+    if (drc != RAMX_OK) return drc;
+    HIPCHK(hipMemcpyAsync(d->d_devdesc, hd.data(), sizeof(CpDevDesc) * (size_t)nb, hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));       // hd goes out of scope
   }
-  if (persistent && multi)
+  ca.dev = d->d_devdesc; ca.vote = d->d_vote; ca.err = d->d_err; ca.S = d->d_state[0]; ca.vote_wave = rt.vwf;
+  { const char *td = getenv("RAMX_TEST_CP_DROP_TICKET"); ca.test_drop_row = td ? atoi(td) : 0; ca.test_drop_id = -1; }
+  cp_test_hooks(ca);
+  ca.nranks = 1; ca.rank = 0;
+  if (rt.multi)
   {
-    // agree over all ranks whether the cross-device launch went through; if any rank gave up (bounded spin) or failed
-    // locally, every rank repeats the direction with the per-column launches and the host collective
-    int bad = prk_local_rc != RAMX_OK;
-    RamxCtl c0[2];
-    unsigned errw = 0;
-    memset(c0, 0, sizeof(c0));
-    if (!bad)
-    {
-      // (both control blocks: a direction that ran in pieces leaves its last one in either; the error word: a refused entry check)
-      if (hipStreamSynchronize(d->stream) != hipSuccess || hipMemcpy(c0, d->d_ctl, sizeof(c0), hipMemcpyDeviceToHost) != hipSuccess ||
-          hipMemcpy(&errw, d->d_err, sizeof(errw), hipMemcpyDeviceToHost) != hipSuccess) bad = 1;
-    }
-    else (void)hipStreamSynchronize(d->stream);
-    bad = bad || c0[0].pad != 0 || c0[1].pad != 0 || errw != 0;
-    int frc = host_allreduce_flag(d, &bad);
-    if (frc != RAMX_OK) return frc;
+    ca.nranks = d->nranks; ca.rank = d->rank; ca.peers = (PeerBox *const *)d->d_peer; ca.box = d->xbox;
+    { const int mrc = mailbox_mirror(d, &ca.mirror); if (mrc != RAMX_OK) return mrc; }
+    const char *tf = getenv("RAMX_TEST_FAIL_PRK_RANK");      // test hook: this rank fails where a launch error would
+    if (tf && atoi(tf) == d->rank) { ramx_set_error("test hook: forced failure of the cell-parallel launch on rank %d", d->rank); return RAMX_ERR_HIP; }
+  }
+  HIPCHK(hipMemsetAsync(d->d_vote, 0, RAMX_CP_NSETS * NSHARD * sizeof(PShard), d->stream));
+  HIPCHK(hipMemsetAsync(d->d_err, 0, 64, d->stream));
+  HIPCHK(hipMemsetAsync(d->d_ctl, 0, 2 * sizeof(RamxCtl), d->stream));
+#ifdef RAMX_CP_TIMING
+  HIPCHK(hipMalloc((void **)&ca.dbg, (16 * 16 + 8) * sizeof(unsigned long long)));
+  HIPCHK(hipMemset(ca.dbg, 0, (16 * 16 + 8) * sizeof(unsigned long long)));
+#endif
+  HIPCHK(hipEventRecord(d->ev_begin, d->stream));
+  if (rt.multi) test_delay_rank(d);
+  int crc = ramx_cp_launch_device(d->stream, a.W, rt.k, rt.th, nb, ca);
+  if (crc != RAMX_OK)
+  {
+#ifdef RAMX_CP_TIMING
+    (void)hipFree(ca.dbg);
+#endif
+    ramx_set_error("cell-parallel device launch failed (W %d, %d lanes per flank, %d workgroups)", a.W, rt.k, nb);
+    return crc;
+  }
+  *accepted = true;
+  HIPCHK(hipEventRecord(d->ev_end, d->stream));
+  HIPCHK(hipStreamSynchronize(d->stream));
+#ifdef RAMX_CP_TIMING
+  if (rt.vwf) { const int trc = cp_timing_report(ca, rt); if (trc != RAMX_OK) return trc; }
+  (void)hipFree(ca.dbg);
+#endif
+  return RAMX_OK;
+}
+
+// The cell-parallel route: K lanes per flank, the whole direction in one launch of at most one workgroup per CU.  *lanes > 0 on
+// return: the direction has run.  Multi-rank: the vote crosses the devices through the mailboxes (ramx_dev_peer_* set-up),
+// exactly as in the lane-per-flank persistent kernels; every rank takes this route or none: one agreement before, one after.
+static int cp_attempt(ramx_dev *d, const KArgs &a, int L, DirRoute &rt, int *lanes)
+{
+  *lanes = 0;
+  if (!rt.cp_try) return RAMX_OK;
+  int k = rt.k, rc;
+  if (rt.multi)
+  {
+    if ((rc = mailbox_clear(d)) != RAMX_OK) return rc;
+    int cannot = k > 0 ? 0 : 1;
+    if ((rc = host_allreduce_flag(d, &cannot)) != RAMX_OK) return rc;
+    if (cannot) k = 0;
+  }
+  if (k <= 0) return RAMX_OK;
+  // from here on a multi-rank run never leaves before the second agreement (a rank that did would leave the others'
+  // kernels spinning to their limit and then waiting in a collective it never joins)
+  bool accepted = false;
+  const int lrc = cp_device_launch(d, a, L, rt, &accepted);
+  RamxCtl c0;
+  memset(&c0, 0, sizeof(c0));
+  int bad = lrc != RAMX_OK;
+  if (!bad && hipMemcpy(&c0, d->d_ctl, sizeof(c0), hipMemcpyDeviceToHost) != hipSuccess) bad = 1;
+  bad = bad || c0.pad != 0;
+  if (rt.multi)
+  {
+    if (lrc != RAMX_OK) (void)hipStreamSynchronize(d->stream);
+    if ((rc = host_allreduce_flag(d, &bad)) != RAMX_OK) return rc;
     if (bad)
     {
-      fprintf(stderr, "ramx: cross-device persistent launch gave up on some rank; repeating the direction with per-column launches "
-                      "and leaving the mailbox path off for the rest of this process\n");
-      persistent = false;
-      d->peer_ready = 0;          // agreed by all ranks (the flag above is reduced): nobody tries the mailboxes again
-      HIPCHK(hipMemsetAsync(d->d_sums, 0, 3 * NSHARD * 4 * sizeof(long long), d->stream));
-      a.r = -1; a.S_in = d->d_state[0]; a.S_out = d->d_state[1]; a.ctl_in = d->d_ctl; a.ctl_out = d->d_ctl + 1;
-      a.sums_in = slot(0); a.sums_out = slot(0); a.sums_zero = slot(1); a.nshards_in = NSHARD;
-      launch_column<true>(d, a);
-      HIPCHK(hipMemsetAsync(d->d_ctl, 0, sizeof(RamxCtl), d->stream));
+      fprintf(stderr, "ramx: cross-device cell-parallel launch gave up or failed on some rank; repeating the direction with per-column "
+                      "launches and leaving the mailbox path off for the rest of this process\n");
+      d->peer_ready = 0;        // agreed by all ranks (the flag above is reduced)
+      rt.mailbox_ok = rt.int32_can = rt.pk = false;      // ... and with the mailboxes go this direction's other single-launch kernels
     }
   }
-  else if (persistent)
+  else if (lrc != RAMX_OK && accepted)
+    return lrc;               // the kernel ran and failed (a fault is sticky: the context is gone): the error as it was reported
+  else if (lrc != RAMX_OK)
   {
-    // single GPU: a barrier that timed out (bounded spin, e.g. a co-tenant holding CUs) is not fatal -- repeat the
-    // direction with the per-column launches, exactly as the multi-rank branch above does
-    HIPCHK(hipStreamSynchronize(d->stream));
-    RamxCtl c0[2];
-    unsigned errw = 0;
-    {
-      unsigned long long ew = 0;
-      int drc;
-      if ((drc = d2h_small(d, c0, d->d_ctl, sizeof(c0))) != RAMX_OK) return drc;
-      if ((drc = d2h_small(d, &ew, d->d_err, sizeof(ew))) != RAMX_OK) return drc;
-      errw = (unsigned)ew;
-    }
+    // single GPU: the other routes can serve the same flank set -- an occupancy query that says no, a launch configuration
+    // this one instantiation refuses -- so a refusal here is not the direction's failure
+    (void)hipStreamSynchronize(d->stream);
+    (void)hipGetLastError();
+    fprintf(stderr, "ramx: cell-parallel device launch not possible (%s); continuing on the lane-per-flank route\n", ramx_last_error());
+  }
+  else if (bad)
+    fprintf(stderr, "ramx: device-wide vote of the cell-parallel launch timed out (bounded spin); repeating the direction with "
+                    "per-column launches\n");
+  if (!bad) *lanes = k;
+  return RAMX_OK;
+}
+
+// The lane-per-flank persistent kernels behind K(-1): the in-place row buffer holds S(-1), d_ctl[1] the initial control block,
+// and the kernel writes its final one to d_ctl[0].  A launch that gave up -- a bounded spin that ran out (e.g. a co-tenant
+// holding CUs), a row the packed kernel refused -- is not fatal: the direction starts over on the per-column route.
+static int prk_attempt(ramx_dev *d, KArgs &a, int L, DirRoute &rt, bool *persistent)
+{
+  if (d->d_state[0] != d->d_state[1]) { ramx_set_error("persistent path needs the in-place row buffer"); return RAMX_OK; }
+  if (rt.tracing) return RAMX_OK;
+  // Single GPU: a failure is simply returned.  Multi-rank: once the ranks have agreed on the persistent path (prk_run sets
+  // `persistent` after that agreement) a rank-local failure -- an allocation, a memset, the launch itself -- must NOT leave
+  // before the agreement below, or the other ranks' kernels spin to their limit and then wait in a collective this rank
+  // never joins.
+  const int lrc = prk_run(d, a, L, rt, persistent);
+  if (lrc != RAMX_OK && !(rt.multi && *persistent)) return lrc;
+  if (!*persistent) return RAMX_OK;
+  RamxCtl c0[2];
+  unsigned errw = 0;
+  int bad = lrc != RAMX_OK, rc;
+  memset(c0, 0, sizeof(c0));
+  if (rt.multi)
+  {
+    // agree over all ranks whether the cross-device launch went through; if any rank gave up or failed locally, every rank
+    // repeats the direction with the per-column launches and the host collective
+    if (bad) (void)hipStreamSynchronize(d->stream);
+    else if (read_launch_state(d, c0, &errw) != RAMX_OK) bad = 1;
+    bad = bad || c0[0].pad != 0 || c0[1].pad != 0 || errw != 0;
+    if ((rc = host_allreduce_flag(d, &bad)) != RAMX_OK) return rc;
+    if (!bad) return RAMX_OK;
+    fprintf(stderr, "ramx: cross-device persistent launch gave up on some rank; repeating the direction with per-column launches "
+                    "and leaving the mailbox path off for the rest of this process\n");
+    d->peer_ready = 0;          // agreed by all ranks (the flag above is reduced): nobody tries the mailboxes again
+  }
+  else
+  {
+    if ((rc = read_launch_state(d, c0, &errw)) != RAMX_OK) return rc;
     rt_mark("after the launch: control blocks, error word");
-    if (c0[0].pad != 0 || c0[1].pad != 0 || errw != 0)
-    {
-      if (errw == 2 || errw == 3)
-        fprintf(stderr, "ramx: the packed-row kernel refused %s (a cell outside the span computed for this scoring system); repeating "
-                        "the direction with per-column launches\n", errw == 3 ? "the rows it was handed" : "a row it computed");
-      else
+    if (c0[0].pad == 0 && c0[1].pad == 0 && errw == 0) return RAMX_OK;
+    if (errw == 2 || errw == 3)
+      fprintf(stderr, "ramx: the packed-row kernel refused %s (a cell outside the span computed for this scoring system); repeating "
+                      "the direction with per-column launches\n", errw == 3 ? "the rows it was handed" : "a row it computed");
+    else
       fprintf(stderr, "ramx: device-wide barrier of the persistent launch timed out (bounded spin); repeating the direction with "
                       "per-column launches\n");
-      persistent = false;
-      HIPCHK(hipMemsetAsync(d->d_sums, 0, 3 * NSHARD * 4 * sizeof(long long), d->stream));
-      a.r = -1; a.S_in = d->d_state[0]; a.S_out = d->d_state[1]; a.ctl_in = d->d_ctl; a.ctl_out = d->d_ctl + 1;
-      a.sums_in = slot(0); a.sums_out = slot(0); a.sums_zero = slot(1); a.nshards_in = NSHARD;
-      launch_column<true>(d, a);
-      HIPCHK(hipMemsetAsync(d->d_ctl, 0, sizeof(RamxCtl), d->stream));
-    }
   }
-  }
-  d->last_persistent = persistent ? 1 : 0;
-  if (!persistent) { const int prc = pack_rest(d); if (prc != RAMX_OK) return prc; }      // the column launches read the whole window
+  *persistent = false;
+  return boundary_row(d, a, true);
+}
+
+// The per-column route: K(0 .. L-1) back to back on one stream, no host synchronisation per column -- the stop decision lives
+// in the control blocks on the device, a stopped launch returns at once; the host looks at a pinned copy every 64 columns, one
+// checkpoint behind, and stops launching.  A trace runs one row at a time instead.
+static int column_loop(ramx_dev *d, KArgs &a, int L, const DirRoute &rt, int *launches, int *nsamp)
+{
   const int CHUNK = 64;
   const int stride = L > MAX_SAMPLES * 4 ? L / MAX_SAMPLES : 4;
+  int pending = -1, chk = 0;
   bool stopped = false;
   memset(d->h_ctl, 0, 4 * sizeof(RamxCtl));
-  for (int r = 0; r < L && !stopped && !persistent; r++)
+  for (int r = 0; r < L && !stopped; r++)
   {
-    if (multi)
+    if (rt.multi)
     {
       // the vote shards of row r (32 x 4 x int64 = 1 KB) are summed across ranks in place; the column kernel then
       // folds them exactly as in the single-GPU case.  One collective per column, no extra kernel.
-      int hrc = host_allreduce_shards(d, slot(r));
+      int hrc = host_allreduce_shards(d, sums_slot(d, r));
       if (hrc != RAMX_OK) return hrc;
     }
-    a.sums_in = slot(r); a.nshards_in = NSHARD;
+    a.sums_in = sums_slot(d, r); a.nshards_in = NSHARD;
     a.r = r; a.S_in = d->d_state[(r + 1) & 1]; a.S_out = d->d_state[r & 1];
     a.ctl_in = d->d_ctl + ((r + 1) & 1); a.ctl_out = d->d_ctl + (r & 1);
-    a.sums_out = slot(r + 1); a.sums_zero = slot(r + 2);
-    if (tracing)
+    a.sums_out = sums_slot(d, r + 1); a.sums_zero = sums_slot(d, r + 2);
+    if (rt.tracing)
     {
       // one row at a time: launch, wait, hand the row's trace to the caller (debugging aid, no attempt at speed)
-      int trc = trace_buffers(a);
+      int trc = trace_buffers(d, a);
       if (trc != RAMX_OK) return trc;
       launch_column_trace(d, a);
-      launches++;
+      (*launches)++;
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(d->stream));
       RamxCtl c;
       HIPCHK(hipMemcpy(&c, a.ctl_out, sizeof(c), hipMemcpyDeviceToHost));
       if (c.rows_done == r + 1)      // the launch ran (a stopped predecessor makes the kernel return at once)
-        if ((trc = deliver_trace(r, c.besta)) != RAMX_OK) return trc;
+        if ((trc = deliver_trace(d, r, c.besta)) != RAMX_OK) return trc;
       if (c.stopped) stopped = true;
       continue;
     }
-    const bool sample = (r % stride) == (stride / 2) && nsamp < MAX_SAMPLES;
-    if (sample) HIPCHK(hipEventRecord(d->ev_s0[nsamp], d->stream));
+    const bool sample = (r % stride) == (stride / 2) && *nsamp < MAX_SAMPLES;
+    if (sample) HIPCHK(hipEventRecord(d->ev_s0[*nsamp], d->stream));
     launch_column<false>(d, a);
-    if (sample) { HIPCHK(hipEventRecord(d->ev_s1[nsamp], d->stream)); nsamp++; }
-    launches++;
+    if (sample) { HIPCHK(hipEventRecord(d->ev_s1[*nsamp], d->stream)); (*nsamp)++; }
+    (*launches)++;
     if (((r + 1) % CHUNK) == 0 || r == L - 1)
     {
       HIPCHK(hipGetLastError());
@@ -3019,11 +2974,79 @@ extern "C" int ramx_dev_run_direction(ramx_dev *d, ramx_run_info *info)
       chk ^= 1;
     }
   }
+  return RAMX_OK;
+}
+
+// f: the direction's final control block (its besta word carries the single-launch kernels' row counts)
+static int fill_run_info(ramx_dev *d, ramx_run_info *info, const RamxCtl &f, int L, int launches, int nsamp, bool persistent, bool cp_done, int lanes)
+{
+  const bool packed = persistent && !cp_done && d->last_packed_r0 >= 0;
+  info->ret = f.max_row + 1;
+  info->rows_executed = f.rows_done;
+  info->limit_warning = (f.stopped && f.rows_done - 1 == L - 1) ? 1 : 0;   // ram_extend.c:1225-1231
+  info->overflow32 = f.overflow;
+  info->n_extendable = d->Nx;
+  info->launches = launches;
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, d->ev_begin, d->ev_end));
+  info->loop_ms = ms;
+  double acc = 0; int cnt = 0;
+  for (int i = 0; i < nsamp; i++)
+  {
+    float t = 0;
+    if (hipEventElapsedTime(&t, d->ev_s0[i], d->ev_s1[i]) == hipSuccess) { acc += t; cnt++; }
+  }
+  info->kernel_ms_avg = cnt ? acc / cnt : 0.0;
+  info->kernel_samples = cnt;
+  info->persistent = persistent ? 1 : 0;
+  info->lanes_per_flank = lanes;
+  info->respeculated_rows = cp_done ? f.besta : packed ? (f.besta >> 16) & 0xffff : 0;
+  info->packed_rows = (packed && f.rows_done > d->last_packed_r0) ? f.rows_done - d->last_packed_r0 : 0;
+  info->lean_rows = packed ? (f.besta & 0xffff) : 0;
+  return RAMX_OK;
+}
+
+extern "C" int ramx_dev_run_direction(ramx_dev *d, ramx_run_info *info)
+{
+  if (!d || !d->ready) { ramx_set_error("ramx_dev_run_direction: begin_direction has not been called"); return RAMX_ERR_STATE; }
+  HIPCHK(hipSetDevice(d->ordinal));
+  const ramx_params &p = d->p;
+  const int L = p.L;
+  KArgs a;
+  memset(&a, 0, sizeof(a));
+  a.bases = d->d_bases; a.bounds = d->d_bounds; a.trim = d->d_trim; a.cons_out = d->d_cons;
+  a.Np = d->Np; a.Nx = d->Nx; a.W = p.bandwidth; a.go = p.gapopen; a.ge = p.gapextn; a.cap = p.cappenalty;
+  a.minimp = p.minimprovement; a.when_to_stop = p.when_to_stop;
+  memcpy(a.tab, d->tab, sizeof(a.tab));
+  int launches = 0, nsamp = 0, lanes = 0, rc;
+  bool persistent = false;
+  DirRoute rt;
+  rt_mark(NULL);
+  if ((rc = direction_route(d, a, L, &rt)) != RAMX_OK) return rc;
+  if (rt.pack_now && (rc = pack_rest(d)) != RAMX_OK) return rc;
+  rt_mark("route (occupancy answers)");
+  if ((rc = cp_attempt(d, a, L, rt, &lanes)) != RAMX_OK) return rc;
+  const bool cp_done = lanes > 0;
+  rt_mark("cell-parallel plan / launch");
+  if (cp_done) persistent = true;
+  else
+  {
+    lanes = 1;
+    if ((rc = boundary_row(d, a, false)) != RAMX_OK) return rc;
+    rt_mark("boundary row launched");
+    if ((rc = prk_attempt(d, a, L, rt, &persistent)) != RAMX_OK) return rc;
+  }
+  d->last_persistent = persistent ? 1 : 0;
+  if (!persistent)
+  {
+    if ((rc = pack_rest(d)) != RAMX_OK) return rc;      // the column launches read the whole window
+    if ((rc = column_loop(d, a, L, rt, &launches, &nsamp)) != RAMX_OK) return rc;
+  }
   if (!cp_done) HIPCHK(hipEventRecord(d->ev_end, d->stream));
   rt_mark("loop enqueued / pieces run");
   HIPCHK(hipStreamSynchronize(d->stream));
   RamxCtl h[2];
-  { const int drc = d2h_small(d, h, d->d_ctl, sizeof(h)); if (drc != RAMX_OK) return drc; }
+  if ((rc = d2h_small(d, h, d->d_ctl, sizeof(h))) != RAMX_OK) return rc;
   rt_mark("final synchronisation, control blocks");
   const RamxCtl &f = (L == 0) ? h[1] : ((h[0].rows_done > h[1].rows_done) ? h[0] : h[1]);
   d->final_ctl = f;
@@ -3032,33 +3055,7 @@ extern "C" int ramx_dev_run_direction(ramx_dev *d, ramx_run_info *info)
     launches = 1;
     if (f.pad != 0) { ramx_set_error("persistent kernel: device-wide barrier timed out (bounded spin gave up)"); return RAMX_ERR_STATE; }
   }
-  if (info)
-  {
-    info->ret = f.max_row + 1;
-    info->rows_executed = f.rows_done;
-    info->limit_warning = (f.stopped && f.rows_done - 1 == L - 1) ? 1 : 0;   // ram_extend.c:1225-1231
-    info->overflow32 = f.overflow;
-    info->n_extendable = d->Nx;
-    info->launches = launches;
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, d->ev_begin, d->ev_end));
-    info->loop_ms = ms;
-    double acc = 0; int cnt = 0;
-    for (int i = 0; i < nsamp; i++)
-    {
-      float t = 0;
-      if (hipEventElapsedTime(&t, d->ev_s0[i], d->ev_s1[i]) == hipSuccess) { acc += t; cnt++; }
-    }
-    info->kernel_ms_avg = cnt ? acc / cnt : 0.0;
-    info->kernel_samples = cnt;
-    info->persistent = persistent ? 1 : 0;
-    info->lanes_per_flank = lanes;
-    info->respeculated_rows = cp_done ? f.besta : 0;
-    info->packed_rows = (persistent && !cp_done && d->last_packed_r0 >= 0 && f.rows_done > d->last_packed_r0) ? f.rows_done - d->last_packed_r0 : 0;
-    info->lean_rows = (persistent && !cp_done && d->last_packed_r0 >= 0) ? (f.besta & 0xffff) : 0;
-    if (persistent && !cp_done && d->last_packed_r0 >= 0) info->respeculated_rows = (f.besta >> 16) & 0xffff;
-  }
-  return RAMX_OK;
+  return info ? fill_run_info(d, info, f, L, launches, nsamp, persistent, cp_done, lanes) : RAMX_OK;
 }
 
 extern "C" int ramx_dev_download(ramx_dev *d, int8_t *cons, int32_t cons_cap, int32_t *trim_high, int32_t *trim_pos)

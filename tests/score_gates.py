@@ -7,7 +7,7 @@ narrow arithmetic.  This module says, independently of the library, which side o
   pk_plan            csrc/ramx_packed.hip ramx_pk_plan          packed int16 rows of the lane-per-flank kernel
   fast_pack_ok       csrc/ramx_device.hip fast_pack_ok          fast band of the int32-row kernels, family kernel, profile replay
   cp_value_range_ok  csrc/ramx_cp.hip ramx_cp_max_family        cell-parallel kernel (the value-range part of it)
-  go_ge_ok           csrc/ramx_device.hip prk_local_can         int32-row persistent kernel (e - m as int16 in LDS)
+  go_ge_ok           csrc/ramx_device.hip route_gates           int32-row persistent kernel (e - m as int16 in LDS)
 
 All of them look at the scores through the class table the device layer builds (ramx_dev_begin_direction): the matrix entries
 [a][b] with a = 0..3 (the four candidate consensus bases) and b = 0..7 and 99 (A C G T, their soft-masked codes, N).
