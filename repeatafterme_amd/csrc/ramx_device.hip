@@ -394,10 +394,21 @@ static int launch_pack(ramx_dev *d, int Nx, int Np, int W, int k_lo, int k_hi, h
 // A direction's windows are L + 2W columns long, and most runs stop after a fraction of them (the reference's default: 100 columns
 // behind the end of the alignment): begin_direction packs the first RAMX_PK_SEGMENT columns, the packed-row route packs the
 // following pieces on a second stream while the piece before them runs (prk_run), and every other route packs the rest here.
+// prk_run counts a piece's words as packed (packed_kw) as soon as their pack is ENQUEUED on pack_stream, and a direction that
+// stops early leaves that pack in flight.  Whoever next reads the windows, or rewrites or reallocates the flank and window
+// buffers it reads and writes, settles it first: a wait on the library's stream, or on the host (before buffers are released).
+static int pack_settle(ramx_dev *d, bool on_host = false)
+{
+  if (!d->pack_busy) return RAMX_OK;
+  if (on_host) HIPCHK(hipEventSynchronize(d->pack_done));
+  else HIPCHK(hipStreamWaitEvent(d->stream, d->pack_done, 0));
+  d->pack_busy = 0;
+  return RAMX_OK;
+}
 static int pack_rest(ramx_dev *d)
 {
+  { const int src = pack_settle(d); if (src != RAMX_OK) return src; }      // before the early return: "packed" may mean "enqueued"
   if (d->packed_kw >= d->KW) return RAMX_OK;
-  if (d->pack_busy) { HIPCHK(hipStreamWaitEvent(d->stream, d->pack_done, 0)); d->pack_busy = 0; }
   const int rc = launch_pack(d, d->Nx, d->Np, d->p.bandwidth, d->packed_kw, d->KW, d->stream);
   d->packed_kw = d->KW;
   return rc;
@@ -422,6 +433,42 @@ static int ensure(T **p, size_t *cap, size_t need_bytes)
   return RAMX_OK;
 }
 
+// flank descriptors, packed windows, bounds and trim records of Np flanks (kept between calls: a hipFree / hipMalloc pair costs
+// ~0.5 ms of device sync per call)
+static int ensure_windows(ramx_dev *d, int Np, int KW)
+{
+  int rc;
+  if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)Np * sizeof(ramx_flank)))) return rc;
+  if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)KW * Np * sizeof(unsigned)))) return rc;
+  if ((rc = ensure(&d->d_bounds, &d->cap_bounds, (size_t)Np * sizeof(int2)))) return rc;
+  return ensure(&d->d_trim, &d->cap_trim, (size_t)Np * sizeof(int2));
+}
+
+// The row buffer, 16 B x (W + 1) slots per flank.  The row is updated IN PLACE: a lane only ever touches its own 16-byte column
+// of the tile, reads slot q+16 before it writes slot q, and launches are serialised, so one buffer serves as S(r-1) and S(r).
+// Halving the footprint (65.6 MB at N = 100,000) keeps the whole row set inside the Infinity Cache.
+static int ensure_rows(ramx_dev *d, size_t bytes, bool pingpong)
+{
+  if (bytes <= d->cap_state && d->d_state[0]) return RAMX_OK;
+  if (d->d_state[0]) HIPCHK(hipFree(d->d_state[0]));
+  if (d->d_state[1] && d->d_state[1] != d->d_state[0]) HIPCHK(hipFree(d->d_state[1]));
+  d->d_state[0] = d->d_state[1] = NULL; d->cap_state = 0;
+  HIPCHK(hipMalloc((void **)&d->d_state[0], bytes));
+  if (pingpong) HIPCHK(hipMalloc((void **)&d->d_state[1], bytes));
+  else d->d_state[1] = d->d_state[0];
+  d->cap_state = bytes;
+  return RAMX_OK;
+}
+
+// the cell-parallel kernels take flanks that are empty or start at or before the first base behind the core edge (t_lo <= 0: the
+// masked band's carry argument needs the out-of-bounds prefix to end at or before the band centre)
+static bool cp_flanks_fit(const ramx_flank *fl, int n)
+{
+  for (int i = 0; i < n; i++)
+    if (fl[i].t_lo > 0 && fl[i].t_lo <= fl[i].t_hi) return false;
+  return true;
+}
+
 extern "C" int ramx_dev_begin_direction(ramx_dev *d, const ramx_flank *flanks, int32_t n_flanks, const ramx_params *p)
 {
   if (!d || !p || n_flanks < 0 || (n_flanks && !flanks)) { ramx_set_error("ramx_dev_begin_direction: bad argument"); return RAMX_ERR_ARG; }
@@ -437,31 +484,14 @@ extern "C" int ramx_dev_begin_direction(ramx_dev *d, const ramx_flank *flanks, i
   d->planes_ready = 0;        // the flank and window buffers the resident bit planes were made from are reused
   class_tab(p, d->tab);
   int rc;
-  if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)Np * sizeof(ramx_flank)))) return rc;
-  if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)KW * Np * sizeof(unsigned)))) return rc;
-  if ((rc = ensure(&d->d_bounds, &d->cap_bounds, (size_t)Np * sizeof(int2)))) return rc;   // kept between calls: hipFree/hipMalloc
-  if ((rc = ensure(&d->d_trim, &d->cap_trim, (size_t)Np * sizeof(int2)))) return rc;       // per call cost ~0.5 ms of device sync
-  const size_t state_bytes = (size_t)Np * Q * sizeof(int4);
-  if (state_bytes > d->cap_state || !d->d_state[0])
-  {
-    // The row is updated IN PLACE: a lane only ever touches its own 16-byte column of the tile, reads slot q+16
-    // before it writes slot q, and launches are serialised, so one buffer serves as S(r-1) and S(r).  Halving the
-    // footprint (65.6 MB at N = 100,000) keeps the whole row set inside the Infinity Cache.
-    const bool pingpong = getenv("RAMX_PINGPONG") != NULL;     // A/B switch kept for profiling
-    if (d->d_state[0]) HIPCHK(hipFree(d->d_state[0]));
-    if (d->d_state[1] && d->d_state[1] != d->d_state[0]) HIPCHK(hipFree(d->d_state[1]));
-    d->d_state[0] = d->d_state[1] = NULL;
-    HIPCHK(hipMalloc((void **)&d->d_state[0], state_bytes));
-    if (pingpong) HIPCHK(hipMalloc((void **)&d->d_state[1], state_bytes));
-    else d->d_state[1] = d->d_state[0];
-    d->cap_state = state_bytes;
-  }
+  if ((rc = ensure_windows(d, Np, KW))) return rc;
+  if ((rc = ensure_rows(d, (size_t)Np * Q * sizeof(int4), getenv("RAMX_PINGPONG") != NULL))) return rc;     // (A/B switch kept for profiling)
   if ((rc = ensure(&d->d_cons, &d->cap_cons, (size_t)p->L + 16))) return rc;
   rt_mark("begin: buffers");
+  if ((rc = pack_settle(d)) != RAMX_OK) return rc;      // (a piece of the direction before still in flight: it reads d_flanks)
   if (Nx) HIPCHK(hipMemcpyAsync(d->d_flanks, flanks, (size_t)Nx * sizeof(ramx_flank), hipMemcpyHostToDevice, d->stream));
   rt_mark("begin: flanks to the device (enqueued)");
   {
-    if (d->pack_busy) { HIPCHK(hipStreamWaitEvent(d->stream, d->pack_done, 0)); d->pack_busy = 0; }    // (a piece of the direction before still in flight)
     const int seg = pk_segment_columns(p->L, p->when_to_stop);
     const int first = seg > 0 ? ((seg + 8) >> 3) + 28 : KW;      // words the first piece's columns read (+ the widest band's window and look-ahead)
     d->packed_kw = first < KW ? first : KW;
@@ -472,10 +502,7 @@ extern "C" int ramx_dev_begin_direction(ramx_dev *d, const ramx_flank *flanks, i
   rt_mark("begin: pack of the first piece enqueued");
   HIPCHK(hipStreamSynchronize(d->stream));
   rt_mark("begin: synchronised");
-  // the cell-parallel kernels take flanks that are empty or start at or before the first base behind the core edge
-  d->cp_flanks_ok = 1;
-  for (int i = 0; i < Nx; i++)
-    if (flanks[i].t_lo > 0 && flanks[i].t_lo <= flanks[i].t_hi) { d->cp_flanks_ok = 0; break; }
+  d->cp_flanks_ok = cp_flanks_fit(flanks, Nx) ? 1 : 0;
   // the packed-row kernel (ramx_kernels_packed.h) takes rows in which no flank has an out-of-bounds cell at the LOW end of the
   // band: cell 0 of row r is flank position t = r - W, so a non-empty flank is clear from row t_lo + W on
   d->pk_r0 = d->cp_flanks_ok ? 0 : -1;
@@ -1009,6 +1036,41 @@ static int prk_timing_report(ramx_dev *d, unsigned long long *dbgbuf, size_t nw,
   (void)hipFree(dbgbuf);
   return RAMX_OK;
 }
+
+// ... of the register-resident family kernel of a batch
+static int fam_timing_report(const unsigned long long *dbg)
+{
+  unsigned long long h[64];
+  HIPCHK(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
+  static const char *nm[6] = { "vote + stop rule", "winner table+barrier", "band + contrib", "wave reduce", "end barrier", "loop top" };
+  const double cols = h[6] ? (double)h[6] : 1.0;
+  fprintf(stderr, "FAM_TIMING family 0 (block 0), %.0f columns, ns per column per wave:\n", cols);
+  for (int k = 0; k < 6; k++)
+    fprintf(stderr, "FAM_TIMING %-22s w0 %7.1f  w1 %7.1f  w2 %7.1f  w3 %7.1f\n", nm[k], 10.0 * h[k] / cols, 10.0 * h[8 + k] / cols,
+            10.0 * h[16 + k] / cols, 10.0 * h[24 + k] / cols);
+  return RAMX_OK;
+}
+#endif
+
+#ifdef RAMX_CP_TIMING
+// -DRAMX_CP_TIMING builds: the cell-parallel launch of a batch whose block 0 wrote dbg (cp_timing_report: the whole-set direction's)
+static int cp_family_timing_report(const unsigned long long *dbg)
+{
+  unsigned long long h[16 * 16 + 8];
+  HIPCHK(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
+  static const char *nm[12] = { "vote read + stop rule", "(after speculative band)", "row update", "reductions", "records/slide/window",
+                                "sum+atomics+barrier", "-", "loop top", "wait: drain", "wait: samples + polling", "wait: fold",
+                                "wait: LDS + barrier" };
+  const double cols = h[16 * 16] ? (double)h[16 * 16] : 1.0;
+  fprintf(stderr, "CP_TIMING block 0, %.0f columns, shader clocks per column (waves 0, 1, last two):\n", cols);
+  int nw = 0;
+  for (int w = 0; w < 16; w++) if (h[w * 16 + 0]) nw = w + 1;
+  for (int k = 0; k < 12; k++)
+    if (k == 6) fprintf(stderr, "CP_TIMING mispredicted columns: %.0f of %.0f\n", (double)h[6], cols);
+    else fprintf(stderr, "CP_TIMING %-24s w0 %7.1f  w1 %7.1f  w%d %7.1f  w%d %7.1f\n", nm[k], h[k] / cols, h[16 + k] / cols,
+                        nw > 1 ? nw - 2 : 0, h[(nw > 1 ? nw - 2 : 0) * 16 + k] / cols, nw > 0 ? nw - 1 : 0, h[(nw > 0 ? nw - 1 : 0) * 16 + k] / cols);
+  return RAMX_OK;
+}
 #endif
 
 // The lane-per-flank persistent kernels on the route rt: the int32 rows, the packed rows, or the packed rows behind first rows
@@ -1128,7 +1190,7 @@ static int prk_run(ramx_dev *d, const KArgs &a, int L, DirRoute &rt, bool *used)
     {
       const int r1 = seg > 0 ? std::min(L, (r / seg + 1) * seg) : L;
       // this piece's words: normally packed already (begin_direction, or beside the piece before)
-      if (d->pack_busy) { HIPCHK(hipStreamWaitEvent(d->stream, d->pack_done, 0)); d->pack_busy = 0; }
+      if ((rc = pack_settle(d)) != RAMX_OK) return rc;
       if (d->packed_kw < words_for(r1))
       {
         if ((rc = launch_pack(d, d->Nx, d->Np, W, d->packed_kw, words_for(r1), d->stream)) != RAMX_OK) break;
@@ -1187,33 +1249,126 @@ static void cp_test_hooks(CPArgs &ca)
   ca.lean_p = lean_p_of(ca.tab, ca.go, ca.ge);
 }
 
-// ---- batch mode -------------------------------------------------------------------------------
-template <int W, int BLOCK>
-static int fam_launch(ramx_dev *d, const FArgs &fa, int F, hipStream_t st)
+// What every cell-parallel launch is told -- a batch's classes, its device-wide families, the whole-set direction: windows,
+// outputs and scoring system.  The caller adds its descriptors, its vote words and what else is its own.
+static CPArgs cp_args(const ramx_dev *d, RamxCtl *ctl, int Np, int KW, const ramx_params &p, const int (&tab)[RAMX_NCLASS][4])
 {
-  (void)d;
-  hipLaunchKernelGGL((ramx_family_kernel<W, BLOCK>), dim3(F), dim3(BLOCK), 0, st, fa);
-  HIPCHK(hipGetLastError());
-  return RAMX_OK;
+  CPArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  ca.bases = d->d_bases; ca.bounds = d->d_bounds; ca.trim = d->d_trim; ca.ctl_out = ctl; ca.cons_out = d->d_cons;
+  ca.Np = Np; ca.KW = KW; ca.L = p.L; ca.go = p.gapopen; ca.ge = p.gapextn; ca.cap = p.cappenalty; ca.minimp = p.minimprovement;
+  ca.when_to_stop = p.when_to_stop;
+  memcpy(ca.tab, tab, sizeof(ca.tab));
+  cp_test_hooks(ca);
+  return ca;
 }
 
-// One pass over a batch.  allow_dev: families above one cell-parallel workgroup may take the device-wide mode (several
-// workgroups voting through ticket words with a bounded spin).  timed_out[f] != 0 on return: that family's device-wide vote
-// gave up (e.g. its workgroups were not all resident because a co-tenant held CUs) -- its outputs are invalid and the caller
-// repeats it with allow_dev = false; with timed_out == NULL such a family makes the whole call fail.
-static int run_families_pass(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
-                             const int32_t *fam_count, int32_t n_families, const ramx_params *p,
-                             ramx_run_info *infos, int8_t *cons, int32_t *trim_high, int32_t *trim_pos,
-                             bool allow_dev, unsigned char *timed_out)
+// ---- batch mode: the route of every family, decided once (family_plan) and read by every later step ----------------------
+struct FamilyPlan
+{
+  bool resident, chain;      // the lane-per-flank families: register-resident kernel, else the streaming one (chain: full candidate recurrence)
+  int n_cp, n_dev;           // families in the cell-parallel classes / in the device-wide launch
+  std::vector<int> grp;      // per family: -1 device-wide, 0 .. RAMX_CP_NCLASS-1 cell-parallel class, above: lane-per-flank shape
+  int cls_first[RAMX_NGROUP + 1], cls_count[RAMX_NGROUP], cp_k[RAMX_CP_NCLASS], cp_threads[RAMX_CP_NCLASS];
+  std::vector<FamDesc> fam;  // the families of the groups >= 0, in group order (cls_first / cls_count)
+  int dev_k, dev_threads, dev_vw;       // the device-wide launch: lanes per flank, threads, vote wave -- what its first family plans
+  std::vector<CpDevDesc> dev;           // ... one descriptor per workgroup
+  std::vector<int2> rounds;             // ... (first descriptor, workgroups): at most one workgroup per CU, one round after the other
+  bool launched[RAMX_NGROUP];           // the group streams something is launched on (families_join)
+};
+
+// Which kernel takes which family -- no HIP call, no session.  Groups 0 .. RAMX_CP_NCLASS-1: the cell-parallel kernel (K lanes
+// per flank, ramx_cp.hip) for families it can take: supported band width and scoring system, small enough for one workgroup at
+// K lanes per flank, a flank set that fits (cp_flanks_fit).  Group -1: families above one such workgroup run on several, the
+// family's vote through its own ticket words -- the device-wide mode of the same kernel, all of them in rounds of at most
+// `cus` workgroups (every workgroup of a launch must be resident).  Groups RAMX_CP_NCLASS ..: one lane per flank, by workgroup
+// shape (64, 128, 256, 512 threads = 1, 2, 4, 8 tiles).
+static FamilyPlan family_plan(const RouteEnv &e, int W, int go, int ge, const int (&tab)[RAMX_NCLASS][4], int L, int cus, bool force_chain,
+                              bool allow_dev, const ramx_flank *flanks, const int32_t *fam_first, const int32_t *fam_count, int n_families)
+{
+  FamilyPlan pl = {};
+  pl.resident = fam_has_width(W) && go <= 0 && ge <= 0 && go + ge >= -32768 && !force_chain && !e.no_persistent;
+  pl.chain = go > 0 || ge > 0 || force_chain;
+  const int cp_max = force_chain ? 0 : ramx_cp_max_family(W, go, ge, tab, L);
+  const bool dev_route = allow_dev && cp_max > 0 && cus > 0 && !e.no_cp_device && !e.no_persistent;
+  // the device-wide plan of a set of nx flanks, asked once per size
+  struct Shape { int k, th, nb, vw; bool known; };
+  const int maxn = n_families > 0 ? *std::max_element(fam_count, fam_count + n_families) : 0;
+  std::vector<Shape> memo[2] = { std::vector<Shape>((size_t)maxn + 1), std::vector<Shape>((size_t)maxn + 1) };
+  auto shape_of = [&](int nx, int wide) -> const Shape &
+  {
+    Shape &s = memo[wide][nx];
+    if (!s.known) { ramx_cp_device_plan(W, nx, cus, wide, &s.k, &s.th, &s.nb, &s.vw); s.known = true; }
+    return s;
+  };
+  // small workgroups (four band waves, lowest latency) when all the multi-workgroup families then fit the CUs together
+  int dev_wide = 0;
+  if (dev_route)
+  {
+    long long need = 0;
+    for (int f = 0; f < n_families; f++)
+      if (fam_count[f] > cp_max && shape_of(fam_count[f], 0).k > 0) need += shape_of(fam_count[f], 0).nb;
+    dev_wide = need > cus;
+  }
+  pl.grp.assign((size_t)n_families, 0);
+  for (int f = 0; f < n_families; f++)
+  {
+    const int nx = fam_count[f];
+    int g = RAMX_CP_NCLASS + (nx <= 64 ? 0 : nx <= 128 ? 1 : nx <= 256 ? 2 : 3);
+    if (nx > 0 && cp_max > 0 && cp_flanks_fit(flanks + fam_first[f], nx))
+    {
+      int k = 0, th = 0;
+      const int c = nx <= cp_max ? ramx_cp_class(W, nx, &k, &th) : -1;
+      if (c >= 0) { g = c; pl.cp_k[c] = k; pl.cp_threads[c] = th; pl.n_cp++; }
+      else if (dev_route)
+      {
+        // the first device-wide family fixes the launch's shape; a later family with another plan stays on its lane-per-flank shape
+        const Shape &s = shape_of(nx, dev_wide);
+        if (s.k > 0 && s.nb <= cus && (pl.dev_k == 0 || (s.k == pl.dev_k && s.th == pl.dev_threads && s.vw == pl.dev_vw)))
+        {
+          pl.dev_k = s.k; pl.dev_threads = s.th; pl.dev_vw = s.vw;
+          if (pl.rounds.empty() || pl.rounds.back().y + s.nb > cus) pl.rounds.push_back(make_int2((int)pl.dev.size(), 0));
+          pl.rounds.back().y += s.nb;
+          for (int b = 0; b < s.nb; b++) pl.dev.push_back(CpDevDesc{ fam_first[f], nx, b, s.nb, f, pl.n_dev, { 0, 0 } });
+          pl.n_dev++;
+          g = -1;
+        }
+      }
+    }
+    pl.grp[f] = g;
+    if (g >= 0) pl.cls_count[g]++;
+  }
+  for (int c = 0; c < RAMX_NGROUP; c++) pl.cls_first[c + 1] = pl.cls_first[c] + pl.cls_count[c];
+  pl.fam.resize((size_t)pl.cls_first[RAMX_NGROUP]);
+  int fill[RAMX_NGROUP];
+  memcpy(fill, pl.cls_first, sizeof(fill));
+  for (int f = 0; f < n_families; f++)
+    if (pl.grp[f] >= 0) pl.fam[(size_t)fill[pl.grp[f]]++] = FamDesc{ fam_first[f] / 64, (fam_count[f] + 63) / 64, fam_count[f], f };
+  // The streams launched on.  The register-resident kernel gains nothing from smaller workgroups (measured: 11.5 vs 10.3 ms): one
+  // launch of 256 threads for the three smaller shapes -- adjacent in `fam` -- on the third one's stream.  The device-wide launch
+  // shares the last shape's.
+  const int g0 = RAMX_CP_NCLASS;
+  for (int c = 0; c < RAMX_NGROUP; c++) pl.launched[c] = pl.cls_count[c] > 0;
+  if (pl.resident) { pl.launched[g0 + 2] = pl.launched[g0] || pl.launched[g0 + 1] || pl.launched[g0 + 2]; pl.launched[g0] = pl.launched[g0 + 1] = false; }
+  if (pl.n_dev > 0) pl.launched[RAMX_NGROUP - 1] = true;
+  return pl;
+}
+
+// one pass over a batch: its arguments, and what its steps hand on
+struct FamilyPass
+{
+  const ramx_flank *flanks; int32_t n_padded; const int32_t *fam_first, *fam_count; int32_t n_families; const ramx_params *p;
+  int W, L, Np, KW, tab[RAMX_NCLASS][4];
+  float ms;                                  // HIP-event time of the launches (families_join)
+  unsigned long long *fam_dbg, *cp_dbg;      // -DRAMX_PRK_TIMING / -DRAMX_CP_TIMING builds: phase sums of block 0
+};
+
+static int families_check(const ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first, const int32_t *fam_count,
+                          int32_t n_families, const ramx_params *p)
 {
   if (!d || !p || !p->matrix || n_families < 0 || n_padded < 0 || (n_padded & 63) || (n_families && (!fam_first || !fam_count || !flanks)))
   { ramx_set_error("ramx_dev_run_families: bad argument"); return RAMX_ERR_ARG; }
-  HIPCHK(hipSetDevice(d->ordinal));
-  const int W = p->bandwidth, L = p->L;
-  if (W < 1 || L < 0) { ramx_set_error("ramx_dev_run_families: bad bandwidth / L"); return RAMX_ERR_ARG; }
-  // register-resident family kernel where it applies, the streaming family kernel for everything else
-  const bool resident = fam_has_width(W) && p->gapopen <= 0 && p->gapextn <= 0 && p->gapopen + p->gapextn >= -32768 &&
-                        !d->force_chain && getenv("RAMX_NO_PERSISTENT") == NULL;
+  if (p->bandwidth < 1 || p->L < 0) { ramx_set_error("ramx_dev_run_families: bad bandwidth / L"); return RAMX_ERR_ARG; }
   int maxn = 0;
   for (int f = 0; f < n_families; f++)
   {
@@ -1221,361 +1376,265 @@ static int run_families_pass(ramx_dev *d, const ramx_flank *flanks, int32_t n_pa
     if (fam_count[f] > maxn) maxn = fam_count[f];
   }
   if (maxn > 512) { ramx_set_error("batch mode: a family has more than 512 flanks"); return RAMX_ERR_UNSUPPORTED; }
-  if (n_families == 0) return RAMX_OK;
-  const int Np = n_padded > 0 ? n_padded : 64;
-  const int KW = window_words(L, W);
+  return RAMX_OK;
+}
+
+// Buffers, then everything the launches read, on the library's stream: descriptors, flanks, their packed windows, the cleared
+// consensus -- and, BEFORE the fork of the group streams, what the device-wide launch needs (descriptors, cleared vote / error
+// words: one set per multi-workgroup family): that launch is then the first thing the idle device sees, and its workgroups are
+// resident before any other group's.
+static int families_upload(ramx_dev *d, FamilyPass &b, const FamilyPlan &pl)
+{
+  const size_t n = (size_t)b.n_families, cons_bytes = n * (b.L > 0 ? b.L : 1) + 16;
   int rc;
-  if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)Np * sizeof(ramx_flank)))) return rc;
-  if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)KW * Np * sizeof(unsigned)))) return rc;
-  if ((rc = ensure(&d->d_bounds, &d->cap_bounds, (size_t)Np * sizeof(int2)))) return rc;   // kept between calls: hipFree/hipMalloc
-  if ((rc = ensure(&d->d_trim, &d->cap_trim, (size_t)Np * sizeof(int2)))) return rc;       // per call cost ~0.5 ms of device sync
-  if ((rc = ensure(&d->d_cons, &d->cap_cons, (size_t)n_families * (L > 0 ? L : 1) + 16))) return rc;
-  // Route of every family.  Groups 0 .. RAMX_CP_NCLASS-1: the cell-parallel kernel (K lanes per flank, ramx_cp.hip) for
-  // families it can take -- supported band width and scoring system, small enough for one workgroup at K lanes per
-  // flank, every flank either empty or starting at or before the first base behind the core edge (t_lo <= 0; the
-  // masked band's carry argument needs the out-of-bounds prefix to end at or before the band centre).  Groups
-  // RAMX_CP_NCLASS ..: one lane per flank, by workgroup shape (64, 128, 256, 512 threads = 1, 2, 4, 8 tiles).
-  int tab9[RAMX_NCLASS][4];
-  class_tab(p, tab9);
-  const int cp_max = d->force_chain ? 0 : ramx_cp_max_family(W, p->gapopen, p->gapextn, tab9, L);
-  FamDesc *hfd = (FamDesc *)malloc(sizeof(FamDesc) * n_families);
-  int *grp = (int *)malloc(sizeof(int) * n_families);
-  int cls_first[RAMX_NGROUP + 1], cls_count[RAMX_NGROUP], cp_k[RAMX_CP_NCLASS], cp_threads[RAMX_CP_NCLASS];
-  memset(cls_count, 0, sizeof(cls_count));
-  memset(cp_k, 0, sizeof(cp_k)); memset(cp_threads, 0, sizeof(cp_threads));
-  auto cls_of = [](int nx) { return nx <= 64 ? 0 : nx <= 128 ? 1 : nx <= 256 ? 2 : 3; };
-  // Families above one cell-parallel workgroup (group -1): several workgroups per family, the family's vote through its
-  // own ticket words -- the device-wide mode of the same kernel, all such families in ONE launch of at most one
-  // workgroup per CU (every workgroup must be resident).
-  int n_cp = 0, n_dev = 0, dev_k = 0, dev_threads = 0, dev_vw = 0;
-  const int cus = d->cus;
-  std::vector<CpDevDesc> hdev;
-  std::vector<int> dev_round_first, dev_round_blocks;   // rounds of at most `cus` workgroups, launched one after the other
-  const bool dev_route = allow_dev && cp_max > 0 && cus > 0 && getenv("RAMX_NO_CP_DEVICE") == NULL && getenv("RAMX_NO_PERSISTENT") == NULL;
-  // small workgroups (four band waves, lowest latency) when all the multi-workgroup families then fit the CUs together
-  int dev_wide = 0;
-  if (dev_route)
+  // the process-wide session serves seam 1 too: a packed-rows direction that stopped early may still be packing beside us
+  if ((rc = pack_settle(d)) != RAMX_OK) return rc;
+  if ((rc = ensure_windows(d, b.Np, b.KW))) return rc;
+  if ((rc = ensure(&d->d_cons, &d->cap_cons, cons_bytes))) return rc;
+  if ((rc = ensure(&d->d_fam, &d->cap_fam, sizeof(FamDesc) * n))) return rc;
+  if ((rc = ensure(&d->d_famctl, &d->cap_famctl, sizeof(RamxCtl) * n))) return rc;
+  // the streaming kernel keeps the rows of every family in the row buffer
+  if (!pl.resident && pl.n_cp + pl.n_dev < b.n_families && (rc = ensure_rows(d, (size_t)b.Np * (b.W + 1) * sizeof(int4), false))) return rc;
+  if (pl.n_dev > 0)
   {
-    long long need = 0;
-    for (int f = 0; f < n_families; f++)
-    {
-      if (fam_count[f] <= cp_max) continue;
-      int k = 0, th = 0, nb = 0;
-      int vwf = 0;
-      ramx_cp_device_plan(W, fam_count[f], cus, 0, &k, &th, &nb, &vwf);
-      need += k > 0 ? nb : 0;
-    }
-    dev_wide = need > cus;
+    if ((rc = ensure(&d->d_devdesc, &d->cap_devdesc, sizeof(CpDevDesc) * pl.dev.size()))) return rc;
+    if ((rc = ensure(&d->d_vote_sets, &d->cap_vote_sets, sizeof(PShard) * RAMX_CP_NSETS * NSHARD * (size_t)pl.n_dev))) return rc;
+    if ((rc = ensure(&d->d_err_sets, &d->cap_err_sets, 64 * (size_t)pl.n_dev))) return rc;
   }
-  for (int f = 0; f < n_families; f++)
-  {
-    int g = RAMX_CP_NCLASS + cls_of(fam_count[f]);
-    if (fam_count[f] > 0 && cp_max > 0)
-    {
-      bool ok = true;
-      for (int i = 0; i < fam_count[f] && ok; i++)
-      {
-        const ramx_flank &x = flanks[fam_first[f] + i];
-        ok = (x.t_lo <= 0) || (x.t_lo > x.t_hi);
-      }
-      int k = 0, th = 0;
-      const int c = (ok && fam_count[f] <= cp_max) ? ramx_cp_class(W, fam_count[f], &k, &th) : -1;
-      if (c >= 0) { g = c; cp_k[c] = k; cp_threads[c] = th; n_cp++; }
-      else if (ok && dev_route)
-      {
-        int nb = 0;
-        int vwf = 0;
-        ramx_cp_device_plan(W, fam_count[f], cus, dev_wide, &k, &th, &nb, &vwf);
-        if (k > 0 && nb <= cus && (dev_k == 0 || (k == dev_k && th == dev_threads && vwf == dev_vw)))
-        {
-          dev_k = k; dev_threads = th; dev_vw = vwf;
-          if (dev_round_first.empty() || dev_round_blocks.back() + nb > cus)
-          {
-            dev_round_first.push_back((int)hdev.size());
-            dev_round_blocks.push_back(0);
-          }
-          dev_round_blocks.back() += nb;
-          for (int b = 0; b < nb; b++)
-          {
-            CpDevDesc x;
-            memset(&x, 0, sizeof(x));
-            x.first = fam_first[f]; x.nx = fam_count[f]; x.b = b; x.nb = nb; x.id = f; x.vs = n_dev;
-            hdev.push_back(x);
-          }
-          n_dev++;
-          g = -1;
-        }
-      }
-    }
-    grp[f] = g;
-    if (g >= 0) cls_count[g]++;
-  }
-  cls_first[0] = 0;
-  for (int c = 0; c < RAMX_NGROUP; c++) cls_first[c + 1] = cls_first[c] + cls_count[c];
-  {
-    int fill[RAMX_NGROUP];
-    for (int c = 0; c < RAMX_NGROUP; c++) fill[c] = cls_first[c];
-    for (int f = 0; f < n_families; f++)
-    {
-      if (grp[f] < 0) continue;
-      FamDesc &x = hfd[fill[grp[f]]++];
-      x.tile0 = fam_first[f] / 64; x.ntiles = (fam_count[f] + 63) / 64; x.nx = fam_count[f]; x.id = f;
-    }
-  }
-  // from here on every failure leaves through `done` (host buffers are released there)
-  RamxCtl *hctl = NULL;
-  int2 *tmp = NULL;
-  float ms = 0;
-  unsigned long long *cp_dbg = NULL;
-#define FAMCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
-    ramx_set_error("HIP error %s at %s:%d (%s)", hipGetErrorString(e_), __FILE__, __LINE__, #call); rc = RAMX_ERR_HIP; goto done; } } while (0)
-  FamDesc *dfd; RamxCtl *dctl;
-  FArgs fa;
-  const bool legacy_any = n_cp + n_dev < n_families;
-  if ((rc = ensure(&d->d_fam, &d->cap_fam, sizeof(FamDesc) * (size_t)n_families))) goto done;
-  if ((rc = ensure(&d->d_famctl, &d->cap_famctl, sizeof(RamxCtl) * (size_t)n_families))) goto done;
-  dfd = (FamDesc *)d->d_fam; dctl = d->d_famctl;
-  FAMCHK(hipMemcpyAsync(dfd, hfd, sizeof(FamDesc) * n_families, hipMemcpyHostToDevice, d->stream));
-  if (n_padded) FAMCHK(hipMemcpyAsync(d->d_flanks, flanks, (size_t)n_padded * sizeof(ramx_flank), hipMemcpyHostToDevice, d->stream));
-  if ((rc = launch_pack(d, n_padded, Np, W, 0, KW, d->stream)) != RAMX_OK) goto done;
-  d->packed_kw = KW;
-  FAMCHK(hipMemsetAsync(d->d_cons, 0, (size_t)n_families * (L > 0 ? L : 1) + 16, d->stream));   // columns a family never ran read as 0
-  memset(&fa, 0, sizeof(fa));
-  fa.bases = d->d_bases; fa.bounds = d->d_bounds; fa.fam = dfd; fa.trim = d->d_trim; fa.ctl_out = dctl; fa.cons_out = d->d_cons;
-  fa.Np = Np; fa.L = L; fa.go = p->gapopen; fa.ge = p->gapextn; fa.cap = p->cappenalty; fa.minimp = p->minimprovement;
-  fa.when_to_stop = p->when_to_stop;
-  memcpy(fa.tab, tab9, sizeof(fa.tab));
-  fa.pack_ok = getenv("RAMX_NO_FASTPACK") ? 0 : fast_pack_ok(fa.tab, fa.go, fa.ge, L, W);
-  if (fa.pack_ok && getenv("RAMX_NO_MASKHI") == NULL) fa.pack_ok = 2;
-  fa.lean_p = lean_p_of(fa.tab, fa.go, fa.ge);
+  if (!pl.fam.empty()) HIPCHK(hipMemcpyAsync(d->d_fam, pl.fam.data(), sizeof(FamDesc) * pl.fam.size(), hipMemcpyHostToDevice, d->stream));
+  if (b.n_padded) HIPCHK(hipMemcpyAsync(d->d_flanks, b.flanks, (size_t)b.n_padded * sizeof(ramx_flank), hipMemcpyHostToDevice, d->stream));
+  if ((rc = launch_pack(d, b.n_padded, b.Np, b.W, 0, b.KW, d->stream)) != RAMX_OK) return rc;
+  d->packed_kw = b.KW;
+  HIPCHK(hipMemsetAsync(d->d_cons, 0, cons_bytes, d->stream));       // columns a family never ran read as 0
 #ifdef RAMX_PRK_TIMING
-  FAMCHK(hipMalloc((void **)&fa.dbg, 8 * 8 * sizeof(unsigned long long)));
-  FAMCHK(hipMemset(fa.dbg, 0, 8 * 8 * sizeof(unsigned long long)));
+  HIPCHK(hipMalloc((void **)&b.fam_dbg, 8 * 8 * sizeof(unsigned long long)));
+  HIPCHK(hipMemset(b.fam_dbg, 0, 8 * 8 * sizeof(unsigned long long)));
 #endif
-  FAMCHK(hipEventRecord(d->ev_begin, d->stream));
+#ifdef RAMX_CP_TIMING
+  HIPCHK(hipMalloc((void **)&b.cp_dbg, (16 * 16 + 8) * sizeof(unsigned long long)));       // the classes', else the device-wide launch's
+  HIPCHK(hipMemset(b.cp_dbg, 0, (16 * 16 + 8) * sizeof(unsigned long long)));
+#endif
+  HIPCHK(hipEventRecord(d->ev_begin, d->stream));
   // the groups run side by side: one stream per group, forked from / joined into the library's stream
   if (!d->cls_init)
   {
     for (int c = 0; c < RAMX_NGROUP; c++)
     {
-      FAMCHK(hipStreamCreateWithFlags(&d->cls_stream[c], hipStreamNonBlocking));
-      FAMCHK(hipEventCreateWithFlags(&d->cls_done[c], hipEventDisableTiming));
+      HIPCHK(hipStreamCreateWithFlags(&d->cls_stream[c], hipStreamNonBlocking));
+      HIPCHK(hipEventCreateWithFlags(&d->cls_done[c], hipEventDisableTiming));
     }
-    FAMCHK(hipEventCreateWithFlags(&d->cls_ready, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&d->cls_ready, hipEventDisableTiming));
     d->cls_init = 1;
   }
-  if (n_dev > 0)
+  if (pl.n_dev > 0)
   {
-    // everything the device-wide launch needs is uploaded and cleared on the library's stream, BEFORE the fork: the launch
-    // itself is then the first thing the idle device sees, and its workgroups are resident before any other group's
-    // (vote / error words: one set per multi-workgroup family, not per family of the batch)
-    if ((rc = ensure(&d->d_devdesc, &d->cap_devdesc, sizeof(CpDevDesc) * hdev.size()))) goto done;
-    if ((rc = ensure(&d->d_vote_sets, &d->cap_vote_sets, sizeof(PShard) * RAMX_CP_NSETS * NSHARD * (size_t)n_dev))) goto done;
-    if ((rc = ensure(&d->d_err_sets, &d->cap_err_sets, 64 * (size_t)n_dev))) goto done;
-    FAMCHK(hipMemcpyAsync(d->d_devdesc, hdev.data(), sizeof(CpDevDesc) * hdev.size(), hipMemcpyHostToDevice, d->stream));
-    FAMCHK(hipMemsetAsync(d->d_vote_sets, 0, sizeof(PShard) * RAMX_CP_NSETS * NSHARD * (size_t)n_dev, d->stream));
-    FAMCHK(hipMemsetAsync(d->d_err_sets, 0, 64 * (size_t)n_dev, d->stream));
+    HIPCHK(hipMemcpyAsync(d->d_devdesc, pl.dev.data(), sizeof(CpDevDesc) * pl.dev.size(), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemsetAsync(d->d_vote_sets, 0, sizeof(PShard) * RAMX_CP_NSETS * NSHARD * (size_t)pl.n_dev, d->stream));
+    HIPCHK(hipMemsetAsync(d->d_err_sets, 0, 64 * (size_t)pl.n_dev, d->stream));
   }
-  FAMCHK(hipEventRecord(d->cls_ready, d->stream));
-  // every group stream waits (the register-resident branch below merges shapes AFTER this point: a stream that is
-  // launched on must never have skipped the wait -- uploads and the pack kernel run on the library's stream)
-  for (int c = 0; c < RAMX_NGROUP; c++) FAMCHK(hipStreamWaitEvent(d->cls_stream[c], d->cls_ready, 0));
-  // ---- families above one workgroup: device-wide mode, one launch, enqueued first ----------------
-  if (n_dev > 0)
+  // every group stream waits, whether the plan launches on it or not: uploads and the pack kernel run on the library's stream
+  HIPCHK(hipEventRecord(d->cls_ready, d->stream));
+  for (int c = 0; c < RAMX_NGROUP; c++) HIPCHK(hipStreamWaitEvent(d->cls_stream[c], d->cls_ready, 0));
+  return RAMX_OK;
+}
+
+// families above one workgroup: the device-wide mode, enqueued first, on the stream of the last lane-per-flank shape
+static int launch_dev_families(ramx_dev *d, FamilyPass &b, const FamilyPlan &pl)
+{
+  if (pl.n_dev == 0) return RAMX_OK;
+  CPArgs ca = cp_args(d, d->d_famctl, b.Np, b.KW, *b.p, b.tab);
+  ca.nranks = 1; ca.rank = 0;
+  ca.vote = d->d_vote_sets; ca.err = d->d_err_sets; ca.vote_wave = pl.dev_vw;
+  // test hooks: RAMX_TEST_CP_DROP_TICKET=row withholds one workgroup's words for that row, in every multi-workgroup family or
+  // only in family RAMX_TEST_CP_DROP_FAMILY (index in the batch)
+  const char *td = getenv("RAMX_TEST_CP_DROP_TICKET"), *tf = getenv("RAMX_TEST_CP_DROP_FAMILY");
+  ca.test_drop_row = td ? atoi(td) : 0; ca.test_drop_id = tf ? atoi(tf) : -1;
+  ca.dbg = pl.n_cp == 0 ? b.cp_dbg : NULL;
+  for (const int2 &ro : pl.rounds)
   {
-    CPArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.bases = d->d_bases; ca.bounds = d->d_bounds; ca.trim = d->d_trim; ca.ctl_out = dctl; ca.cons_out = d->d_cons;
-    ca.Np = Np; ca.KW = KW; ca.L = L; ca.go = p->gapopen; ca.ge = p->gapextn; ca.cap = p->cappenalty; ca.minimp = p->minimprovement;
-    ca.when_to_stop = p->when_to_stop;
-    memcpy(ca.tab, tab9, sizeof(ca.tab));
-    ca.nranks = 1; ca.rank = 0;
-    {
-      hipStream_t st = d->cls_stream[RAMX_NGROUP - 1];       // shares a stream with the last lane-per-flank shape, enqueued before it
-      ca.dev = d->d_devdesc; ca.vote = d->d_vote_sets; ca.err = d->d_err_sets; ca.vote_wave = dev_vw;
-      // test hooks: RAMX_TEST_CP_DROP_TICKET=row withholds one workgroup's words for that row, in every multi-workgroup
-      // family or only in family RAMX_TEST_CP_DROP_FAMILY (index in the batch)
-      { const char *td = getenv("RAMX_TEST_CP_DROP_TICKET"), *tf = getenv("RAMX_TEST_CP_DROP_FAMILY");
-        ca.test_drop_row = td ? atoi(td) : 0; ca.test_drop_id = tf ? atoi(tf) : -1; }
-      cp_test_hooks(ca);
-#ifdef RAMX_CP_TIMING
-      if (n_cp == 0)
-      {
-        FAMCHK(hipMalloc((void **)&ca.dbg, (16 * 16 + 8) * sizeof(unsigned long long)));
-        FAMCHK(hipMemset(ca.dbg, 0, (16 * 16 + 8) * sizeof(unsigned long long)));
-        cp_dbg = ca.dbg;
-      }
-#endif
-      for (size_t ro = 0; ro < dev_round_first.size(); ro++)
-      {
-        ca.dev = d->d_devdesc + dev_round_first[ro];
-        rc = ramx_cp_launch_device(st, W, dev_k, dev_threads, dev_round_blocks[ro], ca);
-        if (rc != RAMX_OK) { ramx_set_error("cell-parallel multi-family device launch failed (W %d, %d workgroups)", W, dev_round_blocks[ro]); goto done; }
-      }
-    }
+    ca.dev = d->d_devdesc + ro.x;
+    const int rc = ramx_cp_launch_device(d->cls_stream[RAMX_NGROUP - 1], b.W, pl.dev_k, pl.dev_threads, ro.y, ca);
+    if (rc != RAMX_OK) { ramx_set_error("cell-parallel multi-family device launch failed (W %d, %d workgroups)", b.W, ro.y); return rc; }
   }
-  // ---- cell-parallel groups ------------------------------------------------------------------
-  if (n_cp > 0)
+  return RAMX_OK;
+}
+
+// the cell-parallel classes, each on its own stream
+static int launch_cp_families(ramx_dev *d, FamilyPass &b, const FamilyPlan &pl)
+{
+  if (pl.n_cp == 0) return RAMX_OK;
+  CPArgs ca = cp_args(d, d->d_famctl, b.Np, b.KW, *b.p, b.tab);
+  if (getenv("RAMX_CP_PEEK") != NULL)
   {
-    CPArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.bases = d->d_bases; ca.bounds = d->d_bounds; ca.trim = d->d_trim; ca.ctl_out = dctl; ca.cons_out = d->d_cons;
-    ca.state_out = NULL;
-    ca.Np = Np; ca.KW = KW; ca.L = L; ca.go = p->gapopen; ca.ge = p->gapextn; ca.cap = p->cappenalty; ca.minimp = p->minimprovement;
-    ca.when_to_stop = p->when_to_stop;
-    memcpy(ca.tab, tab9, sizeof(ca.tab));
-    ca.lean_p = lean_p_of(ca.tab, ca.go, ca.ge);
-    if (getenv("RAMX_CP_PEEK") != NULL)
-    {
-      // test hook: keep the final rows of every flank, [flank][2W+1] (m, e), for ramx_dev_peek_family_state
-      const size_t need = (size_t)Np * (2 * W + 1) * sizeof(int2);
-      if ((rc = ensure(&d->d_cpstate, &d->cap_cpstate, need))) goto done;
-      FAMCHK(hipMemsetAsync(d->d_cpstate, 0, need, d->stream));
-      FAMCHK(hipEventRecord(d->cls_ready, d->stream));
-      for (int c = 0; c < RAMX_CP_NCLASS; c++) FAMCHK(hipStreamWaitEvent(d->cls_stream[c], d->cls_ready, 0));
-      ca.state_out = (int2 *)d->d_cpstate;
-      d->cpstate_W = W; d->cpstate_n = Np;
-    }
-#ifdef RAMX_CP_TIMING
-    FAMCHK(hipMalloc((void **)&ca.dbg, (16 * 16 + 8) * sizeof(unsigned long long)));
-    FAMCHK(hipMemset(ca.dbg, 0, (16 * 16 + 8) * sizeof(unsigned long long)));
-    cp_dbg = ca.dbg;
-#endif
-    for (int c = 0; c < RAMX_CP_NCLASS; c++)
-    {
-      if (cls_count[c] == 0) continue;
-      ca.fam = dfd + cls_first[c];
-      rc = ramx_cp_launch_families(d->cls_stream[c], W, cp_k[c], cp_threads[c], cls_count[c], ca);
-      if (rc != RAMX_OK) { ramx_set_error("cell-parallel family kernel launch failed (W %d, %d lanes per flank)", W, cp_k[c]); goto done; }
-    }
+    // test hook: keep the final rows of every flank, [flank][2W+1] (m, e), for ramx_dev_peek_family_state
+    const size_t need = (size_t)b.Np * (2 * b.W + 1) * sizeof(int2);
+    const int prc = ensure(&d->d_cpstate, &d->cap_cpstate, need);
+    if (prc != RAMX_OK) return prc;
+    HIPCHK(hipMemsetAsync(d->d_cpstate, 0, need, d->stream));
+    HIPCHK(hipEventRecord(d->cls_ready, d->stream));
+    for (int c = 0; c < RAMX_CP_NCLASS; c++) HIPCHK(hipStreamWaitEvent(d->cls_stream[c], d->cls_ready, 0));
+    ca.state_out = (int2 *)d->d_cpstate;
+    d->cpstate_W = b.W; d->cpstate_n = b.Np;
   }
-  // ---- one lane per flank ---------------------------------------------------------------------
-  if (legacy_any && !resident)
+  ca.dbg = b.cp_dbg;
+  for (int c = 0; c < RAMX_CP_NCLASS; c++)
   {
-    // rows of every family in the (in-place) row buffer: 16 B x (W + 1) slots per flank
-    const size_t state_bytes = (size_t)Np * (W + 1) * sizeof(int4);
-    if (state_bytes > d->cap_state || !d->d_state[0])
-    {
-      if (d->d_state[0]) FAMCHK(hipFree(d->d_state[0]));
-      if (d->d_state[1] && d->d_state[1] != d->d_state[0]) FAMCHK(hipFree(d->d_state[1]));
-      d->d_state[0] = d->d_state[1] = NULL; d->cap_state = 0;
-      FAMCHK(hipMalloc((void **)&d->d_state[0], state_bytes));
-      d->d_state[1] = d->d_state[0];
-      d->cap_state = state_bytes;
-    }
+    if (pl.cls_count[c] == 0) continue;
+    ca.fam = (const FamDesc *)d->d_fam + pl.cls_first[c];
+    const int rc = ramx_cp_launch_families(d->cls_stream[c], b.W, pl.cp_k[c], pl.cp_threads[c], pl.cls_count[c], ca);
+    if (rc != RAMX_OK) { ramx_set_error("cell-parallel family kernel launch failed (W %d, %d lanes per flank)", b.W, pl.cp_k[c]); return rc; }
+  }
+  return RAMX_OK;
+}
+
+// one lane per flank, streaming: one launch per workgroup shape (BLOCK threads: 1, 2, 4 or 8 tiles)
+template <bool CHAIN, int BLOCK>
+static void fam_stream_launch(ramx_dev *d, const FamilyPlan &pl, FSArgs fs)
+{
+  const int g = RAMX_CP_NCLASS + (BLOCK == 64 ? 0 : BLOCK == 128 ? 1 : BLOCK == 256 ? 2 : 3);
+  if (pl.cls_count[g] == 0) return;
+  fs.fam = (const FamDesc *)d->d_fam + pl.cls_first[g];
+  hipLaunchKernelGGL((ramx_family_stream_kernel<CHAIN, BLOCK>), dim3(pl.cls_count[g]), dim3(BLOCK), 0, d->cls_stream[g], fs);
+}
+
+// ... register-resident: F families of up to BLOCK flanks, at one of the widths of fam_has_width
+template <int BLOCK>
+static int fam_launch(int W, FArgs fa, const FamDesc *fam, int F, hipStream_t st)
+{
+  if (F == 0) return RAMX_OK;
+  fa.fam = fam;
+  if (W == 14) hipLaunchKernelGGL((ramx_family_kernel<14, BLOCK>), dim3(F), dim3(BLOCK), 0, st, fa);
+  else if (W == 20) hipLaunchKernelGGL((ramx_family_kernel<20, BLOCK>), dim3(F), dim3(BLOCK), 0, st, fa);
+  else hipLaunchKernelGGL((ramx_family_kernel<40, BLOCK>), dim3(F), dim3(BLOCK), 0, st, fa);
+  HIPCHK(hipGetLastError());
+  return RAMX_OK;
+}
+
+// the families no cell-parallel launch took: the streaming kernel, or the register-resident one where it applies
+static int launch_lane_families(ramx_dev *d, FamilyPass &b, const FamilyPlan &pl)
+{
+  if (pl.n_cp + pl.n_dev == b.n_families) return RAMX_OK;
+  const ramx_params &p = *b.p;
+  const int g0 = RAMX_CP_NCLASS;
+  const FamDesc *dfd = (const FamDesc *)d->d_fam;
+  if (!pl.resident)
+  {
     FSArgs fs;
     memset(&fs, 0, sizeof(fs));
     fs.k.bases = d->d_bases; fs.k.bounds = d->d_bounds; fs.k.trim = d->d_trim; fs.k.S_in = d->d_state[0]; fs.k.S_out = d->d_state[0];
-    fs.k.Np = Np; fs.k.Nx = Np; fs.k.W = W; fs.k.go = p->gapopen; fs.k.ge = p->gapextn; fs.k.cap = p->cappenalty;
-    fs.k.minimp = p->minimprovement; fs.k.when_to_stop = p->when_to_stop;
-    memcpy(fs.k.tab, fa.tab, sizeof(fs.k.tab));
-    fs.fam = dfd; fs.ctl_out = dctl; fs.cons_out = d->d_cons; fs.L = L;
-    const bool chain = p->gapopen > 0 || p->gapextn > 0 || d->force_chain;
-#define RAMX_FS_LAUNCH(CH, BL, C) do { const int g_ = RAMX_CP_NCLASS + (C); if (cls_count[g_] > 0) { fs.fam = dfd + cls_first[g_]; \
-      hipLaunchKernelGGL((ramx_family_stream_kernel<CH, BL>), dim3(cls_count[g_]), dim3(BL), 0, d->cls_stream[g_], fs); } } while (0)
-    if (chain) { RAMX_FS_LAUNCH(true, 64, 0); RAMX_FS_LAUNCH(true, 128, 1); RAMX_FS_LAUNCH(true, 256, 2); RAMX_FS_LAUNCH(true, 512, 3); }
-    else { RAMX_FS_LAUNCH(false, 64, 0); RAMX_FS_LAUNCH(false, 128, 1); RAMX_FS_LAUNCH(false, 256, 2); RAMX_FS_LAUNCH(false, 512, 3); }
-#undef RAMX_FS_LAUNCH
-    FAMCHK(hipGetLastError());
+    fs.k.Np = b.Np; fs.k.Nx = b.Np; fs.k.W = b.W; fs.k.go = p.gapopen; fs.k.ge = p.gapextn; fs.k.cap = p.cappenalty;
+    fs.k.minimp = p.minimprovement; fs.k.when_to_stop = p.when_to_stop;
+    memcpy(fs.k.tab, b.tab, sizeof(fs.k.tab));
+    fs.fam = dfd; fs.ctl_out = d->d_famctl; fs.cons_out = d->d_cons; fs.L = b.L;
+    if (pl.chain) { fam_stream_launch<true, 64>(d, pl, fs); fam_stream_launch<true, 128>(d, pl, fs); fam_stream_launch<true, 256>(d, pl, fs); fam_stream_launch<true, 512>(d, pl, fs); }
+    else { fam_stream_launch<false, 64>(d, pl, fs); fam_stream_launch<false, 128>(d, pl, fs); fam_stream_launch<false, 256>(d, pl, fs); fam_stream_launch<false, 512>(d, pl, fs); }
+    HIPCHK(hipGetLastError());
+    return RAMX_OK;
   }
-  else if (legacy_any)
-  {
-    // the register-resident kernel gains nothing from smaller workgroups (measured: 11.5 vs 10.3 ms; rotating the live
-    // waves over the SIMDs by arrival order on the CU did not help either): 256 threads up to 256 flanks (the three
-    // smaller shapes are adjacent in the descriptor array), 512 above
-    const int g0 = RAMX_CP_NCLASS;
-    const int n256 = cls_count[g0] + cls_count[g0 + 1] + cls_count[g0 + 2], n512 = cls_count[g0 + 3];
-    if (n256 > 0)
-    {
-      fa.fam = dfd + cls_first[g0];
-      hipStream_t st = d->cls_stream[g0 + 2];
-      rc = (W == 14) ? fam_launch<14, 256>(d, fa, n256, st) : (W == 20) ? fam_launch<20, 256>(d, fa, n256, st) : fam_launch<40, 256>(d, fa, n256, st);
-      if (rc != RAMX_OK) goto done;
-      cls_count[g0 + 2] = n256; cls_count[g0] = cls_count[g0 + 1] = 0;     // for the join below
-    }
-    if (n512 > 0)
-    {
-      fa.fam = dfd + cls_first[g0 + 3];
-      hipStream_t st = d->cls_stream[g0 + 3];
-      rc = (W == 14) ? fam_launch<14, 512>(d, fa, n512, st) : (W == 20) ? fam_launch<20, 512>(d, fa, n512, st) : fam_launch<40, 512>(d, fa, n512, st);
-      if (rc != RAMX_OK) goto done;
-    }
-  }
+  FArgs fa;
+  memset(&fa, 0, sizeof(fa));
+  fa.bases = d->d_bases; fa.bounds = d->d_bounds; fa.fam = dfd; fa.trim = d->d_trim; fa.ctl_out = d->d_famctl; fa.cons_out = d->d_cons;
+  fa.Np = b.Np; fa.L = b.L; fa.go = p.gapopen; fa.ge = p.gapextn; fa.cap = p.cappenalty; fa.minimp = p.minimprovement;
+  fa.when_to_stop = p.when_to_stop;
+  memcpy(fa.tab, b.tab, sizeof(fa.tab));
+  fa.pack_ok = getenv("RAMX_NO_FASTPACK") ? 0 : fast_pack_ok(fa.tab, fa.go, fa.ge, b.L, b.W);
+  if (fa.pack_ok && getenv("RAMX_NO_MASKHI") == NULL) fa.pack_ok = 2;
+  fa.lean_p = lean_p_of(fa.tab, fa.go, fa.ge);
+  fa.dbg = b.fam_dbg;
+  // 256 threads up to 256 flanks (the three smaller shapes in one launch, see family_plan), 512 above
+  const int n256 = pl.cls_count[g0] + pl.cls_count[g0 + 1] + pl.cls_count[g0 + 2];
+  const int rc = fam_launch<256>(b.W, fa, dfd + pl.cls_first[g0], n256, d->cls_stream[g0 + 2]);
+  return rc != RAMX_OK ? rc : fam_launch<512>(b.W, fa, dfd + pl.cls_first[g0 + 3], pl.cls_count[g0 + 3], d->cls_stream[g0 + 3]);
+}
+
+// every stream the plan launched on back into the library's stream; on return everything has run
+static int families_join(ramx_dev *d, FamilyPass &b, const FamilyPlan &pl)
+{
   for (int c = 0; c < RAMX_NGROUP; c++)
-    if (cls_count[c] > 0 || (c == RAMX_NGROUP - 1 && n_dev > 0))
-    { FAMCHK(hipEventRecord(d->cls_done[c], d->cls_stream[c])); FAMCHK(hipStreamWaitEvent(d->stream, d->cls_done[c], 0)); }
-  FAMCHK(hipEventRecord(d->ev_end, d->stream));
-  FAMCHK(hipStreamSynchronize(d->stream));
-  FAMCHK(hipEventElapsedTime(&ms, d->ev_begin, d->ev_end));
-#ifdef RAMX_PRK_TIMING
-  if (resident && legacy_any)
+    if (pl.launched[c]) { HIPCHK(hipEventRecord(d->cls_done[c], d->cls_stream[c])); HIPCHK(hipStreamWaitEvent(d->stream, d->cls_done[c], 0)); }
+  HIPCHK(hipEventRecord(d->ev_end, d->stream));
+  HIPCHK(hipStreamSynchronize(d->stream));
+  HIPCHK(hipEventElapsedTime(&b.ms, d->ev_begin, d->ev_end));
+  return RAMX_OK;
+}
+
+// control blocks, consensus and trim records to the caller.  timed_out[f] != 0: that family's device-wide vote gave up -- its
+// outputs are invalid; with timed_out == NULL such a family makes the whole call fail.
+static int families_fetch(ramx_dev *d, const FamilyPass &b, const FamilyPlan &pl, ramx_run_info *infos, int8_t *cons, int32_t *trim_high,
+                          int32_t *trim_pos, unsigned char *timed_out)
+{
+  const int n = b.n_families, L = b.L;
+  std::vector<RamxCtl> hctl((size_t)n);
+  HIPCHK(hipMemcpy(hctl.data(), d->d_famctl, sizeof(RamxCtl) * (size_t)n, hipMemcpyDeviceToHost));
+  if (cons && L > 0) HIPCHK(hipMemcpy(cons, d->d_cons, (size_t)n * L, hipMemcpyDeviceToHost));
+  if ((trim_high || trim_pos) && b.n_padded)
   {
-    unsigned long long h[64];
-    FAMCHK(hipMemcpy(h, fa.dbg, sizeof(h), hipMemcpyDeviceToHost));
-    static const char *nm[6] = { "vote + stop rule", "winner table+barrier", "band + contrib", "wave reduce", "end barrier", "loop top" };
-    const double cols = h[6] ? (double)h[6] : 1.0;
-    fprintf(stderr, "FAM_TIMING family 0 (block 0), %.0f columns, ns per column per wave:\n", cols);
-    for (int k = 0; k < 6; k++)
-      fprintf(stderr, "FAM_TIMING %-22s w0 %7.1f  w1 %7.1f  w2 %7.1f  w3 %7.1f\n", nm[k], 10.0 * h[k] / cols, 10.0 * h[8 + k] / cols,
-              10.0 * h[16 + k] / cols, 10.0 * h[24 + k] / cols);
+    std::vector<int2> tmp((size_t)b.n_padded);
+    HIPCHK(hipMemcpy(tmp.data(), d->d_trim, tmp.size() * sizeof(int2), hipMemcpyDeviceToHost));
+    for (int i = 0; i < b.n_padded; i++) { if (trim_high) trim_high[i] = tmp[i].x; if (trim_pos) trim_pos[i] = tmp[i].y; }
   }
-  if (fa.dbg) (void)hipFree(fa.dbg);
-#endif
-#ifdef RAMX_CP_TIMING
-  if (cp_dbg)
+  for (int f = 0; f < n; f++)
   {
-    unsigned long long h[16 * 16 + 8];
-    FAMCHK(hipMemcpy(h, cp_dbg, sizeof(h), hipMemcpyDeviceToHost));
-    static const char *nm[12] = { "vote read + stop rule", "(after speculative band)", "row update", "reductions", "records/slide/window",
-                                  "sum+atomics+barrier", "-", "loop top", "wait: drain", "wait: samples + polling", "wait: fold",
-                                  "wait: LDS + barrier" };
-    const double cols = h[16 * 16] ? (double)h[16 * 16] : 1.0;
-    fprintf(stderr, "CP_TIMING block 0, %.0f columns, shader clocks per column (waves 0, 1, last two):\n", cols);
-    int nw = 0;
-    for (int w = 0; w < 16; w++) if (h[w * 16 + 0]) nw = w + 1;
-    for (int k = 0; k < 12; k++)
-      if (k == 6) fprintf(stderr, "CP_TIMING mispredicted columns: %.0f of %.0f\n", (double)h[6], cols);
-      else fprintf(stderr, "CP_TIMING %-24s w0 %7.1f  w1 %7.1f  w%d %7.1f  w%d %7.1f\n", nm[k], h[k] / cols, h[16 + k] / cols,
-                          nw > 1 ? nw - 2 : 0, h[(nw > 1 ? nw - 2 : 0) * 16 + k] / cols, nw > 0 ? nw - 1 : 0, h[(nw > 0 ? nw - 1 : 0) * 16 + k] / cols);
-  }
-#endif
-  hctl = (RamxCtl *)malloc(sizeof(RamxCtl) * n_families);
-  FAMCHK(hipMemcpy(hctl, dctl, sizeof(RamxCtl) * n_families, hipMemcpyDeviceToHost));
-  if (cons && L > 0) FAMCHK(hipMemcpy(cons, d->d_cons, (size_t)n_families * L, hipMemcpyDeviceToHost));
-  if ((trim_high || trim_pos) && n_padded)
-  {
-    tmp = (int2 *)malloc((size_t)n_padded * sizeof(int2));
-    FAMCHK(hipMemcpy(tmp, d->d_trim, (size_t)n_padded * sizeof(int2), hipMemcpyDeviceToHost));
-    for (int i = 0; i < n_padded; i++) { if (trim_high) trim_high[i] = tmp[i].x; if (trim_pos) trim_pos[i] = tmp[i].y; }
-  }
-  for (int f = 0; f < n_families; f++)
-  {
-    const bool gave_up = grp[f] < 0 && hctl[f].pad != 0;
+    const int g = pl.grp[f];
+    const bool gave_up = g < 0 && hctl[f].pad != 0;
     if (timed_out) timed_out[f] = gave_up ? 1 : 0;
-    if (gave_up && !timed_out) { ramx_set_error("batch mode: the vote of a multi-workgroup family timed out (bounded spin gave up)"); rc = RAMX_ERR_STATE; goto done; }
+    if (gave_up && !timed_out) { ramx_set_error("batch mode: the vote of a multi-workgroup family timed out (bounded spin gave up)"); return RAMX_ERR_STATE; }
     if (!infos) continue;
     memset(&infos[f], 0, sizeof(ramx_run_info));
     infos[f].ret = hctl[f].max_row + 1;
     infos[f].rows_executed = hctl[f].rows_done;
     infos[f].limit_warning = (hctl[f].stopped && hctl[f].rows_done - 1 == L - 1) ? 1 : 0;
     infos[f].overflow32 = hctl[f].overflow;
-    infos[f].n_extendable = fam_count[f];
+    infos[f].n_extendable = b.fam_count[f];
     infos[f].launches = 1;
-    infos[f].loop_ms = ms;
+    infos[f].loop_ms = b.ms;
     /* 1: rows resident in registers (3: of K lanes per flank, the cell-parallel kernel); 2: streaming family kernel */
-    infos[f].persistent = grp[f] < RAMX_CP_NCLASS ? 1 : (resident ? 1 : 2);
-    infos[f].lanes_per_flank = grp[f] < 0 ? dev_k : (grp[f] < RAMX_CP_NCLASS ? cp_k[grp[f]] : 1);
-    infos[f].respeculated_rows = grp[f] < 0 ? hctl[f].besta : 0;
+    infos[f].persistent = g < RAMX_CP_NCLASS ? 1 : (pl.resident ? 1 : 2);
+    infos[f].lanes_per_flank = g < 0 ? pl.dev_k : (g < RAMX_CP_NCLASS ? pl.cp_k[g] : 1);
+    infos[f].respeculated_rows = g < 0 ? hctl[f].besta : 0;
   }
-  rc = RAMX_OK;
-done:
-#undef FAMCHK
-  if (cp_dbg) (void)hipFree(cp_dbg);
-  free(hctl); free(tmp); free(hfd); free(grp);
+  return RAMX_OK;
+}
+
+// One pass over a batch.  allow_dev: families above one cell-parallel workgroup may take the device-wide mode (several
+// workgroups voting through ticket words with a bounded spin); a family whose vote gave up there (e.g. its workgroups were not
+// all resident because a co-tenant held CUs) is reported in timed_out, and the caller repeats it with allow_dev = false.
+static int run_families_pass(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                             const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                             ramx_run_info *infos, int8_t *cons, int32_t *trim_high, int32_t *trim_pos,
+                             bool allow_dev, unsigned char *timed_out)
+{
+  int rc = families_check(d, flanks, n_padded, fam_first, fam_count, n_families, p);
+  if (rc != RAMX_OK || n_families == 0) return rc;
+  HIPCHK(hipSetDevice(d->ordinal));
+  FamilyPass b = {};
+  b.flanks = flanks; b.n_padded = n_padded; b.fam_first = fam_first; b.fam_count = fam_count; b.n_families = n_families; b.p = p;
+  b.W = p->bandwidth; b.L = p->L; b.Np = n_padded > 0 ? n_padded : 64; b.KW = window_words(b.L, b.W);
+  class_tab(p, b.tab);
+  // (the plan and its host arrays live until everything enqueued from them has run: families_join synchronises)
+  const FamilyPlan pl = family_plan(route_env(), b.W, p->gapopen, p->gapextn, b.tab, b.L, d->cus, d->force_chain != 0, allow_dev, flanks,
+                                    fam_first, fam_count, n_families);
+  rc = families_upload(d, b, pl);
+  if (rc == RAMX_OK) rc = launch_dev_families(d, b, pl);
+  if (rc == RAMX_OK) rc = launch_cp_families(d, b, pl);
+  if (rc == RAMX_OK) rc = launch_lane_families(d, b, pl);
+  if (rc == RAMX_OK) rc = families_join(d, b, pl);
+#ifdef RAMX_PRK_TIMING
+  if (rc == RAMX_OK && pl.resident && pl.n_cp + pl.n_dev < n_families) rc = fam_timing_report(b.fam_dbg);
+  (void)hipFree(b.fam_dbg);
+#endif
+#ifdef RAMX_CP_TIMING
+  if (rc == RAMX_OK && pl.n_cp + pl.n_dev > 0) rc = cp_family_timing_report(b.cp_dbg);
+  (void)hipFree(b.cp_dbg);
+#endif
+  if (rc == RAMX_OK) rc = families_fetch(d, b, pl, infos, cons, trim_high, trim_pos, timed_out);
   d->ready = 0;       // the single-family buffers were reused: begin_direction must be called again before run_direction
   d->planes_ready = 0;
   return rc;
 }
+
+static ramx_flank empty_flank(void) { ramx_flank x; memset(&x, 0, sizeof(x)); x.t_lo = 1; x.t_hi = 0; x.step = 1; return x; }
+
 
 extern "C" int ramx_dev_run_families(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
                                      const int32_t *fam_count, int32_t n_families, const ramx_params *p,
@@ -1600,13 +1659,7 @@ extern "C" int ramx_dev_run_families(ramx_dev *d, const ramx_flank *flanks, int3
     first2.push_back((int32_t)fl2.size());
     count2.push_back(fam_count[f]);
     const int padded = ((fam_count[f] + 63) / 64) * 64;
-    for (int i = 0; i < padded; i++)
-    {
-      ramx_flank x;
-      if (i < fam_count[f]) x = flanks[fam_first[f] + i];
-      else { memset(&x, 0, sizeof(x)); x.t_lo = 1; x.t_hi = 0; x.step = 1; }      // empty padding flank
-      fl2.push_back(x);
-    }
+    for (int i = 0; i < padded; i++) fl2.push_back(i < fam_count[f] ? flanks[fam_first[f] + i] : empty_flank());
   }
   const int n2 = (int)redo.size(), np2 = (int)fl2.size();
   std::vector<ramx_run_info> inf2((size_t)n2);
@@ -1691,7 +1744,7 @@ static int replay_setup(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded,
   int rc;
   // a piece of the direction before may still be packing into d_bases on the second stream: it must have finished before the
   // buffer can be reallocated, let alone written
-  if (d->pack_busy) { HIPCHK(hipEventSynchronize(d->pack_done)); d->pack_busy = 0; }
+  if ((rc = pack_settle(d, true)) != RAMX_OK) return rc;
   if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)Np * sizeof(ramx_flank)))) return rc;
   if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)KW * Np * sizeof(unsigned)))) return rc;
   if ((rc = ensure(&d->d_bounds, &d->cap_bounds, (size_t)Np * sizeof(int2)))) return rc;
@@ -2194,7 +2247,7 @@ extern "C" int ramx_dev_tsd(ramx_dev *d, const ramx_tsd_site *sites, int32_t n_s
     room[(size_t)i] = s.hi + 1 - s.lo < 64 ? (int)(s.hi + 1 - s.lo) : 64;
   }
   // the flank and window buffers of the direction are reused, as by the replays
-  if (d->pack_busy) { HIPCHK(hipEventSynchronize(d->pack_done)); d->pack_busy = 0; }
+  if ((rc = pack_settle(d, true)) != RAMX_OK) return rc;
   if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)2 * Np * sizeof(ramx_flank)))) return rc;
   if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)RAMX_TSD_KW * 2 * Np * sizeof(unsigned)))) return rc;
   if ((rc = ensure(&d->d_bounds, &d->cap_bounds, (size_t)2 * Np * sizeof(int2)))) return rc;
@@ -2758,15 +2811,11 @@ static int cp_timing_report(const CPArgs &ca, const DirRoute &rt)
 
 // The device-wide cell-parallel launch of the plan in rt: boundary row and every column inside the kernel.  *accepted: the launch
 // call went through -- from there on an error is the kernel's (an execution error: not something another route can serve).
-static int cp_device_launch(ramx_dev *d, const KArgs &a, int L, const DirRoute &rt, bool *accepted)
+static int cp_device_launch(ramx_dev *d, const KArgs &a, const DirRoute &rt, bool *accepted)
 {
   const int nb = rt.nb;
   { const int prc = pack_rest(d); if (prc != RAMX_OK) return prc; }      // this kernel reads the whole window
-  CPArgs ca;
-  memset(&ca, 0, sizeof(ca));
-  ca.bases = d->d_bases; ca.bounds = d->d_bounds; ca.trim = d->d_trim; ca.ctl_out = d->d_ctl; ca.cons_out = d->d_cons;
-  ca.Np = d->Np; ca.KW = d->KW; ca.L = L; ca.go = a.go; ca.ge = a.ge; ca.cap = a.cap; ca.minimp = a.minimp; ca.when_to_stop = a.when_to_stop;
-  memcpy(ca.tab, d->tab, sizeof(ca.tab));
+  CPArgs ca = cp_args(d, d->d_ctl, d->Np, d->KW, d->p, d->tab);       // (a's scalars are d->p's)
   {
     std::vector<CpDevDesc> hd((size_t)nb);
     for (int i = 0; i < nb; i++) { memset(&hd[i], 0, sizeof(CpDevDesc)); hd[i].first = 0; hd[i].nx = d->Nx; hd[i].b = i; hd[i].nb = nb; hd[i].id = 0; }
@@ -2777,7 +2826,6 @@ static int cp_device_launch(ramx_dev *d, const KArgs &a, int L, const DirRoute &
   }
   ca.dev = d->d_devdesc; ca.vote = d->d_vote; ca.err = d->d_err; ca.S = d->d_state[0]; ca.vote_wave = rt.vwf;
   { const char *td = getenv("RAMX_TEST_CP_DROP_TICKET"); ca.test_drop_row = td ? atoi(td) : 0; ca.test_drop_id = -1; }
-  cp_test_hooks(ca);
   ca.nranks = 1; ca.rank = 0;
   if (rt.multi)
   {
@@ -2833,7 +2881,7 @@ static int cp_attempt(ramx_dev *d, const KArgs &a, int L, DirRoute &rt, int *lan
   // from here on a multi-rank run never leaves before the second agreement (a rank that did would leave the others'
   // kernels spinning to their limit and then waiting in a collective it never joins)
   bool accepted = false;
-  const int lrc = cp_device_launch(d, a, L, rt, &accepted);
+  const int lrc = cp_device_launch(d, a, rt, &accepted);
   RamxCtl c0;
   memset(&c0, 0, sizeof(c0));
   int bad = lrc != RAMX_OK;
@@ -3131,7 +3179,7 @@ extern "C" int ramx_dev_peek_windows(ramx_dev *d, uint32_t *words, int64_t words
   if (!words || !bounds || words_cap < (int64_t)KW * Np || lanes_cap < Np)
   { ramx_set_error("ramx_dev_peek_windows: %d words of %d lanes do not fit the caller's buffers", KW, Np); return RAMX_ERR_ARG; }
   HIPCHK(hipSetDevice(d->ordinal));
-  if (d->pack_busy) { HIPCHK(hipEventSynchronize(d->pack_done)); d->pack_busy = 0; }     // a piece still being packed on the second stream
+  { const int src = pack_settle(d, true); if (src != RAMX_OK) return src; }     // a piece still being packed on the second stream
   HIPCHK(hipStreamSynchronize(d->stream));
   HIPCHK(hipMemcpy(words, d->d_bases, (size_t)KW * Np * sizeof(unsigned), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(bounds, d->d_bounds, (size_t)Np * sizeof(int2), hipMemcpyDeviceToHost));

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Host code of the replays under AddressSanitizer + UBSan, as stand-alone programs on the CPU (no GPU is opened, nothing is
-# loaded into python): replay_plan and the route gates of ramx_device.hip, pad_to_tiles and the sinks' one-family view of ramx_extend.c, all static, so each program includes
+# loaded into python): replay_plan, the route gates and the batch's route plan of ramx_device.hip, pad_to_tiles and the sinks' one-family view of ramx_extend.c, all static, so each program includes
 # its source file and takes the rest of the library from the built libramx.so; and ramx_linkage.c, which stands alone.
 # usage: tools/host_asan/run.sh        (after the library has been built)
 set -euo pipefail
@@ -25,3 +25,7 @@ gcc -std=gnu11 -O1 $san $inc -o "$out/linkage" "$here/linkage_main.c" -lm
 "$rocm/bin/hipcc" --offload-arch=gfx950 -x hip -std=c++17 -O1 -g -fno-omit-frame-pointer $inc -Xarch_host -fsanitize=address,undefined \
   -Xarch_host -fno-sanitize-recover=undefined -o "$out/route" "$here/route_main.cpp" $lib -L"$rocm/lib" -lrccl -lpthread
 "$out/route"
+# the route plan of a batch at the edges of its classes, shapes and rounds (family_plan of ramx_device.hip)
+"$rocm/bin/hipcc" --offload-arch=gfx950 -x hip -std=c++17 -O1 -g -fno-omit-frame-pointer $inc -Xarch_host -fsanitize=address,undefined \
+  -Xarch_host -fno-sanitize-recover=undefined -o "$out/family_plan" "$here/family_plan_main.cpp" $lib -L"$rocm/lib" -lrccl -lpthread
+"$out/family_plan"
