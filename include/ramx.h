@@ -197,6 +197,24 @@ typedef struct ramx_refinement
 typedef void (*ramx_refine_cb)(const ramx_refinement *rf, void *user);
 void ramx_set_refine_sink(ramx_refine_cb cb, void *user, int32_t max_replays);
 
+/* CpG sink of seam 1, as the other sinks: with a sink set the kept consensus of every direction that has run -- rows = ret
+ * columns -- is refined over at most max_replays replays with the CpG-aware re-call (ramx_dev_refine_cpg, below; rows_reversed =
+ * !direction as the copies sink, cpg_ts as ramx_recall_cpg) and handed over once per direction and family: the kept consensus,
+ * the refined one with its pileup and its dinucleotide pileup, replays, converged and n_cpg.  A direction without an extendable
+ * core or with ret = 0 is answered on the host.  It comes after the copies sink.  cb == NULL (the default): off -- nothing is
+ * launched or allocated for it. */
+struct ramx_col_dinuc;
+typedef struct ramx_cpg_refinement
+{
+  int32_t direction, family /* index in a batch, else 0 */, rows /* = ret */, refined_rows, replays, converged, n_flanks, n_cpg;
+  const int8_t *cons;                       /* [rows] */
+  const int8_t *refined_cons;               /* [refined_rows] */
+  const struct ramx_col_pileup *refined_cols;
+  const struct ramx_col_dinuc *refined_di;
+} ramx_cpg_refinement;
+typedef void (*ramx_cpg_cb)(const ramx_cpg_refinement *cr, void *user);
+void ramx_set_cpg_sink(ramx_cpg_cb cb, void *user, int32_t max_replays, int32_t cpg_ts);
+
 /* Copies sink of seam 1, as the other sinks: with a sink set the per-copy statistics of every direction that has run
  * (ramx_dev_copy_stats, below) are taken along the kept consensus -- rows = ret columns, rows_reversed = !direction -- and
  * handed over once per direction and family.  ends and stats are [n_flanks].  A direction without an extendable core or with
@@ -467,6 +485,65 @@ int ramx_dev_refine(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, con
                     const int8_t *cons_in, const int32_t *rows_in, int32_t max_replays,
                     int8_t *cons_out, int32_t *rows_out, int32_t *replays, int32_t *converged,
                     ramx_col_pileup *cols, ramx_aln_end *ends, double *kernel_ms);
+
+/* Dinucleotide pileup of an extension: the joint count of what a copy puts into two ADJACENT columns of a GIVEN consensus
+ * cons[0..rows) -- what the marginals of ramx_col_pileup cannot give.  Everything is defined on each flank's ramx_aln_end,
+ * col_idx[r] and col_ins[r]; base classes are the pileup's.  Record r describes the pair of ROWS (r, r + 1); which of the two is
+ * 5' is the caller's business (rows_reversed, as in ramx_dev_copy_stats).  both == adjacent + split + gapped and adjacent ==
+ * sum of di for every record; the record of row rows - 1 has next = -1 and zeros.  Padding flanks and flanks without an
+ * alignment contribute nothing.  The struct is 128 bytes without padding. */
+typedef struct ramx_col_dinuc
+{
+  int32_t base;                         /* cons[r] */
+  int32_t next;                         /* cons[r + 1]; -1 for r == rows - 1 */
+  int32_t both;                         /* flanks with end_row >= r + 1 */
+  int32_t adjacent;                     /* ... both columns matched (neither RAMX_ALN_DELETED) and col_ins[r + 1] == 0 */
+  int32_t split;                        /* ... both columns matched and col_ins[r + 1] > 0 */
+  int32_t gapped;                       /* ... at least one of the two deleted */
+  int32_t di[5][5];                     /* over the adjacent flanks: class x in row r and class y in row r + 1 */
+  int32_t reserved;                     /* written as 0 */
+} ramx_col_dinuc;
+
+/* The dinucleotide pileup on the device: ONE forward pass and ONE walk per group of tiles, as ramx_dev_pileup, then the pileup
+ * kernel (only if cols is given) and the dinucleotide kernel on the same walked columns: one wave per tile counts the row pairs
+ * of its 64 flanks, and a second kernel adds the tiles of every family.  Flank layout, argument checks, self-containedness, the
+ * budget of RAMX_ALIGN_BYTES and rank-local behaviour exactly as ramx_dev_pileup; the grouping does not show in the result.
+ * cols (may be NULL) and di are [n_families][L]: only the first rows[f] entries of a family are written.  ends is [n_padded] or
+ * NULL.  kernel_ms (may be NULL): FOUR values, the HIP-event times of the forward kernels, of the walk kernels, of the pileup
+ * kernels and their sum (0 without cols), and of the dinucleotide kernels and their sum. */
+int ramx_dev_dinuc(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                   const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                   const int8_t *cons, const int32_t *rows, ramx_col_pileup *cols, ramx_col_dinuc *di, ramx_aln_end *ends,
+                   double *kernel_ms);
+
+/* CpG-aware re-call of a consensus from its pileup and its dinucleotide pileup (plain host C, exact integers).
+ *   Pass 1 is ramx_recall_consensus, rule for rule: for every current row it decides whether the row is kept, with which base
+ *   (its plain call), and which inserted columns are emitted before it (a row the cut to L columns does not reach is not kept).
+ *   Pass 2 runs over every row pair (r, r + 1) of which both rows are kept and no inserted column is emitted before row r + 1.
+ *   In reading order the 5' column is r and the 3' column r + 1, D[x][y] = di[r].di[x][y] (rows_reversed == 0), or the 5'
+ *   column is r + 1, the 3' column r and D[x][y] = di[r].di[y][x] (rows_reversed == 1).  With (a, b) the plain calls of the 5'
+ *   and 3' columns the pair is tested iff a is C or T and b is G or A.  Over x, y < 4 (class 4 is ignored), in int64, with
+ *   M[c][s] = matrix[c * 100 + s]:
+ *     S_plain = sum D[x][y] * (M[a][x] + M[b][y])
+ *     S_CG    = sum D[x][y] * (mC(x) + mG(y)),  mC(x) = cpg_ts if x is T else M[C][x],  mG(y) = cpg_ts if y is A else M[G][y]
+ *   The pair is called CG iff (a, b) is (C, G) already or S_CG > S_plain, strictly.
+ * A column cannot be the 3' column of one tested pair and the 5' column of another: the 3' column's plain call is a purine, the
+ * 5' column's a pyrimidine.  Tested pairs are therefore disjoint and the order of pass 2 does not matter.  cpg_ts is the score a
+ * deaminated base (T for the C, A for the G) gets under the CpG hypothesis, in place of matrix[C][T] / matrix[G][A]; 0 says that
+ * a deaminated CpG neither supports nor contradicts the call.  n_cpg (may be NULL): the pairs that came out as CG.  out holds L
+ * entries; returns the new length, which is ramx_recall_consensus's. */
+int32_t ramx_recall_cpg(const int8_t *cons, int32_t rows, const ramx_col_pileup *cols, const ramx_col_dinuc *di,
+                        int32_t rows_reversed, const int32_t *matrix, int32_t cpg_ts, int32_t L, int8_t *out, int32_t *n_cpg);
+
+/* CpG-aware refinement: ramx_dev_refine, word for word, with ramx_recall_cpg(rows_reversed, p->matrix, cpg_ts) as the re-call
+ * and ramx_dev_dinuc as the replay.  cols and di are [n_families][L] (the result's pileup and dinucleotide pileup), n_cpg
+ * [n_families]: the CG pairs of the re-call of the result (those the result holds when it has converged).  kernel_ms as
+ * ramx_dev_dinuc, summed over the replays. */
+int ramx_dev_refine_cpg(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                        const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                        const int8_t *cons_in, const int32_t *rows_in, int32_t max_replays, int32_t rows_reversed, int32_t cpg_ts,
+                        int8_t *cons_out, int32_t *rows_out, int32_t *replays, int32_t *converged,
+                        ramx_col_pileup *cols, ramx_col_dinuc *di, int32_t *n_cpg, ramx_aln_end *ends, double *kernel_ms);
 
 /* Per-copy statistics of an extension: how the alignment of every flank to a GIVEN consensus cons[0..rows) divides up -- the
  * pileup's transpose, summed over the rows of a flank where the pileup sums over the flanks of a column.  Everything is defined

@@ -22,6 +22,7 @@ EXPORTS = [
     "ramx_dev_profile", "ramx_set_profile_sink",
     "ramx_dev_align", "ramx_set_align_sink",
     "ramx_dev_pileup", "ramx_recall_consensus", "ramx_dev_refine", "ramx_set_refine_sink",
+    "ramx_dev_dinuc", "ramx_recall_cpg", "ramx_dev_refine_cpg", "ramx_set_cpg_sink",
     "ramx_dev_copy_stats", "ramx_copy_kimura", "ramx_family_divergence", "ramx_set_copies_sink",
     "ramx_dev_planes", "ramx_dev_plane_gram", "ramx_dev_plane_gram_ms", "ramx_select_planes", "ramx_link_pairs", "ramx_set_linkage_sink",
     "ramx_link_components", "ramx_dev_subfamilies", "ramx_dev_subfam_masks", "ramx_dev_subfam_ms", "ramx_set_subfam_sink",
@@ -86,6 +87,14 @@ class RefineRec(C.Structure):       # ramx_refinement
 
 
 REFINE_CB = C.CFUNCTYPE(None, C.POINTER(RefineRec), C.c_void_p)
+
+
+class CpgRec(C.Structure):          # ramx_cpg_refinement
+    _fields_ = [(k, C.c_int32) for k in ("direction", "family", "rows", "refined_rows", "replays", "converged", "n_flanks", "n_cpg")] + \
+               [(k, C.c_void_p) for k in ("cons", "refined_cons", "refined_cols", "refined_di")]
+
+
+CPG_CB = C.CFUNCTYPE(None, C.POINTER(CpgRec), C.c_void_p)
 
 
 class CopyStats(C.Structure):       # ramx_copy_stats
@@ -211,6 +220,18 @@ def lib() -> C.CDLL:
         L.ramx_dev_refine.restype = C.c_int
         L.ramx_set_refine_sink.argtypes = [REFINE_CB, C.c_void_p, C.c_int32]
         L.ramx_set_refine_sink.restype = None
+        L.ramx_dev_dinuc.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Params),
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ramx_dev_dinuc.restype = C.c_int
+        L.ramx_recall_cpg.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                      C.c_void_p, C.POINTER(C.c_int32)]
+        L.ramx_recall_cpg.restype = C.c_int32
+        L.ramx_dev_refine_cpg.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Params),
+                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ramx_dev_refine_cpg.restype = C.c_int
+        L.ramx_set_cpg_sink.argtypes = [CPG_CB, C.c_void_p, C.c_int32, C.c_int32]
+        L.ramx_set_cpg_sink.restype = None
         L.ramx_dev_copy_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Params),
                                           C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ramx_dev_copy_stats.restype = C.c_int

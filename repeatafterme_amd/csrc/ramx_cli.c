@@ -92,6 +92,10 @@ static void usage(void)
     "     -outmat <file>        # Dump the dp matrix paths to a file for debugging.\n"
     "     -outcopies <file>     # Save every copy's divergence from the extension consensus\n"
     "                           #   ( matches, transitions, transversions, gaps, Kimura ) to a TSV file.\n"
+    "     -outcpg <file>        # Save the extension consensus re-called with the CpG-aware rule ( a CG whose\n"
+    "                           #   copies have mostly deaminated to TG / CA / TA is called CG ) to a FASTA file,\n"
+    "     -outdinuc <file>      # ... and the dinucleotide counts of its adjacent columns to a TSV file.\n"
+    "     -cpgscore <num>       # ... the score of a deaminated base under the CpG hypothesis (0).\n"
     "     -outlinkage <file>    # Save the pairs of variant columns of the extension consensus whose variants\n"
     "                           #   travel together in the copies ( a sign of subfamilies ) to a TSV file.\n"
     "     -linkcount <num>      # ... a variant needs this many copies (4),\n"
@@ -260,9 +264,9 @@ static void warm_start(void)
 /* everything the command line decides */
 struct cli_opts
 {
-  const char *ranges_file, *outtsv, *outfa, *outmat, *cons_file, *seq_file, *matrix_name, *batch_file, *outprofile, *outaln, *outpileup, *outrefined, *outcopies, *outlinkage, *outsubfam, *outtsd;
+  const char *ranges_file, *outtsv, *outfa, *outmat, *cons_file, *seq_file, *matrix_name, *batch_file, *outprofile, *outaln, *outpileup, *outrefined, *outcpg, *outdinuc, *outcopies, *outlinkage, *outsubfam, *outtsd;
   ramx_tsd_params tsd;
-  int refine, linkcount, linkfrac, linkscore, subfamk, subfammin, subfamiter;
+  int refine, cpgscore, linkcount, linkfrac, linkscore, subfamk, subfammin, subfamiter;
   int flanking, L, bandwidth, maxn, when_to_stop, num_threads, verbose;
   int gap_ext, gap_open, match, mismatch, cappenalty, minimprovement, is_rs;
   struct scoringSystem *sp;
@@ -485,7 +489,7 @@ static void write_results(const struct cli_opts *o, struct coreAlignment *cores,
  */
 struct batch_item
 {
-  char *ranges, *log, *cons, *tsv, *fa, *profile, *aln, *pileup, *refined, *copies, *linkage, *subfam, *tsd;
+  char *ranges, *log, *cons, *tsv, *fa, *profile, *aln, *pileup, *refined, *copies, *linkage, *subfam, *tsd, *cpg;
   struct coreAlignment *cores;
   struct sequenceLibrary *lib;
   int N, rightbp, leftbp;
@@ -730,6 +734,68 @@ static void refined_write(struct refine_family *f)
   {
     if (!f->have[d]) continue;
     fprintf(fp, ">%s-extension-refined %d bp replays=%d converged=%d\n%s\n", d ? "right" : "left", f->rows[d], f->replays[d], f->converged[d], f->seq[d]);
+    free(f->seq[d]);
+    f->seq[d] = NULL; f->have[d] = 0;
+  }
+  fclose(fp);
+}
+
+/*
+ * -outcpg <file>: the kept consensus refined over at most -refine <n> replays with the CpG-aware re-call (include/ramx.h,
+ * ramx_recall_cpg, ramx_set_cpg_sink; -cpgscore <n> is its cpg_ts, default 0) as FASTA, ">right-extension-cpg <n> bp replays=<k>
+ * converged=<0|1> cpg=<pairs called CG>" and the left one, which reads as -cons writes it.  -outdinuc <file>: the dinucleotide
+ * pileup of that result (ramx_col_dinuc) as a TSV, one line per column of the result, the right direction first; the rows are
+ * the device's (a left extension's run outward from the core), xy counts class x in row and class y in row + 1.
+ */
+struct cpg_family { const char *fasta, *dinuc; int have[2], rows[2], replays[2], converged[2], n_cpg[2]; char *seq[2]; };
+struct cpg_out { struct cpg_family *fam; };
+static void dinuc_start(const char *path)
+{
+  FILE *fp = fopen(path, "w");
+  if (!fp) { fprintf(stderr, "Could not create the dinucleotide file %s\n", path); exit(1); }
+  fputs("dir\trow\tbase\tnext\tboth\tadjacent\tsplit\tgapped", fp);
+  for (int x = 0; x < 5; x++)
+    for (int y = 0; y < 5; y++) fprintf(fp, "\t%c%c", "ACGTN"[x], "ACGTN"[y]);
+  fputc('\n', fp);
+  fclose(fp);
+}
+static void cpg_sink(const ramx_cpg_refinement *cr, void *user)
+{
+  struct cpg_family *f = &((const struct cpg_out *)user)->fam[cr->family];
+  const int d = cr->direction ? 1 : 0, n = cr->refined_rows;
+  if (f->dinuc)
+  {
+    FILE *fp = fopen(f->dinuc, "a");
+    if (!fp) { fprintf(stderr, "Could not append to the dinucleotide file %s\n", f->dinuc); exit(1); }
+    for (int r = 0; r < n; r++)
+    {
+      const ramx_col_dinuc *c = &cr->refined_di[r];
+      fprintf(fp, "%s\t%d\t%c\t%c\t%d\t%d\t%d\t%d", d ? "right" : "left", r, code_to_char(c->base), c->next < 0 ? '-' : code_to_char(c->next),
+              c->both, c->adjacent, c->split, c->gapped);
+      for (int x = 0; x < 5; x++)
+        for (int y = 0; y < 5; y++) fprintf(fp, "\t%d", c->di[x][y]);
+      fputc('\n', fp);
+    }
+    fclose(fp);
+  }
+  if (f->fasta)
+  {
+    f->have[d] = 1; f->rows[d] = n; f->replays[d] = cr->replays; f->converged[d] = cr->converged; f->n_cpg[d] = cr->n_cpg;
+    f->seq[d] = (char *)malloc((size_t)n + 1);
+    for (int r = 0; r < n; r++) f->seq[d][r] = code_to_char(cr->refined_cons[d ? r : n - 1 - r]);
+    f->seq[d][n] = 0;
+  }
+}
+static void cpg_write(struct cpg_family *f)
+{
+  if (!f->fasta) return;
+  FILE *fp = fopen(f->fasta, "w");
+  if (!fp) { fprintf(stderr, "Could not create the CpG-aware consensus file %s\n", f->fasta); exit(1); }
+  for (int d = 1; d >= 0; d--)
+  {
+    if (!f->have[d]) continue;
+    fprintf(fp, ">%s-extension-cpg %d bp replays=%d converged=%d cpg=%d\n%s\n", d ? "right" : "left", f->rows[d], f->replays[d], f->converged[d],
+            f->n_cpg[d], f->seq[d]);
     free(f->seq[d]);
     f->seq[d] = NULL; f->have[d] = 0;
   }
@@ -1088,6 +1154,8 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   if (o->outlinkage != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's linkage file is the eleventh field of its line in the list\n"); exit(1); }
   if (o->outsubfam != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's subfamily file is the twelfth field of its line in the list\n"); exit(1); }
   if (o->outtsd != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's target-site duplication file is the thirteenth field of its line in the list\n"); exit(1); }
+  if (o->outcpg != NULL || o->outdinuc != NULL)
+  { fprintf(stderr, "RAMExtend(ramx): with -batch every family's CpG-aware consensus file is the fourteenth field of its line in the list; -outdinuc writes one family\n"); exit(1); }
   FILE *lf = fopen(o->batch_file, "r");
   if (!lf) { fprintf(stderr, "Could not open batch list %s\n", o->batch_file); exit(1); }
   size_t cap = 64, F = 0;
@@ -1099,9 +1167,9 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   {
     while (len > 0 && (line[len - 1] == '\n' || line[len - 1] == '\r')) line[--len] = 0;
     if (line[0] == '#' || line[0] == 0) continue;
-    char *f[13] = { NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL };
+    char *f[14] = { NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL };
     char *p = line;
-    for (int k = 0; k < 13 && p; k++) { f[k] = p; char *t = strchr(p, '\t'); if (t) { *t = 0; p = t + 1; } else p = NULL; }
+    for (int k = 0; k < 14 && p; k++) { f[k] = p; char *t = strchr(p, '\t'); if (t) { *t = 0; p = t + 1; } else p = NULL; }
     if (!f[0] || !f[1]) { fprintf(stderr, "batch list: every line needs at least <ranges><TAB><log>\n"); exit(1); }
     if (F == cap) { cap *= 2; it = (struct batch_item *)realloc(it, cap * sizeof(*it)); memset(it + F, 0, (cap - F) * sizeof(*it)); }
     it[F].ranges = strdup(f[0]); it[F].log = strdup(f[1]);
@@ -1116,6 +1184,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
     it[F].linkage = field_or_null(f[10]) ? strdup(f[10]) : NULL;     /* optional eleventh field: the family's -outlinkage file */
     it[F].subfam = field_or_null(f[11]) ? strdup(f[11]) : NULL;      /* optional twelfth field: the family's -outsubfam file */
     it[F].tsd = field_or_null(f[12]) ? strdup(f[12]) : NULL;         /* optional thirteenth field: the family's -outtsd file */
+    it[F].cpg = field_or_null(f[13]) ? strdup(f[13]) : NULL;         /* optional fourteenth field: the family's -outcpg file */
     F++;
   }
   free(line);
@@ -1176,6 +1245,11 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   for (size_t i = 0; i < F; i++)
     if ((cout.fam[i].path = it[i].copies) != NULL) { cout.fam[i].lib = it[i].lib; any_copies = 1; }
   if (any_copies) ramx_set_copies_sink(copies_sink, &cout);
+  struct cpg_out gout = { (struct cpg_family *)calloc(F ? F : 1, sizeof(struct cpg_family)) };
+  int any_cpg = 0;
+  for (size_t i = 0; i < F; i++)
+    if ((gout.fam[i].fasta = it[i].cpg) != NULL) any_cpg = 1;
+  if (any_cpg) ramx_set_cpg_sink(cpg_sink, &gout, o->refine, o->cpgscore);
   struct linkage_out lout = { (struct linkage_family *)calloc(F ? F : 1, sizeof(struct linkage_family)) };
   int any_linkage = 0;
   for (size_t i = 0; i < F; i++)
@@ -1219,6 +1293,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
     aln_write(&aout.fam[i], it[i].cores, o->flanking);
     refined_write(&rout.fam[i]);
     copies_write(&cout.fam[i], it[i].cores, o->flanking);
+    cpg_write(&gout.fam[i]);
     linkage_write(&lout.fam[i], o->linkscore);
     subfam_write(&sout.fam[i], it[i].cores, o->flanking);
     const double duration = difftime(time(0), t_start);
@@ -1251,15 +1326,16 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   {
     ramx_free_library(it[i].lib, it[i].cores);
     free(it[i].master); free(it[i].ranges); free(it[i].log); free(it[i].cons); free(it[i].tsv); free(it[i].fa); free(it[i].profile); free(it[i].aln);
-    free(it[i].pileup); free(it[i].refined); free(it[i].copies); free(it[i].linkage); free(it[i].subfam); free(it[i].tsd);
+    free(it[i].pileup); free(it[i].refined); free(it[i].copies); free(it[i].linkage); free(it[i].subfam); free(it[i].tsd); free(it[i].cpg);
   }
   ramx_set_profile_sink(NULL, NULL);
   ramx_set_align_sink(NULL, NULL);
   ramx_set_refine_sink(NULL, NULL, 1);
   ramx_set_copies_sink(NULL, NULL);
+  ramx_set_cpg_sink(NULL, NULL, 1, 0);
   ramx_set_linkage_sink(NULL, NULL, 4, 100, 1024);
   ramx_set_subfam_sink(NULL, NULL, 4, 100, 1024, 3.0, 4, 8, 4, 10);
-  free(aout.fam); free(rout.fam); free(cout.fam); free(lout.fam); free(sout.fam);
+  free(aout.fam); free(rout.fam); free(cout.fam); free(gout.fam); free(lout.fam); free(sout.fam);
   free(profile_paths);
   free(it); free(fam); free(ir); free(il); free(mflat);
   ramx_free_scoring_system(o->sp);
@@ -1292,6 +1368,9 @@ int ramx_cli_main(int argc, char **argv)
   opt_string(argc, argv, "-outpileup", &o.outpileup);
   opt_string(argc, argv, "-outrefined", &o.outrefined);
   opt_string(argc, argv, "-outcopies", &o.outcopies);
+  opt_string(argc, argv, "-outcpg", &o.outcpg);
+  opt_string(argc, argv, "-outdinuc", &o.outdinuc);
+  if (!opt_int(argc, argv, "-cpgscore", &o.cpgscore)) o.cpgscore = 0;
   opt_string(argc, argv, "-outlinkage", &o.outlinkage);
   if (!opt_int(argc, argv, "-linkcount", &o.linkcount)) o.linkcount = 4;
   if (!opt_int(argc, argv, "-linkfrac", &o.linkfrac)) o.linkfrac = 100;
@@ -1414,6 +1493,12 @@ int ramx_cli_main(int argc, char **argv)
   cfam.path = o.outcopies; cfam.lib = lib;
   struct copies_out cout = { &cfam };
   if (o.outcopies != NULL) ramx_set_copies_sink(copies_sink, &cout);
+  struct cpg_family gfam;
+  memset(&gfam, 0, sizeof(gfam));
+  gfam.fasta = o.outcpg; gfam.dinuc = o.outdinuc;
+  struct cpg_out gout = { &gfam };
+  if (o.outdinuc != NULL) dinuc_start(o.outdinuc);
+  if (o.outcpg != NULL || o.outdinuc != NULL) ramx_set_cpg_sink(cpg_sink, &gout, o.refine, o.cpgscore);
   struct linkage_family lfam;
   memset(&lfam, 0, sizeof(lfam));
   lfam.path = o.outlinkage;
@@ -1439,12 +1524,14 @@ int ramx_cli_main(int argc, char **argv)
   ramx_set_align_sink(NULL, NULL);
   ramx_set_refine_sink(NULL, NULL, 1);
   ramx_set_copies_sink(NULL, NULL);
+  ramx_set_cpg_sink(NULL, NULL, 1, 0);
   ramx_set_linkage_sink(NULL, NULL, 4, 100, 1024);
   ramx_set_subfam_sink(NULL, NULL, 4, 100, 1024, 3.0, 4, 8, 4, 10);
   write_results(&o, cores, lib, master, rightbp, leftbp, o.cons_file, o.outtsv, o.outfa);
   aln_write(&afam, cores, o.flanking);
   refined_write(&rfam);
   copies_write(&cfam, cores, o.flanking);
+  cpg_write(&gfam);
   linkage_write(&lfam, o.linkscore);
   subfam_write(&sfam, cores, o.flanking);
   if (o.outtsd != NULL)

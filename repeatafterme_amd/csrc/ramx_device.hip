@@ -53,6 +53,7 @@
 #include "ramx_profile_api.h"
 #include "ramx_align_api.h"
 #include "ramx_pileup_api.h"
+#include "ramx_dinuc_api.h"
 #include "ramx_copystats_api.h"
 #include "ramx_linkage_api.h"
 #include "ramx_subfam_api.h"
@@ -169,6 +170,9 @@ struct ramx_dev
   // ramx_dev_copy_stats (allocated on its first call): one record per flank
   ramx_copy_stats *d_cs_stats;
   size_t cap_pl_idx, cap_pl_ins, cap_pl_slab, cap_pl_cols, cap_cs_stats;
+  // ramx_dev_dinuc / ramx_dev_refine_cpg (allocated on their first call): per-tile row-pair records, summed records
+  ramx_col_dinuc *d_dn_slab, *d_dn_cols;
+  size_t cap_dn_slab, cap_dn_cols;
   // ramx_dev_planes / ramx_dev_plane_gram (allocated on their first call): the bit planes of the whole flank set, which stay
   // resident between the two calls (planes_ready, dropped like `ready` by whatever reuses the replays' buffers); the host keeps
   // the resident families' rows, tiles and places (lk_fam: 3 x int64 per family)
@@ -274,6 +278,7 @@ extern "C" void ramx_dev_destroy(ramx_dev *d)
   (void)hipFree(d->d_al_codes); (void)hipFree(d->d_al_ends); (void)hipFree(d->d_al_idx); (void)hipFree(d->d_al_ins);
   (void)hipFree(d->d_pl_idx); (void)hipFree(d->d_pl_ins); (void)hipFree(d->d_pl_slab); (void)hipFree(d->d_pl_cols);
   (void)hipFree(d->d_cs_stats);
+  (void)hipFree(d->d_dn_slab); (void)hipFree(d->d_dn_cols);
   (void)hipFree(d->d_lk_planes); (void)hipFree(d->d_lk_base); (void)hipFree(d->d_lk_at); (void)hipFree(d->d_lk_coat);
   (void)hipFree(d->d_lk_block); (void)hipFree(d->d_lk_gfam); (void)hipFree(d->d_lk_co);
   free(d->lk_fam);
@@ -2037,9 +2042,12 @@ static int pileup_setup(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded,
 // instead: it reads the same group's columns, needs no per-tile records and no sum, and leaves cs->stats filled.
 // With lk (ramx_dev_planes; its planes and fam_base set by the caller, the buffer zeroed) a fourth stage follows the pileup's:
 // the group's bit planes, written into the buffer of the whole flank set.
+// With dn (ramx_dev_dinuc / ramx_dev_refine_cpg) a fourth stage follows the pileup's as well: the row-pair records of the group's
+// tiles (ramx_kernels_dinuc.h) and, after the last group, their sum into d_dn_cols; pile == false leaves the pileup's stage
+// empty (its mark stays, so that the fourth time is the fourth stage's).
 static int pileup_replay(ramx_dev *d, const char *who, AlnArgs aa, int KW, const ReplayPlan &pl, int32_t n_families,
                          const int8_t *cons, const int32_t *rows, double *kernel_ms, const CopyStatsArgs *cs = NULL,
-                         const PlanesArgs *lk = NULL)
+                         const PlanesArgs *lk = NULL, bool dn = false, bool pile = true)
 {
   const int tiles = pl.tiles, maxrows = pl.maxrows, L = aa.L, W = aa.k.W;
   // the budget counts, per tile, the decision codes and the walked columns (col_idx, col_ins) of its 64 flanks: the columns
@@ -2050,7 +2058,8 @@ static int pileup_replay(ramx_dev *d, const char *who, AlnArgs aa, int KW, const
   if ((rc = ensure(&d->d_al_codes, &d->cap_al_codes, (size_t)group * code_bytes))) return rc;
   if ((rc = ensure(&d->d_pl_idx, &d->cap_pl_idx, (size_t)group * col_bytes))) return rc;
   if ((rc = ensure(&d->d_pl_ins, &d->cap_pl_ins, (size_t)group * col_bytes))) return rc;
-  if (!cs && (rc = ensure(&d->d_pl_slab, &d->cap_pl_slab, (size_t)tiles * maxrows * sizeof(ramx_col_pileup)))) return rc;
+  if (!cs && pile && (rc = ensure(&d->d_pl_slab, &d->cap_pl_slab, (size_t)tiles * maxrows * sizeof(ramx_col_pileup)))) return rc;
+  if (dn && (rc = ensure(&d->d_dn_slab, &d->cap_dn_slab, (size_t)tiles * maxrows * sizeof(ramx_col_dinuc)))) return rc;
   if ((rc = replay_upload(d, pl, n_families, L, cons, rows)) != RAMX_OK) return rc;
   const int gn = group * 64;
   aa.codes = d->d_al_codes; aa.gn = gn;
@@ -2078,9 +2087,15 @@ static int pileup_replay(ramx_dev *d, const char *who, AlnArgs aa, int KW, const
   pa.L = L; pa.Np = aa.k.Np; pa.W = W; pa.KW = KW; pa.gn = gn; pa.slab_rows = maxrows;
   PileSumArgs sa;
   sa.slab = d->d_pl_slab; sa.fam = d->d_rp_fam; sa.cons = d->d_rp_cons; sa.cols = d->d_pl_cols; sa.L = L; sa.slab_rows = maxrows;
-  return replay_groups(d, who, tiles, group, lk ? 4 : 3, kernel_ms, [&](int tile0, int nt, auto &mark) {
+  DinucArgs da;
+  da.bases = d->d_bases; da.tile_fam = d->d_rp_tile; da.cons = d->d_rp_cons; da.rows = d->d_rp_rows; da.ends = d->d_al_ends;
+  da.col_idx = d->d_pl_idx; da.col_ins = d->d_pl_ins; da.slab = d->d_dn_slab;
+  da.L = L; da.Np = aa.k.Np; da.W = W; da.KW = KW; da.gn = gn; da.tile0 = 0; da.slab_rows = maxrows;
+  DinucSumArgs ds;
+  ds.slab = d->d_dn_slab; ds.fam = d->d_rp_fam; ds.cons = d->d_rp_cons; ds.di = d->d_dn_cols; ds.L = L; ds.slab_rows = maxrows;
+  return replay_groups(d, who, tiles, group, lk || dn ? 4 : 3, kernel_ms, [&](int tile0, int nt, auto &mark) {
     int lrc;
-    aa.tile0 = pa.tile0 = tile0;
+    aa.tile0 = pa.tile0 = da.tile0 = tile0;
     // the walk addresses its columns as [r * k.Np + n] with n the flank's index in the whole set: given the group's width for
     // k.Np and the arrays' origin moved back by the group's first flank, it writes the group's own [maxrows][gn] arrays
     AlnArgs aw = aa;
@@ -2098,10 +2113,16 @@ static int pileup_replay(ramx_dev *d, const char *who, AlnArgs aa, int KW, const
       mark();
       return RAMX_OK;
     }
-    if ((lrc = ramx_pileup_launch(d->stream, nt, pa)) != RAMX_OK) return lrc;
+    if (pile && (lrc = ramx_pileup_launch(d->stream, nt, pa)) != RAMX_OK) return lrc;
     // the last group's pileup stage ends with the sum over the tiles of every family
-    if (tile0 + nt == tiles && (lrc = ramx_pileup_launch_sum(d->stream, n_families, maxrows, sa)) != RAMX_OK) return lrc;
+    if (pile && tile0 + nt == tiles && (lrc = ramx_pileup_launch_sum(d->stream, n_families, maxrows, sa)) != RAMX_OK) return lrc;
     mark();
+    if (dn)
+    {
+      if ((lrc = ramx_dinuc_launch(d->stream, nt, da)) != RAMX_OK) return lrc;
+      if (tile0 + nt == tiles && (lrc = ramx_dinuc_launch_sum(d->stream, n_families, maxrows, ds)) != RAMX_OK) return lrc;
+      mark();
+    }
     if (lk)
     {
       la.tile0 = tile0;
@@ -2120,7 +2141,7 @@ static int pileup_fetch(ramx_dev *d, bool ran, int32_t n_padded, const int32_t *
   {
     if (run && !run[f]) continue;
     const int t0 = fam_first[f] / 64, nt = (fam_count[f] + 63) / 64;
-    if (rows[f] > 0)
+    if (rows[f] > 0 && cols)               // (cols is optional for ramx_dev_dinuc alone)
     {
       ramx_col_pileup *c = cols + (size_t)f * L;
       if (ran) HIPCHK(hipMemcpy(c, d->d_pl_cols + (size_t)f * L, (size_t)rows[f] * sizeof(ramx_col_pileup), hipMemcpyDeviceToHost));
@@ -2133,6 +2154,24 @@ static int pileup_fetch(ramx_dev *d, bool ran, int32_t n_padded, const int32_t *
     if (!ends || nt == 0) continue;        // ends is optional here
     if (!ran || rows[f] == 0) replay_no_alignment(ends, NULL, NULL, t0 * 64, (t0 + nt) * 64, 0, n_padded);
     else HIPCHK(hipMemcpy(ends + (size_t)t0 * 64, d->d_al_ends + (size_t)t0 * 64, (size_t)nt * 64 * sizeof(ramx_aln_end), hipMemcpyDeviceToHost));
+  }
+  return RAMX_OK;
+}
+
+// the row-pair records of the families with run[f] != 0 (NULL: all) after a replay with dn, or answered here where nothing ran
+static int dinuc_fetch(ramx_dev *d, bool ran, int32_t n_families, int L, const int8_t *cons, const int32_t *rows, const char *run,
+                       ramx_col_dinuc *di)
+{
+  for (int f = 0; f < n_families; f++)
+  {
+    if ((run && !run[f]) || rows[f] <= 0) continue;
+    ramx_col_dinuc *c = di + (size_t)f * L;
+    if (ran) HIPCHK(hipMemcpy(c, d->d_dn_cols + (size_t)f * L, (size_t)rows[f] * sizeof(ramx_col_dinuc), hipMemcpyDeviceToHost));
+    else
+    {
+      memset(c, 0, (size_t)rows[f] * sizeof(ramx_col_dinuc));
+      for (int r = 0; r < rows[f]; r++) { c[r].base = cons[(size_t)f * L + r]; c[r].next = r + 1 < rows[f] ? cons[(size_t)f * L + r + 1] : -1; }
+    }
   }
   return RAMX_OK;
 }
@@ -2158,6 +2197,37 @@ extern "C" int ramx_dev_pileup(ramx_dev *d, const ramx_flank *flanks, int32_t n_
     if ((rc = pileup_setup(d, flanks, n_padded, n_families, p, aa, &KW)) != RAMX_OK) return rc;
     if ((rc = pileup_replay(d, "ramx_dev_pileup", aa, KW, pl, n_families, cons, rows, kernel_ms)) != RAMX_OK) return rc;
   }
+  return pileup_fetch(d, run, n_padded, fam_first, fam_count, n_families, p->L, cons, rows, NULL, cols, ends);
+}
+
+// ------------------------------------------------------------------------------------------
+// dinucleotide pileup: the pileup's replay with the row-pair kernel as a fourth stage (ramx_kernels_dinuc.h)
+// ------------------------------------------------------------------------------------------
+extern "C" int ramx_dev_dinuc(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                              const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                              const int8_t *cons, const int32_t *rows, ramx_col_pileup *cols, ramx_col_dinuc *di, ramx_aln_end *ends,
+                              double *kernel_ms)
+{
+  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = kernel_ms[3] = 0;
+  if (!d || !p || !p->matrix || n_families < 0 || n_padded < 0 || (n_padded & 63) || (n_padded && !flanks) ||
+      (n_families && (!fam_first || !fam_count || !rows)))
+  { ramx_set_error("ramx_dev_dinuc: bad argument"); return RAMX_ERR_ARG; }
+  if (p->bandwidth < 1 || p->L < 0) { ramx_set_error("ramx_dev_dinuc: bad bandwidth / L"); return RAMX_ERR_ARG; }
+  ReplayPlan pl;
+  int rc;
+  if ((rc = replay_plan("ramx_dev_dinuc", n_padded, fam_first, fam_count, n_families, p->L, cons, rows, NULL, true, pl)) != RAMX_OK) return rc;
+  if (pl.maxrows > 0 && !di) { ramx_set_error("ramx_dev_dinuc: di missing"); return RAMX_ERR_ARG; }
+  const bool run = n_families > 0 && pl.maxrows > 0 && pl.tiles > 0;
+  if (run)
+  {
+    AlnArgs aa;
+    int KW = 0;
+    if ((rc = pileup_setup(d, flanks, n_padded, n_families, p, aa, &KW, cols != NULL)) != RAMX_OK) return rc;
+    if ((rc = ensure(&d->d_dn_cols, &d->cap_dn_cols, (size_t)n_families * p->L * sizeof(ramx_col_dinuc)))) return rc;
+    if ((rc = pileup_replay(d, "ramx_dev_dinuc", aa, KW, pl, n_families, cons, rows, kernel_ms, NULL, NULL, true, cols != NULL)) != RAMX_OK) return rc;
+    if (!cols && kernel_ms) kernel_ms[2] = 0;          // (two marks with nothing between them)
+  }
+  if ((rc = dinuc_fetch(d, run, n_families, p->L, cons, rows, NULL, di)) != RAMX_OK) return rc;
   return pileup_fetch(d, run, n_padded, fam_first, fam_count, n_families, p->L, cons, rows, NULL, cols, ends);
 }
 
@@ -2645,24 +2715,30 @@ extern "C" int ramx_dev_subfam_masks(ramx_dev *d, int32_t family, uint64_t *mask
 
 extern "C" void ramx_dev_subfam_ms(ramx_dev *d, double ms[2]) { ms[0] = d ? d->sf_ms[0] : 0; ms[1] = d ? d->sf_ms[1] : 0; }
 
-extern "C" int ramx_dev_refine(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
-                               const int32_t *fam_count, int32_t n_families, const ramx_params *p,
-                               const int8_t *cons_in, const int32_t *rows_in, int32_t max_replays,
-                               int8_t *cons_out, int32_t *rows_out, int32_t *replays, int32_t *converged,
-                               ramx_col_pileup *cols, ramx_aln_end *ends, double *kernel_ms)
+// the loop of ramx_dev_refine and ramx_dev_refine_cpg: with cpg the replay counts the row pairs as well and the re-call is the
+// CpG-aware one (di, n_cpg as ramx_dev_refine_cpg's)
+struct CpgRecall { int32_t rows_reversed, cpg_ts; };
+
+static int refine_loop(ramx_dev *d, const char *who, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                       const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                       const int8_t *cons_in, const int32_t *rows_in, int32_t max_replays,
+                       int8_t *cons_out, int32_t *rows_out, int32_t *replays, int32_t *converged,
+                       ramx_col_pileup *cols, ramx_aln_end *ends, double *kernel_ms,
+                       const CpgRecall *cpg, ramx_col_dinuc *di, int32_t *n_cpg)
 {
-  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0;
+  if (kernel_ms) { kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0; if (cpg) kernel_ms[3] = 0; }
   if (!d || !p || !p->matrix || n_families < 0 || n_padded < 0 || (n_padded & 63) || (n_padded && !flanks) ||
-      (n_families && (!fam_first || !fam_count || !rows_in || !rows_out || !replays || !converged)) || max_replays < 1)
-  { ramx_set_error("ramx_dev_refine: bad argument"); return RAMX_ERR_ARG; }
-  if (p->bandwidth < 1 || p->L < 0) { ramx_set_error("ramx_dev_refine: bad bandwidth / L"); return RAMX_ERR_ARG; }
+      (n_families && (!fam_first || !fam_count || !rows_in || !rows_out || !replays || !converged)) || max_replays < 1 ||
+      (cpg && n_families && !n_cpg))
+  { ramx_set_error("%s: bad argument", who); return RAMX_ERR_ARG; }
+  if (p->bandwidth < 1 || p->L < 0) { ramx_set_error("%s: bad bandwidth / L", who); return RAMX_ERR_ARG; }
   if (dev_is_multi(d))
-  { ramx_set_error("ramx_dev_refine: not with a communicator or mailbox route active (the re-call needs the counts of every rank)"); return RAMX_ERR_UNSUPPORTED; }
+  { ramx_set_error("%s: not with a communicator or mailbox route active (the re-call needs the counts of every rank)", who); return RAMX_ERR_UNSUPPORTED; }
   const int L = p->L;
   ReplayPlan pl;
   int rc;
-  if ((rc = replay_plan("ramx_dev_refine", n_padded, fam_first, fam_count, n_families, L, cons_in, rows_in, NULL, true, pl)) != RAMX_OK) return rc;
-  if (pl.maxrows > 0 && (!cols || !cons_out)) { ramx_set_error("ramx_dev_refine: cons_out / cols missing"); return RAMX_ERR_ARG; }
+  if ((rc = replay_plan(who, n_padded, fam_first, fam_count, n_families, L, cons_in, rows_in, NULL, true, pl)) != RAMX_OK) return rc;
+  if (pl.maxrows > 0 && (!cols || !cons_out || (cpg && !di))) { ramx_set_error("%s: cons_out / cols%s missing", who, cpg ? " / di" : ""); return RAMX_ERR_ARG; }
   std::vector<int8_t> cur((size_t)(n_families > 0 ? n_families : 1) * (L > 0 ? L : 1), 0), next((size_t)(L > 0 ? L : 1));
   std::vector<int32_t> rows(rows_in, rows_in + n_families);
   std::vector<char> active((size_t)n_families, 1);
@@ -2670,6 +2746,7 @@ extern "C" int ramx_dev_refine(ramx_dev *d, const ramx_flank *flanks, int32_t n_
   {
     if (rows[f] > 0) memcpy(cur.data() + (size_t)f * L, cons_in + (size_t)f * L, (size_t)rows[f]);
     replays[f] = 0; converged[f] = 0;
+    if (cpg) n_cpg[f] = 0;
   }
   AlnArgs aa;
   int KW = 0, left = n_families;
@@ -2677,21 +2754,25 @@ extern "C" int ramx_dev_refine(ramx_dev *d, const ramx_flank *flanks, int32_t n_
   for (int it = 0; it < max_replays && left > 0; it++)
   {
     // only the families that have not converged replay: the tiles of the others belong to none in this replay's table
-    if ((rc = replay_plan("ramx_dev_refine", n_padded, fam_first, fam_count, n_families, L, cur.data(), rows.data(), active.data(), false, pl)) != RAMX_OK) return rc;
+    if ((rc = replay_plan(who, n_padded, fam_first, fam_count, n_families, L, cur.data(), rows.data(), active.data(), false, pl)) != RAMX_OK) return rc;
     const bool run = pl.maxrows > 0 && pl.tiles > 0;
     if (run)
     {
       // once per call, not per replay: the flanks and their windows do not change
       if (!set_up && (rc = pileup_setup(d, flanks, n_padded, n_families, p, aa, &KW)) != RAMX_OK) return rc;
+      if (!set_up && cpg && (rc = ensure(&d->d_dn_cols, &d->cap_dn_cols, (size_t)n_families * L * sizeof(ramx_col_dinuc)))) return rc;
       set_up = true;
-      if ((rc = pileup_replay(d, "ramx_dev_refine", aa, KW, pl, n_families, cur.data(), rows.data(), kernel_ms)) != RAMX_OK) return rc;
+      if ((rc = pileup_replay(d, who, aa, KW, pl, n_families, cur.data(), rows.data(), kernel_ms, NULL, NULL, cpg != NULL)) != RAMX_OK) return rc;
     }
+    if (cpg && (rc = dinuc_fetch(d, run, n_families, L, cur.data(), rows.data(), active.data(), di)) != RAMX_OK) return rc;
     if ((rc = pileup_fetch(d, run, n_padded, fam_first, fam_count, n_families, L, cur.data(), rows.data(), active.data(), cols, ends)) != RAMX_OK) return rc;
     for (int f = 0; f < n_families; f++)
     {
       if (!active[f]) continue;
       int8_t *c = cur.data() + (size_t)f * L;
-      const int32_t n = ramx_recall_consensus(c, rows[f], cols + (size_t)f * L, L, next.data());
+      const int32_t n = cpg ? ramx_recall_cpg(c, rows[f], cols + (size_t)f * L, di + (size_t)f * L, cpg->rows_reversed, p->matrix, cpg->cpg_ts, L,
+                                              next.data(), &n_cpg[f])
+                            : ramx_recall_consensus(c, rows[f], cols + (size_t)f * L, L, next.data());
       replays[f] = it + 1;
       if (n == rows[f] && (n == 0 || memcmp(c, next.data(), (size_t)n) == 0)) { converged[f] = 1; active[f] = 0; left--; }
       else if (it + 1 == max_replays) { active[f] = 0; left--; }
@@ -2704,6 +2785,27 @@ extern "C" int ramx_dev_refine(ramx_dev *d, const ramx_flank *flanks, int32_t n_
     if (rows[f] > 0) memcpy(cons_out + (size_t)f * L, cur.data() + (size_t)f * L, (size_t)rows[f]);
   }
   return RAMX_OK;
+}
+
+extern "C" int ramx_dev_refine(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                               const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                               const int8_t *cons_in, const int32_t *rows_in, int32_t max_replays,
+                               int8_t *cons_out, int32_t *rows_out, int32_t *replays, int32_t *converged,
+                               ramx_col_pileup *cols, ramx_aln_end *ends, double *kernel_ms)
+{
+  return refine_loop(d, "ramx_dev_refine", flanks, n_padded, fam_first, fam_count, n_families, p, cons_in, rows_in, max_replays,
+                     cons_out, rows_out, replays, converged, cols, ends, kernel_ms, NULL, NULL, NULL);
+}
+
+extern "C" int ramx_dev_refine_cpg(ramx_dev *d, const ramx_flank *flanks, int32_t n_padded, const int32_t *fam_first,
+                                   const int32_t *fam_count, int32_t n_families, const ramx_params *p,
+                                   const int8_t *cons_in, const int32_t *rows_in, int32_t max_replays, int32_t rows_reversed, int32_t cpg_ts,
+                                   int8_t *cons_out, int32_t *rows_out, int32_t *replays, int32_t *converged,
+                                   ramx_col_pileup *cols, ramx_col_dinuc *di, int32_t *n_cpg, ramx_aln_end *ends, double *kernel_ms)
+{
+  const CpgRecall cpg = { rows_reversed != 0, cpg_ts };
+  return refine_loop(d, "ramx_dev_refine_cpg", flanks, n_padded, fam_first, fam_count, n_families, p, cons_in, rows_in, max_replays,
+                     cons_out, rows_out, replays, converged, cols, ends, kernel_ms, &cpg, di, n_cpg);
 }
 
 // ---- ramx_dev_run_direction and its steps -----------------------------------------------------------

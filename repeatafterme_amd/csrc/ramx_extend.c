@@ -587,6 +587,44 @@ static int refine_families(const struct sink_view *v)
   return rc;
 }
 
+static ramx_cpg_cb g_cpg_cb = NULL;
+static void *g_cpg_user = NULL;
+static int g_cpg_replays = 10, g_cpg_ts = 0;
+void ramx_set_cpg_sink(ramx_cpg_cb cb, void *user, int32_t max_replays, int32_t cpg_ts)
+{
+  g_cpg_cb = cb;
+  g_cpg_user = user;
+  g_cpg_replays = max_replays >= 1 ? max_replays : 1;
+  g_cpg_ts = cpg_ts;
+}
+
+/* With a CpG sink set: the CpG-aware refinement of the families' kept consensus (rows = ret, rows_reversed = !direction as the
+ * copies sink), handed over family by family. */
+static int cpg_families(const struct sink_view *v)
+{
+  const ramx_params *p = v->p;
+  const int nb = v->nb;
+  const size_t L = (size_t)(p->L > 0 ? p->L : 1);
+  int32_t *rrows = (int32_t *)calloc((size_t)(nb > 0 ? nb : 1) * 4, sizeof(int32_t)), *replays = rrows + nb, *conv = replays + nb, *ncpg = conv + nb;
+  ramx_col_pileup *cols = (ramx_col_pileup *)calloc((size_t)nb * L, sizeof(ramx_col_pileup));
+  ramx_col_dinuc *di = (ramx_col_dinuc *)calloc((size_t)nb * L, sizeof(ramx_col_dinuc));
+  int8_t *rcons = (int8_t *)calloc((size_t)nb * L, 1);
+  const int rc = ramx_dev_refine_cpg(v->d, v->fl, v->npad, v->first, v->count, nb, p, v->cons, v->ret, g_cpg_replays, !v->direction, g_cpg_ts,
+                                     rcons, rrows, replays, conv, cols, di, ncpg, NULL, NULL);
+  for (int b = 0; b < nb && rc == RAMX_OK; b++)
+  {
+    ramx_cpg_refinement cr;
+    memset(&cr, 0, sizeof(cr));
+    cr.direction = v->direction; cr.family = v->fidx[b]; cr.rows = v->ret[b]; cr.refined_rows = rrows[b];
+    cr.replays = replays[b]; cr.converged = conv[b]; cr.n_flanks = v->count[b]; cr.n_cpg = ncpg[b];
+    cr.cons = v->cons + (size_t)b * p->L; cr.refined_cons = rcons + (size_t)b * p->L;
+    cr.refined_cols = cols + (size_t)b * p->L; cr.refined_di = di + (size_t)b * p->L;
+    g_cpg_cb(&cr, g_cpg_user);
+  }
+  free(rrows); free(cols); free(di); free(rcons);
+  return rc;
+}
+
 static ramx_copies_cb g_copies_cb = NULL;
 static void *g_copies_user = NULL;
 void ramx_set_copies_sink(ramx_copies_cb cb, void *user)
@@ -897,7 +935,7 @@ static int subfam_families(const struct sink_view *v)
   return rc;
 }
 
-static int any_sink(void) { return g_profile_cb || g_align_cb || g_refine_cb || g_copies_cb || g_linkage_cb || g_subfam_cb; }
+static int any_sink(void) { return g_profile_cb || g_align_cb || g_refine_cb || g_cpg_cb || g_copies_cb || g_linkage_cb || g_subfam_cb; }
 
 /* one RAMX_TIMING line: the time since the phase before, under the caller's name */
 static void phase_line(const char *who, int width, const char *name, double *since)
@@ -915,6 +953,7 @@ static int run_sinks(const struct sink_view *v, const char *who, int width, int 
     { g_align_cb != NULL, align_families, "alignment replay" },
     { g_refine_cb != NULL, refine_families, "pileup + refinement" },
     { g_copies_cb != NULL, copies_families, "per-copy statistics" },
+    { g_cpg_cb != NULL, cpg_families, "CpG-aware refinement" },
     { g_linkage_cb != NULL, linkage_families, "linkage" },
     { g_subfam_cb != NULL, subfam_families, "subfamilies" },
   };

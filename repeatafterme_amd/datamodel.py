@@ -133,6 +133,12 @@ PILEUP_DTYPE = np.dtype([("base", np.int32), ("cover", np.int32), ("match", np.i
 assert PILEUP_DTYPE.itemsize == 128 and PILEUP_DTYPE.fields["ins_bases"][1] == 40
 
 
+# one pair of adjacent columns (rows r, r + 1) of a dinucleotide pileup: C-ABI ramx_col_dinuc (include/ramx.h), 128 bytes
+DINUC_DTYPE = np.dtype([("base", np.int32), ("next", np.int32), ("both", np.int32), ("adjacent", np.int32), ("split", np.int32),
+                        ("gapped", np.int32), ("di", np.int32, (5, 5)), ("reserved", np.int32)])
+assert DINUC_DTYPE.itemsize == 128
+
+
 # per-copy statistics of an alignment: C-ABI ramx_copy_stats (include/ramx.h), 48 bytes
 COPY_STATS_FIELDS = ("cols", "match", "ts", "tv", "n_match", "del", "del_open", "ins", "ins_open", "cpg_cols", "cpg_ts", "score")
 COPY_STATS_DTYPE = np.dtype([(k, np.int32) for k in COPY_STATS_FIELDS])
@@ -215,6 +221,20 @@ class Refinement:
     refined_cols: np.ndarray         # PILEUP_DTYPE [refined rows]
     replays: int
     converged: int
+
+
+@dataclass
+class CpgRefinement:
+    """CpG-aware refinement of one direction of one family (C-ABI ramx_cpg_refinement / ramx_dev_refine_cpg)."""
+    direction: int
+    family: int                      # index in a batch, else 0
+    cons: np.ndarray                 # int8 [ret]: the kept consensus
+    refined_cons: np.ndarray         # int8 [refined rows]
+    refined_cols: np.ndarray         # PILEUP_DTYPE [refined rows]
+    refined_di: np.ndarray           # DINUC_DTYPE [refined rows]
+    replays: int
+    converged: int
+    n_cpg: int                       # row pairs the last re-call called CG
 
 
 # target-site duplications: C-ABI ramx_tsd_site (32 bytes), ramx_tsd (16 bytes), ramx_tsd_params

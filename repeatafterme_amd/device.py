@@ -10,8 +10,8 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .datamodel import (ALN_END_DTYPE, ALN_NONE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, LINK_DTYPE, PILEUP_DTYPE, PLANE_DTYPE, TSD_DTYPE, TSD_SITE_DTYPE,
-                        CoreSet, ExtendParams, TsdParams)
+from .datamodel import (ALN_END_DTYPE, ALN_NONE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, DINUC_DTYPE, LINK_DTYPE, PILEUP_DTYPE, PILEUP_INS, PLANE_DTYPE,
+                        TSD_DTYPE, TSD_SITE_DTYPE, CoreSet, ExtendParams, TsdParams)
 from .extend import RunInfo, _info, _params
 
 
@@ -65,6 +65,27 @@ class RefineResult:
     forward_ms: float                      # summed over the replays
     walk_ms: float
     pileup_ms: float
+
+
+@dataclass
+class DinucResult:
+    di: np.ndarray                         # DINUC_DTYPE [n_families][L]; only rows[f] entries per family are written
+    cols: Optional[np.ndarray]             # PILEUP_DTYPE [n_families][L], or None (pileup=False)
+    ends: np.ndarray                       # ALN_END_DTYPE [n_padded]
+    kernel_ms: tuple                       # HIP-event times: forward, walk, pileup + sum, dinucleotide kernel + sum
+
+
+@dataclass
+class RefineCpgResult:
+    cons: np.ndarray                       # int8 [n_families][L]: the refined consensus, rows[f] entries per family
+    rows: np.ndarray                       # int32 [n_families]
+    replays: np.ndarray                    # int32 [n_families]
+    converged: np.ndarray                  # int32 [n_families]
+    n_cpg: np.ndarray                      # int32 [n_families]: row pairs the last re-call called CG
+    cols: np.ndarray                       # PILEUP_DTYPE [n_families][L]: the pileup of `cons`
+    di: np.ndarray                         # DINUC_DTYPE [n_families][L]: its dinucleotide pileup
+    ends: np.ndarray                       # ALN_END_DTYPE [n_padded]: the alignments along `cons`
+    kernel_ms: tuple                       # as DinucResult's, summed over the replays
 
 
 @dataclass
@@ -156,6 +177,22 @@ def recall_consensus(cons, cols, L: int) -> np.ndarray:
     out = np.zeros(max(L, 1), np.int8)
     n = _lib.lib().ramx_recall_consensus(c.ctypes.data, len(c), cols.ctypes.data, int(L), out.ctypes.data)
     return out[:n].copy()
+
+
+def recall_cpg(cons, cols, di, matrix, rows_reversed: bool = False, cpg_ts: int = 0, L: Optional[int] = None):
+    """CpG-aware re-call of a consensus from its pileup and dinucleotide pileup (C-ABI ramx_recall_cpg, host C); matrix as
+    ExtendParams.matrix.  -> (the new consensus, at most L columns, and the row pairs it called CG)."""
+    c = np.ascontiguousarray(cons, np.int8)
+    cols = np.ascontiguousarray(cols, PILEUP_DTYPE)
+    di = np.ascontiguousarray(di, DINUC_DTYPE)
+    m = np.ascontiguousarray(matrix, np.int32)
+    assert len(cols) >= len(c) and len(di) >= len(c) and m.size == 100 * 100
+    L = len(c) + PILEUP_INS * len(c) if L is None else int(L)
+    out = np.zeros(max(L, 1), np.int8)
+    n_cpg = C.c_int32()
+    n = _lib.lib().ramx_recall_cpg(c.ctypes.data, len(c), cols.ctypes.data, di.ctypes.data, int(bool(rows_reversed)), m.ctypes.data,
+                                   int(cpg_ts), L, out.ctypes.data, C.byref(n_cpg))
+    return out[:n].copy(), int(n_cpg.value)
 
 
 def pad_flanks(flanks):
@@ -331,6 +368,41 @@ class Device:
                                            cons.ctypes.data, rows_a.ctypes.data, cols.ctypes.data, ends.ctypes.data, ms),
                    "ramx_dev_pileup")
         return PileupResult(cols, ends, ms[0], ms[1], ms[2])
+
+    def dinuc(self, flanks, p: ExtendParams, cons, rows=None, fam_first=None, fam_count=None, pileup: bool = True) -> DinucResult:
+        """Dinucleotide pileup of every family along a given consensus, and its pileup from the same walk unless pileup=False
+        (C-ABI ramx_dev_dinuc): arguments as profile()."""
+        cp, keep = _params(p)
+        arr, npad, first, count, cons, rows_a = self._families(flanks, p, cons, rows, fam_first, fam_count)
+        nf = len(first)
+        di = np.zeros((nf, max(p.L, 1)), DINUC_DTYPE)
+        cols = np.zeros((nf, max(p.L, 1)), PILEUP_DTYPE) if pileup else None
+        ends = self._no_ends(npad)
+        ms = (C.c_double * 4)()
+        _lib.check(self._L.ramx_dev_dinuc(self._h, arr, npad, first.ctypes.data, count.ctypes.data, nf, C.byref(cp),
+                                          cons.ctypes.data, rows_a.ctypes.data, cols.ctypes.data if pileup else None, di.ctypes.data,
+                                          ends.ctypes.data, ms), "ramx_dev_dinuc")
+        return DinucResult(di, cols, ends, tuple(ms))
+
+    def refine_cpg(self, flanks, p: ExtendParams, cons, rows=None, fam_first=None, fam_count=None, max_replays: int = 10,
+                   rows_reversed: bool = False, cpg_ts: int = 0) -> RefineCpgResult:
+        """refine() with the CpG-aware re-call (C-ABI ramx_dev_refine_cpg): arguments as profile(); rows_reversed: the rows run
+        against the reading order (a left extension)."""
+        cp, keep = _params(p)
+        arr, npad, first, count, cons, rows_a = self._families(flanks, p, cons, rows, fam_first, fam_count)
+        nf = len(first)
+        out = np.zeros((nf, max(p.L, 1)), np.int8)
+        rows_out, replays, conv, n_cpg = (np.zeros(max(nf, 1), np.int32) for _ in range(4))
+        cols = np.zeros((nf, max(p.L, 1)), PILEUP_DTYPE)
+        di = np.zeros((nf, max(p.L, 1)), DINUC_DTYPE)
+        ends = self._no_ends(npad)
+        ms = (C.c_double * 4)()
+        _lib.check(self._L.ramx_dev_refine_cpg(self._h, arr, npad, first.ctypes.data, count.ctypes.data, nf, C.byref(cp),
+                                               cons.ctypes.data, rows_a.ctypes.data, int(max_replays), int(bool(rows_reversed)),
+                                               int(cpg_ts), out.ctypes.data, rows_out.ctypes.data, replays.ctypes.data,
+                                               conv.ctypes.data, cols.ctypes.data, di.ctypes.data, n_cpg.ctypes.data,
+                                               ends.ctypes.data, ms), "ramx_dev_refine_cpg")
+        return RefineCpgResult(out, rows_out[:nf], replays[:nf], conv[:nf], n_cpg[:nf], cols, di, ends, tuple(ms))
 
     def copy_stats(self, flanks, p: ExtendParams, cons, rows=None, fam_first=None, fam_count=None, rows_reversed: bool = False,
                    out: Optional[np.ndarray] = None) -> CopyStatsResult:

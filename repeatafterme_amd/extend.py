@@ -13,8 +13,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .datamodel import (ALN_END_DTYPE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, FLANK_DTYPE, PILEUP_DTYPE, PLANE_DTYPE, Alignment, Copies, SubfamGroup, Subfamilies,
-                        CoreSet, ExtendParams, Linkage, Profile, Refinement, TSD_DTYPE, TSD_SITE_DTYPE, TsdParams, TsdSummary)
+from .datamodel import (ALN_END_DTYPE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, DINUC_DTYPE, FLANK_DTYPE, PILEUP_DTYPE, PLANE_DTYPE, Alignment, Copies, SubfamGroup, Subfamilies,
+                        CoreSet, CpgRefinement, ExtendParams, Linkage, Profile, Refinement, TSD_DTYPE, TSD_SITE_DTYPE, TsdParams, TsdSummary)
 
 
 @dataclass
@@ -141,6 +141,36 @@ class _RefineSink:
         return False
 
 
+class _CpgSink:
+    """Collects what seam 1 hands to the CpG sink (ramx_set_cpg_sink) while the block runs."""
+
+    def __init__(self, max_replays, cpg_ts=0):
+        self.got = []
+        self.args = (int(max_replays), int(cpg_ts))
+
+        def _cb(ptr, _user):
+            cr = ptr.contents
+
+            def grab(src, count, dtype):
+                out = np.zeros(count, dtype)
+                if count and src:
+                    C.memmove(out.ctypes.data, src, count * out.dtype.itemsize)
+                return out
+            self.got.append(CpgRefinement(cr.direction, cr.family, grab(cr.cons, cr.rows, np.int8),
+                                          grab(cr.refined_cons, cr.refined_rows, np.int8),
+                                          grab(cr.refined_cols, cr.refined_rows, PILEUP_DTYPE),
+                                          grab(cr.refined_di, cr.refined_rows, DINUC_DTYPE), cr.replays, cr.converged, cr.n_cpg))
+        self._cb = _lib.CPG_CB(_cb)
+
+    def __enter__(self):
+        _lib.lib().ramx_set_cpg_sink(self._cb, None, *self.args)
+        return self
+
+    def __exit__(self, *exc):
+        _lib.lib().ramx_set_cpg_sink(_lib.CPG_CB(), None, 1, 0)
+        return False
+
+
 class _CopiesSink:
     """Collects what seam 1 hands to the copies sink (ramx_set_copies_sink) while the block runs."""
 
@@ -243,7 +273,7 @@ class _SubfamSink:
 
 def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, master: np.ndarray,
                      p: ExtendParams, profile: bool = False, align: bool = False, refine: int = 0, copies: bool = False,
-                     linkage=None, subfam=None):
+                     linkage=None, subfam=None, cpg=None):
     """direction: 1 = right, 0 = left (reference ram_extend.c:424,506).  profile=True: returns (RunInfo, Profile) -- the
     direction is replayed along the consensus it chose (C-ABI ramx_dev_profile) after the loop.  align=True: returns
     (RunInfo, Alignment), or (RunInfo, Profile, Alignment) with both -- every flank aligned to the kept consensus (C-ABI
@@ -252,7 +282,15 @@ def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, maste
     statistics along the kept consensus (C-ABI ramx_dev_copy_stats).  linkage=True or (min_count, min_permille, max_variants): a
     Linkage comes behind everything else -- the variants of the kept consensus and their Gram matrix (C-ABI ramx_dev_planes,
     ramx_select_planes, ramx_dev_plane_gram).  subfam=True or the eight arguments of ramx_set_subfam_sink behind its callback: a
-    Subfamilies comes last of all -- the copies split by their linked variants, every kept group with its own consensus."""
+    Subfamilies comes behind those -- the copies split by their linked variants, every kept group with its own consensus.
+    cpg=n > 0 or (n, cpg_ts): a CpgRefinement comes last of all -- the kept consensus refined over at most n replays with the
+    CpG-aware re-call (C-ABI ramx_dev_refine_cpg)."""
+    if cpg:
+        with _CpgSink(*((cpg,) if isinstance(cpg, int) else cpg)) as gsink:
+            res = extend_alignment(direction, cores, sequence, master, p, profile=profile, align=align, refine=refine, copies=copies,
+                                   linkage=linkage, subfam=subfam)
+        assert len(gsink.got) == 1
+        return (res + (gsink.got[0],)) if isinstance(res, tuple) else (res, gsink.got[0])
     if subfam:
         with _SubfamSink(_SubfamSink.DEFAULT if subfam is True else subfam) as ssink:
             res = extend_alignment(direction, cores, sequence, master, p, profile=profile, align=align, refine=refine, copies=copies,

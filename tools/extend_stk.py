@@ -19,6 +19,8 @@ per direction the family's mean Kimura divergence over the extension beside the 
 -- the check that the matrix chosen from the seed alignment was the right one for the extended part; with -linkage,
 <id>-linkage.tsv: the pairs of variant columns of both extensions whose variants travel together in the copies (RAMExtend
 -outlinkage) -- the sign that the family is two subfamilies under one consensus.
+<id>-cpg-cons.fa: with -cpg, the consensus of both extensions re-called with the CpG-aware rule (RAMExtend -outcpg; the replays are
+--refine's, 10 without it) -- a CG that most copies have deaminated to TG / CA / TA comes back as CG.
 <id>-tsd.tsv: with -tsd, the target-site duplication of every extended copy and the family's modal length (RAMExtend -outtsd).
 
 (the re-alignment and Stockholm rewriting that follow in the wrapper belong to RepeatModeler and are out of scope).
@@ -54,6 +56,7 @@ def main(argv=None):
     ap.add_argument("-linkage", action="store_true", help="also write <id>-linkage.tsv per family (RAMExtend -outlinkage)")
     ap.add_argument("-tsd", action="store_true", help="also write <id>-tsd.tsv per family (RAMExtend -outtsd) and print the modal "
                     "target-site duplication of the extended copies")
+    ap.add_argument("-cpg", action="store_true", help="also write <id>-cpg-cons.fa per family (RAMExtend -outcpg)")
     ap.add_argument("-one_by_one", action="store_true", help="start one RAMExtend per family, as the wrapper does")
     a = ap.parse_args(argv)
 
@@ -96,7 +99,8 @@ def main(argv=None):
                                          str(a.refine)] if a.refine > 0 else []) +
                                        (["-outcopies", base + "-copies.tsv"] if a.copies else []) +
                                        (["-outlinkage", base + "-linkage.tsv"] if a.linkage else []) +
-                                       (["-outtsd", base + "-tsd.tsv"] if a.tsd else []),
+                                       (["-outtsd", base + "-tsd.tsv"] if a.tsd else []) +
+                                       (["-outcpg", base + "-cpg-cons.fa"] if a.cpg else []),
                                        stdout=log, stderr=subprocess.STDOUT).returncode
                 if rc:
                     sys.exit(f"  RAMExtend failed! [{rc}] see {base}-repam.log")
@@ -104,11 +108,11 @@ def main(argv=None):
             lst = os.path.join(a.outdir, f"batch-{matrix}-{minimp}.list")
             with open(lst, "w") as fh:
                 for seed, base in fams:
-                    # fields six to thirteen are optional (the twelfth, the subfamily file, is never asked for here): "-" holds the place of one that is not asked for before one that is
+                    # fields six to fourteen are optional (the twelfth, the subfamily file, is never asked for here): "-" holds the place of one that is not asked for before one that is
                     opt = [base + "-profile.tsv" if a.profile else "-", base + "-aln.a2m" if a.aln else "-",
                            base + "-pileup.tsv" if a.refine > 0 else "-", base + "-refined-cons.fa" if a.refine > 0 else "-",
                            base + "-copies.tsv" if a.copies else "-", base + "-linkage.tsv" if a.linkage else "-", "-",
-                           base + "-tsd.tsv" if a.tsd else "-"]
+                           base + "-tsd.tsv" if a.tsd else "-", base + "-cpg-cons.fa" if a.cpg else "-"]
                     while opt and opt[-1] == "-":
                         opt.pop()
                     fh.write("\t".join([base + "-linup.tsv", base + "-repam.log", base + "-ext-cons.fa",
