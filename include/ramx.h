@@ -808,6 +808,77 @@ int ramx_tsd_flat(const ramx_flat_cores *cores, const int8_t *sequence, uint64_t
 int ramx_tsd_alignment(struct coreAlignment *coreAlign, struct sequenceLibrary *seqLib, const ramx_tsd_params *params, ramx_tsd *out);
 int ramx_tsd_batch(const ramx_family *families, int32_t n_families, const ramx_tsd_params *params, ramx_tsd *out);
 
+/* Tandem periodicity of the extended copies: did the extension run into a tandem repeat -- a (CA)n, a poly-A tail, the next
+ * units of a satellite?  For every shift p, how well does a copy's extension agree with itself moved by p, and where: an
+ * ungapped local self-alignment on every diagonal of the dot plot.  Exact integer arithmetic, every segment on its own.
+ *   Segment: library positions lo..hi inclusive on the forward strand; lo == hi + 1 is an empty segment, lo > hi + 1 is
+ *   RAMX_ERR_ARG.  Its length is n = hi + 1 - lo; a length above RAMX_PERIOD_LEN_MAX is RAMX_ERR_UNSUPPORTED.
+ *   Class x_j of position lo + j: library codes 0..3 are classes 0..3, codes 4..7 are code - 4, everything else is class 4,
+ *   including any position outside the library.
+ *   Pair: for a period p with 1 <= p <= min(pmax, n - 1), a pair is (j, j + p) with 0 <= j and j + p < n.  It AGREES iff both
+ *   classes are below 4 and equal, DISAGREES iff both are below 4 and unequal; otherwise it counts for nothing.
+ *   Block b holds the pairs with 8b <= j <= 8b + 7 that exist (the last block may be short): a_b is its number of agreeing
+ *   pairs, d_b of disagreeing pairs, and its score is s_b = a_b - mm * d_b.
+ *   Tract of p: a run of consecutive blocks b0..b1 with S = the sum of their s_b.  The best tract has the largest S; ties go to
+ *   the smallest b1, then the largest b0.  That is the one-pass scan over b = 0, 1, ... which keeps a running sum and a start
+ *   block, begins anew at b (running sum s_b, start b) whenever the running sum before b is <= 0 and adds s_b otherwise, and
+ *   records (running sum, start, b) whenever the running sum is strictly above everything recorded before, beginning from 0.
+ *   Record of the segment: the best tract over all p with the largest S, ties to the smallest p.  If S < min_score, or n < 2,
+ *   the record is all zeros.  Otherwise period = p, score = S, start = 8 * b0, end = min(8 * b1 + 7, n - p - 1) -- the first
+ *   members of the tract's first and last pair --, agree and disagree the sums of a_b and d_b over the tract; the periodic
+ *   region is offsets start .. end + p of the segment.  reserved is written as 0.
+ * Parameters: pmax 1..8192, mm 1..15, min_score >= 1; anything else is RAMX_ERR_ARG, raised before anything is launched or
+ * written.  Defaults: 1024, 3, 16. */
+#define RAMX_PERIOD_LEN_MAX 65536
+#define RAMX_PERIOD_PMAX 8192
+typedef struct ramx_period_params { int32_t pmax, mm, min_score, reserved; } ramx_period_params;
+typedef struct ramx_period_seg { int64_t lo, hi; } ramx_period_seg;                      /* 16 bytes */
+typedef struct ramx_period { int32_t period, score, start, end, agree, disagree, reserved[2]; } ramx_period;  /* 32 bytes */
+
+/* The records on the device, from the library it holds (ramx_dev_load_library*, either form): every segment is packed as a
+ * flank (start = lo, step = +1, t = 0 .. n - 1, W = 0) by the pack kernels of the extension loop; one wave per tile of 64
+ * segments squeezes the transposed windows into every segment's own stream (two bits a base and a validity bit), and one
+ * workgroup per segment scans it from LDS, a lane per period.  The windows and streams live in a device buffer of at most
+ * RAMX_PERIOD_BYTES bytes (environment, read per call; default 1 GiB): a tile takes 64 * (4 * (ceil(nmax / 8) + 1) + 12 *
+ * max(ceil(nmax / 32), 1)) bytes, nmax the longest segment of the call; the tiles are processed in groups that fit,
+ * RAMX_ERR_UNSUPPORTED if one tile alone does not; the grouping does not show in the result.  Self-contained like the replays
+ * and ramx_dev_tsd (a following ramx_dev_run_direction needs a new ramx_dev_begin_direction; resident bit planes are dropped);
+ * rank-local under a communicator: the records are per segment.  n_segs == 0 returns RAMX_OK and launches nothing.  kernel_ms
+ * (may be NULL): three values, the HIP-event times of the pack, the squeeze and the scan, summed over the groups. */
+int ramx_dev_period(ramx_dev *d, const ramx_period_seg *segs, int32_t n_segs, const ramx_period_params *params, ramx_period *out,
+                    double *kernel_ms);
+
+/* The contract on an array of n library codes (plain host C; the class of codes[j] is x_j): what the device computes for a
+ * segment, used for the kept consensus of a direction.  RAMX_ERR_ARG for bad parameters, n < 0 or a missing pointer,
+ * RAMX_ERR_UNSUPPORTED for n > RAMX_PERIOD_LEN_MAX. */
+int ramx_period_sequence(const int8_t *codes, int32_t n, const ramx_period_params *params, ramx_period *out);
+
+/* One segment per core, in list order, from cores that both directions have extended (plain host C), with the extents of
+ * ramx_tsd_sites (ram_extend.c:721-727).  which = 0, the left extension: orient == 0: [left_pos - left_len, left_pos - 1],
+ * otherwise [left_pos + 1, left_pos + left_len]; which = 1, the right extension: orient == 0: [right_pos + 1, right_pos +
+ * right_len], otherwise [right_pos - right_len, right_pos - 1]; which = 2, the whole element: lo..hi of the core's TSD site.
+ * out holds cores->n segments; returns their number, RAMX_ERR_ARG for which outside 0..2. */
+int32_t ramx_period_segments(const ramx_flat_cores *cores, int32_t which, ramx_period_seg *out);
+
+/* What a family's records say together (plain host C): n; n_tract counts the records with period > 0, n_mono those with
+ * period 1, n_simple 2..6, n_tandem >= 7; at_lo the records with period > 0 and start == 0, at_hi those with end == len -
+ * period - 1 (the tract reaches the segment's first / last base; len = hi + 1 - lo of segs[i]); mode is the most frequent
+ * period > 0, ties to the smaller one, 0 if there is none, and mode_count its count.  RAMX_ERR_ARG for bad parameters, n < 0,
+ * a missing pointer or a record with a period outside 0..RAMX_PERIOD_PMAX. */
+typedef struct ramx_period_hist { int32_t n, n_tract, n_mono, n_simple, n_tandem, at_lo, at_hi, mode, mode_count, reserved[3]; } ramx_period_hist;
+int ramx_period_summary(const ramx_period *records, const ramx_period_seg *segs, int32_t n, const ramx_period_params *params,
+                        ramx_period_hist *out);
+
+/* Seam 1, called after both extension calls: ramx_period_segments(cores, which) and ramx_dev_period on the session's device.
+ * out holds one record per core in list order.  The library rule is that of ramx_tsd_flat / _alignment / _batch; in a batch a
+ * position outside a family's own library is outside the library (class 4), whatever lies beside it in the concatenation. */
+int ramx_period_flat(const ramx_flat_cores *cores, const int8_t *sequence, uint64_t seq_len, int32_t which,
+                     const ramx_period_params *params, ramx_period *out);
+int ramx_period_alignment(struct coreAlignment *coreAlign, struct sequenceLibrary *seqLib, int32_t which,
+                          const ramx_period_params *params, ramx_period *out);
+int ramx_period_batch(const ramx_family *families, int32_t n_families, int32_t which, const ramx_period_params *params,
+                      ramx_period *out);
+
 /* multi-GPU: flanks are sharded over ranks; each column's 4 candidate sums are all-reduced
  * (4 x int64, RCCL over xGMI).  unique_id is the 128-byte ncclUniqueId made by rank 0
  * (ramx_comm_unique_id) and handed to the other ranks by the launcher (e.g. torch.distributed). */

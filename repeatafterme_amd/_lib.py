@@ -27,6 +27,7 @@ EXPORTS = [
     "ramx_dev_planes", "ramx_dev_plane_gram", "ramx_dev_plane_gram_ms", "ramx_select_planes", "ramx_link_pairs", "ramx_set_linkage_sink",
     "ramx_link_components", "ramx_dev_subfamilies", "ramx_dev_subfam_masks", "ramx_dev_subfam_ms", "ramx_set_subfam_sink",
     "ramx_dev_tsd", "ramx_tsd_sites", "ramx_tsd_summary", "ramx_termini", "ramx_tsd_flat", "ramx_tsd_alignment", "ramx_tsd_batch",
+    "ramx_dev_period", "ramx_period_sequence", "ramx_period_segments", "ramx_period_summary", "ramx_period_flat", "ramx_period_alignment", "ramx_period_batch",
 ]
 
 
@@ -147,6 +148,15 @@ class TsdParams(C.Structure):       # ramx_tsd_params
 
 class TsdHist(C.Structure):         # ramx_tsd_hist
     _fields_ = [("hist", C.c_int32 * 33), ("mode", C.c_int32), ("mode_count", C.c_int32), ("pad_", C.c_int32), ("null", C.c_double * 33)]
+
+
+class PeriodParams(C.Structure):    # ramx_period_params
+    _fields_ = [(k, C.c_int32) for k in ("pmax", "mm", "min_score", "reserved")]
+
+
+class PeriodHist(C.Structure):      # ramx_period_hist
+    _fields_ = [(k, C.c_int32) for k in ("n", "n_tract", "n_mono", "n_simple", "n_tandem", "at_lo", "at_hi", "mode", "mode_count")] + \
+               [("reserved", C.c_int32 * 3)]
 
 
 def build(force: bool = False) -> None:
@@ -281,6 +291,20 @@ def lib() -> C.CDLL:
         L.ramx_tsd_alignment.restype = C.c_int
         L.ramx_tsd_batch.argtypes = [C.POINTER(Family), C.c_int32, C.POINTER(TsdParams), C.c_void_p]
         L.ramx_tsd_batch.restype = C.c_int
+        L.ramx_dev_period.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(PeriodParams), C.c_void_p, C.POINTER(C.c_double)]
+        L.ramx_dev_period.restype = C.c_int
+        L.ramx_period_sequence.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PeriodParams), C.c_void_p]
+        L.ramx_period_sequence.restype = C.c_int
+        L.ramx_period_segments.argtypes = [C.POINTER(FlatCores), C.c_int32, C.c_void_p]
+        L.ramx_period_segments.restype = C.c_int32
+        L.ramx_period_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(PeriodParams), C.POINTER(PeriodHist)]
+        L.ramx_period_summary.restype = C.c_int
+        L.ramx_period_flat.argtypes = [C.POINTER(FlatCores), C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(PeriodParams), C.c_void_p]
+        L.ramx_period_flat.restype = C.c_int
+        L.ramx_period_alignment.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(PeriodParams), C.c_void_p]
+        L.ramx_period_alignment.restype = C.c_int
+        L.ramx_period_batch.argtypes = [C.POINTER(Family), C.c_int32, C.c_int32, C.POINTER(PeriodParams), C.c_void_p]
+        L.ramx_period_batch.restype = C.c_int
         if hasattr(L, "ramx_cli_main"):
             L.ramx_cli_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
         _lib = L

@@ -113,6 +113,12 @@ static void usage(void)
     "     -tsdmin <num>         # ... shortest and\n"
     "     -tsdmax <num>         # ... longest duplication looked for, 1..32 (4, 20),\n"
     "     -tsdmm <num>          # ... one mismatch allowed per this many bases, 0 = none (10).\n"
+    "     -outperiod <file>     # Save the tandem periodicity of every copy's left and right extension ( did the\n"
+    "                           #   extension run into a simple repeat or a satellite? ) to a TSV file.\n"
+    "     -periodmax <num>      # ... the longest period looked for, 1..8192 (1024),\n"
+    "     -periodmm <num>       # ... what a disagreeing pair costs, 1..15 (3),\n"
+    "     -periodmin <num>      # ... the lowest score reported (16),\n"
+    "     -periodwhole          # ... also for the whole extended copy.\n"
     "     -version              # Print out one-line version information\n"
     "     -v[v[v[v]]]           # How verbose do you want it to be?  -vvvv is super-verbose.\n"
     "\n"
@@ -264,8 +270,10 @@ static void warm_start(void)
 /* everything the command line decides */
 struct cli_opts
 {
-  const char *ranges_file, *outtsv, *outfa, *outmat, *cons_file, *seq_file, *matrix_name, *batch_file, *outprofile, *outaln, *outpileup, *outrefined, *outcpg, *outdinuc, *outcopies, *outlinkage, *outsubfam, *outtsd;
+  const char *ranges_file, *outtsv, *outfa, *outmat, *cons_file, *seq_file, *matrix_name, *batch_file, *outprofile, *outaln, *outpileup, *outrefined, *outcpg, *outdinuc, *outcopies, *outlinkage, *outsubfam, *outtsd, *outperiod;
   ramx_tsd_params tsd;
+  ramx_period_params period;
+  int periodwhole;
   int refine, cpgscore, linkcount, linkfrac, linkscore, subfamk, subfammin, subfamiter;
   int flanking, L, bandwidth, maxn, when_to_stop, num_threads, verbose;
   int gap_ext, gap_open, match, mismatch, cappenalty, minimprovement, is_rs;
@@ -489,7 +497,7 @@ static void write_results(const struct cli_opts *o, struct coreAlignment *cores,
  */
 struct batch_item
 {
-  char *ranges, *log, *cons, *tsv, *fa, *profile, *aln, *pileup, *refined, *copies, *linkage, *subfam, *tsd, *cpg;
+  char *ranges, *log, *cons, *tsv, *fa, *profile, *aln, *pileup, *refined, *copies, *linkage, *subfam, *tsd, *cpg, *period;
   struct coreAlignment *cores;
   struct sequenceLibrary *lib;
   int N, rightbp, leftbp;
@@ -1095,6 +1103,79 @@ static void tsd_write(const char *path, const ramx_tsd_params *tp, struct coreAl
   fclose(fp);
 }
 
+/*
+ * -outperiod <file>: the tandem periodicity of the extended copies (include/ramx.h, ramx_period) as a TSV.  "#period" carries the
+ * parameters; per part -- left, right, and whole with -periodwhole -- "#part" carries what the family's records say together
+ * and "#consensus" the record of that direction's kept consensus in reading order (whole: the left one followed by the right
+ * one).  Then one line per core and part, the cores in list order: named and placed as -outtsv places the copy, the part and its
+ * length, the record, the periodic region in the coordinates of start and end, and the first bases of the region as the library
+ * has them on its forward strand ("-" without a tract).  Like -outtsd this is no sink: it is computed when both directions are done.
+ */
+static const char *const k_period_part[3] = { "left", "right", "whole" };
+static const char k_period_header[] = "core\tseqid\tstart\tend\tstrand\tpart\tlength\tperiod\tunits\tscore\tregion_start\tregion_end\tagree\tdisagree\tunit\n";
+
+/* rec[w] / segs[w]: the n records and segments of part w (w = 2 only with whole) */
+static void period_write(const char *path, const ramx_period_params *pp, int whole, struct coreAlignment *cores, struct sequenceLibrary *lib,
+                         const char *master, int L, int rightbp, int leftbp, ramx_period *const rec[3], ramx_period_seg *const segs[3], int n)
+{
+  FILE *fp = fopen(path, "w");
+  if (!fp) { fprintf(stderr, "Could not create the periodicity file %s\n", path); exit(1); }
+  const int l = 1, nl = leftbp > 0 ? leftbp : 0, nr = rightbp > 0 ? rightbp : 0, parts = whole ? 3 : 2;
+  int8_t *cons = (int8_t *)malloc((size_t)(nl + nr > 0 ? nl + nr : 1));
+  for (int r = 0; r < nl; r++) cons[r] = (int8_t)master[(size_t)L - nl + r];          /* the left rows run outward from the core */
+  for (int r = 0; r < nr; r++) cons[nl + r] = (int8_t)master[(size_t)L + l + r];
+  fprintf(fp, "#period\tpmax=%d\tmm=%d\tmin_score=%d\n", pp->pmax, pp->mm, pp->min_score);
+  for (int w = 0; w < parts; w++)
+  {
+    ramx_period_hist h;
+    ramx_period cr;
+    const int8_t *cw = w == 1 ? cons + nl : cons;
+    const int cn = w == 0 ? nl : w == 1 ? nr : nl + nr;
+    if (ramx_period_summary(rec[w], segs[w], n, pp, &h) != RAMX_OK || ramx_period_sequence(cw, cn, pp, &cr) != RAMX_OK)
+    { fprintf(stderr, "RAMExtend(ramx): periodicity: %s\n", ramx_last_error()); exit(1); }
+    fprintf(fp, "#part\tpart=%s\tn=%d\tn_tract=%d\tn_mono=%d\tn_simple=%d\tn_tandem=%d\tat_lo=%d\tat_hi=%d\tmode=%d\tmode_count=%d\n", k_period_part[w],
+            h.n, h.n_tract, h.n_mono, h.n_simple, h.n_tandem, h.at_lo, h.at_hi, h.mode, h.mode_count);
+    fprintf(fp, "#consensus\tpart=%s\tlength=%d\tperiod=%d\tscore=%d\tstart=%d\tend=%d\tagree=%d\tdisagree=%d\n", k_period_part[w], cn, cr.period,
+            cr.score, cr.start, cr.end, cr.agree, cr.disagree);
+  }
+  free(cons);
+  fputs(k_period_header, fp);
+  int x = 0;
+  for (struct coreAlignment *s = cores; s != NULL && x < n; s = s->next, x++)
+  {
+    const int si = s->seqIdx;
+    const uint64_t lo = si > 0 ? lib->boundaries[si - 1] : 0;
+    const uint64_t off = (lib->offsets != NULL && lib->offsets[si] > 0) ? lib->offsets[si] : 0;
+    /* the copy's ends in the library, and as -outtsv prints them */
+    const int64_t e_lo = s->orient ? (int64_t)s->rightSeqPos - s->rightExtensionLen : (int64_t)s->leftSeqPos - s->leftExtensionLen;
+    const int64_t e_hi = s->orient ? (int64_t)s->leftSeqPos + s->leftExtensionLen : (int64_t)s->rightSeqPos + s->rightExtensionLen;
+    const int64_t shift = (int64_t)off - (int64_t)lo + 1;
+    for (int w = 0; w < parts; w++)
+    {
+      const ramx_period *t = &rec[w][x];
+      const ramx_period_seg *g = &segs[w][x];
+      char unit[33] = "-";
+      int64_t r_lo = 0, r_hi = 0;
+      if (t->period > 0)
+      {
+        r_lo = g->lo + t->start; r_hi = g->lo + t->end + t->period;
+        const int k = t->period < 32 ? t->period : 32;
+        for (int j = 0; j < k; j++)
+        {
+          const int64_t p = r_lo + j;
+          unit[j] = p >= 0 && (uint64_t)p < lib->length ? (char)toupper((unsigned char)code_to_char(ramx_lib_code(lib, (uint64_t)p))) : 'N';
+        }
+        unit[k] = 0;
+      }
+      fprintf(fp, "%d\t%s\t%ld\t%ld\t%c\t%s\t%ld\t%d\t%.2f\t%d\t%ld\t%ld\t%d\t%d\t%s\n", x, lib->identifiers[si], (long)(e_lo + shift), (long)(e_hi + shift),
+              s->orient ? '-' : '+', k_period_part[w], (long)(g->hi + 1 - g->lo), t->period,
+              t->period > 0 ? (double)(t->end - t->start + 1 + t->period) / (double)t->period : 0.0, t->score,
+              t->period > 0 ? (long)(r_lo + shift) : 0L, t->period > 0 ? (long)(r_hi + shift) : 0L, t->agree, t->disagree, unit);
+    }
+  }
+  fclose(fp);
+}
+
 /* flat view of a core list for ramx_extend_batch (arrays owned by the caller's arena) */
 static void flatten_cores(struct coreAlignment *cores, int N, ramx_flat_cores *fc)
 {
@@ -1154,6 +1235,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   if (o->outlinkage != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's linkage file is the eleventh field of its line in the list\n"); exit(1); }
   if (o->outsubfam != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's subfamily file is the twelfth field of its line in the list\n"); exit(1); }
   if (o->outtsd != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's target-site duplication file is the thirteenth field of its line in the list\n"); exit(1); }
+  if (o->outperiod != NULL) { fprintf(stderr, "RAMExtend(ramx): with -batch every family's periodicity file is the fifteenth field of its line in the list\n"); exit(1); }
   if (o->outcpg != NULL || o->outdinuc != NULL)
   { fprintf(stderr, "RAMExtend(ramx): with -batch every family's CpG-aware consensus file is the fourteenth field of its line in the list; -outdinuc writes one family\n"); exit(1); }
   FILE *lf = fopen(o->batch_file, "r");
@@ -1167,9 +1249,9 @@ static int run_batch(struct cli_opts *o, time_t t_start)
   {
     while (len > 0 && (line[len - 1] == '\n' || line[len - 1] == '\r')) line[--len] = 0;
     if (line[0] == '#' || line[0] == 0) continue;
-    char *f[14] = { NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL };
+    char *f[15] = { NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL };
     char *p = line;
-    for (int k = 0; k < 14 && p; k++) { f[k] = p; char *t = strchr(p, '\t'); if (t) { *t = 0; p = t + 1; } else p = NULL; }
+    for (int k = 0; k < 15 && p; k++) { f[k] = p; char *t = strchr(p, '\t'); if (t) { *t = 0; p = t + 1; } else p = NULL; }
     if (!f[0] || !f[1]) { fprintf(stderr, "batch list: every line needs at least <ranges><TAB><log>\n"); exit(1); }
     if (F == cap) { cap *= 2; it = (struct batch_item *)realloc(it, cap * sizeof(*it)); memset(it + F, 0, (cap - F) * sizeof(*it)); }
     it[F].ranges = strdup(f[0]); it[F].log = strdup(f[1]);
@@ -1185,6 +1267,7 @@ static int run_batch(struct cli_opts *o, time_t t_start)
     it[F].subfam = field_or_null(f[11]) ? strdup(f[11]) : NULL;      /* optional twelfth field: the family's -outsubfam file */
     it[F].tsd = field_or_null(f[12]) ? strdup(f[12]) : NULL;         /* optional thirteenth field: the family's -outtsd file */
     it[F].cpg = field_or_null(f[13]) ? strdup(f[13]) : NULL;         /* optional fourteenth field: the family's -outcpg file */
+    it[F].period = field_or_null(f[14]) ? strdup(f[14]) : NULL;      /* optional fifteenth field: the family's -outperiod file */
     F++;
   }
   free(line);
@@ -1321,12 +1404,42 @@ static int run_batch(struct cli_opts *o, time_t t_start)
     }
     free(rec);
   }
+  /* phase 7, only where a family asks for it: the periodicity of all families, one call per part */
+  int any_period = 0;
+  for (size_t i = 0; i < F; i++) any_period |= it[i].period != NULL;
+  if (any_period)
+  {
+    size_t total = 0;
+    for (size_t i = 0; i < F; i++) { flatten_cores(it[i].cores, it[i].N, &fam[i].cores); total += (size_t)it[i].N; }
+    const int parts = o->periodwhole ? 3 : 2;
+    ramx_period *rec[3] = { NULL, NULL, NULL };
+    ramx_period_seg *segs[3] = { NULL, NULL, NULL };
+    for (int w = 0; w < parts; w++)
+    {
+      rec[w] = (ramx_period *)calloc(total ? total : 1, sizeof(ramx_period));
+      segs[w] = (ramx_period_seg *)calloc(total ? total : 1, sizeof(ramx_period_seg));
+      if (ramx_period_batch(fam, (int32_t)F, w, &o->period, rec[w]) < 0) { fprintf(stderr, "RAMExtend(ramx): periodicity failed: %s\n", ramx_last_error()); exit(1); }
+      size_t at = 0;
+      for (size_t i = 0; i < F; i++) { ramx_period_segments(&fam[i].cores, w, segs[w] + at); at += (size_t)it[i].N; }
+    }
+    size_t at = 0;
+    for (size_t i = 0; i < F; i++)
+    {
+      ramx_period *const r3[3] = { rec[0] + at, rec[1] + at, rec[2] ? rec[2] + at : NULL };
+      ramx_period_seg *const s3[3] = { segs[0] + at, segs[1] + at, segs[2] ? segs[2] + at : NULL };
+      if (it[i].period != NULL)
+        period_write(it[i].period, &o->period, o->periodwhole, it[i].cores, it[i].lib, it[i].master, L, it[i].rightbp, it[i].leftbp, r3, s3, it[i].N);
+      at += (size_t)it[i].N;
+      free_flat(&fam[i].cores);
+    }
+    for (int w = 0; w < 3; w++) { free(rec[w]); free(segs[w]); }
+  }
   printf("RAMExtend(ramx) batch: %zu families done\n", F);
   for (size_t i = 0; i < F; i++)
   {
     ramx_free_library(it[i].lib, it[i].cores);
     free(it[i].master); free(it[i].ranges); free(it[i].log); free(it[i].cons); free(it[i].tsv); free(it[i].fa); free(it[i].profile); free(it[i].aln);
-    free(it[i].pileup); free(it[i].refined); free(it[i].copies); free(it[i].linkage); free(it[i].subfam); free(it[i].tsd); free(it[i].cpg);
+    free(it[i].pileup); free(it[i].refined); free(it[i].copies); free(it[i].linkage); free(it[i].subfam); free(it[i].tsd); free(it[i].cpg); free(it[i].period);
   }
   ramx_set_profile_sink(NULL, NULL);
   ramx_set_align_sink(NULL, NULL);
@@ -1387,6 +1500,13 @@ int ramx_cli_main(int argc, char **argv)
   if (!opt_int(argc, argv, "-tsdmax", &o.tsd.kmax)) o.tsd.kmax = 20;
   if (!opt_int(argc, argv, "-tsdmm", &o.tsd.mm_div)) o.tsd.mm_div = 10;
   if (ramx_tsd_check_params(&o.tsd) != RAMX_OK) { fprintf(stderr, "RAMExtend(ramx): %s\n", ramx_last_error()); exit(1); }
+  opt_string(argc, argv, "-outperiod", &o.outperiod);
+  if (!opt_int(argc, argv, "-periodmax", &o.period.pmax)) o.period.pmax = 1024;
+  if (!opt_int(argc, argv, "-periodmm", &o.period.mm)) o.period.mm = 3;
+  if (!opt_int(argc, argv, "-periodmin", &o.period.min_score)) o.period.min_score = 16;
+  o.period.reserved = 0;
+  o.periodwhole = opt_bool(argc, argv, "-periodwhole");
+  if (ramx_period_check_params(&o.period) != RAMX_OK) { fprintf(stderr, "RAMExtend(ramx): %s\n", ramx_last_error()); exit(1); }
   if (!opt_int(argc, argv, "-refine", &o.refine)) o.refine = 10;
   if (o.refine < 1) { fprintf(stderr, "RAMExtend(ramx): -refine takes the largest number of replays, at least 1\n"); exit(1); }
   if (!opt_int(argc, argv, "-L", &o.L)) o.L = 10000;
@@ -1543,6 +1663,26 @@ int ramx_cli_main(int argc, char **argv)
     if (ramx_tsd_alignment(cores, lib, &o.tsd, rec) != RAMX_OK) { fprintf(stderr, "RAMExtend(ramx): target-site duplications failed: %s\n", ramx_last_error()); exit(1); }
     tsd_write(o.outtsd, &o.tsd, cores, lib, master, L, rightbp, leftbp, rec, cnt);
     free(rec);
+  }
+  if (o.outperiod != NULL)
+  {
+    /* after both directions, on the library they left on the device: one call per part */
+    int cnt = 0;
+    for (struct coreAlignment *s = cores; s != NULL; s = s->next) cnt++;
+    ramx_flat_cores fc;
+    flatten_cores(cores, cnt, &fc);
+    ramx_period *rec[3] = { NULL, NULL, NULL };
+    ramx_period_seg *segs[3] = { NULL, NULL, NULL };
+    for (int w = 0; w < (o.periodwhole ? 3 : 2); w++)
+    {
+      rec[w] = (ramx_period *)calloc((size_t)(cnt ? cnt : 1), sizeof(ramx_period));
+      segs[w] = (ramx_period_seg *)calloc((size_t)(cnt ? cnt : 1), sizeof(ramx_period_seg));
+      ramx_period_segments(&fc, w, segs[w]);
+      if (ramx_period_alignment(cores, lib, w, &o.period, rec[w]) != RAMX_OK) { fprintf(stderr, "RAMExtend(ramx): periodicity failed: %s\n", ramx_last_error()); exit(1); }
+    }
+    period_write(o.outperiod, &o.period, o.periodwhole, cores, lib, master, L, rightbp, leftbp, rec, segs, cnt);
+    for (int w = 0; w < 3; w++) { free(rec[w]); free(segs[w]); }
+    free_flat(&fc);
   }
   if (fp_mat != NULL) fclose(fp_mat);     /* ram_extend.c:778-779 */
   phase_done("report + outputs");

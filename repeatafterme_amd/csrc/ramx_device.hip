@@ -58,6 +58,7 @@
 #include "ramx_linkage_api.h"
 #include "ramx_subfam_api.h"
 #include "ramx_tsd_api.h"
+#include "ramx_period_api.h"
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
@@ -191,6 +192,9 @@ struct ramx_dev
   double sf_ms[2];          // HIP-event times of the assign and the count kernels of the last ramx_dev_subfamilies, summed
   // ramx_dev_tsd (allocated on its first call): per site the room between the two words, and its record
   int *d_tsd_room; ramx_tsd *d_tsd_out; size_t cap_tsd_room, cap_tsd_out;
+  // ramx_dev_period (allocated on its first call): the segments' streams (bases, validity), their lengths and records
+  unsigned long long *d_per_bases; unsigned *d_per_valid; int *d_per_len; ramx_period *d_per_out;
+  size_t cap_per_bases, cap_per_valid, cap_per_len, cap_per_out;
 };
 
 extern "C" int ramx_device_count(void)
@@ -287,6 +291,7 @@ extern "C" void ramx_dev_destroy(ramx_dev *d)
   (void)hipFree(d->d_sf_changed); (void)hipFree(d->d_sf_cnt); (void)hipFree(d->d_sf_mask);
   free(d->lk_place); free(d->sf_lay);
   (void)hipFree(d->d_tsd_room); (void)hipFree(d->d_tsd_out);
+  (void)hipFree(d->d_per_bases); (void)hipFree(d->d_per_valid); (void)hipFree(d->d_per_len); (void)hipFree(d->d_per_out);
   if (d->hostbox_mirror) (void)hipFree(d->hostbox_mirror);
   if (d->d_peer) (void)hipFree(d->d_peer);
   for (int i = 0; i < 2; i++) if (d->ev_chk[i]) (void)hipEventDestroy(d->ev_chk[i]);
@@ -2348,6 +2353,112 @@ extern "C" int ramx_dev_tsd(ramx_dev *d, const ramx_tsd_site *sites, int32_t n_s
     for (auto &e : ev) (void)hipEventDestroy(e);
   }
   return RAMX_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// tandem periodicity: every segment packed as a flank, squeezed into a stream of its own, then one workgroup per segment and a
+// lane per period (ramx_kernels_period.h)
+// ------------------------------------------------------------------------------------------
+extern "C" int ramx_dev_period_bounded(ramx_dev *d, const ramx_period_seg *segs, const ramx_period_seg *bounds, int32_t n_segs,
+                                       const ramx_period_params *params, ramx_period *out, double *kernel_ms)
+{
+  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0;
+  if (!d || n_segs < 0 || (n_segs && (!segs || !out))) { ramx_set_error("ramx_dev_period: bad argument"); return RAMX_ERR_ARG; }
+  int rc;
+  if ((rc = ramx_period_check_params(params)) != RAMX_OK) return rc;
+  long long nmax = 0;
+  for (int i = 0; i < n_segs; i++)
+  {
+    if (segs[i].lo < -RAMX_TSD_POS_MAX || segs[i].hi > RAMX_TSD_POS_MAX || segs[i].lo > segs[i].hi + 1)       // (so that no difference below overflows)
+    { ramx_set_error("ramx_dev_period: segment %d: lo %lld hi %lld: lo > hi + 1, or out of range", i, (long long)segs[i].lo, (long long)segs[i].hi); return RAMX_ERR_ARG; }
+    if (bounds && (bounds[i].lo < -RAMX_TSD_POS_MAX || bounds[i].hi > RAMX_TSD_POS_MAX))
+    { ramx_set_error("ramx_dev_period: segment %d: bounds out of range", i); return RAMX_ERR_ARG; }
+    const long long len = (long long)(segs[i].hi + 1 - segs[i].lo);
+    if (len > nmax) nmax = len;
+  }
+  if (nmax > RAMX_PERIOD_LEN_MAX)
+  { ramx_set_error("ramx_dev_period: a segment of %lld bases, at most %d", nmax, RAMX_PERIOD_LEN_MAX); return RAMX_ERR_UNSUPPORTED; }
+  if (n_segs == 0) return RAMX_OK;
+  if (n_segs > (1 << 29)) { ramx_set_error("ramx_dev_period: more than 2^29 segments in one call"); return RAMX_ERR_UNSUPPORTED; }
+  // the windows and streams of one tile of 64 segments, at the length of the call's longest segment
+  const int KW = period_window_words((int)nmax), SW = period_stream_words((int)nmax) > 0 ? period_stream_words((int)nmax) : 1;
+  const size_t tile_bytes = (size_t)64 * ((size_t)KW * sizeof(unsigned) + (size_t)SW * (sizeof(unsigned long long) + sizeof(unsigned)));
+  size_t budget = (size_t)1 << 30;
+  if (const char *e = getenv("RAMX_PERIOD_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+  if (tile_bytes > budget)
+  {
+    ramx_set_error("ramx_dev_period: the windows and streams of one tile of 64 segments (%lld bases: %zu bytes) do not fit RAMX_PERIOD_BYTES = %zu",
+                   nmax, tile_bytes, budget);
+    return RAMX_ERR_UNSUPPORTED;
+  }
+  const int tiles = (n_segs + 63) / 64;
+  const int group = (int)(budget / tile_bytes < (size_t)tiles ? budget / tile_bytes : (size_t)tiles);
+  HIPCHK(hipSetDevice(d->ordinal));
+  // the flank and window buffers of the direction are reused, as by the replays
+  if ((rc = pack_settle(d, true)) != RAMX_OK) return rc;
+  const int Gp = group * 64;
+  if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)Gp * sizeof(ramx_flank)))) return rc;
+  if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)KW * Gp * sizeof(unsigned)))) return rc;
+  if ((rc = ensure(&d->d_bounds, &d->cap_bounds, (size_t)Gp * sizeof(int2)))) return rc;
+  if ((rc = ensure(&d->d_per_bases, &d->cap_per_bases, (size_t)Gp * SW * sizeof(unsigned long long)))) return rc;
+  if ((rc = ensure(&d->d_per_valid, &d->cap_per_valid, (size_t)Gp * SW * sizeof(unsigned)))) return rc;
+  if ((rc = ensure(&d->d_per_len, &d->cap_per_len, (size_t)Gp * sizeof(int)))) return rc;
+  if ((rc = ensure(&d->d_per_out, &d->cap_per_out, (size_t)Gp * sizeof(ramx_period)))) return rc;
+  d->ready = 0;
+  d->planes_ready = 0;
+  hipEvent_t ev[4] = { NULL, NULL, NULL, NULL };
+  if (kernel_ms) for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+  std::vector<ramx_flank> fl((size_t)Gp);
+  std::vector<int> len((size_t)Gp);
+  for (int t0 = 0; t0 < tiles && rc == RAMX_OK; t0 += group)
+  {
+    const int nt = tiles - t0 < group ? tiles - t0 : group, Np = nt * 64, s0 = t0 * 64;
+    const int n = n_segs - s0 < Np ? n_segs - s0 : Np;
+    for (int i = 0; i < Np; i++)
+    {
+      ramx_flank &f = fl[(size_t)i];
+      memset(&f, 0, sizeof(f));
+      f.step = 1; f.t_lo = 1; len[(size_t)i] = 0;                // (padding, or an empty segment: no base)
+      if (i >= n) continue;
+      const ramx_period_seg &s = segs[s0 + i];
+      long long a = 0, b = (long long)(s.hi - s.lo);            // offsets of the segment that may be read
+      if (bounds)
+      {
+        if (bounds[s0 + i].lo - s.lo > a) a = (long long)(bounds[s0 + i].lo - s.lo);
+        if (bounds[s0 + i].hi - s.lo < b) b = (long long)(bounds[s0 + i].hi - s.lo);
+      }
+      f.start = s.lo;
+      if (a <= b) { f.t_lo = (int32_t)a; f.t_hi = (int32_t)b; }
+      len[(size_t)i] = (int)(s.hi + 1 - s.lo);
+    }
+    HIPCHK(hipMemcpyAsync(d->d_flanks, fl.data(), (size_t)Np * sizeof(ramx_flank), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(d->d_per_len, len.data(), (size_t)Np * sizeof(int), hipMemcpyHostToDevice, d->stream));
+    if (kernel_ms) HIPCHK(hipEventRecord(ev[0], d->stream));
+    if ((rc = launch_pack(d, Np, Np, RAMX_PERIOD_W, 0, KW, d->stream)) != RAMX_OK) break;
+    d->packed_kw = KW;
+    if (kernel_ms) HIPCHK(hipEventRecord(ev[1], d->stream));
+    PeriodArgs pa;
+    pa.win = d->d_bases; pa.bases = d->d_per_bases; pa.valid = d->d_per_valid; pa.len = d->d_per_len; pa.out = d->d_per_out;
+    pa.n = n; pa.Np = Np; pa.KW = KW; pa.SW = SW;
+    pa.pmax = params->pmax; pa.mm = params->mm; pa.min_score = params->min_score;
+    if ((rc = ramx_period_squeeze_launch(d->stream, pa)) != RAMX_OK) { ramx_set_error("ramx_dev_period: launch failed (%s)", hipGetErrorString(hipGetLastError())); break; }
+    if (kernel_ms) HIPCHK(hipEventRecord(ev[2], d->stream));
+    if ((rc = ramx_period_scan_launch(d->stream, pa)) != RAMX_OK) { ramx_set_error("ramx_dev_period: launch failed (%s)", hipGetErrorString(hipGetLastError())); break; }
+    if (kernel_ms) HIPCHK(hipEventRecord(ev[3], d->stream));
+    HIPCHK(hipMemcpyAsync(out + s0, d->d_per_out, (size_t)n * sizeof(ramx_period), hipMemcpyDeviceToHost, d->stream));
+    // (the next group writes the host and device buffers of this one again)
+    HIPCHK(hipStreamSynchronize(d->stream));
+    if (kernel_ms)
+      for (int k = 0; k < 3; k++) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1])); kernel_ms[k] += ms; }
+  }
+  if (kernel_ms) for (auto &e : ev) (void)hipEventDestroy(e);
+  return rc;
+}
+
+extern "C" int ramx_dev_period(ramx_dev *d, const ramx_period_seg *segs, int32_t n_segs, const ramx_period_params *params, ramx_period *out,
+                               double *kernel_ms)
+{
+  return ramx_dev_period_bounded(d, segs, NULL, n_segs, params, out, kernel_ms);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1550,6 +1550,106 @@ int ramx_tsd_batch(const ramx_family *fam, int32_t F, const ramx_tsd_params *par
   return rc;
 }
 
+/* ---- tandem periodicity (include/ramx.h): called after both extension calls, with the library rule of the calls above ---- */
+
+int ramx_period_flat(const ramx_flat_cores *cores, const int8_t *sequence, uint64_t seq_len, int32_t which,
+                     const ramx_period_params *params, ramx_period *out)
+{
+  int rc;
+  if ((rc = ramx_period_check_params(params)) != RAMX_OK) return rc;
+  if (!cores || cores->n < 0 || (cores->n > 0 && (!sequence || !out)) || which < 0 || which > 2)
+  { ramx_set_error("ramx_period_flat: bad argument"); return RAMX_ERR_ARG; }
+  if (cores->n == 0) return RAMX_OK;
+  ramx_dev *d = ramx_default_device();
+  if (!d) return RAMX_ERR_NO_DEVICE;
+  ramx_period_seg *segs = (ramx_period_seg *)malloc(sizeof(ramx_period_seg) * (size_t)cores->n);
+  ramx_period_segments(cores, which, segs);
+  if ((rc = library_resident(d, sequence, seq_len)) == RAMX_OK) rc = ramx_dev_period(d, segs, cores->n, params, out, NULL);
+  free(segs);
+  return rc;
+}
+
+int ramx_period_alignment(struct coreAlignment *coreAlign, struct sequenceLibrary *seqLib, int32_t which,
+                          const ramx_period_params *params, ramx_period *out)
+{
+  int rc;
+  if ((rc = ramx_period_check_params(params)) != RAMX_OK) return rc;
+  if (!seqLib || which < 0 || which > 2) { ramx_set_error("ramx_period_alignment: bad argument"); return RAMX_ERR_ARG; }
+  int n = 0;
+  for (struct coreAlignment *cc = coreAlign; cc != NULL; cc = cc->next) n++;
+  if (n == 0) return RAMX_OK;
+  if (!out) { ramx_set_error("ramx_period_alignment: bad argument"); return RAMX_ERR_ARG; }
+  ramx_dev *d = ramx_default_device();
+  if (!d) return RAMX_ERR_NO_DEVICE;
+  ramx_period_seg *segs = (ramx_period_seg *)malloc(sizeof(ramx_period_seg) * (size_t)n);
+  int k = 0;
+  for (struct coreAlignment *cc = coreAlign; cc != NULL; cc = cc->next, k++)
+  {
+    /* ramx_period_segments on the list's own fields */
+    const int64_t lp = (int64_t)cc->leftSeqPos, rp = (int64_t)cc->rightSeqPos, ll = cc->leftExtensionLen, rl = cc->rightExtensionLen;
+    if (which == 0) { segs[k].lo = cc->orient ? lp + 1 : lp - ll; segs[k].hi = cc->orient ? lp + ll : lp - 1; }
+    else if (which == 1) { segs[k].lo = cc->orient ? rp - rl : rp + 1; segs[k].hi = cc->orient ? rp - 1 : rp + rl; }
+    else { segs[k].lo = cc->orient ? rp - rl : lp - ll; segs[k].hi = cc->orient ? lp + ll : rp + rl; }
+  }
+  if (seqLib->sequence == NULL)
+  {
+    /* loaded packed: the twin goes to the device unless it is the library there already */
+    const ramx_packed_library *packed = ramx_packed_of(seqLib);
+    if (!packed) { ramx_set_error("ramx_period_alignment: the sequence library holds no bases (sequence == NULL and no packed twin)"); rc = RAMX_ERR_ARG; }
+    else if (g_packed_owner != seqLib) rc = ramx_preload_library_packed(seqLib, packed);
+  }
+  else
+    rc = library_resident(d, (const int8_t *)seqLib->sequence, seqLib->length);
+  if (rc == RAMX_OK) rc = ramx_dev_period(d, segs, n, params, out, NULL);
+  free(segs);
+  return rc;
+}
+
+int ramx_period_batch(const ramx_family *fam, int32_t F, int32_t which, const ramx_period_params *params, ramx_period *out)
+{
+  int rc;
+  if ((rc = ramx_period_check_params(params)) != RAMX_OK) return rc;
+  if (F < 0 || (F && !fam) || which < 0 || which > 2) { ramx_set_error("ramx_period_batch: bad argument"); return RAMX_ERR_ARG; }
+  int64_t total = 0;
+  for (int f = 0; f < F; f++)
+  {
+    if (fam[f].cores.n < 0 || (fam[f].cores.n > 0 && !fam[f].sequence)) { ramx_set_error("ramx_period_batch: bad family %d", f); return RAMX_ERR_ARG; }
+    total += fam[f].cores.n;
+  }
+  if (total == 0) return RAMX_OK;
+  if (!out || total > 0x7fffffff) { ramx_set_error("ramx_period_batch: bad argument"); return RAMX_ERR_ARG; }
+  ramx_dev *d = ramx_default_device();
+  if (!d) return RAMX_ERR_NO_DEVICE;
+  /* every family at the offset ramx_extend_batch gives it in the concatenated library */
+  uint64_t *at_of = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)F), *fps = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)F);
+  uint64_t total_len = 0;
+  for (int f = 0; f < F; f++) { at_of[f] = total_len; total_len += fam[f].seq_len; }
+  if (!batch_lib_cached(fam, F, at_of, total_len, fps))
+  {
+    int8_t *lib = (int8_t *)malloc(total_len ? total_len : 1);
+    struct batch_lib_ctx bc = { fam, NULL, at_of, lib, 0 };
+    ramx_parallel_for(F, 8, batch_lib_range, &bc);
+    rc = batch_lib_upload(d, fam, F, lib, total_len, fps);
+    free(lib);
+  }
+  ramx_period_seg *segs = (ramx_period_seg *)malloc(sizeof(ramx_period_seg) * 2 * (size_t)total), *bounds = segs + total;
+  int64_t at = 0;
+  for (int f = 0; f < F; f++)
+  {
+    ramx_period_segments(&fam[f].cores, which, segs + at);
+    for (int i = 0; i < fam[f].cores.n; i++)
+    {
+      /* outside the family's own library is outside the library: its neighbours in the concatenation are never read */
+      segs[at + i].lo += (int64_t)at_of[f]; segs[at + i].hi += (int64_t)at_of[f];
+      bounds[at + i].lo = (int64_t)at_of[f]; bounds[at + i].hi = (int64_t)at_of[f] + (int64_t)fam[f].seq_len - 1;
+    }
+    at += fam[f].cores.n;
+  }
+  if (rc == RAMX_OK) rc = ramx_dev_period_bounded(d, segs, bounds, (int32_t)total, params, out, NULL);
+  free(segs); free(at_of); free(fps);
+  return rc;
+}
+
 /* bnw_extend.c:87-155 -- kept for link compatibility: the device path never reads it.  The block has the reference's
  * index shape score[2][num_align][2*bandwidth+1][2], so code written against the reference that dereferences it (the
  * VERBOSE >= 12 dump of ram_extend.c:949-959, unit tests) reads zeros instead of faulting -- but every [n] shares ONE

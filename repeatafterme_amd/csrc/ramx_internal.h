@@ -34,6 +34,13 @@ int ramx_lib_code(const struct sequenceLibrary *lib, uint64_t at);
 int ramx_tsd_check_params(const ramx_tsd_params *tp);
 #define RAMX_TSD_POS_MAX ((int64_t)1 << 61)  /* positions of a ramx_tsd_site lie within +- this */
 
+/* the checks of ramx_period_params (csrc/ramx_period.c): RAMX_OK, or RAMX_ERR_ARG with the error text set */
+int ramx_period_check_params(const ramx_period_params *pp);
+/* ramx_dev_period with bounds (csrc/ramx_device.hip): bounds[i].lo .. bounds[i].hi are the library positions segment i may read,
+ * every other position is class 4; NULL: the whole library (ramx_period_batch keeps a family inside its own library with it) */
+int ramx_dev_period_bounded(ramx_dev *d, const ramx_period_seg *segs, const ramx_period_seg *bounds, int32_t n_segs,
+                            const ramx_period_params *params, ramx_period *out, double *kernel_ms);
+
 /* host threads for a loop over `items` (at most 16, at most one per min_items_per_thread; RAMX_HOST_THREADS overrides) */
 int ramx_host_threads(long items, long min_items_per_thread);
 /* fn formats items [lo, hi) into outs[0..n_outs) (memory streams; an entry is NULL where the real stream is); the chunks'

@@ -16,17 +16,10 @@
 #pragma once
 
 #include "ramx_tsd_api.h"
+#include "ramx_kernels_squeeze.h"       // tsd_squeeze
 
 static_assert(sizeof(ramx_tsd) == 16, "ramx_tsd is 4 words");
 
-// eight 4-bit fields -> their low two bits, packed: field i to bits 2i, 2i + 1
-__device__ __forceinline__ unsigned tsd_squeeze(unsigned x)
-{
-  x &= 0x33333333u;
-  x = (x | (x >> 2)) & 0x0f0f0f0fu;
-  x = (x | (x >> 4)) & 0x00ff00ffu;
-  return (x | (x >> 8)) & 0xffffu;
-}
 // eight 2-bit fields in reverse order
 __device__ __forceinline__ unsigned tsd_reverse(unsigned x)
 {

@@ -260,6 +260,34 @@ class TsdSummary:
     null: np.ndarray                 # float64 [33]: copies expected to show a word of that length by chance
 
 
+# tandem periodicity: C-ABI ramx_period_seg (16 bytes), ramx_period (32 bytes), ramx_period_params
+PERIOD_SEG_DTYPE = np.dtype([("lo", np.int64), ("hi", np.int64)])
+PERIOD_DTYPE = np.dtype([("period", np.int32), ("score", np.int32), ("start", np.int32), ("end", np.int32), ("agree", np.int32),
+                         ("disagree", np.int32), ("reserved", np.int32, (2,))])
+assert PERIOD_SEG_DTYPE.itemsize == 16 and PERIOD_DTYPE.itemsize == 32
+
+
+@dataclass
+class PeriodParams:
+    pmax: int = 1024
+    mm: int = 3
+    min_score: int = 16
+
+
+@dataclass
+class PeriodSummary:
+    """What a family's records say together (C-ABI ramx_period_hist)."""
+    n: int
+    n_tract: int                     # records with a period
+    n_mono: int                      # period 1
+    n_simple: int                    # period 2..6
+    n_tandem: int                    # period >= 7
+    at_lo: int                       # tracts that begin at the segment's first base
+    at_hi: int                       # tracts that reach its last base
+    mode: int                        # the most frequent period, ties to the smaller; 0: none
+    mode_count: int
+
+
 FLANK_DTYPE = np.dtype([("start", np.int64), ("t_lo", np.int32), ("t_hi", np.int32), ("step", np.int8), ("compl_", np.int8),
                         ("pad_", np.int8, (6,))])
 assert FLANK_DTYPE.itemsize == 24

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 from .datamodel import (ALN_END_DTYPE, ALN_NONE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, DINUC_DTYPE, LINK_DTYPE, PILEUP_DTYPE, PILEUP_INS, PLANE_DTYPE,
-                        TSD_DTYPE, TSD_SITE_DTYPE, CoreSet, ExtendParams, TsdParams)
+                        TSD_DTYPE, TSD_SITE_DTYPE, PERIOD_DTYPE, PERIOD_SEG_DTYPE, CoreSet, ExtendParams, PeriodParams, TsdParams)
 from .extend import RunInfo, _info, _params
 
 
@@ -257,6 +257,18 @@ class Device:
         _lib.check(self._L.ramx_dev_tsd(self._h, s.ctypes.data if len(s) else None, len(s), C.byref(cp),
                                         out.ctypes.data if len(s) else None, ms), "ramx_dev_tsd")
         return (out, [ms[0], ms[1]]) if timing else out
+
+    def period(self, segs, pp: Optional[PeriodParams] = None, timing: bool = False):
+        """The tandem periodicity of every segment (lo, hi) on the library this device holds (C-ABI ramx_dev_period): ->
+        PERIOD_DTYPE [n_segs]; timing=True: (records, [pack ms, squeeze ms, scan ms])."""
+        s = np.ascontiguousarray(segs, PERIOD_SEG_DTYPE).reshape(-1)
+        pp = PeriodParams() if pp is None else pp
+        cp = _lib.PeriodParams(int(pp.pmax), int(pp.mm), int(pp.min_score), 0)
+        out = np.zeros(len(s), PERIOD_DTYPE)
+        ms = (C.c_double * 3)()
+        _lib.check(self._L.ramx_dev_period(self._h, s.ctypes.data if len(s) else None, len(s), C.byref(cp),
+                                           out.ctypes.data if len(s) else None, ms), "ramx_dev_period")
+        return (out, [ms[0], ms[1], ms[2]]) if timing else out
 
     def begin_direction(self, flanks, p: ExtendParams):
         arr, nx = flanks

@@ -14,7 +14,8 @@ import numpy as np
 
 from . import _lib
 from .datamodel import (ALN_END_DTYPE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, DINUC_DTYPE, FLANK_DTYPE, PILEUP_DTYPE, PLANE_DTYPE, Alignment, Copies, SubfamGroup, Subfamilies,
-                        CoreSet, CpgRefinement, ExtendParams, Linkage, Profile, Refinement, TSD_DTYPE, TSD_SITE_DTYPE, TsdParams, TsdSummary)
+                        CoreSet, CpgRefinement, ExtendParams, Linkage, Profile, Refinement, TSD_DTYPE, TSD_SITE_DTYPE, TsdParams, TsdSummary,
+                        PERIOD_DTYPE, PERIOD_SEG_DTYPE, PeriodParams, PeriodSummary)
 
 
 @dataclass
@@ -273,7 +274,7 @@ class _SubfamSink:
 
 def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, master: np.ndarray,
                      p: ExtendParams, profile: bool = False, align: bool = False, refine: int = 0, copies: bool = False,
-                     linkage=None, subfam=None, cpg=None):
+                     linkage=None, subfam=None, cpg=None, period=None):
     """direction: 1 = right, 0 = left (reference ram_extend.c:424,506).  profile=True: returns (RunInfo, Profile) -- the
     direction is replayed along the consensus it chose (C-ABI ramx_dev_profile) after the loop.  align=True: returns
     (RunInfo, Alignment), or (RunInfo, Profile, Alignment) with both -- every flank aligned to the kept consensus (C-ABI
@@ -284,7 +285,14 @@ def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, maste
     ramx_select_planes, ramx_dev_plane_gram).  subfam=True or the eight arguments of ramx_set_subfam_sink behind its callback: a
     Subfamilies comes behind those -- the copies split by their linked variants, every kept group with its own consensus.
     cpg=n > 0 or (n, cpg_ts): a CpgRefinement comes last of all -- the kept consensus refined over at most n replays with the
-    CpG-aware re-call (C-ABI ramx_dev_refine_cpg)."""
+    CpG-aware re-call (C-ABI ramx_dev_refine_cpg).  period=True or a PeriodParams: the tandem periodicity of every core's
+    extension in this direction, PERIOD_DTYPE [cores.n], comes behind everything (C-ABI ramx_period_flat with which = direction,
+    on the library the call left on the device)."""
+    if period:
+        res = extend_alignment(direction, cores, sequence, master, p, profile=profile, align=align, refine=refine, copies=copies,
+                               linkage=linkage, subfam=subfam, cpg=cpg)
+        rec = period_flat(cores, sequence, 1 if direction else 0, None if period is True else period)
+        return (res + (rec,)) if isinstance(res, tuple) else (res, rec)
     if cpg:
         with _CpgSink(*((cpg,) if isinstance(cpg, int) else cpg)) as gsink:
             res = extend_alignment(direction, cores, sequence, master, p, profile=profile, align=align, refine=refine, copies=copies,
@@ -337,13 +345,18 @@ def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, maste
 
 
 def extend_batch(direction: int, families, p: ExtendParams, profile: bool = False, align: bool = False, copies: bool = False,
-                 linkage=None, subfam=None):
+                 linkage=None, subfam=None, period=None):
     """Many families in one launch (C-ABI ramx_extend_batch).  `families` is a list of (cores, sequence, master);
     every family is updated in place exactly like extend_alignment does for one.  Returns one RunInfo per family;
     profile=True: (RunInfos, Profiles), one Profile per family in the order of `families`; align=True: (RunInfos,
     Alignments), or (RunInfos, Profiles, Alignments) with both.  copies=True: the families' Copies come last in the tuple.
     linkage (as extend_alignment): the families' Linkages come behind everything else; subfam (as extend_alignment): their
-    Subfamilies last of all."""
+    Subfamilies last of all.  period (as extend_alignment): one PERIOD_DTYPE array per family behind everything (C-ABI
+    ramx_period_batch with which = direction)."""
+    if period:
+        res = extend_batch(direction, families, p, profile=profile, align=align, copies=copies, linkage=linkage, subfam=subfam)
+        recs = period_batch(families, 1 if direction else 0, None if period is True else period)
+        return (res + (recs,)) if isinstance(res, tuple) else (res, recs)
     if subfam:
         with _SubfamSink(_SubfamSink.DEFAULT if subfam is True else subfam) as ssink:
             res = extend_batch(direction, families, p, profile=profile, align=align, copies=copies, linkage=linkage)
@@ -475,5 +488,82 @@ def tsd_batch(families, tp: TsdParams = None):
     out = np.zeros(total, TSD_DTYPE)
     cp = _tsd_params(tp)
     _lib.check(_lib.lib().ramx_tsd_batch(arr, n, C.byref(cp), out.ctypes.data if total else None), "ramx_tsd_batch")
+    ends = np.cumsum([0] + [f[0].n for f in families])
+    return [out[ends[i]:ends[i + 1]].copy() for i in range(n)]
+
+
+# ---- tandem periodicity (include/ramx.h, ramx_period): after the extension calls ----
+
+def _period_params(pp):
+    pp = PeriodParams() if pp is None else pp
+    return _lib.PeriodParams(int(pp.pmax), int(pp.mm), int(pp.min_score), 0)
+
+
+def period_sequence(codes, pp: PeriodParams = None) -> np.ndarray:
+    """The record of an array of library codes, e.g. the kept consensus of a direction (C-ABI ramx_period_sequence, host C):
+    -> one PERIOD_DTYPE record."""
+    c = np.ascontiguousarray(codes, np.int8).reshape(-1)
+    out = np.zeros(1, PERIOD_DTYPE)
+    cp = _period_params(pp)
+    _lib.check(_lib.lib().ramx_period_sequence(c.ctypes.data if len(c) else None, len(c), C.byref(cp), out.ctypes.data), "ramx_period_sequence")
+    return out[0]
+
+
+def period_segments(cores: CoreSet, which: int) -> np.ndarray:
+    """One segment per core: which = 0 the left extension, 1 the right one, 2 the whole element (C-ABI ramx_period_segments)."""
+    out = np.zeros(cores.n, PERIOD_SEG_DTYPE)
+    fc = _flat_cores(cores)
+    _lib.check(_lib.lib().ramx_period_segments(C.byref(fc), int(which), out.ctypes.data if cores.n else None), "ramx_period_segments")
+    return out
+
+
+def period_summary(records, segs, pp: PeriodParams = None) -> PeriodSummary:
+    """What a family's records say together (C-ABI ramx_period_summary, host C)."""
+    r = np.ascontiguousarray(records, PERIOD_DTYPE).reshape(-1)
+    s = np.ascontiguousarray(segs, PERIOD_SEG_DTYPE).reshape(-1)
+    assert len(r) == len(s)
+    h = _lib.PeriodHist()
+    cp = _period_params(pp)
+    _lib.check(_lib.lib().ramx_period_summary(r.ctypes.data if len(r) else None, s.ctypes.data if len(s) else None, len(r), C.byref(cp),
+                                              C.byref(h)), "ramx_period_summary")
+    return PeriodSummary(*[int(getattr(h, k)) for k in ("n", "n_tract", "n_mono", "n_simple", "n_tandem", "at_lo", "at_hi", "mode", "mode_count")])
+
+
+def period_flat(cores: CoreSet, sequence: np.ndarray, which: int, pp: PeriodParams = None) -> np.ndarray:
+    """The tandem periodicity of every core's left extension (which = 0), right extension (1) or whole element (2) after the
+    extension calls, on the library they left on the session's device (C-ABI ramx_period_flat): -> PERIOD_DTYPE [cores.n]."""
+    assert sequence.dtype == np.int8 and sequence.flags.c_contiguous
+    out = np.zeros(cores.n, PERIOD_DTYPE)
+    fc = _flat_cores(cores)
+    cp = _period_params(pp)
+    _lib.check(_lib.lib().ramx_period_flat(C.byref(fc), sequence.ctypes.data, len(sequence), int(which), C.byref(cp),
+                                           out.ctypes.data if cores.n else None), "ramx_period_flat")
+    return out
+
+
+def period_alignment(core_list, seq_lib, n: int, which: int, pp: PeriodParams = None) -> np.ndarray:
+    """The same on the reference's data model, as tsd_alignment takes it (C-ABI ramx_period_alignment)."""
+    out = np.zeros(n, PERIOD_DTYPE)
+    cp = _period_params(pp)
+    _lib.check(_lib.lib().ramx_period_alignment(C.cast(core_list, C.c_void_p), C.cast(seq_lib, C.c_void_p), int(which), C.byref(cp),
+                                                out.ctypes.data if n else None), "ramx_period_alignment")
+    return out
+
+
+def period_batch(families, which: int, pp: PeriodParams = None):
+    """The same for the families of an extend_batch, in one call on the concatenated library it leaves on the device (C-ABI
+    ramx_period_batch).  `families` as extend_batch takes them; -> one PERIOD_DTYPE array per family."""
+    n = len(families)
+    arr = (_lib.Family * max(n, 1))()
+    for i, (cores, sequence, master) in enumerate(families):
+        assert sequence.dtype == np.int8 and sequence.flags.c_contiguous
+        arr[i].cores = _flat_cores(cores)
+        arr[i].sequence = sequence.ctypes.data
+        arr[i].seq_len = len(sequence)
+        arr[i].master = master.ctypes.data if master is not None else None
+    total = sum(f[0].n for f in families)
+    out = np.zeros(total, PERIOD_DTYPE)
+    cp = _period_params(pp)
+    _lib.check(_lib.lib().ramx_period_batch(arr, n, int(which), C.byref(cp), out.ctypes.data if total else None), "ramx_period_batch")
     ends = np.cumsum([0] + [f[0].n for f in families])
     return [out[ends[i]:ends[i + 1]].copy() for i in range(n)]

@@ -22,6 +22,8 @@ per direction the family's mean Kimura divergence over the extension beside the 
 <id>-cpg-cons.fa: with -cpg, the consensus of both extensions re-called with the CpG-aware rule (RAMExtend -outcpg; the replays are
 --refine's, 10 without it) -- a CG that most copies have deaminated to TG / CA / TA comes back as CG.
 <id>-tsd.tsv: with -tsd, the target-site duplication of every extended copy and the family's modal length (RAMExtend -outtsd).
+<id>-period.tsv: with -period, the tandem periodicity of every copy's left and right extension -- did the extension run into a
+simple repeat or a satellite? -- and the family's modal period per part (RAMExtend -outperiod).
 
 (the re-alignment and Stockholm rewriting that follow in the wrapper belong to RepeatModeler and are out of scope).
 """
@@ -56,6 +58,8 @@ def main(argv=None):
     ap.add_argument("-linkage", action="store_true", help="also write <id>-linkage.tsv per family (RAMExtend -outlinkage)")
     ap.add_argument("-tsd", action="store_true", help="also write <id>-tsd.tsv per family (RAMExtend -outtsd) and print the modal "
                     "target-site duplication of the extended copies")
+    ap.add_argument("-period", action="store_true", help="also write <id>-period.tsv per family (RAMExtend -outperiod) and print the "
+                    "modal period of the copies' extensions")
     ap.add_argument("-cpg", action="store_true", help="also write <id>-cpg-cons.fa per family (RAMExtend -outcpg)")
     ap.add_argument("-one_by_one", action="store_true", help="start one RAMExtend per family, as the wrapper does")
     a = ap.parse_args(argv)
@@ -100,7 +104,8 @@ def main(argv=None):
                                        (["-outcopies", base + "-copies.tsv"] if a.copies else []) +
                                        (["-outlinkage", base + "-linkage.tsv"] if a.linkage else []) +
                                        (["-outtsd", base + "-tsd.tsv"] if a.tsd else []) +
-                                       (["-outcpg", base + "-cpg-cons.fa"] if a.cpg else []),
+                                       (["-outcpg", base + "-cpg-cons.fa"] if a.cpg else []) +
+                                       (["-outperiod", base + "-period.tsv"] if a.period else []),
                                        stdout=log, stderr=subprocess.STDOUT).returncode
                 if rc:
                     sys.exit(f"  RAMExtend failed! [{rc}] see {base}-repam.log")
@@ -108,11 +113,12 @@ def main(argv=None):
             lst = os.path.join(a.outdir, f"batch-{matrix}-{minimp}.list")
             with open(lst, "w") as fh:
                 for seed, base in fams:
-                    # fields six to fourteen are optional (the twelfth, the subfamily file, is never asked for here): "-" holds the place of one that is not asked for before one that is
+                    # fields six to fifteen are optional (the twelfth, the subfamily file, is never asked for here): "-" holds the place of one that is not asked for before one that is
                     opt = [base + "-profile.tsv" if a.profile else "-", base + "-aln.a2m" if a.aln else "-",
                            base + "-pileup.tsv" if a.refine > 0 else "-", base + "-refined-cons.fa" if a.refine > 0 else "-",
                            base + "-copies.tsv" if a.copies else "-", base + "-linkage.tsv" if a.linkage else "-", "-",
-                           base + "-tsd.tsv" if a.tsd else "-", base + "-cpg-cons.fa" if a.cpg else "-"]
+                           base + "-tsd.tsv" if a.tsd else "-", base + "-cpg-cons.fa" if a.cpg else "-",
+                           base + "-period.tsv" if a.period else "-"]
                     while opt and opt[-1] == "-":
                         opt.pop()
                     fh.write("\t".join([base + "-linup.tsv", base + "-repam.log", base + "-ext-cons.fa",
@@ -159,6 +165,12 @@ def main(argv=None):
                     if line.startswith("#mode"):
                         mode, count, null = (kv.split("=")[1] for kv in line.rstrip("\n").split("\t")[1:])
                         print(f"  - Target-site duplication: {mode} bp in {count} copies ({null} expected by chance)")
+            if a.period and os.path.exists(base + "-period.tsv"):
+                for line in open(base + "-period.tsv"):                 # the summary line of each part
+                    if line.startswith("#part"):
+                        kv = dict(f.split("=") for f in line.rstrip("\n").split("\t")[1:])
+                        print(f"  - Tandem periodicity [{kv['part']}]: period {kv['mode']} in {kv['mode_count']} of {kv['n']} copies "
+                              f"({kv['n_tract']} with a tract)")
     return 0
 
 
