@@ -30,6 +30,18 @@ void ramx_forget_library_owner(const struct sequenceLibrary *lib);
 /* one base of a library of either kind (1 byte per base, or packed) */
 int ramx_lib_code(const struct sequenceLibrary *lib, uint64_t at);
 
+/* a base code as the reports print it, and its complement (reference sequence.c:1090-1110, :1141-1160) */
+static inline char code_to_char(int z)
+{
+  return (z >= 0 && z < 8) ? "ACGTacgt"[z] : 'N';
+}
+static inline int code_compl(int c)
+{
+  if (c >= 0 && c <= 3) return 3 - c;
+  if (c >= 4 && c <= 7) return 4 + (7 - c);
+  return RAMX_SYM_N;
+}
+
 /* the checks of ramx_tsd_params (csrc/ramx_tsd.c): RAMX_OK, or RAMX_ERR_ARG with the error text set */
 int ramx_tsd_check_params(const ramx_tsd_params *tp);
 #define RAMX_TSD_POS_MAX ((int64_t)1 << 61)  /* positions of a ramx_tsd_site lie within +- this */

@@ -13,19 +13,6 @@
 
 #include "ramx_internal.h"
 
-static char code_to_char(int z)
-{
-  static const char t[8] = { 'A', 'C', 'G', 'T', 'a', 'c', 'g', 't' };
-  return (z >= 0 && z < 8) ? t[z] : 'N';      /* sequence.c:1090-1110 */
-}
-
-static int code_compl(int c)                   /* sequence.c:1141-1160 */
-{
-  if (c >= 0 && c <= 3) return 3 - c;
-  if (c >= 4 && c <= 7) return 4 + (7 - c);
-  return RAMX_SYM_N;
-}
-
 static void append_base(char *dst, const struct sequenceLibrary *lib, uint64_t at, int complement)
 {
   size_t n = strlen(dst);

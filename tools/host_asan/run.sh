@@ -20,6 +20,10 @@ gcc -std=gnu11 -O1 $san $inc -o "$out/linkage" "$here/linkage_main.c" -lm
 # the CpG-aware re-call on random records (ramx_recall.c is compiled into the program, under the sanitizers too)
 gcc -std=gnu11 -O1 $san $inc -o "$out/recall_cpg" "$here/recall_cpg_main.c" "$root/repeatafterme_amd/csrc/ramx_recall.c"
 "$out/recall_cpg"
+# the command line's analysis outputs: hand-made records through the sinks, the writers and the post-passes of two families
+# (ramx_cli_outputs.c is compiled into the program, under the sanitizers too)
+gcc -std=gnu11 -O1 $san $inc -o "$out/cli_outputs" "$here/cli_outputs_main.c" $lib -lm
+"$out/cli_outputs"
 # (the device side of ramx_device.hip is compiled too, which takes a minute or two: the host object refers to its code object)
 "$rocm/bin/hipcc" --offload-arch=gfx950 -x hip -std=c++17 -O1 -g -fno-omit-frame-pointer $inc -Xarch_host -fsanitize=address,undefined \
   -Xarch_host -fno-sanitize-recover=undefined -o "$out/replay_plan" "$here/replay_plan_main.cpp" $lib -L"$rocm/lib" -lrccl -lpthread
