@@ -879,6 +879,79 @@ int ramx_period_alignment(struct coreAlignment *coreAlign, struct sequenceLibrar
 int ramx_period_batch(const ramx_family *families, int32_t n_families, int32_t which, const ramx_period_params *params,
                       ramx_period *out);
 
+/* Terminal repeats of the extended copies: is the beginning of a copy repeated at its end -- directly (the long terminal
+ * repeats of an LTR retrotransposon) or as its reverse complement (the terminal inverted repeats of a DNA transposon)?  The TSDs
+ * look just outside the termini of an element, this looks just inside them: a gapped local alignment of the element's first T
+ * bases with its last T, once per orientation.  Exact integer arithmetic, every site on its own.
+ *   Site: a ramx_tsd_site as defined for the TSDs: the element is library positions lo..hi, with the bounds seq_lo..seq_hi and
+ *   the same argument checks.  n = hi + 1 - lo.
+ *   Window length: T = min(tmax, n / 2) with integer division, so the two windows never overlap.  For T == 0 both records are
+ *   all zeros.
+ *   Class of a position: the rule of the TSDs: codes 0..3 and 4..7 are classes 0..3, everything else is class 4, including
+ *   positions outside seq_lo..seq_hi and outside the library.
+ *   Windows: a_i = class(lo + i), i = 0..T-1: the 5' end read inward.  Direct partner: b_j = class(hi + 1 - T + j): the 3' end in
+ *   the same reading order; a 3' LTR ends at j = T - 1.  Inverted partner: c_j = class(hi - j), complemented (3 - x) when the
+ *   class is below 4: the 3' end read inward on the other strand; a TIR begins at i = 0, j = 0.
+ *   Agreement: a pair agrees iff both classes are below 4 and equal.  Every other pair is a mismatch.
+ *   Cells: i, j = 1..T with H[0][*] = H[*][0] = 0 and
+ *     D = H[i-1][j-1] + (agree(a_{i-1}, b_{j-1}) ? match : -mismatch),  U = H[i-1][j] - gap,  L = H[i][j-1] - gap,
+ *     H[i][j] = max(0, D, U, L).  The gap cost is linear.
+ *   Payload: every cell carries (i0, j0, matches, columns).  If H[i][j] == 0 the payload is (i, j, 0, 0).  Otherwise it is the
+ *   payload of the first of D, U, L, in that order, whose value equals H[i][j]; columns goes up by 1, and through D matches goes
+ *   up by 1 if the pair agrees.  Boundary cells carry (i, j, 0, 0).
+ *   Record of one orientation: the cell with the largest H, ties to the smallest i, then the smallest j.  If that H < min_score
+ *   the record is all zeros except T.  Otherwise score = H, a_start = i0, a_end = i - 1, b_start = j0, b_end = j - 1, matches
+ *   and columns from the payload, T as above: the starts and ends are 0-based window offsets of the first and last aligned base.
+ *   Output order: out[2 s] is site s direct, out[2 s + 1] is site s inverted.
+ * Parameters: tmax 1..RAMX_TERM_TMAX, match 1..15, mismatch 1..15, gap 1..31, min_score >= 1, slack 0..15, reserved 0; anything
+ * else is RAMX_ERR_ARG, raised before anything is launched or written.  Defaults: 512, 2, 3, 5, 40, 3 (the largest best score of
+ * 200 pairs of independent random windows at T = 512 under these scores was 30 in the restatement tests/term_ref.py). */
+#define RAMX_TERM_TMAX 1024
+typedef struct ramx_term_params { int32_t tmax, match, mismatch, gap, min_score, slack, reserved[2]; } ramx_term_params;
+typedef struct ramx_term { int32_t score, a_start, a_end, b_start, b_end, matches, columns, T; } ramx_term;   /* 32 bytes */
+
+/* The records on the device, from the library it holds (ramx_dev_load_library*, either form): every site packs three windows
+ * with the pack kernels of the extension loop at W = 0 (A: start = lo, step = +1; B: start = hi + 1 - T, step = +1; C: start =
+ * hi, step = -1, complemented; t = 0 .. T - 1 cut by the site's bounds), the squeeze kernel of ramx_dev_period turns them into
+ * one stream per window (two bits a base and a validity bit), and one wave per (site, orientation) sweeps the T x T cells in
+ * registers (csrc/ramx_kernels_term.h).  The windows and streams live in a device buffer of at most RAMX_TERM_BYTES bytes
+ * (environment, read per call; default 1 GiB): a tile of 64 sites takes 3 * 64 * (4 * (ceil(Tmax / 8) + 1) + 12 * max(ceil(Tmax /
+ * 32), 1)) bytes, Tmax the longest window of the call; the tiles are processed in groups that fit, RAMX_ERR_UNSUPPORTED if one
+ * tile alone does not; the grouping does not show in the result.  Self-contained like ramx_dev_tsd and ramx_dev_period (a
+ * following ramx_dev_run_direction needs a new ramx_dev_begin_direction; resident bit planes are dropped); rank-local under a
+ * communicator.  out holds 2 * n_sites records.  n_sites == 0 returns RAMX_OK and launches nothing; more than 2^29 sites are
+ * RAMX_ERR_UNSUPPORTED.  kernel_ms (may be NULL): three values, the HIP-event times of the pack, the squeeze and the alignment,
+ * summed over the groups. */
+int ramx_dev_term(ramx_dev *d, const ramx_tsd_site *sites, int32_t n_sites, const ramx_term_params *params, ramx_term *out,
+                  double *kernel_ms);
+
+/* The contract on two arrays of library codes (plain host C): the cells are i = 1..na, j = 1..nb, a_i the class of a[i], b_j the
+ * class of b[j] as given (the caller reverses and complements for the inverted orientation); the record's T is min(na, nb).
+ * The device case is na == nb == T.  RAMX_ERR_ARG for bad parameters, a negative length or a missing pointer,
+ * RAMX_ERR_UNSUPPORTED for a length above 65536. */
+int ramx_term_pair(const int8_t *a, int32_t na, const int8_t *b, int32_t nb, const ramx_term_params *params, ramx_term *out);
+
+/* What a family's records say together (plain host C, integers only); records holds 2 * n records in the output order above.
+ * n_direct, n_inverted: records with score > 0.  direct_anchored: score > 0, a_start <= slack and b_end >= T - 1 - slack;
+ * inverted_anchored: score > 0, a_start <= slack and b_start <= slack.  direct_median, inverted_median: the lower median of
+ * a_end - a_start + 1 over the anchored records, 0 if there are none; the sums of matches and columns run over the anchored
+ * records of each orientation.  verdict: 1 (LTR) if 2 * direct_anchored > n and direct_anchored >= inverted_anchored; 2 (TIR) if
+ * 2 * inverted_anchored > n and inverted_anchored > direct_anchored; 0 otherwise.  RAMX_ERR_ARG for bad parameters, n < 0 or a
+ * missing pointer. */
+typedef struct ramx_term_family
+{
+  int32_t n, n_direct, n_inverted, direct_anchored, inverted_anchored, direct_median, inverted_median, verdict;
+  int64_t direct_matches, direct_columns, inverted_matches, inverted_columns;
+} ramx_term_family;                                                                      /* 64 bytes */
+int ramx_term_summary(const ramx_term *records, int32_t n, const ramx_term_params *params, ramx_term_family *out);
+
+/* Seam 1, called after both extension calls: ramx_tsd_sites of the cores and ramx_dev_term on the session's device.  out holds
+ * two records per core in list order.  The library rule is that of ramx_tsd_flat / _alignment / _batch; in a batch a family's
+ * records come after those of the families before it, and a position outside a family's own library is class 4. */
+int ramx_term_flat(const ramx_flat_cores *cores, const int8_t *sequence, uint64_t seq_len, const ramx_term_params *params, ramx_term *out);
+int ramx_term_alignment(struct coreAlignment *coreAlign, struct sequenceLibrary *seqLib, const ramx_term_params *params, ramx_term *out);
+int ramx_term_batch(const ramx_family *families, int32_t n_families, const ramx_term_params *params, ramx_term *out);
+
 /* multi-GPU: flanks are sharded over ranks; each column's 4 candidate sums are all-reduced
  * (4 x int64, RCCL over xGMI).  unique_id is the 128-byte ncclUniqueId made by rank 0
  * (ramx_comm_unique_id) and handed to the other ranks by the launcher (e.g. torch.distributed). */

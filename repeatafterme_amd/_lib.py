@@ -28,6 +28,7 @@ EXPORTS = [
     "ramx_link_components", "ramx_dev_subfamilies", "ramx_dev_subfam_masks", "ramx_dev_subfam_ms", "ramx_set_subfam_sink",
     "ramx_dev_tsd", "ramx_tsd_sites", "ramx_tsd_summary", "ramx_termini", "ramx_tsd_flat", "ramx_tsd_alignment", "ramx_tsd_batch",
     "ramx_dev_period", "ramx_period_sequence", "ramx_period_segments", "ramx_period_summary", "ramx_period_flat", "ramx_period_alignment", "ramx_period_batch",
+    "ramx_dev_term", "ramx_term_pair", "ramx_term_summary", "ramx_term_flat", "ramx_term_alignment", "ramx_term_batch",
 ]
 
 
@@ -157,6 +158,16 @@ class PeriodParams(C.Structure):    # ramx_period_params
 class PeriodHist(C.Structure):      # ramx_period_hist
     _fields_ = [(k, C.c_int32) for k in ("n", "n_tract", "n_mono", "n_simple", "n_tandem", "at_lo", "at_hi", "mode", "mode_count")] + \
                [("reserved", C.c_int32 * 3)]
+
+
+class TermParams(C.Structure):      # ramx_term_params
+    _fields_ = [(k, C.c_int32) for k in ("tmax", "match", "mismatch", "gap", "min_score", "slack")] + [("reserved", C.c_int32 * 2)]
+
+
+class TermFamily(C.Structure):      # ramx_term_family
+    _fields_ = [(k, C.c_int32) for k in ("n", "n_direct", "n_inverted", "direct_anchored", "inverted_anchored", "direct_median",
+                                         "inverted_median", "verdict")] + \
+               [(k, C.c_int64) for k in ("direct_matches", "direct_columns", "inverted_matches", "inverted_columns")]
 
 
 def build(force: bool = False) -> None:
@@ -305,6 +316,18 @@ def lib() -> C.CDLL:
         L.ramx_period_alignment.restype = C.c_int
         L.ramx_period_batch.argtypes = [C.POINTER(Family), C.c_int32, C.c_int32, C.POINTER(PeriodParams), C.c_void_p]
         L.ramx_period_batch.restype = C.c_int
+        L.ramx_dev_term.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(TermParams), C.c_void_p, C.POINTER(C.c_double)]
+        L.ramx_dev_term.restype = C.c_int
+        L.ramx_term_pair.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(TermParams), C.c_void_p]
+        L.ramx_term_pair.restype = C.c_int
+        L.ramx_term_summary.argtypes = [C.c_void_p, C.c_int32, C.POINTER(TermParams), C.POINTER(TermFamily)]
+        L.ramx_term_summary.restype = C.c_int
+        L.ramx_term_flat.argtypes = [C.POINTER(FlatCores), C.c_void_p, C.c_uint64, C.POINTER(TermParams), C.c_void_p]
+        L.ramx_term_flat.restype = C.c_int
+        L.ramx_term_alignment.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(TermParams), C.c_void_p]
+        L.ramx_term_alignment.restype = C.c_int
+        L.ramx_term_batch.argtypes = [C.POINTER(Family), C.c_int32, C.POINTER(TermParams), C.c_void_p]
+        L.ramx_term_batch.restype = C.c_int
         if hasattr(L, "ramx_cli_main"):
             L.ramx_cli_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
         _lib = L

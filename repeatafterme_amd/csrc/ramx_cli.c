@@ -2,7 +2,7 @@
  * ramx_cli.c -- the RAMExtend command line (reference ram_extend.c:123-826 main/usage/
  * print_parameters, cmd_line_opts.c).  Same argv semantics (prefix matching, per-matrix
  * defaults), same stdout / -cons / -outtsv / -outfa bytes; the two extend_alignment calls go to
- * the device path (ramx_extend_alignment).  The analysis outputs (-outprofile ... -outperiod) are ramx_cli_outputs.c; the two
+ * the device path (ramx_extend_alignment).  The analysis outputs (-outprofile ... -outterm) are ramx_cli_outputs.c; the two
  * drivers here reach them through outputs_begin / outputs_family_done / outputs_post / outputs_end.
  */
 #include <fcntl.h>
@@ -107,6 +107,15 @@ static void usage(void)
     "     -periodmm <num>       # ... what a disagreeing pair costs, 1..15 (3),\n"
     "     -periodmin <num>      # ... the lowest score reported (16),\n"
     "     -periodwhole          # ... also for the whole extended copy.\n"
+    "     -outterm <file>       # Save the terminal repeats of every extended copy ( its first bases repeated at its\n"
+    "                           #   end: directly, LTR, or as their reverse complement, TIR ) and the family's\n"
+    "                           #   verdict to a TSV file.\n"
+    "     -termmax <num>        # ... the longest window compared at either end, 1..1024 (512),\n"
+    "     -termmatch <num>      # ... what an agreeing pair scores, 1..15 (2),\n"
+    "     -termmismatch <num>   # ... what a disagreeing pair costs, 1..15 (3),\n"
+    "     -termgap <num>        # ... what a base left out costs, 1..31 (5),\n"
+    "     -termmin <num>        # ... the lowest score reported (40),\n"
+    "     -termslack <num>      # ... a repeat is anchored within this many bases of the termini, 0..15 (3).\n"
     "     -version              # Print out one-line version information\n"
     "     -v[v[v[v]]]           # How verbose do you want it to be?  -vvvv is super-verbose.\n"
     "\n"
@@ -421,11 +430,12 @@ static void write_results(const struct cli_opts *o, struct family_outputs *fo, s
 /*
  * -batch <list>: many families in one process and ONE launch per direction (no counterpart in the reference, whose
  * wrapper util/extend-stk.pl:242-371 starts one RAMExtend per family).  Every non-empty, non-# line of <list> holds up to
- * fifteen tab-separated fields, the first two required, "-" or nothing for a file that is not wanted:
+ * sixteen tab-separated fields, the first two required, "-" or nothing for a file that is not wanted:
  *      1 ranges.tsv      2 log             3 -cons           4 -outtsv         5 -outfa
  *      6 -outprofile     7 -outaln         8 -outpileup      9 -outrefined    10 -outcopies
  *     11 -outlinkage    12 -outsubfam     13 -outtsd        14 -outcpg        15 -outperiod
- * (fields 6 to 15 are the batch_field column of k_outputs, ramx_cli_outputs.c; -outdinuc has none).  All other options
+ *     16 -outterm
+ * (fields 6 to 16 are the batch_field column of k_outputs, ramx_cli_outputs.c; -outdinuc has none).  All other options
  * (-twobit, -L, -bandwidth, -matrix ...) are shared.  For every family the log file receives exactly what a stand-alone run
  * prints on stdout, and every file is what its flag gives.
  */
@@ -526,7 +536,16 @@ static int batch_period(void *ctx, int part, const ramx_period_params *pp, ramx_
   return rc < 0 ? -1 : 0;
 }
 
-static const struct outputs_post_fns k_batch_compute = { batch_tsd, batch_period };
+static int batch_term(void *ctx, const ramx_term_params *tp, ramx_term *rec)
+{
+  const struct batch_ctx *b = (const struct batch_ctx *)ctx;
+  batch_flatten(b);
+  const int rc = ramx_term_batch(b->fam, (int32_t)b->F, tp, rec);
+  batch_free_flat(b);
+  return rc < 0 ? -1 : 0;
+}
+
+static const struct outputs_post_fns k_batch_compute = { batch_tsd, batch_period, batch_term };
 
 /* ... a single family runs on its own, packed, library */
 struct single_ctx { struct coreAlignment *cores; struct sequenceLibrary *lib; int N; };
@@ -546,7 +565,13 @@ static int single_period(void *ctx, int part, const ramx_period_params *pp, ramx
   return ramx_period_alignment(c->cores, c->lib, part, pp, rec) != RAMX_OK ? -1 : 0;
 }
 
-static const struct outputs_post_fns k_single_compute = { single_tsd, single_period };
+static int single_term(void *ctx, const ramx_term_params *tp, ramx_term *rec)
+{
+  const struct single_ctx *c = (const struct single_ctx *)ctx;
+  return ramx_term_alignment(c->cores, c->lib, tp, rec) != RAMX_OK ? -1 : 0;
+}
+
+static const struct outputs_post_fns k_single_compute = { single_tsd, single_period, single_term };
 
 static int run_batch(struct cli_opts *o, time_t t_start)
 {
@@ -713,6 +738,14 @@ int ramx_cli_main(int argc, char **argv)
   o.period.reserved = 0;
   o.periodwhole = opt_bool(argc, argv, "-periodwhole");
   if (ramx_period_check_params(&o.period) != RAMX_OK) { fprintf(stderr, "RAMExtend(ramx): %s\n", ramx_last_error()); exit(1); }
+  if (!opt_int(argc, argv, "-termmax", &o.term.tmax)) o.term.tmax = 512;
+  if (!opt_int(argc, argv, "-termmatch", &o.term.match)) o.term.match = 2;
+  if (!opt_int(argc, argv, "-termmismatch", &o.term.mismatch)) o.term.mismatch = 3;
+  if (!opt_int(argc, argv, "-termgap", &o.term.gap)) o.term.gap = 5;
+  if (!opt_int(argc, argv, "-termmin", &o.term.min_score)) o.term.min_score = 40;
+  if (!opt_int(argc, argv, "-termslack", &o.term.slack)) o.term.slack = 3;
+  o.term.reserved[0] = o.term.reserved[1] = 0;
+  if (ramx_term_check_params(&o.term) != RAMX_OK) { fprintf(stderr, "RAMExtend(ramx): %s\n", ramx_last_error()); exit(1); }
   if (!opt_int(argc, argv, "-refine", &o.refine)) o.refine = DEF_REFINE;
   if (o.refine < 1) { fprintf(stderr, "RAMExtend(ramx): -refine takes the largest number of replays, at least 1\n"); exit(1); }
   if (!opt_int(argc, argv, "-L", &o.L)) o.L = 10000;

@@ -630,7 +630,79 @@ static void period_write(FILE *fp, const struct family_outputs *fo, const ramx_p
   }
 }
 
-/* the two post-passes: after both directions of every family, one compute call for all of them (fns), then the files */
+/*
+ * -outterm <file>: the terminal repeats of the extended copies (include/ramx.h, ramx_term) as a TSV.  "#term" carries the
+ * parameters, "#family" what the family's records say together (the verdict spelled none, LTR or TIR), and one "#consensus"
+ * line per orientation the record of the extended consensus: its outermost min(tmax, left rows, right rows) kept columns at
+ * either end (ramx_term_pair).  Then two lines per core in list order, direct and inverted: named and placed as -outtsv places
+ * the copy, T, the record, both aligned stretches in the coordinates of start and end (0 without a repeat), matches / columns to
+ * three decimals, and whether the record is anchored.  Like -outtsd this is no sink: it is computed when both directions are done.
+ */
+static const char *const k_term_orient[2] = { "direct", "inverted" };
+static const char *const k_term_verdict[3] = { "none", "LTR", "TIR" };
+
+static int term_anchored(const ramx_term *t, int w, int slack)
+{
+  if (t->score <= 0 || t->a_start > slack) return 0;
+  return w == 0 ? t->b_end >= t->T - 1 - slack : t->b_start <= slack;
+}
+
+/* rec: two records per core of the family */
+static void term_write(FILE *fp, const struct family_outputs *fo, const ramx_term_params *tp, const ramx_term *rec)
+{
+  const int L = fo->o->L, l = 1, nl = fo->leftbp > 0 ? fo->leftbp : 0, nr = fo->rightbp > 0 ? fo->rightbp : 0, n = fo->n_cores;
+  const char *master = fo->master;
+  int w = tp->tmax < nl ? tp->tmax : nl;
+  if (nr < w) w = nr;
+  int8_t *win = (int8_t *)malloc(3 * (size_t)(w > 0 ? w : 1)), *a = win, *b = win + w, *c = win + 2 * w;
+  for (int j = 0; j < w; j++)
+  {
+    a[j] = (int8_t)master[(size_t)L - nl + j];                            /* the left rows run outward from the core */
+    b[j] = (int8_t)master[(size_t)L + l + nr - w + j];
+    const int8_t x = (int8_t)master[(size_t)L + l + nr - 1 - j];
+    c[j] = (int8_t)(x >= 0 && x <= 3 ? 3 - x : x);
+  }
+  ramx_term_family fam;
+  ramx_term cr[2];
+  if (ramx_term_summary(rec, n, tp, &fam) != RAMX_OK || ramx_term_pair(a, w, b, w, tp, &cr[0]) != RAMX_OK ||
+      ramx_term_pair(a, w, c, w, tp, &cr[1]) != RAMX_OK)
+  { fprintf(stderr, "RAMExtend(ramx): terminal repeats: %s\n", ramx_last_error()); exit(1); }
+  free(win);
+  fprintf(fp, "#term\ttmax=%d\tmatch=%d\tmismatch=%d\tgap=%d\tmin_score=%d\tslack=%d\n", tp->tmax, tp->match, tp->mismatch, tp->gap,
+          tp->min_score, tp->slack);
+  fprintf(fp, "#family\tn=%d\tn_direct=%d\tn_inverted=%d\tdirect_anchored=%d\tinverted_anchored=%d\tdirect_median=%d\tinverted_median=%d\t"
+          "direct_matches=%lld\tdirect_columns=%lld\tinverted_matches=%lld\tinverted_columns=%lld\tverdict=%s\n", fam.n, fam.n_direct,
+          fam.n_inverted, fam.direct_anchored, fam.inverted_anchored, fam.direct_median, fam.inverted_median, (long long)fam.direct_matches,
+          (long long)fam.direct_columns, (long long)fam.inverted_matches, (long long)fam.inverted_columns, k_term_verdict[fam.verdict]);
+  for (int o = 0; o < 2; o++)
+    fprintf(fp, "#consensus\torientation=%s\tT=%d\tscore=%d\ta_start=%d\ta_end=%d\tb_start=%d\tb_end=%d\tmatches=%d\tcolumns=%d\n",
+            k_term_orient[o], cr[o].T, cr[o].score, cr[o].a_start, cr[o].a_end, cr[o].b_start, cr[o].b_end, cr[o].matches, cr[o].columns);
+  fputs("core\tseqid\tstart\tend\tstrand\torientation\tT\tscore\ta_start\ta_end\tb_start\tb_end\tfive_start\tfive_end\tthree_start\tthree_end\t"
+        "matches\tcolumns\tidentity\tanchored\n", fp);
+  for (int x = 0; x < n; x++)
+  {
+    const struct core_view *v = &fo->cores[x];
+    const int64_t shift = (int64_t)v->off - (int64_t)v->lo + 1;          /* library position -> what -outtsv prints */
+    for (int o = 0; o < 2; o++)
+    {
+      const ramx_term *t = &rec[2 * (size_t)x + o];
+      int64_t f_lo = 0, f_hi = 0, t_lo = 0, t_hi = 0;
+      if (t->score > 0)
+      {
+        f_lo = v->e_lo + t->a_start + shift; f_hi = v->e_lo + t->a_end + shift;
+        /* the direct partner is read forward from hi + 1 - T, the inverted one backward from hi */
+        if (o == 0) { t_lo = v->e_hi + 1 - t->T + t->b_start + shift; t_hi = v->e_hi + 1 - t->T + t->b_end + shift; }
+        else { t_lo = v->e_hi - t->b_end + shift; t_hi = v->e_hi - t->b_start + shift; }
+      }
+      fprintf(fp, "%d\t%s\t%ld\t%ld\t%c\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%ld\t%ld\t%ld\t%ld\t%d\t%d\t%.3f\t%d\n", x, v->ident,
+              (long)(v->e_lo + shift), (long)(v->e_hi + shift), v->orient, k_term_orient[o], t->T, t->score, t->a_start, t->a_end,
+              t->b_start, t->b_end, (long)f_lo, (long)f_hi, (long)t_lo, (long)t_hi, t->matches, t->columns,
+              t->columns > 0 ? (double)t->matches / (double)t->columns : 0.0, term_anchored(t, o, tp->slack));
+    }
+  }
+}
+
+/* the post-passes: after both directions of every family, one compute call for all of them (fns), then the files */
 static void tsd_post(const struct cli_opts *o, struct family_outputs *fams, int F, size_t total, const struct outputs_post_fns *fns, void *ctx)
 {
   ramx_tsd *rec = (ramx_tsd *)calloc(total ? total : 1, sizeof(ramx_tsd));
@@ -667,6 +739,17 @@ static void period_post(const struct cli_opts *o, struct family_outputs *fams, i
   for (int w = 0; w < 3; w++) { free(rec[w]); free(segs[w]); }
 }
 
+static void term_post(const struct cli_opts *o, struct family_outputs *fams, int F, size_t total, const struct outputs_post_fns *fns, void *ctx)
+{
+  ramx_term *rec = (ramx_term *)calloc(total ? 2 * total : 1, sizeof(ramx_term));
+  if (fns->term(ctx, &o->term, rec) < 0) { fprintf(stderr, "RAMExtend(ramx): terminal repeats failed: %s\n", ramx_last_error()); exit(1); }
+  size_t at = 0;
+  FILE *fp;
+  for (int i = 0; i < F; at += (size_t)fams[i].n_cores, i++)
+    if ((fp = row_open(&fams[i], OUT_TERM, "w")) != NULL) { term_write(fp, &fams[i], &o->term, rec + 2 * at); fclose(fp); }
+  free(rec);
+}
+
 /* ------------------------------------------------------------------ the table: one row per output file */
 #define REFUSE(what) "RAMExtend(ramx): with -batch every family's " what "\n"
 #define REFUSE_PILEUP REFUSE("pileup file is the eighth field of its line in the list and its refined consensus the ninth")
@@ -684,6 +767,7 @@ const struct output_row k_outputs[N_OUTPUTS] = {
   [OUT_SUBFAM]  = { "-outsubfam",  12, "subfamily",               REFUSE("subfamily file is the twelfth field of its line in the list"), .write = subfam_write },
   [OUT_TSD]     = { "-outtsd",     13, "target-site duplication", REFUSE("target-site duplication file is the thirteenth field of its line in the list"), .post = tsd_post },
   [OUT_PERIOD]  = { "-outperiod",  15, "periodicity",             REFUSE("periodicity file is the fifteenth field of its line in the list"), .post = period_post },
+  [OUT_TERM]    = { "-outterm",    16, "terminal repeat",         REFUSE("terminal repeat file is the sixteenth field of its line in the list"), .post = term_post },
 };
 
 void outputs_refuse_flags(const struct cli_opts *o)

@@ -10,9 +10,10 @@
 enum
 {
   OUT_PROFILE, OUT_ALN, OUT_PILEUP, OUT_REFINED, OUT_COPIES, OUT_CPG, OUT_DINUC, OUT_LINKAGE, OUT_SUBFAM, OUT_TSD, OUT_PERIOD,
+  OUT_TERM,
   N_OUTPUTS
 };
-#define BATCH_FIELDS 15          /* of a -batch line: ranges, log, -cons, -outtsv, -outfa and the rows' batch_field */
+#define BATCH_FIELDS 16          /* of a -batch line: ranges, log, -cons, -outtsv, -outfa and the rows' batch_field */
 
 /* the defaults of the options the sinks take: what the command line starts from and what a sink is reset to */
 enum { DEF_REFINE = 10, DEF_CPGSCORE = 0, DEF_LINKCOUNT = 4, DEF_LINKFRAC = 100, DEF_LINKSCORE = 3, DEF_SUBFAMK = 4, DEF_SUBFAMMIN = 4, DEF_SUBFAMITER = 8 };
@@ -25,6 +26,7 @@ struct cli_opts
   ramx_tsd_params tsd;
   ramx_period_params period;
   int periodwhole;
+  ramx_term_params term;
   int refine, cpgscore, linkcount, linkfrac, linkscore, subfamk, subfammin, subfamiter;
   int flanking, L, bandwidth, maxn, when_to_stop, num_threads, verbose;
   int gap_ext, gap_open, match, mismatch, cappenalty, minimprovement, is_rs;
@@ -48,13 +50,15 @@ void core_fa_range(const struct core_view *v, int flanking, uint64_t *from, uint
 /* the record id -outfa gives that stretch: ident:from-to_orient */
 void core_fa_id(char *buf, size_t n, const struct core_view *v, int flanking);
 
-/* -outtsd and -outperiod are computed after both directions, on the library they left on the device.  All of it is shared but
- * the compute entries: tsd fills rec with the records of every core of every family, in order; period does so for one part
- * (0 left, 1 right, 2 whole) and gives the cores' segments of that part.  Both return < 0 on failure. */
+/* -outtsd, -outperiod and -outterm are computed after both directions, on the library they left on the device.  All of it is
+ * shared but the compute entries: tsd fills rec with the records of every core of every family, in order; period does so for
+ * one part (0 left, 1 right, 2 whole) and gives the cores' segments of that part; term fills two records per core, direct and
+ * inverted.  All return < 0 on failure. */
 struct outputs_post_fns
 {
   int (*tsd)(void *ctx, const ramx_tsd_params *tp, ramx_tsd *rec);
   int (*period)(void *ctx, int part, const ramx_period_params *pp, ramx_period *rec, ramx_period_seg *segs);
+  int (*term)(void *ctx, const ramx_term_params *tp, ramx_term *rec);
 };
 
 /* one row per output file */

@@ -59,6 +59,7 @@
 #include "ramx_subfam_api.h"
 #include "ramx_tsd_api.h"
 #include "ramx_period_api.h"
+#include "ramx_term_api.h"
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
@@ -195,6 +196,8 @@ struct ramx_dev
   // ramx_dev_period (allocated on its first call): the segments' streams (bases, validity), their lengths and records
   unsigned long long *d_per_bases; unsigned *d_per_valid; int *d_per_len; ramx_period *d_per_out;
   size_t cap_per_bases, cap_per_valid, cap_per_len, cap_per_out;
+  // ramx_dev_term (allocated on its first call; its streams and window lengths live in the buffers of ramx_dev_period): the records
+  ramx_term *d_term_out; size_t cap_term_out;
 };
 
 extern "C" int ramx_device_count(void)
@@ -292,6 +295,7 @@ extern "C" void ramx_dev_destroy(ramx_dev *d)
   free(d->lk_place); free(d->sf_lay);
   (void)hipFree(d->d_tsd_room); (void)hipFree(d->d_tsd_out);
   (void)hipFree(d->d_per_bases); (void)hipFree(d->d_per_valid); (void)hipFree(d->d_per_len); (void)hipFree(d->d_per_out);
+  (void)hipFree(d->d_term_out);
   if (d->hostbox_mirror) (void)hipFree(d->hostbox_mirror);
   if (d->d_peer) (void)hipFree(d->d_peer);
   for (int i = 0; i < 2; i++) if (d->ev_chk[i]) (void)hipEventDestroy(d->ev_chk[i]);
@@ -2459,6 +2463,117 @@ extern "C" int ramx_dev_period(ramx_dev *d, const ramx_period_seg *segs, int32_t
                                double *kernel_ms)
 {
   return ramx_dev_period_bounded(d, segs, NULL, n_segs, params, out, kernel_ms);
+}
+
+// ------------------------------------------------------------------------------------------
+// terminal repeats: the three windows of every site packed as flanks and squeezed into streams by the period's kernel, then one
+// wave per (site, orientation) (ramx_kernels_term.h)
+// ------------------------------------------------------------------------------------------
+extern "C" int ramx_dev_term(ramx_dev *d, const ramx_tsd_site *sites, int32_t n_sites, const ramx_term_params *params, ramx_term *out,
+                             double *kernel_ms)
+{
+  if (kernel_ms) kernel_ms[0] = kernel_ms[1] = kernel_ms[2] = 0;
+  if (!d || n_sites < 0 || (n_sites && (!sites || !out))) { ramx_set_error("ramx_dev_term: bad argument"); return RAMX_ERR_ARG; }
+  int rc;
+  if ((rc = ramx_term_check_params(params)) != RAMX_OK) return rc;
+  long long Tmax = 0;
+  for (int i = 0; i < n_sites; i++)
+  {
+    if (sites[i].seq_lo < -RAMX_TSD_POS_MAX || sites[i].seq_hi > RAMX_TSD_POS_MAX ||       // (so that no difference below overflows)
+        sites[i].seq_lo > sites[i].lo || sites[i].lo > sites[i].hi + 1 || sites[i].hi > sites[i].seq_hi)
+    { ramx_set_error("ramx_dev_term: site %d: lo %lld hi %lld outside its bounds %lld..%lld, or lo > hi + 1", i, (long long)sites[i].lo,
+                     (long long)sites[i].hi, (long long)sites[i].seq_lo, (long long)sites[i].seq_hi); return RAMX_ERR_ARG; }
+    const long long half = (long long)(sites[i].hi + 1 - sites[i].lo) / 2, T = half < params->tmax ? half : params->tmax;
+    if (T > Tmax) Tmax = T;
+  }
+  if (n_sites == 0) return RAMX_OK;
+  if (n_sites > (1 << 29)) { ramx_set_error("ramx_dev_term: more than 2^29 sites in one call"); return RAMX_ERR_UNSUPPORTED; }
+  // the three windows and streams of one tile of 64 sites, at the length of the call's longest window
+  const int KW = period_window_words((int)Tmax), SW = period_stream_words((int)Tmax) > 0 ? period_stream_words((int)Tmax) : 1;
+  const size_t tile_bytes = (size_t)3 * 64 * ((size_t)KW * sizeof(unsigned) + (size_t)SW * (sizeof(unsigned long long) + sizeof(unsigned)));
+  size_t budget = (size_t)1 << 30;
+  if (const char *e = getenv("RAMX_TERM_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+  if (tile_bytes > budget)
+  {
+    ramx_set_error("ramx_dev_term: the windows and streams of one tile of 64 sites (%lld bases a window: %zu bytes) do not fit RAMX_TERM_BYTES = %zu",
+                   Tmax, tile_bytes, budget);
+    return RAMX_ERR_UNSUPPORTED;
+  }
+  const int tiles = (n_sites + 63) / 64;
+  const int group = (int)(budget / tile_bytes < (size_t)tiles ? budget / tile_bytes : (size_t)tiles);
+  HIPCHK(hipSetDevice(d->ordinal));
+  // the flank and window buffers of the direction are reused, as by the replays
+  if ((rc = pack_settle(d, true)) != RAMX_OK) return rc;
+  const int Gp = group * 64;
+  if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)3 * Gp * sizeof(ramx_flank)))) return rc;
+  if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)KW * 3 * Gp * sizeof(unsigned)))) return rc;
+  if ((rc = ensure(&d->d_bounds, &d->cap_bounds, (size_t)3 * Gp * sizeof(int2)))) return rc;
+  if ((rc = ensure(&d->d_per_bases, &d->cap_per_bases, (size_t)3 * Gp * SW * sizeof(unsigned long long)))) return rc;
+  if ((rc = ensure(&d->d_per_valid, &d->cap_per_valid, (size_t)3 * Gp * SW * sizeof(unsigned)))) return rc;
+  if ((rc = ensure(&d->d_per_len, &d->cap_per_len, (size_t)Gp * sizeof(int)))) return rc;
+  if ((rc = ensure(&d->d_term_out, &d->cap_term_out, (size_t)2 * Gp * sizeof(ramx_term)))) return rc;
+  d->ready = 0;
+  d->planes_ready = 0;
+  hipEvent_t ev[4] = { NULL, NULL, NULL, NULL };
+  if (kernel_ms) for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+  std::vector<ramx_flank> fl((size_t)3 * Gp);
+  std::vector<int> len((size_t)Gp);
+  for (int t0 = 0; t0 < tiles && rc == RAMX_OK; t0 += group)
+  {
+    const int nt = tiles - t0 < group ? tiles - t0 : group, Np = nt * 64, s0 = t0 * 64;
+    const int n = n_sites - s0 < Np ? n_sites - s0 : Np;
+    int Tgroup = 0;
+    // a window of T bases from `start` in direction `step`, t = 0 .. T - 1 cut to the positions inside seq_lo..seq_hi
+    auto window = [](ramx_flank &f, const ramx_tsd_site &s, long long start, int step, int T) {
+      f.start = start; f.step = (int8_t)step;
+      long long a = 0, b = T - 1;
+      if (step > 0) { if (s.seq_lo - start > a) a = s.seq_lo - start; if (s.seq_hi - start < b) b = s.seq_hi - start; }
+      else { if (start - s.seq_hi > a) a = start - s.seq_hi; if (start - s.seq_lo < b) b = start - s.seq_lo; }
+      if (a <= b) { f.t_lo = (int32_t)a; f.t_hi = (int32_t)b; }
+    };
+    for (int i = 0; i < Np; i++)
+    {
+      ramx_flank &fa = fl[(size_t)i], &fb = fl[(size_t)Np + i], &fc = fl[(size_t)2 * Np + i];
+      memset(&fa, 0, sizeof(fa)); memset(&fb, 0, sizeof(fb)); memset(&fc, 0, sizeof(fc));
+      fa.step = fb.step = 1; fc.step = -1; fc.compl_ = 1;
+      fa.t_lo = fb.t_lo = fc.t_lo = 1; len[(size_t)i] = 0;       // (padding, or T == 0: no base)
+      if (i >= n) continue;
+      const ramx_tsd_site &s = sites[s0 + i];
+      const long long half = (long long)(s.hi + 1 - s.lo) / 2;
+      const int T = (int)(half < params->tmax ? half : params->tmax);
+      if (T == 0) continue;
+      window(fa, s, s.lo, 1, T);
+      window(fb, s, s.hi + 1 - T, 1, T);
+      window(fc, s, s.hi, -1, T);
+      len[(size_t)i] = T;
+      if (T > Tgroup) Tgroup = T;
+    }
+    HIPCHK(hipMemcpyAsync(d->d_flanks, fl.data(), (size_t)3 * Np * sizeof(ramx_flank), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(d->d_per_len, len.data(), (size_t)Np * sizeof(int), hipMemcpyHostToDevice, d->stream));
+    if (kernel_ms) HIPCHK(hipEventRecord(ev[0], d->stream));
+    if ((rc = launch_pack(d, 3 * Np, 3 * Np, RAMX_PERIOD_W, 0, KW, d->stream)) != RAMX_OK) break;
+    d->packed_kw = KW;
+    if (kernel_ms) HIPCHK(hipEventRecord(ev[1], d->stream));
+    PeriodArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.win = d->d_bases; pa.bases = d->d_per_bases; pa.valid = d->d_per_valid; pa.len = d->d_per_len;
+    pa.n = 3 * Np; pa.Np = 3 * Np; pa.KW = KW; pa.SW = SW;
+    if ((rc = ramx_period_squeeze_launch(d->stream, pa)) != RAMX_OK) { ramx_set_error("ramx_dev_term: launch failed (%s)", hipGetErrorString(hipGetLastError())); break; }
+    if (kernel_ms) HIPCHK(hipEventRecord(ev[2], d->stream));
+    TermArgs ta;
+    ta.bases = d->d_per_bases; ta.valid = d->d_per_valid; ta.T = d->d_per_len; ta.out = d->d_term_out;
+    ta.n = n; ta.Np = Np; ta.SW = SW;
+    ta.match = params->match; ta.mismatch = params->mismatch; ta.gap = params->gap; ta.min_score = params->min_score;
+    if ((rc = ramx_term_align_launch(d->stream, ta, Tgroup)) != RAMX_OK) { ramx_set_error("ramx_dev_term: launch failed (%s)", hipGetErrorString(hipGetLastError())); break; }
+    if (kernel_ms) HIPCHK(hipEventRecord(ev[3], d->stream));
+    HIPCHK(hipMemcpyAsync(out + (size_t)2 * s0, d->d_term_out, (size_t)2 * n * sizeof(ramx_term), hipMemcpyDeviceToHost, d->stream));
+    // (the next group writes the host and device buffers of this one again)
+    HIPCHK(hipStreamSynchronize(d->stream));
+    if (kernel_ms)
+      for (int k = 0; k < 3; k++) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1])); kernel_ms[k] += ms; }
+  }
+  if (kernel_ms) for (auto &e : ev) (void)hipEventDestroy(e);
+  return rc;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1650,6 +1650,106 @@ int ramx_period_batch(const ramx_family *fam, int32_t F, int32_t which, const ra
   return rc;
 }
 
+/* ---- terminal repeats (include/ramx.h): called after both extension calls, with the sites and the library rule of the TSDs ---- */
+
+int ramx_term_flat(const ramx_flat_cores *cores, const int8_t *sequence, uint64_t seq_len, const ramx_term_params *params, ramx_term *out)
+{
+  int rc;
+  if ((rc = ramx_term_check_params(params)) != RAMX_OK) return rc;
+  if (!cores || cores->n < 0 || (cores->n > 0 && (!sequence || !out))) { ramx_set_error("ramx_term_flat: bad argument"); return RAMX_ERR_ARG; }
+  if (cores->n == 0) return RAMX_OK;
+  ramx_dev *d = ramx_default_device();
+  if (!d) return RAMX_ERR_NO_DEVICE;
+  ramx_tsd_site *sites = (ramx_tsd_site *)malloc(sizeof(ramx_tsd_site) * (size_t)cores->n);
+  ramx_tsd_sites(cores, sites);
+  if ((rc = library_resident(d, sequence, seq_len)) == RAMX_OK) rc = ramx_dev_term(d, sites, cores->n, params, out, NULL);
+  free(sites);
+  return rc;
+}
+
+int ramx_term_alignment(struct coreAlignment *coreAlign, struct sequenceLibrary *seqLib, const ramx_term_params *params, ramx_term *out)
+{
+  int rc;
+  if ((rc = ramx_term_check_params(params)) != RAMX_OK) return rc;
+  if (!seqLib) { ramx_set_error("ramx_term_alignment: bad argument"); return RAMX_ERR_ARG; }
+  int n = 0;
+  for (struct coreAlignment *cc = coreAlign; cc != NULL; cc = cc->next) n++;
+  if (n == 0) return RAMX_OK;
+  if (!out) { ramx_set_error("ramx_term_alignment: bad argument"); return RAMX_ERR_ARG; }
+  ramx_dev *d = ramx_default_device();
+  if (!d) return RAMX_ERR_NO_DEVICE;
+  ramx_tsd_site *sites = (ramx_tsd_site *)malloc(sizeof(ramx_tsd_site) * (size_t)n);
+  int k = 0;
+  for (struct coreAlignment *cc = coreAlign; cc != NULL; cc = cc->next, k++)
+  {
+    /* ramx_tsd_sites on the list's own fields */
+    const int64_t lp = (int64_t)cc->leftSeqPos, rp = (int64_t)cc->rightSeqPos;
+    sites[k].lo = cc->orient ? rp - cc->rightExtensionLen : lp - cc->leftExtensionLen;
+    sites[k].hi = cc->orient ? lp + cc->leftExtensionLen : rp + cc->rightExtensionLen;
+    sites[k].seq_lo = (int64_t)cc->lowerSeqBound;
+    sites[k].seq_hi = (int64_t)cc->upperSeqBound;
+  }
+  if (seqLib->sequence == NULL)
+  {
+    /* loaded packed: the twin goes to the device unless it is the library there already */
+    const ramx_packed_library *packed = ramx_packed_of(seqLib);
+    if (!packed) { ramx_set_error("ramx_term_alignment: the sequence library holds no bases (sequence == NULL and no packed twin)"); rc = RAMX_ERR_ARG; }
+    else if (g_packed_owner != seqLib) rc = ramx_preload_library_packed(seqLib, packed);
+  }
+  else
+    rc = library_resident(d, (const int8_t *)seqLib->sequence, seqLib->length);
+  if (rc == RAMX_OK) rc = ramx_dev_term(d, sites, n, params, out, NULL);
+  free(sites);
+  return rc;
+}
+
+int ramx_term_batch(const ramx_family *fam, int32_t F, const ramx_term_params *params, ramx_term *out)
+{
+  int rc;
+  if ((rc = ramx_term_check_params(params)) != RAMX_OK) return rc;
+  if (F < 0 || (F && !fam)) { ramx_set_error("ramx_term_batch: bad argument"); return RAMX_ERR_ARG; }
+  int64_t total = 0;
+  for (int f = 0; f < F; f++)
+  {
+    if (fam[f].cores.n < 0 || (fam[f].cores.n > 0 && !fam[f].sequence)) { ramx_set_error("ramx_term_batch: bad family %d", f); return RAMX_ERR_ARG; }
+    total += fam[f].cores.n;
+  }
+  if (total == 0) return RAMX_OK;
+  if (!out || total > 0x7fffffff) { ramx_set_error("ramx_term_batch: bad argument"); return RAMX_ERR_ARG; }
+  ramx_dev *d = ramx_default_device();
+  if (!d) return RAMX_ERR_NO_DEVICE;
+  /* every family at the offset ramx_extend_batch gives it in the concatenated library */
+  uint64_t *at_of = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)F), *fps = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)F);
+  uint64_t total_len = 0;
+  for (int f = 0; f < F; f++) { at_of[f] = total_len; total_len += fam[f].seq_len; }
+  if (!batch_lib_cached(fam, F, at_of, total_len, fps))
+  {
+    int8_t *lib = (int8_t *)malloc(total_len ? total_len : 1);
+    struct batch_lib_ctx bc = { fam, NULL, at_of, lib, 0 };
+    ramx_parallel_for(F, 8, batch_lib_range, &bc);
+    rc = batch_lib_upload(d, fam, F, lib, total_len, fps);
+    free(lib);
+  }
+  ramx_tsd_site *sites = (ramx_tsd_site *)malloc(sizeof(ramx_tsd_site) * (size_t)total);
+  int64_t at = 0;
+  for (int f = 0; f < F; f++)
+  {
+    ramx_tsd_sites(&fam[f].cores, sites + at);
+    for (int i = 0; i < fam[f].cores.n; i++)
+    {
+      ramx_tsd_site *s = &sites[at + i];
+      /* outside the family's own library is outside the library: its neighbours in the concatenation are never read */
+      if (s->seq_lo < 0) s->seq_lo = 0;
+      if (s->seq_hi > (int64_t)fam[f].seq_len - 1) s->seq_hi = (int64_t)fam[f].seq_len - 1;
+      s->lo += (int64_t)at_of[f]; s->hi += (int64_t)at_of[f]; s->seq_lo += (int64_t)at_of[f]; s->seq_hi += (int64_t)at_of[f];
+    }
+    at += fam[f].cores.n;
+  }
+  if (rc == RAMX_OK) rc = ramx_dev_term(d, sites, (int32_t)total, params, out, NULL);
+  free(sites); free(at_of); free(fps);
+  return rc;
+}
+
 /* bnw_extend.c:87-155 -- kept for link compatibility: the device path never reads it.  The block has the reference's
  * index shape score[2][num_align][2*bandwidth+1][2], so code written against the reference that dereferences it (the
  * VERBOSE >= 12 dump of ram_extend.c:949-959, unit tests) reads zeros instead of faulting -- but every [n] shares ONE

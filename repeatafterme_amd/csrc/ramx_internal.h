@@ -53,6 +53,9 @@ int ramx_period_check_params(const ramx_period_params *pp);
 int ramx_dev_period_bounded(ramx_dev *d, const ramx_period_seg *segs, const ramx_period_seg *bounds, int32_t n_segs,
                             const ramx_period_params *params, ramx_period *out, double *kernel_ms);
 
+/* the checks of ramx_term_params (csrc/ramx_term.c): RAMX_OK, or RAMX_ERR_ARG with the error text set */
+int ramx_term_check_params(const ramx_term_params *tp);
+
 /* host threads for a loop over `items` (at most 16, at most one per min_items_per_thread; RAMX_HOST_THREADS overrides) */
 int ramx_host_threads(long items, long min_items_per_thread);
 /* fn formats items [lo, hi) into outs[0..n_outs) (memory streams; an entry is NULL where the real stream is); the chunks'

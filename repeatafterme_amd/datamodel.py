@@ -288,6 +288,39 @@ class PeriodSummary:
     mode_count: int
 
 
+# terminal repeats: C-ABI ramx_term (32 bytes), ramx_term_params, ramx_term_family; the sites are TSD_SITE_DTYPE
+TERM_DTYPE = np.dtype([(k, np.int32) for k in ("score", "a_start", "a_end", "b_start", "b_end", "matches", "columns", "T")])
+assert TERM_DTYPE.itemsize == 32
+TERM_VERDICTS = ("none", "LTR", "TIR")
+
+
+@dataclass
+class TermParams:
+    tmax: int = 512
+    match: int = 2
+    mismatch: int = 3
+    gap: int = 5
+    min_score: int = 40
+    slack: int = 3
+
+
+@dataclass
+class TermSummary:
+    """What a family's records say together (C-ABI ramx_term_family)."""
+    n: int
+    n_direct: int                    # records with a score
+    n_inverted: int
+    direct_anchored: int             # ... that begin at the 5' terminus and end at the 3' terminus
+    inverted_anchored: int           # ... that begin at both termini
+    direct_median: int               # lower median of the 5' lengths of the anchored records
+    inverted_median: int
+    verdict: int                     # 0 none, 1 LTR, 2 TIR (TERM_VERDICTS)
+    direct_matches: int
+    direct_columns: int
+    inverted_matches: int
+    inverted_columns: int
+
+
 FLANK_DTYPE = np.dtype([("start", np.int64), ("t_lo", np.int32), ("t_hi", np.int32), ("step", np.int8), ("compl_", np.int8),
                         ("pad_", np.int8, (6,))])
 assert FLANK_DTYPE.itemsize == 24

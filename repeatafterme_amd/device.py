@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 from .datamodel import (ALN_END_DTYPE, ALN_NONE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, DINUC_DTYPE, LINK_DTYPE, PILEUP_DTYPE, PILEUP_INS, PLANE_DTYPE,
-                        TSD_DTYPE, TSD_SITE_DTYPE, PERIOD_DTYPE, PERIOD_SEG_DTYPE, CoreSet, ExtendParams, PeriodParams, TsdParams)
+                        TSD_DTYPE, TSD_SITE_DTYPE, PERIOD_DTYPE, PERIOD_SEG_DTYPE, TERM_DTYPE, CoreSet, ExtendParams, PeriodParams, TermParams, TsdParams)
 from .extend import RunInfo, _info, _params
 
 
@@ -268,6 +268,18 @@ class Device:
         ms = (C.c_double * 3)()
         _lib.check(self._L.ramx_dev_period(self._h, s.ctypes.data if len(s) else None, len(s), C.byref(cp),
                                            out.ctypes.data if len(s) else None, ms), "ramx_dev_period")
+        return (out, [ms[0], ms[1], ms[2]]) if timing else out
+
+    def term(self, sites, tp: Optional[TermParams] = None, timing: bool = False):
+        """The terminal repeats of every site on the library this device holds (C-ABI ramx_dev_term): -> TERM_DTYPE [n_sites][2],
+        direct and inverted; timing=True: (records, [pack ms, squeeze ms, align ms])."""
+        s = np.ascontiguousarray(sites, TSD_SITE_DTYPE).reshape(-1)
+        tp = TermParams() if tp is None else tp
+        cp = _lib.TermParams(int(tp.tmax), int(tp.match), int(tp.mismatch), int(tp.gap), int(tp.min_score), int(tp.slack))
+        out = np.zeros((len(s), 2), TERM_DTYPE)
+        ms = (C.c_double * 3)()
+        _lib.check(self._L.ramx_dev_term(self._h, s.ctypes.data if len(s) else None, len(s), C.byref(cp),
+                                         out.ctypes.data if len(s) else None, ms), "ramx_dev_term")
         return (out, [ms[0], ms[1], ms[2]]) if timing else out
 
     def begin_direction(self, flanks, p: ExtendParams):

@@ -15,7 +15,7 @@ import numpy as np
 from . import _lib
 from .datamodel import (ALN_END_DTYPE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, DINUC_DTYPE, FLANK_DTYPE, PILEUP_DTYPE, PLANE_DTYPE, Alignment, Copies, SubfamGroup, Subfamilies,
                         CoreSet, CpgRefinement, ExtendParams, Linkage, Profile, Refinement, TSD_DTYPE, TSD_SITE_DTYPE, TsdParams, TsdSummary,
-                        PERIOD_DTYPE, PERIOD_SEG_DTYPE, PeriodParams, PeriodSummary)
+                        PERIOD_DTYPE, PERIOD_SEG_DTYPE, PeriodParams, PeriodSummary, TERM_DTYPE, TermParams, TermSummary)
 
 
 @dataclass
@@ -565,5 +565,73 @@ def period_batch(families, which: int, pp: PeriodParams = None):
     out = np.zeros(total, PERIOD_DTYPE)
     cp = _period_params(pp)
     _lib.check(_lib.lib().ramx_period_batch(arr, n, int(which), C.byref(cp), out.ctypes.data if total else None), "ramx_period_batch")
+    ends = np.cumsum([0] + [f[0].n for f in families])
+    return [out[ends[i]:ends[i + 1]].copy() for i in range(n)]
+
+
+# ---- terminal repeats (include/ramx.h, ramx_term): after both extension calls, on the sites of tsd_sites ----
+
+def _term_params(tp):
+    tp = TermParams() if tp is None else tp
+    return _lib.TermParams(int(tp.tmax), int(tp.match), int(tp.mismatch), int(tp.gap), int(tp.min_score), int(tp.slack))
+
+
+def term_pair(a, b, tp: TermParams = None) -> np.ndarray:
+    """The record of two arrays of library codes, b as given (C-ABI ramx_term_pair, host C): -> one TERM_DTYPE record."""
+    a = np.ascontiguousarray(a, np.int8).reshape(-1)
+    b = np.ascontiguousarray(b, np.int8).reshape(-1)
+    out = np.zeros(1, TERM_DTYPE)
+    cp = _term_params(tp)
+    _lib.check(_lib.lib().ramx_term_pair(a.ctypes.data if len(a) else None, len(a), b.ctypes.data if len(b) else None, len(b), C.byref(cp),
+                                         out.ctypes.data), "ramx_term_pair")
+    return out[0]
+
+
+def term_summary(records, tp: TermParams = None) -> TermSummary:
+    """What a family's records [n][2] say together (C-ABI ramx_term_summary, host C)."""
+    r = np.ascontiguousarray(records, TERM_DTYPE).reshape(-1)
+    assert len(r) % 2 == 0
+    h = _lib.TermFamily()
+    cp = _term_params(tp)
+    _lib.check(_lib.lib().ramx_term_summary(r.ctypes.data if len(r) else None, len(r) // 2, C.byref(cp), C.byref(h)), "ramx_term_summary")
+    return TermSummary(*[int(getattr(h, k)) for k, _ in _lib.TermFamily._fields_])
+
+
+def term_flat(cores: CoreSet, sequence: np.ndarray, tp: TermParams = None) -> np.ndarray:
+    """The terminal repeats of every core's element after both extension calls, on the library they left on the session's device
+    (C-ABI ramx_term_flat): -> TERM_DTYPE [cores.n][2], direct and inverted."""
+    assert sequence.dtype == np.int8 and sequence.flags.c_contiguous
+    out = np.zeros((cores.n, 2), TERM_DTYPE)
+    fc = _flat_cores(cores)
+    cp = _term_params(tp)
+    _lib.check(_lib.lib().ramx_term_flat(C.byref(fc), sequence.ctypes.data, len(sequence), C.byref(cp), out.ctypes.data if cores.n else None),
+               "ramx_term_flat")
+    return out
+
+
+def term_alignment(core_list, seq_lib, n: int, tp: TermParams = None) -> np.ndarray:
+    """The same on the reference's data model, as tsd_alignment takes it (C-ABI ramx_term_alignment)."""
+    out = np.zeros((n, 2), TERM_DTYPE)
+    cp = _term_params(tp)
+    _lib.check(_lib.lib().ramx_term_alignment(C.cast(core_list, C.c_void_p), C.cast(seq_lib, C.c_void_p), C.byref(cp),
+                                              out.ctypes.data if n else None), "ramx_term_alignment")
+    return out
+
+
+def term_batch(families, tp: TermParams = None):
+    """The same for the families of an extend_batch, in one call on the concatenated library it leaves on the device (C-ABI
+    ramx_term_batch).  `families` as extend_batch takes them; -> one TERM_DTYPE [n][2] array per family."""
+    n = len(families)
+    arr = (_lib.Family * max(n, 1))()
+    for i, (cores, sequence, master) in enumerate(families):
+        assert sequence.dtype == np.int8 and sequence.flags.c_contiguous
+        arr[i].cores = _flat_cores(cores)
+        arr[i].sequence = sequence.ctypes.data
+        arr[i].seq_len = len(sequence)
+        arr[i].master = master.ctypes.data if master is not None else None
+    total = sum(f[0].n for f in families)
+    out = np.zeros((total, 2), TERM_DTYPE)
+    cp = _term_params(tp)
+    _lib.check(_lib.lib().ramx_term_batch(arr, n, C.byref(cp), out.ctypes.data if total else None), "ramx_term_batch")
     ends = np.cumsum([0] + [f[0].n for f in families])
     return [out[ends[i]:ends[i + 1]].copy() for i in range(n)]

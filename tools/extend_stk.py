@@ -24,6 +24,8 @@ per direction the family's mean Kimura divergence over the extension beside the 
 <id>-tsd.tsv: with -tsd, the target-site duplication of every extended copy and the family's modal length (RAMExtend -outtsd).
 <id>-period.tsv: with -period, the tandem periodicity of every copy's left and right extension -- did the extension run into a
 simple repeat or a satellite? -- and the family's modal period per part (RAMExtend -outperiod).
+<id>-term.tsv: with -term, the terminal repeats of every extended copy -- its first bases repeated at its end, directly (LTR) or
+as their reverse complement (TIR) -- and the family's verdict (RAMExtend -outterm).
 
 (the re-alignment and Stockholm rewriting that follow in the wrapper belong to RepeatModeler and are out of scope).
 """
@@ -60,6 +62,8 @@ def main(argv=None):
                     "target-site duplication of the extended copies")
     ap.add_argument("-period", action="store_true", help="also write <id>-period.tsv per family (RAMExtend -outperiod) and print the "
                     "modal period of the copies' extensions")
+    ap.add_argument("-term", action="store_true", help="also write <id>-term.tsv per family (RAMExtend -outterm) and print the "
+                    "family's verdict (none, LTR, TIR) and the median lengths of the anchored repeats")
     ap.add_argument("-cpg", action="store_true", help="also write <id>-cpg-cons.fa per family (RAMExtend -outcpg)")
     ap.add_argument("-one_by_one", action="store_true", help="start one RAMExtend per family, as the wrapper does")
     a = ap.parse_args(argv)
@@ -105,7 +109,8 @@ def main(argv=None):
                                        (["-outlinkage", base + "-linkage.tsv"] if a.linkage else []) +
                                        (["-outtsd", base + "-tsd.tsv"] if a.tsd else []) +
                                        (["-outcpg", base + "-cpg-cons.fa"] if a.cpg else []) +
-                                       (["-outperiod", base + "-period.tsv"] if a.period else []),
+                                       (["-outperiod", base + "-period.tsv"] if a.period else []) +
+                                       (["-outterm", base + "-term.tsv"] if a.term else []),
                                        stdout=log, stderr=subprocess.STDOUT).returncode
                 if rc:
                     sys.exit(f"  RAMExtend failed! [{rc}] see {base}-repam.log")
@@ -113,12 +118,12 @@ def main(argv=None):
             lst = os.path.join(a.outdir, f"batch-{matrix}-{minimp}.list")
             with open(lst, "w") as fh:
                 for seed, base in fams:
-                    # fields six to fifteen are optional (the twelfth, the subfamily file, is never asked for here): "-" holds the place of one that is not asked for before one that is
+                    # fields six to sixteen are optional (the twelfth, the subfamily file, is never asked for here): "-" holds the place of one that is not asked for before one that is
                     opt = [base + "-profile.tsv" if a.profile else "-", base + "-aln.a2m" if a.aln else "-",
                            base + "-pileup.tsv" if a.refine > 0 else "-", base + "-refined-cons.fa" if a.refine > 0 else "-",
                            base + "-copies.tsv" if a.copies else "-", base + "-linkage.tsv" if a.linkage else "-", "-",
                            base + "-tsd.tsv" if a.tsd else "-", base + "-cpg-cons.fa" if a.cpg else "-",
-                           base + "-period.tsv" if a.period else "-"]
+                           base + "-period.tsv" if a.period else "-", base + "-term.tsv" if a.term else "-"]
                     while opt and opt[-1] == "-":
                         opt.pop()
                     fh.write("\t".join([base + "-linup.tsv", base + "-repam.log", base + "-ext-cons.fa",
@@ -171,6 +176,12 @@ def main(argv=None):
                         kv = dict(f.split("=") for f in line.rstrip("\n").split("\t")[1:])
                         print(f"  - Tandem periodicity [{kv['part']}]: period {kv['mode']} in {kv['mode_count']} of {kv['n']} copies "
                               f"({kv['n_tract']} with a tract)")
+            if a.term and os.path.exists(base + "-term.tsv"):
+                for line in open(base + "-term.tsv"):                   # the summary line
+                    if line.startswith("#family"):
+                        kv = dict(f.split("=") for f in line.rstrip("\n").split("\t")[1:])
+                        print(f"  - Terminal repeats: {kv['verdict']} (direct: {kv['direct_anchored']} of {kv['n']} copies anchored, median "
+                              f"{kv['direct_median']} bp; inverted: {kv['inverted_anchored']}, median {kv['inverted_median']} bp)")
     return 0
 
 

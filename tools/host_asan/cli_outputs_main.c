@@ -51,7 +51,15 @@ static int give_period(void *ctx, int part, const ramx_period_params *pp, ramx_p
   if (part == 1) { rec[0] = rec[3] = (ramx_period){ 2, 20, 1, 8, 10, 0, { 0, 0 } }; segs[0].lo = segs[3].lo = 50; }
   return 0;
 }
-static const struct outputs_post_fns k_give = { give_tsd, give_period };
+static int give_term(void *ctx, const ramx_term_params *tp, ramx_term *rec)
+{
+  /* the first core of either family carries a direct repeat of six bases at both termini */
+  memset(rec, 0, 12 * sizeof(ramx_term));
+  for (int i = 0; i < 12; i++) rec[i].T = 11;
+  rec[0] = rec[6] = (ramx_term){ 12, 0, 5, 5, 10, 6, 6, 11 };
+  return 0;
+}
+static const struct outputs_post_fns k_give = { give_tsd, give_period, give_term };
 
 int main(void)
 {
@@ -85,6 +93,7 @@ int main(void)
   o.linkscore = DEF_LINKSCORE; o.subfamk = 2; o.subfammin = 1; o.subfamiter = DEF_SUBFAMITER; o.periodwhole = 1;
   o.tsd = (ramx_tsd_params){ 3, 4, 20, 10 };
   o.period = (ramx_period_params){ 1024, 3, 16, 0 };
+  o.term = (ramx_term_params){ 512, 2, 3, 5, 40, 3, { 0, 0 } };
 
   struct family_outputs fams[2];
   memset(fams, 0, sizeof(fams));
