@@ -43,6 +43,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
+#include <memory>
 #include <vector>
 
 #include "ramx_kernels_common.h"
@@ -1790,15 +1791,15 @@ static int replay_upload(ramx_dev *d, const ReplayPlan &pl, int32_t n_families, 
   return RAMX_OK;
 }
 
-// the group of tiles whose `what` (tile_bytes per tile of 64 flanks) fit RAMX_ALIGN_BYTES
-static int replay_group(const char *who, const char *what, int tiles, size_t tile_bytes, int maxrows, int W, int *group)
+// the group of tiles whose `what` (tile_bytes per tile) fit the bytes the environment variable `env` allows (1 GiB unless it
+// is set; read per call)
+static int tile_group(const char *who, const char *env, const char *what, int tiles, size_t tile_bytes, int *group)
 {
   size_t budget = (size_t)1 << 30;
-  if (const char *e = getenv("RAMX_ALIGN_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+  if (const char *e = getenv(env)) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
   if (tile_bytes > budget)
   {
-    ramx_set_error("%s: the %s of one tile of 64 flanks (%d rows, bandwidth %d: %zu bytes) do not fit RAMX_ALIGN_BYTES = %zu",
-                   who, what, maxrows, W, tile_bytes, budget);
+    ramx_set_error("%s: the %s (%zu bytes) do not fit %s = %zu", who, what, tile_bytes, env, budget);
     return RAMX_ERR_UNSUPPORTED;
   }
   *group = (int)(budget / tile_bytes < (size_t)tiles ? budget / tile_bytes : (size_t)tiles);
@@ -1806,10 +1807,12 @@ static int replay_group(const char *who, const char *what, int tiles, size_t til
 }
 
 // group after group on one stream: a group's later stages have read what its earlier ones wrote before the next group's kernels
-// write it again.  body(tile0, nt, mark) launches the nstage stages of one group and calls mark() after each; with kernel_ms
-// the marks are HIP events and stage i's time, summed over the groups, is added to kernel_ms[i].  On return the stream is idle.
+// write it again.  body(tile0, nt, mark) launches the nstage stages of one group and calls mark() before the first and after
+// each; with kernel_ms the marks are HIP events and stage i's time, summed over the groups, is added to kernel_ms[i].  With
+// host_reuse the stream is synchronised after every group, because the next one fills the same host buffers; on return the
+// stream is idle either way.
 template <class Body>
-static int replay_groups(ramx_dev *d, const char *who, int tiles, int group, int nstage, double *kernel_ms, Body body)
+static int tile_groups(ramx_dev *d, const char *who, int tiles, int group, int nstage, double *kernel_ms, bool host_reuse, Body body)
 {
   const int ngroups = (tiles + group - 1) / group;
   std::vector<hipEvent_t> ev(kernel_ms ? (size_t)(nstage + 1) * ngroups : 0, (hipEvent_t)NULL);
@@ -1817,15 +1820,16 @@ static int replay_groups(ramx_dev *d, const char *who, int tiles, int group, int
   for (auto &e : ev) if (he == hipSuccess) he = hipEventCreate(&e);
   size_t marks = 0;
   auto mark = [&]() { if (marks < ev.size() && he == hipSuccess) he = hipEventRecord(ev[marks++], d->stream); };
+  hipError_t se = hipSuccess;
   int rc = RAMX_OK;
-  for (int g = 0; g < ngroups && rc == RAMX_OK && he == hipSuccess; g++)
+  for (int g = 0; g < ngroups && rc == RAMX_OK && he == hipSuccess && se == hipSuccess; g++)
   {
     const int tile0 = g * group;
-    mark();
     rc = body(tile0, tiles - tile0 < group ? tiles - tile0 : group, mark);
+    if (host_reuse && rc == RAMX_OK) se = hipStreamSynchronize(d->stream);
   }
   if (rc != RAMX_OK) ramx_set_error("%s: launch failed (%s)", who, hipGetErrorString(hipGetLastError()));
-  const hipError_t se = hipStreamSynchronize(d->stream);
+  if (!host_reuse || rc != RAMX_OK) se = hipStreamSynchronize(d->stream);
   for (size_t i = 0; i + 1 < ev.size() && rc == RAMX_OK && he == hipSuccess && se == hipSuccess; i++)
   {
     if ((int)(i % (nstage + 1)) == nstage) continue;       // from a group's last mark to the next group's first: no stage
@@ -1984,7 +1988,7 @@ extern "C" int ramx_dev_align(ramx_dev *d, const ramx_flank *flanks, int32_t n_p
   // the budget counts the decision codes only: the columns are whole-set [maxrows][Np] arrays of their own
   const size_t tile_bytes = (size_t)maxrows * ramx_align_dwords(W) * 64 * sizeof(unsigned);
   int group, KW;
-  if ((rc = replay_group("ramx_dev_align", "decision codes", tiles, tile_bytes, maxrows, W, &group)) != RAMX_OK) return rc;
+  if ((rc = tile_group("ramx_dev_align", "RAMX_ALIGN_BYTES", "decision codes of one tile of 64 flanks", tiles, tile_bytes, &group)) != RAMX_OK) return rc;
   KArgs k;
   AlnArgs aa;
   if ((rc = replay_setup(d, flanks, n_padded, n_padded, n_families, p, true, k, &KW)) != RAMX_OK) return rc;
@@ -2001,9 +2005,10 @@ extern "C" int ramx_dev_align(ramx_dev *d, const ramx_flank *flanks, int32_t n_p
   if (col_idx && (rc = ramx_align_launch_preset(d->stream, d->d_al_idx, d->d_al_ins, ncol)) != RAMX_OK) return rc;
   aa.codes = d->d_al_codes; aa.gn = group * 64;
   aa.col_idx = col_idx ? d->d_al_idx : NULL; aa.col_ins = col_idx ? d->d_al_ins : NULL;
-  rc = replay_groups(d, "ramx_dev_align", tiles, group, 2, kernel_ms, [&](int tile0, int nt, auto &mark) {
+  rc = tile_groups(d, "ramx_dev_align", tiles, group, 2, kernel_ms, false, [&](int tile0, int nt, auto &mark) {
     int lrc;
     aa.tile0 = tile0;
+    mark();
     if ((lrc = ramx_align_launch_forward(d->stream, nt, aa)) != RAMX_OK) return lrc;
     mark();
     if ((lrc = ramx_align_launch_walk(d->stream, nt, aa)) != RAMX_OK) return lrc;
@@ -2063,7 +2068,8 @@ static int pileup_replay(ramx_dev *d, const char *who, AlnArgs aa, int KW, const
   // exist for one group at a time
   const size_t code_bytes = (size_t)maxrows * aa.nd * 64 * sizeof(unsigned), col_bytes = (size_t)maxrows * 64 * sizeof(int);
   int group, rc;
-  if ((rc = replay_group(who, "decision codes and columns", tiles, code_bytes + 2 * col_bytes, maxrows, W, &group)) != RAMX_OK) return rc;
+  if ((rc = tile_group(who, "RAMX_ALIGN_BYTES", "decision codes and columns of one tile of 64 flanks", tiles, code_bytes + 2 * col_bytes, &group)) != RAMX_OK)
+    return rc;
   if ((rc = ensure(&d->d_al_codes, &d->cap_al_codes, (size_t)group * code_bytes))) return rc;
   if ((rc = ensure(&d->d_pl_idx, &d->cap_pl_idx, (size_t)group * col_bytes))) return rc;
   if ((rc = ensure(&d->d_pl_ins, &d->cap_pl_ins, (size_t)group * col_bytes))) return rc;
@@ -2102,9 +2108,10 @@ static int pileup_replay(ramx_dev *d, const char *who, AlnArgs aa, int KW, const
   da.L = L; da.Np = aa.k.Np; da.W = W; da.KW = KW; da.gn = gn; da.tile0 = 0; da.slab_rows = maxrows;
   DinucSumArgs ds;
   ds.slab = d->d_dn_slab; ds.fam = d->d_rp_fam; ds.cons = d->d_rp_cons; ds.di = d->d_dn_cols; ds.L = L; ds.slab_rows = maxrows;
-  return replay_groups(d, who, tiles, group, lk || dn ? 4 : 3, kernel_ms, [&](int tile0, int nt, auto &mark) {
+  return tile_groups(d, who, tiles, group, lk || dn ? 4 : 3, kernel_ms, false, [&](int tile0, int nt, auto &mark) {
     int lrc;
     aa.tile0 = pa.tile0 = da.tile0 = tile0;
+    mark();
     // the walk addresses its columns as [r * k.Np + n] with n the flank's index in the whole set: given the group's width for
     // k.Np and the arrays' origin moved back by the group's first flank, it writes the group's own [maxrows][gn] arrays
     AlnArgs aw = aa;
@@ -2287,8 +2294,53 @@ extern "C" int ramx_dev_copy_stats(ramx_dev *d, const ramx_flank *flanks, int32_
 }
 
 // ------------------------------------------------------------------------------------------
-// target-site duplications: the two outside windows of every site packed as flanks, then one lane per site (ramx_kernels_tsd.h)
+// the site-window analyses (target-site duplications, tandem periodicity, terminal repeats): sites or segments become windows
+// clipped to their bounds, the windows are packed as flanks into the direction's own buffers, tile group after tile group, and
+// one or two small kernels run over the packed windows
 // ------------------------------------------------------------------------------------------
+// The window of positions start + step * t, t = t_first .. t_last, as a flank: cut to the t whose position lies inside
+// bound_lo..bound_hi, or the empty window t_lo = 1, t_hi = 0 where there is none (no base is read: the padding lanes of a tile
+// are this one).  This is what keeps a batch's copies from reading a neighbouring family's bases in the concatenated library.
+// Positions and bounds lie within +-RAMX_TSD_POS_MAX (checked before the first call) and |t| < 2^31: no difference overflows.
+static void window_flank(ramx_flank &f, long long start, int step, bool compl_, long long t_first, long long t_last,
+                         long long bound_lo, long long bound_hi)
+{
+  memset(&f, 0, sizeof(f));
+  f.start = start; f.step = (int8_t)step; f.compl_ = compl_;
+  const long long t_in = step > 0 ? bound_lo - start : start - bound_hi, t_out = step > 0 ? bound_hi - start : start - bound_lo;
+  const long long a = t_in > t_first ? t_in : t_first, b = t_out < t_last ? t_out : t_last;
+  if (a > b) { f.t_lo = 1; f.t_hi = 0; } else { f.t_lo = (int32_t)a; f.t_hi = (int32_t)b; }
+}
+
+static const ramx_tsd_site NO_SITE = { 0, -1, 0, -1 };         // the padding of a tile: an empty site in empty bounds
+
+// the sites of ramx_dev_tsd and ramx_dev_term: seq_lo <= lo <= hi + 1, hi <= seq_hi, everything within +-RAMX_TSD_POS_MAX
+static int check_sites(const char *who, const ramx_tsd_site *sites, int32_t n_sites)
+{
+  for (int i = 0; i < n_sites; i++)
+    if (sites[i].seq_lo < -RAMX_TSD_POS_MAX || sites[i].seq_hi > RAMX_TSD_POS_MAX ||
+        sites[i].seq_lo > sites[i].lo || sites[i].lo > sites[i].hi + 1 || sites[i].hi > sites[i].seq_hi)
+    { ramx_set_error("%s: site %d: lo %lld hi %lld outside its bounds %lld..%lld, or lo > hi + 1", who, i, (long long)sites[i].lo,
+                     (long long)sites[i].hi, (long long)sites[i].seq_lo, (long long)sites[i].seq_hi); return RAMX_ERR_ARG; }
+  return RAMX_OK;
+}
+
+// the flank and window buffers of the direction are reused, as by the replays: room for `lanes` windows of KW words
+static int site_windows_setup(ramx_dev *d, size_t lanes, int KW)
+{
+  int rc;
+  HIPCHK(hipSetDevice(d->ordinal));
+  if ((rc = pack_settle(d, true)) != RAMX_OK) return rc;
+  if ((rc = ensure(&d->d_flanks, &d->cap_flanks, lanes * sizeof(ramx_flank)))) return rc;
+  if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)KW * lanes * sizeof(unsigned)))) return rc;
+  if ((rc = ensure(&d->d_bounds, &d->cap_bounds, lanes * sizeof(int2)))) return rc;
+  d->ready = 0;
+  d->planes_ready = 0;
+  d->packed_kw = KW;
+  return RAMX_OK;
+}
+
+// target-site duplications: the two outside windows of every site packed as flanks, then one lane per site (ramx_kernels_tsd.h)
 extern "C" int ramx_dev_tsd(ramx_dev *d, const ramx_tsd_site *sites, int32_t n_sites, const ramx_tsd_params *params, ramx_tsd *out,
                             double *kernel_ms)
 {
@@ -2296,73 +2348,45 @@ extern "C" int ramx_dev_tsd(ramx_dev *d, const ramx_tsd_site *sites, int32_t n_s
   if (!d || n_sites < 0 || (n_sites && (!sites || !out))) { ramx_set_error("ramx_dev_tsd: bad argument"); return RAMX_ERR_ARG; }
   int rc;
   if ((rc = ramx_tsd_check_params(params)) != RAMX_OK) return rc;
-  for (int i = 0; i < n_sites; i++)
-    if (sites[i].seq_lo < -RAMX_TSD_POS_MAX || sites[i].seq_hi > RAMX_TSD_POS_MAX ||       // (so that no difference below overflows)
-        sites[i].seq_lo > sites[i].lo || sites[i].lo > sites[i].hi + 1 || sites[i].hi > sites[i].seq_hi)
-    { ramx_set_error("ramx_dev_tsd: site %d: lo %lld hi %lld outside its bounds %lld..%lld, or lo > hi + 1", i, (long long)sites[i].lo,
-                     (long long)sites[i].hi, (long long)sites[i].seq_lo, (long long)sites[i].seq_hi); return RAMX_ERR_ARG; }
+  if ((rc = check_sites("ramx_dev_tsd", sites, n_sites)) != RAMX_OK) return rc;
   if (n_sites == 0) return RAMX_OK;
   if (n_sites > (1 << 29)) { ramx_set_error("ramx_dev_tsd: more than 2^29 sites in one call"); return RAMX_ERR_UNSUPPORTED; }
-  HIPCHK(hipSetDevice(d->ordinal));
-  // the windows: the left one runs down from lo - 1, the right one up from hi + 1, t = -slack .. kmax + slack - 1 cut by the
-  // site's bounds; the left windows of all (padded) sites first, then the right ones
   const int n = n_sites, Np = (n + 63) & ~63, S = params->slack, t_last = params->kmax + S - 1;
-  std::vector<ramx_flank> fl((size_t)2 * Np);
-  std::vector<int> room((size_t)Np, 0);
-  auto cut = [&](ramx_flank &f, long long lo_t, long long hi_t) {
-    const long long a = lo_t > -S ? lo_t : -S, b = hi_t < t_last ? hi_t : t_last;
-    if (a > b) { f.t_lo = 1; f.t_hi = 0; } else { f.t_lo = (int32_t)a; f.t_hi = (int32_t)b; }
-  };
-  for (int i = 0; i < Np; i++)
-  {
-    ramx_flank &l = fl[(size_t)i], &r = fl[(size_t)Np + i];
-    memset(&l, 0, sizeof(l)); memset(&r, 0, sizeof(r));
-    l.step = -1; r.step = 1; l.t_lo = r.t_lo = 1;             // (padding: no base)
-    if (i >= n) continue;
-    const ramx_tsd_site &s = sites[i];
-    l.start = s.lo - 1; r.start = s.hi + 1;
-    cut(l, s.lo - 1 - s.seq_hi, s.lo - 1 - s.seq_lo);         // position lo - 1 - t inside seq_lo..seq_hi
-    cut(r, s.seq_lo - s.hi - 1, s.seq_hi - s.hi - 1);         // position hi + 1 + t
-    room[(size_t)i] = s.hi + 1 - s.lo < 64 ? (int)(s.hi + 1 - s.lo) : 64;
-  }
-  // the flank and window buffers of the direction are reused, as by the replays
-  if ((rc = pack_settle(d, true)) != RAMX_OK) return rc;
-  if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)2 * Np * sizeof(ramx_flank)))) return rc;
-  if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)RAMX_TSD_KW * 2 * Np * sizeof(unsigned)))) return rc;
-  if ((rc = ensure(&d->d_bounds, &d->cap_bounds, (size_t)2 * Np * sizeof(int2)))) return rc;
+  if ((rc = site_windows_setup(d, (size_t)2 * Np, RAMX_TSD_KW)) != RAMX_OK) return rc;
   if ((rc = ensure(&d->d_tsd_room, &d->cap_tsd_room, (size_t)Np * sizeof(int)))) return rc;
   if ((rc = ensure(&d->d_tsd_out, &d->cap_tsd_out, (size_t)Np * sizeof(ramx_tsd)))) return rc;
-  d->ready = 0;
-  d->planes_ready = 0;
-  hipEvent_t ev[3] = { NULL, NULL, NULL };
-  if (kernel_ms) for (auto &e : ev) HIPCHK(hipEventCreate(&e));
-  HIPCHK(hipMemcpyAsync(d->d_flanks, fl.data(), fl.size() * sizeof(ramx_flank), hipMemcpyHostToDevice, d->stream));
-  HIPCHK(hipMemcpyAsync(d->d_tsd_room, room.data(), room.size() * sizeof(int), hipMemcpyHostToDevice, d->stream));
-  if (kernel_ms) HIPCHK(hipEventRecord(ev[0], d->stream));
-  if ((rc = launch_pack(d, 2 * Np, 2 * Np, RAMX_TSD_W, 0, RAMX_TSD_KW, d->stream)) != RAMX_OK) return rc;
-  d->packed_kw = RAMX_TSD_KW;
-  if (kernel_ms) HIPCHK(hipEventRecord(ev[1], d->stream));
+  // the windows: the left one runs down from lo - 1, the right one up from hi + 1, t = -slack .. kmax + slack - 1; the left
+  // windows of all (padded) sites first, then the right ones
+  // (every lane is written below: nothing is zeroed first)
+  std::unique_ptr<ramx_flank[]> fl(new ramx_flank[(size_t)2 * Np]);
+  std::unique_ptr<int[]> room(new int[(size_t)Np]);
+  for (int i = 0; i < Np; i++)
+  {
+    const ramx_tsd_site &s = i < n ? sites[i] : NO_SITE;
+    window_flank(fl[(size_t)i], s.lo - 1, -1, false, -S, t_last, s.seq_lo, s.seq_hi);
+    window_flank(fl[(size_t)Np + i], s.hi + 1, 1, false, -S, t_last, s.seq_lo, s.seq_hi);
+    room[(size_t)i] = s.hi + 1 - s.lo < 64 ? (int)(s.hi + 1 - s.lo) : 64;
+  }
   TsdArgs ta;
   ta.bases = d->d_bases; ta.room = d->d_tsd_room; ta.out = d->d_tsd_out; ta.n = n; ta.Np = Np;
   ta.slack = S; ta.kmin = params->kmin; ta.kmax = params->kmax; ta.mm_div = params->mm_div;
-  if ((rc = ramx_tsd_launch(d->stream, ta)) != RAMX_OK) { ramx_set_error("ramx_dev_tsd: launch failed (%s)", hipGetErrorString(hipGetLastError())); return rc; }
-  if (kernel_ms) HIPCHK(hipEventRecord(ev[2], d->stream));
-  HIPCHK(hipMemcpyAsync(out, d->d_tsd_out, (size_t)n * sizeof(ramx_tsd), hipMemcpyDeviceToHost, d->stream));
-  HIPCHK(hipStreamSynchronize(d->stream));
-  if (kernel_ms)
-  {
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1])); kernel_ms[0] = ms;
-    HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2])); kernel_ms[1] = ms;
-    for (auto &e : ev) (void)hipEventDestroy(e);
-  }
-  return RAMX_OK;
+  // one group of all the tiles
+  return tile_groups(d, "ramx_dev_tsd", Np / 64, Np / 64, 2, kernel_ms, true, [&](int, int, auto &mark) {
+    int lrc;
+    HIPCHK(hipMemcpyAsync(d->d_flanks, fl.get(), (size_t)2 * Np * sizeof(ramx_flank), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(d->d_tsd_room, room.get(), (size_t)Np * sizeof(int), hipMemcpyHostToDevice, d->stream));
+    mark();
+    if ((lrc = launch_pack(d, 2 * Np, 2 * Np, RAMX_TSD_W, 0, RAMX_TSD_KW, d->stream)) != RAMX_OK) return lrc;
+    mark();
+    if ((lrc = ramx_tsd_launch(d->stream, ta)) != RAMX_OK) return lrc;
+    mark();
+    HIPCHK(hipMemcpyAsync(out, d->d_tsd_out, (size_t)n * sizeof(ramx_tsd), hipMemcpyDeviceToHost, d->stream));
+    return RAMX_OK;
+  });
 }
 
-// ------------------------------------------------------------------------------------------
 // tandem periodicity: every segment packed as a flank, squeezed into a stream of its own, then one workgroup per segment and a
 // lane per period (ramx_kernels_period.h)
-// ------------------------------------------------------------------------------------------
 extern "C" int ramx_dev_period_bounded(ramx_dev *d, const ramx_period_seg *segs, const ramx_period_seg *bounds, int32_t n_segs,
                                        const ramx_period_params *params, ramx_period *out, double *kernel_ms)
 {
@@ -2373,7 +2397,7 @@ extern "C" int ramx_dev_period_bounded(ramx_dev *d, const ramx_period_seg *segs,
   long long nmax = 0;
   for (int i = 0; i < n_segs; i++)
   {
-    if (segs[i].lo < -RAMX_TSD_POS_MAX || segs[i].hi > RAMX_TSD_POS_MAX || segs[i].lo > segs[i].hi + 1)       // (so that no difference below overflows)
+    if (segs[i].lo < -RAMX_TSD_POS_MAX || segs[i].hi > RAMX_TSD_POS_MAX || segs[i].lo > segs[i].hi + 1)
     { ramx_set_error("ramx_dev_period: segment %d: lo %lld hi %lld: lo > hi + 1, or out of range", i, (long long)segs[i].lo, (long long)segs[i].hi); return RAMX_ERR_ARG; }
     if (bounds && (bounds[i].lo < -RAMX_TSD_POS_MAX || bounds[i].hi > RAMX_TSD_POS_MAX))
     { ramx_set_error("ramx_dev_period: segment %d: bounds out of range", i); return RAMX_ERR_ARG; }
@@ -2387,76 +2411,51 @@ extern "C" int ramx_dev_period_bounded(ramx_dev *d, const ramx_period_seg *segs,
   // the windows and streams of one tile of 64 segments, at the length of the call's longest segment
   const int KW = period_window_words((int)nmax), SW = period_stream_words((int)nmax) > 0 ? period_stream_words((int)nmax) : 1;
   const size_t tile_bytes = (size_t)64 * ((size_t)KW * sizeof(unsigned) + (size_t)SW * (sizeof(unsigned long long) + sizeof(unsigned)));
-  size_t budget = (size_t)1 << 30;
-  if (const char *e = getenv("RAMX_PERIOD_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
-  if (tile_bytes > budget)
-  {
-    ramx_set_error("ramx_dev_period: the windows and streams of one tile of 64 segments (%lld bases: %zu bytes) do not fit RAMX_PERIOD_BYTES = %zu",
-                   nmax, tile_bytes, budget);
-    return RAMX_ERR_UNSUPPORTED;
-  }
   const int tiles = (n_segs + 63) / 64;
-  const int group = (int)(budget / tile_bytes < (size_t)tiles ? budget / tile_bytes : (size_t)tiles);
-  HIPCHK(hipSetDevice(d->ordinal));
-  // the flank and window buffers of the direction are reused, as by the replays
-  if ((rc = pack_settle(d, true)) != RAMX_OK) return rc;
-  const int Gp = group * 64;
-  if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)Gp * sizeof(ramx_flank)))) return rc;
-  if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)KW * Gp * sizeof(unsigned)))) return rc;
-  if ((rc = ensure(&d->d_bounds, &d->cap_bounds, (size_t)Gp * sizeof(int2)))) return rc;
-  if ((rc = ensure(&d->d_per_bases, &d->cap_per_bases, (size_t)Gp * SW * sizeof(unsigned long long)))) return rc;
-  if ((rc = ensure(&d->d_per_valid, &d->cap_per_valid, (size_t)Gp * SW * sizeof(unsigned)))) return rc;
-  if ((rc = ensure(&d->d_per_len, &d->cap_per_len, (size_t)Gp * sizeof(int)))) return rc;
-  if ((rc = ensure(&d->d_per_out, &d->cap_per_out, (size_t)Gp * sizeof(ramx_period)))) return rc;
-  d->ready = 0;
-  d->planes_ready = 0;
-  hipEvent_t ev[4] = { NULL, NULL, NULL, NULL };
-  if (kernel_ms) for (auto &e : ev) HIPCHK(hipEventCreate(&e));
-  std::vector<ramx_flank> fl((size_t)Gp);
-  std::vector<int> len((size_t)Gp);
-  for (int t0 = 0; t0 < tiles && rc == RAMX_OK; t0 += group)
-  {
-    const int nt = tiles - t0 < group ? tiles - t0 : group, Np = nt * 64, s0 = t0 * 64;
-    const int n = n_segs - s0 < Np ? n_segs - s0 : Np;
+  int group;
+  if ((rc = tile_group("ramx_dev_period", "RAMX_PERIOD_BYTES", "windows and streams of one tile of 64 segments", tiles, tile_bytes, &group)) != RAMX_OK)
+    return rc;
+  const size_t Gp = (size_t)group * 64;
+  if ((rc = site_windows_setup(d, Gp, KW)) != RAMX_OK) return rc;
+  if ((rc = ensure(&d->d_per_bases, &d->cap_per_bases, Gp * SW * sizeof(unsigned long long)))) return rc;
+  if ((rc = ensure(&d->d_per_valid, &d->cap_per_valid, Gp * SW * sizeof(unsigned)))) return rc;
+  if ((rc = ensure(&d->d_per_len, &d->cap_per_len, Gp * sizeof(int)))) return rc;
+  if ((rc = ensure(&d->d_per_out, &d->cap_per_out, Gp * sizeof(ramx_period)))) return rc;
+  // (a group writes every lane it sends: nothing is zeroed first)
+  std::unique_ptr<ramx_flank[]> fl(new ramx_flank[Gp]);
+  std::unique_ptr<int[]> len(new int[Gp]);
+  PeriodArgs pa;
+  pa.win = d->d_bases; pa.bases = d->d_per_bases; pa.valid = d->d_per_valid; pa.len = d->d_per_len; pa.out = d->d_per_out;
+  pa.KW = KW; pa.SW = SW;
+  pa.pmax = params->pmax; pa.mm = params->mm; pa.min_score = params->min_score;
+  return tile_groups(d, "ramx_dev_period", tiles, group, 3, kernel_ms, true, [&](int tile0, int nt, auto &mark) {
+    const int Np = nt * 64, s0 = tile0 * 64, n = n_segs - s0 < Np ? n_segs - s0 : Np;
+    int lrc;
+    // the window of a segment: all of it, or with bounds what of it lies inside them; its length stays the segment's
+    // (the arrays through pointers of the loop's own: the flanks' byte stores would have the captured ones read again per lane)
+    const ramx_period_seg none = { 0, -1 }, all = { -RAMX_TSD_POS_MAX, RAMX_TSD_POS_MAX };
+    const ramx_period_seg *const sg = segs + s0, *const bd = bounds ? bounds + s0 : NULL;
+    ramx_flank *const f = fl.get();
+    int *const ln = len.get();
     for (int i = 0; i < Np; i++)
     {
-      ramx_flank &f = fl[(size_t)i];
-      memset(&f, 0, sizeof(f));
-      f.step = 1; f.t_lo = 1; len[(size_t)i] = 0;                // (padding, or an empty segment: no base)
-      if (i >= n) continue;
-      const ramx_period_seg &s = segs[s0 + i];
-      long long a = 0, b = (long long)(s.hi - s.lo);            // offsets of the segment that may be read
-      if (bounds)
-      {
-        if (bounds[s0 + i].lo - s.lo > a) a = (long long)(bounds[s0 + i].lo - s.lo);
-        if (bounds[s0 + i].hi - s.lo < b) b = (long long)(bounds[s0 + i].hi - s.lo);
-      }
-      f.start = s.lo;
-      if (a <= b) { f.t_lo = (int32_t)a; f.t_hi = (int32_t)b; }
-      len[(size_t)i] = (int)(s.hi + 1 - s.lo);
+      const ramx_period_seg &s = i < n ? sg[i] : none, &b = i < n && bd ? bd[i] : all;
+      window_flank(f[i], s.lo, 1, false, 0, (long long)(s.hi - s.lo), b.lo, b.hi);
+      ln[i] = (int)(s.hi + 1 - s.lo);
     }
-    HIPCHK(hipMemcpyAsync(d->d_flanks, fl.data(), (size_t)Np * sizeof(ramx_flank), hipMemcpyHostToDevice, d->stream));
-    HIPCHK(hipMemcpyAsync(d->d_per_len, len.data(), (size_t)Np * sizeof(int), hipMemcpyHostToDevice, d->stream));
-    if (kernel_ms) HIPCHK(hipEventRecord(ev[0], d->stream));
-    if ((rc = launch_pack(d, Np, Np, RAMX_PERIOD_W, 0, KW, d->stream)) != RAMX_OK) break;
-    d->packed_kw = KW;
-    if (kernel_ms) HIPCHK(hipEventRecord(ev[1], d->stream));
-    PeriodArgs pa;
-    pa.win = d->d_bases; pa.bases = d->d_per_bases; pa.valid = d->d_per_valid; pa.len = d->d_per_len; pa.out = d->d_per_out;
-    pa.n = n; pa.Np = Np; pa.KW = KW; pa.SW = SW;
-    pa.pmax = params->pmax; pa.mm = params->mm; pa.min_score = params->min_score;
-    if ((rc = ramx_period_squeeze_launch(d->stream, pa)) != RAMX_OK) { ramx_set_error("ramx_dev_period: launch failed (%s)", hipGetErrorString(hipGetLastError())); break; }
-    if (kernel_ms) HIPCHK(hipEventRecord(ev[2], d->stream));
-    if ((rc = ramx_period_scan_launch(d->stream, pa)) != RAMX_OK) { ramx_set_error("ramx_dev_period: launch failed (%s)", hipGetErrorString(hipGetLastError())); break; }
-    if (kernel_ms) HIPCHK(hipEventRecord(ev[3], d->stream));
+    HIPCHK(hipMemcpyAsync(d->d_flanks, f, (size_t)Np * sizeof(ramx_flank), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(d->d_per_len, ln, (size_t)Np * sizeof(int), hipMemcpyHostToDevice, d->stream));
+    mark();
+    if ((lrc = launch_pack(d, Np, Np, RAMX_PERIOD_W, 0, KW, d->stream)) != RAMX_OK) return lrc;
+    mark();
+    pa.n = n; pa.Np = Np;
+    if ((lrc = ramx_period_squeeze_launch(d->stream, pa)) != RAMX_OK) return lrc;
+    mark();
+    if ((lrc = ramx_period_scan_launch(d->stream, pa)) != RAMX_OK) return lrc;
+    mark();
     HIPCHK(hipMemcpyAsync(out + s0, d->d_per_out, (size_t)n * sizeof(ramx_period), hipMemcpyDeviceToHost, d->stream));
-    // (the next group writes the host and device buffers of this one again)
-    HIPCHK(hipStreamSynchronize(d->stream));
-    if (kernel_ms)
-      for (int k = 0; k < 3; k++) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1])); kernel_ms[k] += ms; }
-  }
-  if (kernel_ms) for (auto &e : ev) (void)hipEventDestroy(e);
-  return rc;
+    return RAMX_OK;      // (the next group writes the host and device buffers of this one again: host_reuse)
+  });
 }
 
 extern "C" int ramx_dev_period(ramx_dev *d, const ramx_period_seg *segs, int32_t n_segs, const ramx_period_params *params, ramx_period *out,
@@ -2465,10 +2464,8 @@ extern "C" int ramx_dev_period(ramx_dev *d, const ramx_period_seg *segs, int32_t
   return ramx_dev_period_bounded(d, segs, NULL, n_segs, params, out, kernel_ms);
 }
 
-// ------------------------------------------------------------------------------------------
 // terminal repeats: the three windows of every site packed as flanks and squeezed into streams by the period's kernel, then one
 // wave per (site, orientation) (ramx_kernels_term.h)
-// ------------------------------------------------------------------------------------------
 extern "C" int ramx_dev_term(ramx_dev *d, const ramx_tsd_site *sites, int32_t n_sites, const ramx_term_params *params, ramx_term *out,
                              double *kernel_ms)
 {
@@ -2476,104 +2473,72 @@ extern "C" int ramx_dev_term(ramx_dev *d, const ramx_tsd_site *sites, int32_t n_
   if (!d || n_sites < 0 || (n_sites && (!sites || !out))) { ramx_set_error("ramx_dev_term: bad argument"); return RAMX_ERR_ARG; }
   int rc;
   if ((rc = ramx_term_check_params(params)) != RAMX_OK) return rc;
-  long long Tmax = 0;
-  for (int i = 0; i < n_sites; i++)
-  {
-    if (sites[i].seq_lo < -RAMX_TSD_POS_MAX || sites[i].seq_hi > RAMX_TSD_POS_MAX ||       // (so that no difference below overflows)
-        sites[i].seq_lo > sites[i].lo || sites[i].lo > sites[i].hi + 1 || sites[i].hi > sites[i].seq_hi)
-    { ramx_set_error("ramx_dev_term: site %d: lo %lld hi %lld outside its bounds %lld..%lld, or lo > hi + 1", i, (long long)sites[i].lo,
-                     (long long)sites[i].hi, (long long)sites[i].seq_lo, (long long)sites[i].seq_hi); return RAMX_ERR_ARG; }
-    const long long half = (long long)(sites[i].hi + 1 - sites[i].lo) / 2, T = half < params->tmax ? half : params->tmax;
-    if (T > Tmax) Tmax = T;
-  }
+  if ((rc = check_sites("ramx_dev_term", sites, n_sites)) != RAMX_OK) return rc;
+  // the length of a site's windows: half the site, at most tmax
+  auto window_len = [](const ramx_tsd_site &s, int tmax) {
+    const long long half = (long long)(s.hi + 1 - s.lo) / 2;
+    return (int)(half < tmax ? half : tmax);
+  };
+  int Tmax = 0;
+  for (int i = 0; i < n_sites; i++) if (window_len(sites[i], params->tmax) > Tmax) Tmax = window_len(sites[i], params->tmax);
   if (n_sites == 0) return RAMX_OK;
   if (n_sites > (1 << 29)) { ramx_set_error("ramx_dev_term: more than 2^29 sites in one call"); return RAMX_ERR_UNSUPPORTED; }
   // the three windows and streams of one tile of 64 sites, at the length of the call's longest window
-  const int KW = period_window_words((int)Tmax), SW = period_stream_words((int)Tmax) > 0 ? period_stream_words((int)Tmax) : 1;
+  const int KW = period_window_words(Tmax), SW = period_stream_words(Tmax) > 0 ? period_stream_words(Tmax) : 1;
   const size_t tile_bytes = (size_t)3 * 64 * ((size_t)KW * sizeof(unsigned) + (size_t)SW * (sizeof(unsigned long long) + sizeof(unsigned)));
-  size_t budget = (size_t)1 << 30;
-  if (const char *e = getenv("RAMX_TERM_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
-  if (tile_bytes > budget)
-  {
-    ramx_set_error("ramx_dev_term: the windows and streams of one tile of 64 sites (%lld bases a window: %zu bytes) do not fit RAMX_TERM_BYTES = %zu",
-                   Tmax, tile_bytes, budget);
-    return RAMX_ERR_UNSUPPORTED;
-  }
   const int tiles = (n_sites + 63) / 64;
-  const int group = (int)(budget / tile_bytes < (size_t)tiles ? budget / tile_bytes : (size_t)tiles);
-  HIPCHK(hipSetDevice(d->ordinal));
-  // the flank and window buffers of the direction are reused, as by the replays
-  if ((rc = pack_settle(d, true)) != RAMX_OK) return rc;
-  const int Gp = group * 64;
-  if ((rc = ensure(&d->d_flanks, &d->cap_flanks, (size_t)3 * Gp * sizeof(ramx_flank)))) return rc;
-  if ((rc = ensure(&d->d_bases, &d->cap_bases, (size_t)KW * 3 * Gp * sizeof(unsigned)))) return rc;
-  if ((rc = ensure(&d->d_bounds, &d->cap_bounds, (size_t)3 * Gp * sizeof(int2)))) return rc;
-  if ((rc = ensure(&d->d_per_bases, &d->cap_per_bases, (size_t)3 * Gp * SW * sizeof(unsigned long long)))) return rc;
-  if ((rc = ensure(&d->d_per_valid, &d->cap_per_valid, (size_t)3 * Gp * SW * sizeof(unsigned)))) return rc;
-  if ((rc = ensure(&d->d_per_len, &d->cap_per_len, (size_t)Gp * sizeof(int)))) return rc;
-  if ((rc = ensure(&d->d_term_out, &d->cap_term_out, (size_t)2 * Gp * sizeof(ramx_term)))) return rc;
-  d->ready = 0;
-  d->planes_ready = 0;
-  hipEvent_t ev[4] = { NULL, NULL, NULL, NULL };
-  if (kernel_ms) for (auto &e : ev) HIPCHK(hipEventCreate(&e));
-  std::vector<ramx_flank> fl((size_t)3 * Gp);
-  std::vector<int> len((size_t)Gp);
-  for (int t0 = 0; t0 < tiles && rc == RAMX_OK; t0 += group)
-  {
-    const int nt = tiles - t0 < group ? tiles - t0 : group, Np = nt * 64, s0 = t0 * 64;
-    const int n = n_sites - s0 < Np ? n_sites - s0 : Np;
-    int Tgroup = 0;
-    // a window of T bases from `start` in direction `step`, t = 0 .. T - 1 cut to the positions inside seq_lo..seq_hi
-    auto window = [](ramx_flank &f, const ramx_tsd_site &s, long long start, int step, int T) {
-      f.start = start; f.step = (int8_t)step;
-      long long a = 0, b = T - 1;
-      if (step > 0) { if (s.seq_lo - start > a) a = s.seq_lo - start; if (s.seq_hi - start < b) b = s.seq_hi - start; }
-      else { if (start - s.seq_hi > a) a = start - s.seq_hi; if (start - s.seq_lo < b) b = start - s.seq_lo; }
-      if (a <= b) { f.t_lo = (int32_t)a; f.t_hi = (int32_t)b; }
-    };
+  int group;
+  if ((rc = tile_group("ramx_dev_term", "RAMX_TERM_BYTES", "windows and streams of one tile of 64 sites", tiles, tile_bytes, &group)) != RAMX_OK) return rc;
+  const size_t Gp = (size_t)group * 64;
+  if ((rc = site_windows_setup(d, 3 * Gp, KW)) != RAMX_OK) return rc;
+  if ((rc = ensure(&d->d_per_bases, &d->cap_per_bases, 3 * Gp * SW * sizeof(unsigned long long)))) return rc;
+  if ((rc = ensure(&d->d_per_valid, &d->cap_per_valid, 3 * Gp * SW * sizeof(unsigned)))) return rc;
+  if ((rc = ensure(&d->d_per_len, &d->cap_per_len, Gp * sizeof(int)))) return rc;
+  if ((rc = ensure(&d->d_term_out, &d->cap_term_out, 2 * Gp * sizeof(ramx_term)))) return rc;
+  // (a group writes every lane it sends: nothing is zeroed first)
+  std::unique_ptr<ramx_flank[]> fl(new ramx_flank[3 * Gp]);
+  std::unique_ptr<int[]> len(new int[Gp]);
+  PeriodArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  pa.win = d->d_bases; pa.bases = d->d_per_bases; pa.valid = d->d_per_valid; pa.len = d->d_per_len;
+  pa.KW = KW; pa.SW = SW;
+  TermArgs ta;
+  ta.bases = d->d_per_bases; ta.valid = d->d_per_valid; ta.T = d->d_per_len; ta.out = d->d_term_out; ta.SW = SW;
+  ta.match = params->match; ta.mismatch = params->mismatch; ta.gap = params->gap; ta.min_score = params->min_score;
+  return tile_groups(d, "ramx_dev_term", tiles, group, 3, kernel_ms, true, [&](int tile0, int nt, auto &mark) {
+    const int Np = nt * 64, s0 = tile0 * 64, n = n_sites - s0 < Np ? n_sites - s0 : Np;
+    int lrc, Tgroup = 0;
+    // the windows of T bases: the 5' one up from lo, the 3' one up from hi + 1 - T, and the 3' one down from hi, complemented;
+    // the first of all (padded) sites first, then the second, then the third
+    // (the arrays through pointers of the loop's own, as in ramx_dev_period_bounded)
+    const ramx_tsd_site *const st = sites + s0;
+    ramx_flank *const f = fl.get();
+    int *const ln = len.get();
+    const int tmax = params->tmax;
     for (int i = 0; i < Np; i++)
     {
-      ramx_flank &fa = fl[(size_t)i], &fb = fl[(size_t)Np + i], &fc = fl[(size_t)2 * Np + i];
-      memset(&fa, 0, sizeof(fa)); memset(&fb, 0, sizeof(fb)); memset(&fc, 0, sizeof(fc));
-      fa.step = fb.step = 1; fc.step = -1; fc.compl_ = 1;
-      fa.t_lo = fb.t_lo = fc.t_lo = 1; len[(size_t)i] = 0;       // (padding, or T == 0: no base)
-      if (i >= n) continue;
-      const ramx_tsd_site &s = sites[s0 + i];
-      const long long half = (long long)(s.hi + 1 - s.lo) / 2;
-      const int T = (int)(half < params->tmax ? half : params->tmax);
-      if (T == 0) continue;
-      window(fa, s, s.lo, 1, T);
-      window(fb, s, s.hi + 1 - T, 1, T);
-      window(fc, s, s.hi, -1, T);
-      len[(size_t)i] = T;
+      const ramx_tsd_site &s = i < n ? st[i] : NO_SITE;
+      const int T = window_len(s, tmax);
+      window_flank(f[i], s.lo, 1, false, 0, T - 1, s.seq_lo, s.seq_hi);
+      window_flank(f[(size_t)Np + i], s.hi + 1 - T, 1, false, 0, T - 1, s.seq_lo, s.seq_hi);
+      window_flank(f[(size_t)2 * Np + i], s.hi, -1, true, 0, T - 1, s.seq_lo, s.seq_hi);
+      ln[i] = T;
       if (T > Tgroup) Tgroup = T;
     }
-    HIPCHK(hipMemcpyAsync(d->d_flanks, fl.data(), (size_t)3 * Np * sizeof(ramx_flank), hipMemcpyHostToDevice, d->stream));
-    HIPCHK(hipMemcpyAsync(d->d_per_len, len.data(), (size_t)Np * sizeof(int), hipMemcpyHostToDevice, d->stream));
-    if (kernel_ms) HIPCHK(hipEventRecord(ev[0], d->stream));
-    if ((rc = launch_pack(d, 3 * Np, 3 * Np, RAMX_PERIOD_W, 0, KW, d->stream)) != RAMX_OK) break;
-    d->packed_kw = KW;
-    if (kernel_ms) HIPCHK(hipEventRecord(ev[1], d->stream));
-    PeriodArgs pa;
-    memset(&pa, 0, sizeof(pa));
-    pa.win = d->d_bases; pa.bases = d->d_per_bases; pa.valid = d->d_per_valid; pa.len = d->d_per_len;
-    pa.n = 3 * Np; pa.Np = 3 * Np; pa.KW = KW; pa.SW = SW;
-    if ((rc = ramx_period_squeeze_launch(d->stream, pa)) != RAMX_OK) { ramx_set_error("ramx_dev_term: launch failed (%s)", hipGetErrorString(hipGetLastError())); break; }
-    if (kernel_ms) HIPCHK(hipEventRecord(ev[2], d->stream));
-    TermArgs ta;
-    ta.bases = d->d_per_bases; ta.valid = d->d_per_valid; ta.T = d->d_per_len; ta.out = d->d_term_out;
-    ta.n = n; ta.Np = Np; ta.SW = SW;
-    ta.match = params->match; ta.mismatch = params->mismatch; ta.gap = params->gap; ta.min_score = params->min_score;
-    if ((rc = ramx_term_align_launch(d->stream, ta, Tgroup)) != RAMX_OK) { ramx_set_error("ramx_dev_term: launch failed (%s)", hipGetErrorString(hipGetLastError())); break; }
-    if (kernel_ms) HIPCHK(hipEventRecord(ev[3], d->stream));
+    HIPCHK(hipMemcpyAsync(d->d_flanks, f, (size_t)3 * Np * sizeof(ramx_flank), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(d->d_per_len, ln, (size_t)Np * sizeof(int), hipMemcpyHostToDevice, d->stream));
+    mark();
+    if ((lrc = launch_pack(d, 3 * Np, 3 * Np, RAMX_PERIOD_W, 0, KW, d->stream)) != RAMX_OK) return lrc;
+    mark();
+    pa.n = 3 * Np; pa.Np = 3 * Np;
+    if ((lrc = ramx_period_squeeze_launch(d->stream, pa)) != RAMX_OK) return lrc;
+    mark();
+    ta.n = n; ta.Np = Np;
+    if ((lrc = ramx_term_align_launch(d->stream, ta, Tgroup)) != RAMX_OK) return lrc;
+    mark();
     HIPCHK(hipMemcpyAsync(out + (size_t)2 * s0, d->d_term_out, (size_t)2 * n * sizeof(ramx_term), hipMemcpyDeviceToHost, d->stream));
-    // (the next group writes the host and device buffers of this one again)
-    HIPCHK(hipStreamSynchronize(d->stream));
-    if (kernel_ms)
-      for (int k = 0; k < 3; k++) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev[k], ev[k + 1])); kernel_ms[k] += ms; }
-  }
-  if (kernel_ms) for (auto &e : ev) (void)hipEventDestroy(e);
-  return rc;
+    return RAMX_OK;      // (the next group writes the host and device buffers of this one again: host_reuse)
+  });
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1437,7 +1437,11 @@ int ramx_extend_batch(int direction, ramx_family *fam, int32_t F, const ramx_par
   return rc;
 }
 
-/* ---- target-site duplications (include/ramx.h): called after both extension calls, on whatever library they left resident ---- */
+/* ---- the site-window analyses (include/ramx.h: target-site duplications, tandem periodicity, terminal repeats): called after
+ * the extension calls, on whatever library they left resident.  The three calls of an analysis -- flat, alignment, batch -- differ
+ * from the other analyses' in their sites or segments and in the device call; what they share is written once, here ---- */
+
+static int no_memory(const char *who) { ramx_set_error("%s: out of memory", who); return RAMX_ERR_ARG; }
 
 /* the one-byte library on the device, by seam 1's cache key: the check extend_flat_impl makes, without its helper thread */
 static int library_resident(ramx_dev *d, const int8_t *sequence, uint64_t seq_len)
@@ -1452,87 +1456,80 @@ static int library_resident(ramx_dev *d, const int8_t *sequence, uint64_t seq_le
   return RAMX_OK;
 }
 
-int ramx_tsd_flat(const ramx_flat_cores *cores, const int8_t *sequence, uint64_t seq_len, const ramx_tsd_params *params, ramx_tsd *out)
+/* The checks of an *_alignment call after its parameters', the list's length and the session's device with the library of this
+ * sequenceLibrary on it: the packed twin where it was loaded packed, its bytes otherwise.  *n == 0: nothing to do. */
+static int alignment_resident(const char *who, struct coreAlignment *coreAlign, struct sequenceLibrary *seqLib, const void *out,
+                              ramx_dev **d, int *n)
 {
-  int rc;
-  if ((rc = ramx_tsd_check_params(params)) != RAMX_OK) return rc;
-  if (!cores || cores->n < 0 || (cores->n > 0 && (!sequence || !out))) { ramx_set_error("ramx_tsd_flat: bad argument"); return RAMX_ERR_ARG; }
-  if (cores->n == 0) return RAMX_OK;
-  ramx_dev *d = ramx_default_device();
-  if (!d) return RAMX_ERR_NO_DEVICE;
-  ramx_tsd_site *sites = (ramx_tsd_site *)malloc(sizeof(ramx_tsd_site) * (size_t)cores->n);
-  ramx_tsd_sites(cores, sites);
-  if ((rc = library_resident(d, sequence, seq_len)) == RAMX_OK) rc = ramx_dev_tsd(d, sites, cores->n, params, out, NULL);
-  free(sites);
-  return rc;
+  *d = NULL; *n = 0;
+  if (!seqLib) { ramx_set_error("%s: bad argument", who); return RAMX_ERR_ARG; }
+  for (struct coreAlignment *cc = coreAlign; cc != NULL; cc = cc->next) (*n)++;
+  if (*n == 0) return RAMX_OK;
+  if (!out) { ramx_set_error("%s: bad argument", who); return RAMX_ERR_ARG; }
+  if (!(*d = ramx_default_device())) return RAMX_ERR_NO_DEVICE;
+  if (seqLib->sequence != NULL) return library_resident(*d, (const int8_t *)seqLib->sequence, seqLib->length);
+  /* loaded packed: the twin goes to the device unless it is the library there already */
+  const ramx_packed_library *packed = ramx_packed_of(seqLib);
+  if (!packed) { ramx_set_error("%s: the sequence library holds no bases (sequence == NULL and no packed twin)", who); return RAMX_ERR_ARG; }
+  return g_packed_owner != seqLib ? ramx_preload_library_packed(seqLib, packed) : RAMX_OK;
 }
 
-int ramx_tsd_alignment(struct coreAlignment *coreAlign, struct sequenceLibrary *seqLib, const ramx_tsd_params *params, ramx_tsd *out)
+/* the n cores of a list as sites: ramx_tsd_sites on the list's own fields (NULL: no memory) */
+static ramx_tsd_site *list_sites(struct coreAlignment *coreAlign, int n)
 {
-  int rc;
-  if ((rc = ramx_tsd_check_params(params)) != RAMX_OK) return rc;
-  if (!seqLib) { ramx_set_error("ramx_tsd_alignment: bad argument"); return RAMX_ERR_ARG; }
-  int n = 0;
-  for (struct coreAlignment *cc = coreAlign; cc != NULL; cc = cc->next) n++;
-  if (n == 0) return RAMX_OK;
-  if (!out) { ramx_set_error("ramx_tsd_alignment: bad argument"); return RAMX_ERR_ARG; }
-  ramx_dev *d = ramx_default_device();
-  if (!d) return RAMX_ERR_NO_DEVICE;
   ramx_tsd_site *sites = (ramx_tsd_site *)malloc(sizeof(ramx_tsd_site) * (size_t)n);
   int k = 0;
-  for (struct coreAlignment *cc = coreAlign; cc != NULL; cc = cc->next, k++)
+  for (struct coreAlignment *cc = coreAlign; cc != NULL && sites; cc = cc->next, k++)
   {
-    /* ramx_tsd_sites on the list's own fields */
     const int64_t lp = (int64_t)cc->leftSeqPos, rp = (int64_t)cc->rightSeqPos;
     sites[k].lo = cc->orient ? rp - cc->rightExtensionLen : lp - cc->leftExtensionLen;
     sites[k].hi = cc->orient ? lp + cc->leftExtensionLen : rp + cc->rightExtensionLen;
     sites[k].seq_lo = (int64_t)cc->lowerSeqBound;
     sites[k].seq_hi = (int64_t)cc->upperSeqBound;
   }
-  if (seqLib->sequence == NULL)
-  {
-    /* loaded packed: the twin goes to the device unless it is the library there already */
-    const ramx_packed_library *packed = ramx_packed_of(seqLib);
-    if (!packed) { ramx_set_error("ramx_tsd_alignment: the sequence library holds no bases (sequence == NULL and no packed twin)"); rc = RAMX_ERR_ARG; }
-    else if (g_packed_owner != seqLib) rc = ramx_preload_library_packed(seqLib, packed);
-  }
-  else
-    rc = library_resident(d, (const int8_t *)seqLib->sequence, seqLib->length);
-  if (rc == RAMX_OK) rc = ramx_dev_tsd(d, sites, n, params, out, NULL);
-  free(sites);
-  return rc;
+  return sites;
 }
 
-int ramx_tsd_batch(const ramx_family *fam, int32_t F, const ramx_tsd_params *params, ramx_tsd *out)
+/* The checks of a *_batch call after its parameters', the number of cores in all and the session's device with the concatenated
+ * library of the batch on it: every family at the offset ramx_extend_batch gives it, at_of[f] (the caller's to free).
+ * *total == 0: nothing to do, and no at_of. */
+static int batch_resident(const char *who, const ramx_family *fam, int32_t F, const void *out, ramx_dev **d, uint64_t **at_of, int64_t *total)
 {
-  int rc;
-  if ((rc = ramx_tsd_check_params(params)) != RAMX_OK) return rc;
-  if (F < 0 || (F && !fam)) { ramx_set_error("ramx_tsd_batch: bad argument"); return RAMX_ERR_ARG; }
-  int64_t total = 0;
+  *d = NULL; *at_of = NULL; *total = 0;
+  if (F < 0 || (F && !fam)) { ramx_set_error("%s: bad argument", who); return RAMX_ERR_ARG; }
+  int64_t n = 0;
   for (int f = 0; f < F; f++)
   {
-    if (fam[f].cores.n < 0 || (fam[f].cores.n > 0 && !fam[f].sequence)) { ramx_set_error("ramx_tsd_batch: bad family %d", f); return RAMX_ERR_ARG; }
-    total += fam[f].cores.n;
+    if (fam[f].cores.n < 0 || (fam[f].cores.n > 0 && !fam[f].sequence)) { ramx_set_error("%s: bad family %d", who, f); return RAMX_ERR_ARG; }
+    n += fam[f].cores.n;
   }
-  if (total == 0) return RAMX_OK;
-  if (!out || total > 0x7fffffff) { ramx_set_error("ramx_tsd_batch: bad argument"); return RAMX_ERR_ARG; }
-  ramx_dev *d = ramx_default_device();
-  if (!d) return RAMX_ERR_NO_DEVICE;
-  /* every family at the offset ramx_extend_batch gives it in the concatenated library */
-  uint64_t *at_of = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)F), *fps = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)F);
+  if (n == 0) return RAMX_OK;
+  if (!out || n > 0x7fffffff) { ramx_set_error("%s: bad argument", who); return RAMX_ERR_ARG; }
+  if (!(*d = ramx_default_device())) return RAMX_ERR_NO_DEVICE;
+  uint64_t *at = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)F), *fps = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)F);
+  int rc = at && fps ? RAMX_OK : no_memory(who);
   uint64_t total_len = 0;
-  for (int f = 0; f < F; f++) { at_of[f] = total_len; total_len += fam[f].seq_len; }
-  if (!batch_lib_cached(fam, F, at_of, total_len, fps))
+  for (int f = 0; f < F && rc == RAMX_OK; f++) { at[f] = total_len; total_len += fam[f].seq_len; }
+  if (rc == RAMX_OK && !batch_lib_cached(fam, F, at, total_len, fps))
   {
     int8_t *lib = (int8_t *)malloc(total_len ? total_len : 1);
-    struct batch_lib_ctx bc = { fam, NULL, at_of, lib, 0 };
-    ramx_parallel_for(F, 8, batch_lib_range, &bc);
-    rc = batch_lib_upload(d, fam, F, lib, total_len, fps);
+    struct batch_lib_ctx bc = { fam, NULL, at, lib, 0 };
+    if (lib) ramx_parallel_for(F, 8, batch_lib_range, &bc);
+    rc = lib ? batch_lib_upload(*d, fam, F, lib, total_len, fps) : no_memory(who);
     free(lib);
   }
+  free(fps);
+  if (rc != RAMX_OK) { free(at); return rc; }
+  *at_of = at; *total = n;
+  return RAMX_OK;
+}
+
+/* the sites of a batch's `total` cores in the concatenated library, family after family (NULL: no memory) */
+static ramx_tsd_site *batch_sites(const ramx_family *fam, int32_t F, const uint64_t *at_of, int64_t total)
+{
   ramx_tsd_site *sites = (ramx_tsd_site *)malloc(sizeof(ramx_tsd_site) * (size_t)total);
   int64_t at = 0;
-  for (int f = 0; f < F; f++)
+  for (int f = 0; f < F && sites; f++)
   {
     ramx_tsd_sites(&fam[f].cores, sites + at);
     for (int i = 0; i < fam[f].cores.n; i++)
@@ -1545,12 +1542,54 @@ int ramx_tsd_batch(const ramx_family *fam, int32_t F, const ramx_tsd_params *par
     }
     at += fam[f].cores.n;
   }
-  if (rc == RAMX_OK) rc = ramx_dev_tsd(d, sites, (int32_t)total, params, out, NULL);
-  free(sites); free(at_of); free(fps);
+  return sites;
+}
+
+/* ---- target-site duplications ---- */
+
+int ramx_tsd_flat(const ramx_flat_cores *cores, const int8_t *sequence, uint64_t seq_len, const ramx_tsd_params *params, ramx_tsd *out)
+{
+  int rc;
+  if ((rc = ramx_tsd_check_params(params)) != RAMX_OK) return rc;
+  if (!cores || cores->n < 0 || (cores->n > 0 && (!sequence || !out))) { ramx_set_error("ramx_tsd_flat: bad argument"); return RAMX_ERR_ARG; }
+  if (cores->n == 0) return RAMX_OK;
+  ramx_dev *d = ramx_default_device();
+  if (!d) return RAMX_ERR_NO_DEVICE;
+  ramx_tsd_site *sites = (ramx_tsd_site *)malloc(sizeof(ramx_tsd_site) * (size_t)cores->n);
+  if (!sites) return no_memory("ramx_tsd_flat");
+  ramx_tsd_sites(cores, sites);
+  if ((rc = library_resident(d, sequence, seq_len)) == RAMX_OK) rc = ramx_dev_tsd(d, sites, cores->n, params, out, NULL);
+  free(sites);
   return rc;
 }
 
-/* ---- tandem periodicity (include/ramx.h): called after both extension calls, with the library rule of the calls above ---- */
+int ramx_tsd_alignment(struct coreAlignment *coreAlign, struct sequenceLibrary *seqLib, const ramx_tsd_params *params, ramx_tsd *out)
+{
+  int rc, n;
+  ramx_dev *d;
+  if ((rc = ramx_tsd_check_params(params)) != RAMX_OK) return rc;
+  if ((rc = alignment_resident("ramx_tsd_alignment", coreAlign, seqLib, out, &d, &n)) != RAMX_OK || n == 0) return rc;
+  ramx_tsd_site *sites = list_sites(coreAlign, n);
+  rc = sites ? ramx_dev_tsd(d, sites, n, params, out, NULL) : no_memory("ramx_tsd_alignment");
+  free(sites);
+  return rc;
+}
+
+int ramx_tsd_batch(const ramx_family *fam, int32_t F, const ramx_tsd_params *params, ramx_tsd *out)
+{
+  int rc;
+  ramx_dev *d;
+  uint64_t *at_of;
+  int64_t total;
+  if ((rc = ramx_tsd_check_params(params)) != RAMX_OK) return rc;
+  if ((rc = batch_resident("ramx_tsd_batch", fam, F, out, &d, &at_of, &total)) != RAMX_OK || total == 0) return rc;
+  ramx_tsd_site *sites = batch_sites(fam, F, at_of, total);
+  rc = sites ? ramx_dev_tsd(d, sites, (int32_t)total, params, out, NULL) : no_memory("ramx_tsd_batch");
+  free(sites); free(at_of);
+  return rc;
+}
+
+/* ---- tandem periodicity ---- */
 
 int ramx_period_flat(const ramx_flat_cores *cores, const int8_t *sequence, uint64_t seq_len, int32_t which,
                      const ramx_period_params *params, ramx_period *out)
@@ -1563,6 +1602,7 @@ int ramx_period_flat(const ramx_flat_cores *cores, const int8_t *sequence, uint6
   ramx_dev *d = ramx_default_device();
   if (!d) return RAMX_ERR_NO_DEVICE;
   ramx_period_seg *segs = (ramx_period_seg *)malloc(sizeof(ramx_period_seg) * (size_t)cores->n);
+  if (!segs) return no_memory("ramx_period_flat");
   ramx_period_segments(cores, which, segs);
   if ((rc = library_resident(d, sequence, seq_len)) == RAMX_OK) rc = ramx_dev_period(d, segs, cores->n, params, out, NULL);
   free(segs);
@@ -1572,16 +1612,13 @@ int ramx_period_flat(const ramx_flat_cores *cores, const int8_t *sequence, uint6
 int ramx_period_alignment(struct coreAlignment *coreAlign, struct sequenceLibrary *seqLib, int32_t which,
                           const ramx_period_params *params, ramx_period *out)
 {
-  int rc;
+  int rc, n;
+  ramx_dev *d;
   if ((rc = ramx_period_check_params(params)) != RAMX_OK) return rc;
-  if (!seqLib || which < 0 || which > 2) { ramx_set_error("ramx_period_alignment: bad argument"); return RAMX_ERR_ARG; }
-  int n = 0;
-  for (struct coreAlignment *cc = coreAlign; cc != NULL; cc = cc->next) n++;
-  if (n == 0) return RAMX_OK;
-  if (!out) { ramx_set_error("ramx_period_alignment: bad argument"); return RAMX_ERR_ARG; }
-  ramx_dev *d = ramx_default_device();
-  if (!d) return RAMX_ERR_NO_DEVICE;
+  if (which < 0 || which > 2) { ramx_set_error("ramx_period_alignment: bad argument"); return RAMX_ERR_ARG; }
+  if ((rc = alignment_resident("ramx_period_alignment", coreAlign, seqLib, out, &d, &n)) != RAMX_OK || n == 0) return rc;
   ramx_period_seg *segs = (ramx_period_seg *)malloc(sizeof(ramx_period_seg) * (size_t)n);
+  if (!segs) return no_memory("ramx_period_alignment");
   int k = 0;
   for (struct coreAlignment *cc = coreAlign; cc != NULL; cc = cc->next, k++)
   {
@@ -1591,16 +1628,7 @@ int ramx_period_alignment(struct coreAlignment *coreAlign, struct sequenceLibrar
     else if (which == 1) { segs[k].lo = cc->orient ? rp - rl : rp + 1; segs[k].hi = cc->orient ? rp - 1 : rp + rl; }
     else { segs[k].lo = cc->orient ? rp - rl : lp - ll; segs[k].hi = cc->orient ? lp + ll : rp + rl; }
   }
-  if (seqLib->sequence == NULL)
-  {
-    /* loaded packed: the twin goes to the device unless it is the library there already */
-    const ramx_packed_library *packed = ramx_packed_of(seqLib);
-    if (!packed) { ramx_set_error("ramx_period_alignment: the sequence library holds no bases (sequence == NULL and no packed twin)"); rc = RAMX_ERR_ARG; }
-    else if (g_packed_owner != seqLib) rc = ramx_preload_library_packed(seqLib, packed);
-  }
-  else
-    rc = library_resident(d, (const int8_t *)seqLib->sequence, seqLib->length);
-  if (rc == RAMX_OK) rc = ramx_dev_period(d, segs, n, params, out, NULL);
+  rc = ramx_dev_period(d, segs, n, params, out, NULL);
   free(segs);
   return rc;
 }
@@ -1608,33 +1636,15 @@ int ramx_period_alignment(struct coreAlignment *coreAlign, struct sequenceLibrar
 int ramx_period_batch(const ramx_family *fam, int32_t F, int32_t which, const ramx_period_params *params, ramx_period *out)
 {
   int rc;
+  ramx_dev *d;
+  uint64_t *at_of;
+  int64_t total;
   if ((rc = ramx_period_check_params(params)) != RAMX_OK) return rc;
-  if (F < 0 || (F && !fam) || which < 0 || which > 2) { ramx_set_error("ramx_period_batch: bad argument"); return RAMX_ERR_ARG; }
-  int64_t total = 0;
-  for (int f = 0; f < F; f++)
-  {
-    if (fam[f].cores.n < 0 || (fam[f].cores.n > 0 && !fam[f].sequence)) { ramx_set_error("ramx_period_batch: bad family %d", f); return RAMX_ERR_ARG; }
-    total += fam[f].cores.n;
-  }
-  if (total == 0) return RAMX_OK;
-  if (!out || total > 0x7fffffff) { ramx_set_error("ramx_period_batch: bad argument"); return RAMX_ERR_ARG; }
-  ramx_dev *d = ramx_default_device();
-  if (!d) return RAMX_ERR_NO_DEVICE;
-  /* every family at the offset ramx_extend_batch gives it in the concatenated library */
-  uint64_t *at_of = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)F), *fps = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)F);
-  uint64_t total_len = 0;
-  for (int f = 0; f < F; f++) { at_of[f] = total_len; total_len += fam[f].seq_len; }
-  if (!batch_lib_cached(fam, F, at_of, total_len, fps))
-  {
-    int8_t *lib = (int8_t *)malloc(total_len ? total_len : 1);
-    struct batch_lib_ctx bc = { fam, NULL, at_of, lib, 0 };
-    ramx_parallel_for(F, 8, batch_lib_range, &bc);
-    rc = batch_lib_upload(d, fam, F, lib, total_len, fps);
-    free(lib);
-  }
+  if (which < 0 || which > 2) { ramx_set_error("ramx_period_batch: bad argument"); return RAMX_ERR_ARG; }
+  if ((rc = batch_resident("ramx_period_batch", fam, F, out, &d, &at_of, &total)) != RAMX_OK || total == 0) return rc;
   ramx_period_seg *segs = (ramx_period_seg *)malloc(sizeof(ramx_period_seg) * 2 * (size_t)total), *bounds = segs + total;
   int64_t at = 0;
-  for (int f = 0; f < F; f++)
+  for (int f = 0; f < F && segs; f++)
   {
     ramx_period_segments(&fam[f].cores, which, segs + at);
     for (int i = 0; i < fam[f].cores.n; i++)
@@ -1645,12 +1655,12 @@ int ramx_period_batch(const ramx_family *fam, int32_t F, int32_t which, const ra
     }
     at += fam[f].cores.n;
   }
-  if (rc == RAMX_OK) rc = ramx_dev_period_bounded(d, segs, bounds, (int32_t)total, params, out, NULL);
-  free(segs); free(at_of); free(fps);
+  rc = segs ? ramx_dev_period_bounded(d, segs, bounds, (int32_t)total, params, out, NULL) : no_memory("ramx_period_batch");
+  free(segs); free(at_of);
   return rc;
 }
 
-/* ---- terminal repeats (include/ramx.h): called after both extension calls, with the sites and the library rule of the TSDs ---- */
+/* ---- terminal repeats: the sites of the TSDs ---- */
 
 int ramx_term_flat(const ramx_flat_cores *cores, const int8_t *sequence, uint64_t seq_len, const ramx_term_params *params, ramx_term *out)
 {
@@ -1661,6 +1671,7 @@ int ramx_term_flat(const ramx_flat_cores *cores, const int8_t *sequence, uint64_
   ramx_dev *d = ramx_default_device();
   if (!d) return RAMX_ERR_NO_DEVICE;
   ramx_tsd_site *sites = (ramx_tsd_site *)malloc(sizeof(ramx_tsd_site) * (size_t)cores->n);
+  if (!sites) return no_memory("ramx_term_flat");
   ramx_tsd_sites(cores, sites);
   if ((rc = library_resident(d, sequence, seq_len)) == RAMX_OK) rc = ramx_dev_term(d, sites, cores->n, params, out, NULL);
   free(sites);
@@ -1669,36 +1680,12 @@ int ramx_term_flat(const ramx_flat_cores *cores, const int8_t *sequence, uint64_
 
 int ramx_term_alignment(struct coreAlignment *coreAlign, struct sequenceLibrary *seqLib, const ramx_term_params *params, ramx_term *out)
 {
-  int rc;
+  int rc, n;
+  ramx_dev *d;
   if ((rc = ramx_term_check_params(params)) != RAMX_OK) return rc;
-  if (!seqLib) { ramx_set_error("ramx_term_alignment: bad argument"); return RAMX_ERR_ARG; }
-  int n = 0;
-  for (struct coreAlignment *cc = coreAlign; cc != NULL; cc = cc->next) n++;
-  if (n == 0) return RAMX_OK;
-  if (!out) { ramx_set_error("ramx_term_alignment: bad argument"); return RAMX_ERR_ARG; }
-  ramx_dev *d = ramx_default_device();
-  if (!d) return RAMX_ERR_NO_DEVICE;
-  ramx_tsd_site *sites = (ramx_tsd_site *)malloc(sizeof(ramx_tsd_site) * (size_t)n);
-  int k = 0;
-  for (struct coreAlignment *cc = coreAlign; cc != NULL; cc = cc->next, k++)
-  {
-    /* ramx_tsd_sites on the list's own fields */
-    const int64_t lp = (int64_t)cc->leftSeqPos, rp = (int64_t)cc->rightSeqPos;
-    sites[k].lo = cc->orient ? rp - cc->rightExtensionLen : lp - cc->leftExtensionLen;
-    sites[k].hi = cc->orient ? lp + cc->leftExtensionLen : rp + cc->rightExtensionLen;
-    sites[k].seq_lo = (int64_t)cc->lowerSeqBound;
-    sites[k].seq_hi = (int64_t)cc->upperSeqBound;
-  }
-  if (seqLib->sequence == NULL)
-  {
-    /* loaded packed: the twin goes to the device unless it is the library there already */
-    const ramx_packed_library *packed = ramx_packed_of(seqLib);
-    if (!packed) { ramx_set_error("ramx_term_alignment: the sequence library holds no bases (sequence == NULL and no packed twin)"); rc = RAMX_ERR_ARG; }
-    else if (g_packed_owner != seqLib) rc = ramx_preload_library_packed(seqLib, packed);
-  }
-  else
-    rc = library_resident(d, (const int8_t *)seqLib->sequence, seqLib->length);
-  if (rc == RAMX_OK) rc = ramx_dev_term(d, sites, n, params, out, NULL);
+  if ((rc = alignment_resident("ramx_term_alignment", coreAlign, seqLib, out, &d, &n)) != RAMX_OK || n == 0) return rc;
+  ramx_tsd_site *sites = list_sites(coreAlign, n);
+  rc = sites ? ramx_dev_term(d, sites, n, params, out, NULL) : no_memory("ramx_term_alignment");
   free(sites);
   return rc;
 }
@@ -1706,47 +1693,14 @@ int ramx_term_alignment(struct coreAlignment *coreAlign, struct sequenceLibrary 
 int ramx_term_batch(const ramx_family *fam, int32_t F, const ramx_term_params *params, ramx_term *out)
 {
   int rc;
+  ramx_dev *d;
+  uint64_t *at_of;
+  int64_t total;
   if ((rc = ramx_term_check_params(params)) != RAMX_OK) return rc;
-  if (F < 0 || (F && !fam)) { ramx_set_error("ramx_term_batch: bad argument"); return RAMX_ERR_ARG; }
-  int64_t total = 0;
-  for (int f = 0; f < F; f++)
-  {
-    if (fam[f].cores.n < 0 || (fam[f].cores.n > 0 && !fam[f].sequence)) { ramx_set_error("ramx_term_batch: bad family %d", f); return RAMX_ERR_ARG; }
-    total += fam[f].cores.n;
-  }
-  if (total == 0) return RAMX_OK;
-  if (!out || total > 0x7fffffff) { ramx_set_error("ramx_term_batch: bad argument"); return RAMX_ERR_ARG; }
-  ramx_dev *d = ramx_default_device();
-  if (!d) return RAMX_ERR_NO_DEVICE;
-  /* every family at the offset ramx_extend_batch gives it in the concatenated library */
-  uint64_t *at_of = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)F), *fps = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)F);
-  uint64_t total_len = 0;
-  for (int f = 0; f < F; f++) { at_of[f] = total_len; total_len += fam[f].seq_len; }
-  if (!batch_lib_cached(fam, F, at_of, total_len, fps))
-  {
-    int8_t *lib = (int8_t *)malloc(total_len ? total_len : 1);
-    struct batch_lib_ctx bc = { fam, NULL, at_of, lib, 0 };
-    ramx_parallel_for(F, 8, batch_lib_range, &bc);
-    rc = batch_lib_upload(d, fam, F, lib, total_len, fps);
-    free(lib);
-  }
-  ramx_tsd_site *sites = (ramx_tsd_site *)malloc(sizeof(ramx_tsd_site) * (size_t)total);
-  int64_t at = 0;
-  for (int f = 0; f < F; f++)
-  {
-    ramx_tsd_sites(&fam[f].cores, sites + at);
-    for (int i = 0; i < fam[f].cores.n; i++)
-    {
-      ramx_tsd_site *s = &sites[at + i];
-      /* outside the family's own library is outside the library: its neighbours in the concatenation are never read */
-      if (s->seq_lo < 0) s->seq_lo = 0;
-      if (s->seq_hi > (int64_t)fam[f].seq_len - 1) s->seq_hi = (int64_t)fam[f].seq_len - 1;
-      s->lo += (int64_t)at_of[f]; s->hi += (int64_t)at_of[f]; s->seq_lo += (int64_t)at_of[f]; s->seq_hi += (int64_t)at_of[f];
-    }
-    at += fam[f].cores.n;
-  }
-  if (rc == RAMX_OK) rc = ramx_dev_term(d, sites, (int32_t)total, params, out, NULL);
-  free(sites); free(at_of); free(fps);
+  if ((rc = batch_resident("ramx_term_batch", fam, F, out, &d, &at_of, &total)) != RAMX_OK || total == 0) return rc;
+  ramx_tsd_site *sites = batch_sites(fam, F, at_of, total);
+  rc = sites ? ramx_dev_term(d, sites, (int32_t)total, params, out, NULL) : no_memory("ramx_term_batch");
+  free(sites); free(at_of);
   return rc;
 }
 

@@ -378,3 +378,50 @@ def test_period_batch_with_an_empty_family_between():
     # once more on copies of the libraries: the concatenation is built and sent again, the records are the same
     again = period_batch([(c, s.copy(), m) for c, s, m in batch], 2)
     assert all(a.tobytes() == g.tobytes() for a, g in zip(again, got))
+
+
+def border_families():
+    """Three families of five copies each, the extension lengths set by hand.  Every library begins with 20 A and ends with 24 A:
+    across a border they are one tract of 44.  Copy 0 begins at base 0 of its library and copy 4 ends at its last base; copy 1's
+    left extension begins 10 bases in front of the library and copy 3's right extension ends 10 bases behind it: read across the
+    border, both would hold more of the tract.  Copy 2 lies in the middle, on the reverse strand, with a (CA)20 in its left
+    extension.  -> [(cores, sequence)]"""
+    rng = np.random.default_rng(43)
+    fams = []
+    for f in range(3):
+        seq = rng.integers(0, 4, 300).astype(np.int8)
+        seq[:20] = 0
+        seq[-24:] = 0
+        seq[20], seq[-25] = 1, 2                    # (the tracts end where they are said to)
+        seq[160:200] = np.tile([1, 0], 20)
+        n = len(seq)
+        # (lo, hi, core's first base, core's last base, reverse strand)
+        ext = [(0, 69, 30, 40, 0), (-10, 59, 25, 35, 0), (100, 219, 140, 150, 1), (240, n + 9, 255, 265, 0), (230, n - 1, 250, 260, 0)]
+        lp = [c1 if m else c0 for lo, hi, c0, c1, m in ext]
+        rp = [c0 if m else c1 for lo, hi, c0, c1, m in ext]
+        ll = [hi - c1 if m else c0 - lo for lo, hi, c0, c1, m in ext]
+        rl = [c0 - lo if m else hi - c1 for lo, hi, c0, c1, m in ext]
+        cores = CoreSet(left_pos=lp, right_pos=rp, lower=[0] * 5, upper=[n - 1] * 5, orient=[e[4] for e in ext], left_ext=[1] * 5,
+                        right_ext=[1] * 5, left_len=ll, right_len=rl)
+        assert pr.segments_of(cores, 2) == [e[:2] for e in ext]
+        fams.append((cores, seq))
+    return fams
+
+
+def test_a_batch_never_reads_across_a_familys_border():
+    """ramx_period_batch on the concatenated library: every family's records are those of the family alone, although the
+    neighbouring library continues the tract at either end."""
+    from repeatafterme_amd.extend import period_batch
+    fams = border_families()
+    cat = np.concatenate([s for _, s in fams])
+    at = np.cumsum([0] + [len(s) for _, s in fams])
+    for which in (0, 1, 2):
+        got = period_batch([(c, s, None) for c, s in fams], which)
+        alone = [pr.records(s, pr.segments_of(c, which)) for c, s in fams]
+        assert [[tup(r) for r in g] for g in got] == alone, which
+        # not empty ground: tracts are found, and the same segments read on the concatenation hold longer ones
+        assert all(sum(a != pr.ZERO for a in al) >= 2 for al in alone), which
+        wide = [pr.records(cat, [(lo + int(at[f]), hi + int(at[f])) for lo, hi in pr.segments_of(c, which)]) for f, (c, _) in enumerate(fams)]
+        differ = [[w != a for w, a in zip(wide[f], alone[f])] for f in range(3)]
+        # (copy 1's left extension, copy 3's right one; the first library has nothing in front of it, the last nothing behind)
+        assert differ == [[False, f > 0 and which != 1, False, f < 2 and which != 0, False] for f in range(3)], (which, differ)

@@ -340,3 +340,60 @@ def test_term_batch_with_an_empty_family_between():
     # once more on copies of the libraries: the concatenation is built and sent again, the records are the same
     again = term_batch([(c, s.copy(), m) for c, s, m in batch])
     assert all(a.tobytes() == g.tobytes() for a, g in zip(again, got))
+
+
+def border_families(reach=False):
+    """Three families of four copies each, the extension lengths set by hand.  Copy 0 begins at base 0 of its library with 30
+    bases that it ends with again (a direct repeat); copy 3 ends at the library's last base with the reverse complement of its
+    first 30; copies 1 and 2 (one on the reverse strand) lie in the middle, with a direct and an inverted repeat; half the
+    copies have bounds wider than their library.  Every library but the last holds, 50 bases in front of its end, the first 30
+    bases of the next one.  With reach, the first two families have a fifth copy that begins there and ends 30 bases behind the
+    library: read across the border it would end with the 30 bases it begins with.  -> [(cores, sequence)]"""
+    rng = np.random.default_rng(47)
+    seqs = [rng.integers(0, 4, 400).astype(np.int8) for _ in range(3)]
+    fams = []
+    for f, seq in enumerate(seqs):
+        n = len(seq)
+        ext = [(0, 79, 0), (100, 189, 0), (200, 299, 1), (n - 90, n - 1, 0)]
+        for i, (lo, hi, _) in enumerate(ext):
+            seq[hi - 29:hi + 1] = seq[lo:lo + 30] if i < 2 else tr.revcomp(seq[lo:lo + 30])
+        if f < 2:
+            seq[n - 50:n - 20] = seqs[f + 1][:30]             # (written after copy 3's repeat, of which it keeps the last 20 bases)
+            if reach:
+                ext.append((n - 50, n + 29, 0))
+        m = len(ext)
+        lp = [lo + (44 if minus else 40) for lo, hi, minus in ext]
+        rp = [lo + (40 if minus else 44) for lo, hi, minus in ext]
+        ll = [hi - lo - 44 if minus else 40 for lo, hi, minus in ext]
+        rl = [40 if minus else hi - lo - 44 for lo, hi, minus in ext]
+        cores = CoreSet(left_pos=lp, right_pos=rp, lower=([-50, 0, -50, 0, 0])[:m], upper=([n - 1, n + 50, n - 1, n + 50, n + 50])[:m],
+                        orient=[e[2] for e in ext], left_ext=[1] * m, right_ext=[1] * m, left_len=ll, right_len=rl)
+        assert [s[:2] for s in tr.sites_of(cores)] == [e[:2] for e in ext]
+        fams.append((cores, seq))
+    return fams
+
+
+def test_a_batch_never_reads_across_a_familys_border():
+    """ramx_term_batch on the concatenated library: every family's records are those of the family alone.  The windows of a site
+    lie inside it and a site lies inside its bounds, which the batch cuts to the family's own library: so a copy that reaches
+    behind its library -- where the neighbour's bases would complete a repeat -- is refused, not read."""
+    from repeatafterme_amd.extend import term_batch
+    fams = border_families()
+    got = term_batch([(c, s, None) for c, s in fams])
+    alone = [[tr.site_records(s, site) for site in tr.sites_of(c)] for c, s in fams]
+    assert [as_pairs(g) for g in got] == alone
+    # not empty ground: the planted repeats are found in their orientation ...
+    for f, al in enumerate(alone):
+        assert al[0][0][0] >= 40 and al[1][0][0] >= 40 and al[2][1][0] >= 40, (f, al)
+        assert al[3][1][0] >= (40 if f == 2 else 0)
+    # ... and the reaching copy, read on the concatenation with its whole length for bounds, has the repeat the neighbour completes
+    reach = border_families(reach=True)
+    cat = np.concatenate([s for _, s in reach])
+    at = np.cumsum([0] + [len(s) for _, s in reach])
+    for f in range(2):
+        c, s = reach[f]
+        lo, hi = tr.sites_of(c)[4][:2]
+        assert tr.site_records(s, (lo, hi, 0, hi)) == ((0, 0, 0, 0, 0, 0, 0, 40),) * 2
+        assert tr.site_records(cat, (lo + int(at[f]), hi + int(at[f]), 0, len(cat) - 1))[0] == (60, 0, 29, 10, 39, 30, 30, 40)
+    with pytest.raises(_lib.RamxError, match=r"\(-103\)"):
+        term_batch([(c, s, None) for c, s in reach])

@@ -1,6 +1,7 @@
 """ramx_dev_tsd and the three seam-1 calls against the brute-force restatement (tests/tsd_ref.py), record for record: site
 counts round the wave of 64, every slack / length range / mismatch rule, both library forms, sites at both ends of the library,
-bounds that cut a word, N runs and window boundaries of the packed form; then the seam-1 calls after real extension calls."""
+bounds that cut a word, N runs and window boundaries of the packed form; then the seam-1 calls after real extension calls, and a
+batch whose families' libraries would complete each other's duplications."""
 import ctypes as C
 
 import numpy as np
@@ -15,7 +16,7 @@ import tsd_ref as tr
 from helpers import to_extend_params
 
 pytestmark = pytest.mark.gpu
-ERR_ARG = -103
+ERR_ARG, ERR_STATE = -103, -104
 N_SITES = 130
 
 
@@ -148,6 +149,11 @@ def test_the_shapes_are_not_empty_ground():
         nofold = np.where(lib == 99, 0, lib)
         assert sum(a != tuple(b) for a, b in zip(tr.tsd_all(nofold, [tuple(int(v) for v in s) for s in sites]), want)) > 0
     assert (np.array(expected("byte", 130, TsdParams(3, 32, 32, 10)))[:, 0] == 32).sum() >= 5
+    # the calls of 65 sites have two tiles, the second with one site; windows wholly outside their bounds (seq_lo == lo: no left
+    # word; seq_hi == hi: no right one) share the first tile with ordinary sites
+    _, sites, _ = library("byte")
+    assert (sites["seq_lo"][:64] == sites["lo"][:64]).any() and (sites["seq_hi"][:64] == sites["hi"][:64]).any()
+    assert ((sites["seq_lo"][:64] < sites["lo"][:64] - 40) & (sites["seq_hi"][:64] > sites["hi"][:64] + 40)).any()
     assert (np.array(expected("packed", 130, TsdParams(0, 32, 32, 4)))[:, 0] == 32).sum() >= 2
 
 
@@ -175,6 +181,29 @@ def test_no_site_and_bad_arguments(devices):
     # raised before anything is written
     assert out.tobytes() == keep.tobytes()
     assert L.ramx_dev_tsd(d._h, sites.ctypes.data, 0, C.byref(ok), None, None) == 0
+
+
+def test_timing_and_a_direction_needs_a_new_begin_after_a_tsd_call():
+    from repeatafterme_amd.device import Device, resolve_flanks
+    e = tr.planted_expectation()
+    p = to_extend_params(e["p"])
+    d = Device(0)
+    try:
+        d.load_library(np.ascontiguousarray(e["seq"]))
+        flanks, _ = resolve_flanks(1, e["cores"], p.bandwidth, p.L)
+        d.begin_direction(flanks, p)
+        sites = np.array(e["sites"], np.int64).view(TSD_SITE_DTYPE).reshape(-1)
+        got, ms = d.tsd(sites, timing=True)
+        assert [tuple(int(v) for v in r) for r in got] == e["records"]
+        assert len(ms) == 2 and all(m > 0 for m in ms)
+        ci = _lib.RunInfo()
+        assert d._L.ramx_dev_run_direction(d._h, C.byref(ci)) == ERR_STATE
+        d.begin_direction(flanks, p)
+        assert d.run_direction().rows_executed > 0
+        # without the times: the same bytes
+        assert d.tsd(sites).tobytes() == got.tobytes()
+    finally:
+        d.close()
 
 
 # ---- seam 1 ----
@@ -274,3 +303,56 @@ def test_an_extension_after_a_tsd_call_is_unchanged():
     for key in ("left_len", "right_len", "score"):
         assert np.array_equal(getattr(c, key), getattr(oc, key)), key
     assert len(mid) == 200
+
+
+def border_families(k=6):
+    """Three families of four copies each, the extension lengths set by hand.  In every family copy 0 begins at base 0 of its
+    library and copy 3 ends at its last base; copies 1 and 2 (one on the reverse strand) lie between planted words.  The
+    libraries complete each other: the word in front of a family's last copy is the first word of the next family's library,
+    and the word behind a family's first copy is the last word of the family before -- read across the border, both would be
+    duplications of k bases.  Half the copies have bounds wider than their library.  -> [(cores, sequence)], [(lo, hi)] per family"""
+    rng = np.random.default_rng(41)
+    r = lambda n: rng.integers(0, 4, n).astype(np.int8)                         # noqa: E731
+    seqs = []
+    for f in range(3):
+        a, b, w1, w2 = r(40), r(40), r(k), r(k)
+        seqs.append([a, r(k), r(50), w1, r(30), w1, r(45), w2, r(33), w2, r(50), r(k), b])
+    for f in range(2):
+        seqs[f + 1][0][:k] = seqs[f][11]            # the next library begins with the word in front of this one's last copy
+        seqs[f][12][-k:] = seqs[f + 1][1]           # this library ends with the word behind the next one's first copy
+    fams, where = [], []
+    for f in range(3):
+        at = np.cumsum([0] + [len(x) for x in seqs[f]])
+        seq = np.concatenate(seqs[f]).astype(np.int8)
+        ext = [(int(at[i]), int(at[i + 1]) - 1) for i in (0, 4, 8, 12)]
+        lp, rp, ll, rl = [], [], [], []
+        for i, (lo, hi) in enumerate(ext):
+            c0, c1 = lo + 10, lo + 14                                           # the core; copy 2 is on the reverse strand
+            lp.append(c1 if i == 2 else c0); rp.append(c0 if i == 2 else c1)
+            ll.append(hi - c1 if i == 2 else c0 - lo); rl.append(c0 - lo if i == 2 else hi - c1)
+        n = len(seq)
+        cores = CoreSet(left_pos=lp, right_pos=rp, lower=[-50, 0, -50, 0], upper=[n - 1, n + 50, n - 1, n + 50],
+                        orient=[0, 0, 1, 0], left_ext=[1] * 4, right_ext=[1] * 4, left_len=ll, right_len=rl)
+        assert tr.sites_of(cores)[0][0] == 0 and tr.sites_of(cores)[3][1] == n - 1
+        assert [s[:2] for s in tr.sites_of(cores)] == ext
+        fams.append((cores, seq))
+        where.append(ext)
+    return fams, where
+
+
+def test_a_batch_never_reads_across_a_familys_border():
+    """ramx_tsd_batch on the concatenated library: every family's records are those of the family alone, although the
+    neighbouring library holds the word that would complete a duplication at either end."""
+    from repeatafterme_amd.extend import tsd_batch
+    fams, where = border_families()
+    got = tsd_batch([(c, s, None) for c, s in fams])
+    alone = [tr.tsd_all(s, tr.sites_of(c)) for c, s in fams]
+    assert [[tuple(int(v) for v in r) for r in g] for g in got] == alone
+    # not empty ground: the planted words are found, the copies at the libraries' ends have none ...
+    assert all(a[0] == (0, 0, 0, 0) == a[3] and a[1] == (6, 0, 0, 0) == a[2] for a in alone)
+    # ... and the same sites on the concatenation with its whole length for bounds find the neighbours' words
+    cat = np.concatenate([s for _, s in fams])
+    at = np.cumsum([0] + [len(s) for _, s in fams])
+    wide = [tr.tsd_all(cat, [(lo + int(at[f]), hi + int(at[f]), 0, len(cat) - 1) for lo, hi in where[f]]) for f in range(3)]
+    assert [[w != a for w, a in zip(wide[f], alone[f])] for f in range(3)] == [[False, False, False, True], [True, False, False, True],
+                                                                             [True, False, False, False]]
