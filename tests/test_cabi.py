@@ -21,6 +21,35 @@ def test_header_and_export_list_agree():
     assert _declared() == set(_lib.EXPORTS)
 
 
+def _declared_arity():
+    """-> {name: number of parameters} of every function include/ramx.h declares: the top-level commas of its parameter list"""
+    txt = open(os.path.join(ROOT, "include", "ramx.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    arity = {}
+    for m in re.finditer(r"\b(ramx_[a-z0-9_]+)\s*\(", txt):
+        depth, commas, at = 1, 0, m.end()
+        while depth:
+            ch = txt[at]
+            depth += (ch == "(") - (ch == ")")
+            commas += ch == "," and depth == 1
+            at += 1
+        inside = txt[m.end():at - 1].strip()
+        arity[m.group(1)] = 0 if inside in ("", "void") else commas + 1
+    arity.pop("ramx_allreduce_cb", None)
+    return arity
+
+
+def test_every_prototype_has_the_headers_parameter_count():
+    arity = _declared_arity()
+    assert set(arity) == _declared() == set(_lib.EXPORTS) and len(arity) == len(_lib.EXPORTS) == 93
+    lib = _lib.lib()
+    bound = {name: getattr(lib, name).argtypes for name in _lib.EXPORTS}
+    bound = {name: argtypes for name, argtypes in bound.items() if argtypes is not None}
+    assert len(bound) >= 70                                           # lib() sets the prototypes of most entries
+    for name, argtypes in bound.items():
+        assert len(argtypes) == arity[name], name
+
+
 def test_library_exports_every_declared_symbol():
     assert os.path.exists(_lib.LIB_PATH), "build libramx.so first (__graft_entry__.build())"
     lib = ctypes.CDLL(_lib.LIB_PATH)
