@@ -1185,6 +1185,8 @@ static int prk_run(ramx_dev *d, const KArgs &a, int L, DirRoute &rt, bool *used)
     ka.lean_p = pa.lean_p; ka.leader_max = pa.leader_max;
     ka.spec_on = getenv("RAMX_NO_PK_SPEC") == NULL ? 1 : 0;
     { const char *we = getenv("RAMX_TEST_PK_WRONG_EVERY"); ka.test_wrong_every = we ? atoi(we) : 0; }
+    // distance between two checkpoints of a speculating workgroup: 1, 2, 4 or 8 columns; anything else: the kernel adapts it
+    { const char *ck = getenv("RAMX_PK_CKPT"); const int v = ck ? atoi(ck) : 0; ka.ckpt = (v == 1 || v == 2 || v == 4 || v == 8) ? v : 0; }
     // test hook: a span smaller than the scoring system's makes the kernel's own checks (rows at entry, every 64th row) refuse
     { const char *ts = getenv("RAMX_TEST_PK_SPREAD"); if (ts) ka.spread = atoi(ts); }
     ka.spread_rows = ka.spread;

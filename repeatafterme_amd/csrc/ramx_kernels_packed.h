@@ -361,7 +361,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void ramx_packed_kernel(const P
     int cnt[2][2];                                     // waves that have added theirs
     int st[4];                                         // the stop rule's state, kept by the vote wave: max_ext (2 words), max_row, overflow
     int lead[WPB][2 * NP + NW + 1];                    // pkb_leader_rows: a leader's row, chain registers and base words, per wave
-    int eb[SPEC ? BLOCK * NP : 1];                     // the chain registers of row r-1 while row r stands on a guess: [thread][pair]
+    int eb[SPEC ? BLOCK * NP : 1];                     // the chain registers of the checkpoint (the row rows on a guess go back to): [thread][pair]
                                                        // (NP is odd: a wave's 64 columns start in different banks)
   };
   __shared__ __attribute__((aligned(16))) Smem sm;
@@ -538,7 +538,22 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void ramx_packed_kernel(const P
   // workgroup, and a row is only ever one unconfirmed step ahead, so results cannot differ from the lock-step order.  A
   // workgroup whose sums are all equal (all its flanks at their caps) knows nothing about the winner: it waits for the vote
   // as before, but its LEAN waves have sent their sums before the band, so the exchange runs beside its band as well.
-  int spec = 0, guess = 0;               // this column: compute on the workgroup's own argmax before the vote is known
+  //
+  // What comes back after a wrong guess is a CHECKPOINT: the state at the top of column ck_row (row ck_row - 1: m in registers,
+  // e in LDS, the records), taken ahead of a speculative column at most once per `dist` columns (1, 2, 4 or 8) and never kept
+  // across the column in which w[] shifts -- so every row since the checkpoint reads the base words the wave still holds.
+  // ck_log keeps the confirmed winner of every row since ck_row (2 bits each).  Wrong guess at row r: the checkpoint comes back,
+  // the column loop steps back to ck_row and comes through rows ck_row .. r-1 again SILENTLY on the logged winners (no vote, no
+  // arrival, no ticket, no trim, no counts: all of that left the workgroup when those rows were confirmed; span check and rebase
+  // run as they did), then through row r on the device's winner, whose decision waits in `pend`.  A wrong guess makes the
+  // workgroup checkpoint every column again (what it did before there were checkpoints) for 32 columns -- wrong guesses come in
+  // clusters, and with a fixed distance of 8 the rows computed again cost more than the backups saved -- and the distance then
+  // doubles every 8 columns while the guesses stand.  RAMX_PK_CKPT = 1 / 2 / 4 / 8 fixes it (1: a backup per row).
+  int Rb[SPEC ? NP : 1], high_b = 0, pos_b = 0, prev_b = 0, pbase_b = 0;       // the checkpoint: m in registers, e in LDS (sm.eb)
+  int ck_row = 0, ck_valid = 0, ck_calm = 64;      // (wave-uniform) its column; usable; columns since the last wrong guess, saturating
+  unsigned ck_log = 0;
+  int replay_to = -1, pend = 0;                    // the row whose guess was wrong while the rows before it run again, and its decision
+  int spec = 0, guess = 0;              // this column: compute on the workgroup's own argmax before the vote is known
   for (int r = a.r0; r < a.Lseg; r++)
   {
     PKB_TICK(5);
@@ -546,7 +561,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void ramx_packed_kernel(const P
     // scalar copy of the base pointer makes every column recompute them, ramx_kernels_resident.h round 3)
     PShard *vb = a.vote;
     asm volatile("" : "+s"(vb));
-    if (((r + 8) & 7) == 0 && r > a.r0)
+    if (((r + 8) & 7) == 0 && r > a.r0 && replay_to < 0)       // (a checkpoint at the top of a block is behind this shift)
     {
       static_for([&](auto kc) __attribute__((always_inline)) { constexpr int k = decltype(kc)::value; w[k] = w[k + 1]; }, std::make_integer_sequence<int, NW - 1>{});
       const int kn = ((r + 8) >> 3) + NW;
@@ -554,6 +569,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void ramx_packed_kernel(const P
       asm volatile("" : "+v"(nn), "+v"(bb));           // (address and mask are formed here, not carried through the loop)
       w[NW - 1] = pkb_mask_word(wnext, kn - 1, PKB_BDY9X4(bb));      // the word loaded eight columns ago (unmasked until now: nobody waited for it)
       wnext = a.bases[(size_t)kn * a.Np + nn];
+      if (ck_row != r) ck_valid = 0;                   // the rows behind an older checkpoint read words that have just left
     }
     const int par = r & 1, npar = (r + 1) & 1;
     // the last column of a launch that is not the last of the direction (the host runs a long direction in segments, packing the
@@ -665,23 +681,21 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void ramx_packed_kernel(const P
     };
 
     // ---- row r: on the guess first (if this workgroup has one), on the winner otherwise / afterwards -----------------------
-    int Rb[SPEC ? NP : 1], high_b = 0, pos_b = 0, prev_b = 0, pbase_b = 0;       // row r-1: m in registers, e in LDS (sm.eb)
     int *myEb = sm.eb + (SPEC ? threadIdx.x * NP : 0);
     bool pass_spec = false;
     int wsel = 0;
-    if (spec)
+    const bool silent = r < replay_to;     // a row since the checkpoint, computed again without a word to anybody
+    if (silent) wsel = (int)((ck_log >> (2 * ((r - ck_row) & 7))) & 3u);
+    else if (r == replay_to)
     {
-      if constexpr (SPEC)
-      {
-#ifndef PKB_PROBE_NO_BACKUP      // timing probe (wrong results after a wrong guess)
-        if (live)         // (a wave without flanks -- the vote wave of the 320-thread shape, padding tiles -- has nothing to keep)
-        static_for([&](auto kc) __attribute__((always_inline)) { constexpr int k = decltype(kc)::value; Rb[k] = R[k]; myEb[k] = E[k]; }, std::make_integer_sequence<int, NP>{});
-#else
-        Rb[0] = R[0];
-#endif
-        high_b = high; pos_b = pos; prev_b = prevBest; pbase_b = pbase;
-      }
-      pass_spec = true;
+      // back at the row whose guess was wrong: the vote has been seen, the winner is known
+      besta = pend & 3; new_max = (pend & 4) != 0; last_col = (pend & 8) != 0;
+      wsel = besta;
+      replay_to = -1;
+    }
+    else if (spec)
+    {
+      pass_spec = true;                    // (the checkpoint behind this row was taken, if one was due, at the end of the column before)
       wsel = guess;
       if (a.test_wrong_every > 0 && (r % a.test_wrong_every) == 0) wsel = (guess + 1) & 3;      // test hook: a deliberately wrong guess
     }
@@ -692,7 +706,8 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void ramx_packed_kernel(const P
     }
     bool confirmed_arrival = false;        // this wave's sums of row r+1 (from the confirmed row r) have joined set 1
     bool gave_up = false;                  // (wave-uniform, unlike `failed`, which the vote wave's lanes set one by one)
-    for (;;)
+    bool rewind = false;                   // a wrong guess: the column loop steps back to the checkpoint
+    do
     {
       const int set = pass_spec ? 0 : 1;
       // ---- LEAN?  (ramx_kernels_resident.h: no lane can contribute more than its cap to the vote of row r+1 or set a record in
@@ -709,7 +724,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void ramx_packed_kernel(const P
         else if (__popcll(keep) <= a.leader_max) { lean = true; leaders = keep; }
       }
       if (!live) early = true;
-      const bool send = pass_spec || !last_col;
+      const bool send = !silent && (pass_spec || !last_col);
       if (early && send)
       {
         // this wave's contribution to row r+1 is the sum of its caps whatever the row holds (ram_extend.c:1042, 1052-1062)
@@ -808,7 +823,7 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void ramx_packed_kernel(const P
             contrib[c] = (b >= capv) ? b : capv;
           }
         }
-        if (!pass_spec) { if (lean) lean_rows++; else full_rows++; }
+        if (!pass_spec && !silent) { if (lean) lean_rows++; else full_rows++; }
       }
       PKB_TICK(2);                 // band done
       if (!early && send)
@@ -860,18 +875,30 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void ramx_packed_kernel(const P
         if (lane == 0) asm volatile("ds_write_b32 %0, %1" : : "v"(pkb_lds_off(&sm.cnt[0][npar])), "v"(0) : "memory");
       }
       if (right) break;
-      // guessed wrong: back to row r-1 and the records behind it
+      // guessed wrong: back to the checkpoint (row ck_row - 1 and the records behind it), and from there to row r-1 in silence
       if constexpr (SPEC)
       {
         if (live)
         static_for([&](auto kc) __attribute__((always_inline)) { constexpr int k = decltype(kc)::value; R[k] = Rb[k]; E[k] = myEb[k]; }, std::make_integer_sequence<int, NP>{});
         high = high_b; pos = pos_b; prevBest = prev_b; pbase = pbase_b;
+        ck_calm = 0;
+        // the column loop goes back to ck_row and comes through rows ck_row .. r-1 again on the logged winners, then through
+        // row r on the device's winner (the band keeps its one call site, and no pass of it follows another inside a column)
+        pend = besta | (new_max ? 4 : 0) | (last_col ? 8 : 0);
+        replay_to = r;
+        r = ck_row - 1;
+        rewind = true;
       }
       wrong_rows++;
-      pass_spec = false;
-      wsel = besta;
-    }
+    } while (false);
     if (gave_up) break;
+    if (rewind || silent) continue;
+    if constexpr (SPEC)
+    {
+      // the confirmed winner of row r joins the log; a column further from the last wrong guess
+      ck_log |= (unsigned)besta << (2 * ((r - ck_row) & 7));
+      ck_calm = ck_calm < 64 ? ck_calm + 1 : 64;
+    }
 #ifndef PKB_PROBE_NO_TRIM
     if (new_max && live)                                        // ram_extend.c:1203-1207 (the confirmed records)
 #else
@@ -895,6 +922,24 @@ __global__ __launch_bounds__(BLOCK, BLOCK / 256) void ramx_packed_kernel(const P
         next_guess = __builtin_amdgcn_readfirstlane(gw);
       }
       spec = next_guess >> 8; guess = next_guess & 3;
+      // ---- the checkpoint, if the next column runs on a guess and one is due: the state at its top.  (Taken HERE, on the
+      // straight path at the end of the column: under the branches at the top of the column the checkpoint registers took part
+      // in the merges of that branching and were copied, all 41, into a second set and back in every column.) ----
+      if (spec)
+      {
+        const int dist = a.ckpt > 0 ? a.ckpt : ck_calm < 32 ? 1 : ck_calm < 40 ? 2 : ck_calm < 48 ? 4 : 8;
+        if (!ck_valid || ((r + 1) & (dist - 1)) == 0)
+        {
+#ifndef PKB_PROBE_NO_BACKUP      // timing probe (wrong results after a wrong guess)
+          if (live)         // (a wave without flanks -- the vote wave of the 320-thread shape, padding tiles -- has nothing to keep)
+          static_for([&](auto kc) __attribute__((always_inline)) { constexpr int k = decltype(kc)::value; Rb[k] = R[k]; myEb[k] = E[k]; }, std::make_integer_sequence<int, NP>{});
+#else
+          Rb[0] = R[0];
+#endif
+          high_b = high; pos_b = pos; prev_b = prevBest; pbase_b = pbase;
+          ck_row = r + 1; ck_valid = 1; ck_log = 0;
+        }
+      }
     }
   }
 #ifdef RAMX_PRK_TIMING

@@ -36,6 +36,8 @@ struct PKArgs
   int rebase;                   // |best cell - base| that moves the base (looked at every 16th row)
   int spec_on;                  // 1: a workgroup computes a row on its own argmax before the vote is known (RAMX_NO_PK_SPEC=1: 0)
   int test_wrong_every;         // test hook (RAMX_TEST_PK_WRONG_EVERY=n): every n-th guess is replaced by another base; 0 = off
+  int ckpt;                     // columns between two checkpoints of a speculating workgroup (RAMX_PK_CKPT = 1, 2, 4, 8; 1: a backup
+                                // per row); 0: 8, falling to 1 for 32 columns after a wrong guess and doubling from there
   unsigned long long *dbg;      // -DRAMX_PRK_TIMING builds only: [wave][8] phase sums in 10 ns ticks
 };
 
