@@ -1,4 +1,4 @@
-"""ctypes loader for libramx.so (include/ramx.h).  Fails loudly: there is no CPU path."""
+"""ctypes loader for libramx.so (include/ramx.h, include/ramx_dist.h).  Fails loudly: there is no CPU path."""
 from __future__ import annotations
 
 import ctypes as C
@@ -29,6 +29,11 @@ EXPORTS = [
     "ramx_dev_tsd", "ramx_tsd_sites", "ramx_tsd_summary", "ramx_termini", "ramx_tsd_flat", "ramx_tsd_alignment", "ramx_tsd_batch",
     "ramx_dev_period", "ramx_period_sequence", "ramx_period_segments", "ramx_period_summary", "ramx_period_flat", "ramx_period_alignment", "ramx_period_batch",
     "ramx_dev_term", "ramx_term_pair", "ramx_term_summary", "ramx_term_flat", "ramx_term_alignment", "ramx_term_batch",
+]
+
+# every symbol include/ramx_dist.h declares (tests/test_cabi_dist.py checks the .so exports all of them)
+EXPORTS_DIST = [
+    "ramx_dev_copy_dist", "ramx_dev_copy_dist_ms", "ramx_select_copies", "ramx_dist_kimura", "ramx_dist_summary", "ramx_set_dist_sink",
 ]
 
 
@@ -168,6 +173,22 @@ class TermFamily(C.Structure):      # ramx_term_family
     _fields_ = [(k, C.c_int32) for k in ("n", "n_direct", "n_inverted", "direct_anchored", "inverted_anchored", "direct_median",
                                          "inverted_median", "verdict")] + \
                [(k, C.c_int64) for k in ("direct_matches", "direct_columns", "inverted_matches", "inverted_columns")]
+
+
+class CopyDistRec(C.Structure):     # ramx_copy_dist
+    _fields_ = [(k, C.c_int32) for k in ("cover", "sites", "ts", "tv", "del_one", "del_both")]
+
+
+class DistFamily(C.Structure):      # ramx_dist_family
+    _fields_ = [(k, C.c_int32) for k in ("n", "pairs", "used", "medoid")] + [("mean", C.c_double), ("medoid_mean", C.c_double)]
+
+
+class DistRec(C.Structure):         # ramx_dist
+    _fields_ = [(k, C.c_int32) for k in ("direction", "family", "rows", "n_flanks", "n_copies")] + \
+               [(k, C.c_void_p) for k in ("cons", "core_index", "ends", "copies", "dist")]
+
+
+DIST_CB = C.CFUNCTYPE(None, C.POINTER(DistRec), C.c_void_p)
 
 
 def build(force: bool = False) -> None:
@@ -328,6 +349,18 @@ def lib() -> C.CDLL:
         L.ramx_term_alignment.restype = C.c_int
         L.ramx_term_batch.argtypes = [C.POINTER(Family), C.c_int32, C.POINTER(TermParams), C.c_void_p]
         L.ramx_term_batch.restype = C.c_int
+        L.ramx_dev_copy_dist.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ramx_dev_copy_dist.restype = C.c_int
+        L.ramx_dev_copy_dist_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        L.ramx_dev_copy_dist_ms.restype = None
+        L.ramx_select_copies.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+        L.ramx_select_copies.restype = C.c_int32
+        L.ramx_dist_kimura.argtypes = [C.c_void_p]
+        L.ramx_dist_kimura.restype = C.c_double
+        L.ramx_dist_summary.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DistFamily)]
+        L.ramx_dist_summary.restype = C.c_int
+        L.ramx_set_dist_sink.argtypes = [DIST_CB, C.c_void_p, C.c_int32, C.c_int32]
+        L.ramx_set_dist_sink.restype = None
         if hasattr(L, "ramx_cli_main"):
             L.ramx_cli_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
         _lib = L

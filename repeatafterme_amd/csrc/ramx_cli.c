@@ -2,7 +2,7 @@
  * ramx_cli.c -- the RAMExtend command line (reference ram_extend.c:123-826 main/usage/
  * print_parameters, cmd_line_opts.c).  Same argv semantics (prefix matching, per-matrix
  * defaults), same stdout / -cons / -outtsv / -outfa bytes; the two extend_alignment calls go to
- * the device path (ramx_extend_alignment).  The analysis outputs (-outprofile ... -outterm) are ramx_cli_outputs.c; the two
+ * the device path (ramx_extend_alignment).  The analysis outputs (-outprofile ... -outdist) are ramx_cli_outputs.c; the two
  * drivers here reach them through outputs_begin / outputs_family_done / outputs_post / outputs_end.
  */
 #include <fcntl.h>
@@ -116,6 +116,10 @@ static void usage(void)
     "     -termgap <num>        # ... what a base left out costs, 1..31 (5),\n"
     "     -termmin <num>        # ... the lowest score reported (40),\n"
     "     -termslack <num>      # ... a repeat is anchored within this many bases of the termini, 0..15 (3).\n"
+    "     -outdist <file>       # Save the pairwise divergence between the extended copies ( is the family a star, has\n"
+    "                           #   it structure, which copy is the medoid? ) to a TSV file: one line per pair.\n"
+    "     -distmin <num>        # ... a copy is compared from this many columns, a pair counts from as many sites (20),\n"
+    "     -distmax <num>        # ... at most this many copies a direction, those of the most columns, 2..2048 (256).\n"
     "     -version              # Print out one-line version information\n"
     "     -v[v[v[v]]]           # How verbose do you want it to be?  -vvvv is super-verbose.\n"
     "\n"
@@ -430,12 +434,12 @@ static void write_results(const struct cli_opts *o, struct family_outputs *fo, s
 /*
  * -batch <list>: many families in one process and ONE launch per direction (no counterpart in the reference, whose
  * wrapper util/extend-stk.pl:242-371 starts one RAMExtend per family).  Every non-empty, non-# line of <list> holds up to
- * sixteen tab-separated fields, the first two required, "-" or nothing for a file that is not wanted:
+ * seventeen tab-separated fields, the first two required, "-" or nothing for a file that is not wanted:
  *      1 ranges.tsv      2 log             3 -cons           4 -outtsv         5 -outfa
  *      6 -outprofile     7 -outaln         8 -outpileup      9 -outrefined    10 -outcopies
  *     11 -outlinkage    12 -outsubfam     13 -outtsd        14 -outcpg        15 -outperiod
- *     16 -outterm
- * (fields 6 to 16 are the batch_field column of k_outputs, ramx_cli_outputs.c; -outdinuc has none).  All other options
+ *     16 -outterm       17 -outdist
+ * (fields 6 to 17 are the batch_field column of k_outputs, ramx_cli_outputs.c; -outdinuc has none).  All other options
  * (-twobit, -L, -bandwidth, -matrix ...) are shared.  For every family the log file receives exactly what a stand-alone run
  * prints on stdout, and every file is what its flag gives.
  */
@@ -746,6 +750,10 @@ int ramx_cli_main(int argc, char **argv)
   if (!opt_int(argc, argv, "-termslack", &o.term.slack)) o.term.slack = 3;
   o.term.reserved[0] = o.term.reserved[1] = 0;
   if (ramx_term_check_params(&o.term) != RAMX_OK) { fprintf(stderr, "RAMExtend(ramx): %s\n", ramx_last_error()); exit(1); }
+  if (!opt_int(argc, argv, "-distmin", &o.distmin)) o.distmin = DEF_DISTMIN;
+  if (!opt_int(argc, argv, "-distmax", &o.distmax)) o.distmax = DEF_DISTMAX;
+  if (o.distmax < 2 || o.distmax > RAMX_DIST_MAX_COPIES)
+  { fprintf(stderr, "RAMExtend(ramx): -distmax %d outside 2..%d\n", o.distmax, RAMX_DIST_MAX_COPIES); exit(1); }
   if (!opt_int(argc, argv, "-refine", &o.refine)) o.refine = DEF_REFINE;
   if (o.refine < 1) { fprintf(stderr, "RAMExtend(ramx): -refine takes the largest number of replays, at least 1\n"); exit(1); }
   if (!opt_int(argc, argv, "-L", &o.L)) o.L = 10000;

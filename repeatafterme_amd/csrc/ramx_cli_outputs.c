@@ -484,6 +484,106 @@ static void subfam_write(FILE *fp, struct family_outputs *fo)
 }
 
 /* ------------------------------------------------------------------ the sinks */
+/*
+ * -outdist <file>: the pairwise divergence between the selected copies of both extensions (include/ramx_dist.h,
+ * ramx_set_dist_sink; -distmin <cols> and -distmax <copies> are its selection) as a TSV, the right block first: one line per
+ * pair a < b of selected copies in flank order, named as -outcopies names them, with the pair's record and its Kimura distance
+ * (NA: undefined), then one summary line "#<dir> copies= selected= pairs= used= kimura= medoid= medoid_kimura=" (ramx_dist_summary
+ * with min_sites = -distmin; medoid NA when no pair is used).  If both directions ran, a third block "both" follows: the cores
+ * selected in both directions, in the right block's order, every record the field-wise sum of the two directions' records.
+ * The names need both directions' lengths, so the sink keeps the records and the file is written with the other results.
+ */
+static void dist_sink(const ramx_dist *ds, void *user)
+{
+  struct family_outputs *fo = &((struct family_outputs *)user)[ds->family];
+  if (!fo->paths[OUT_DIST]) return;
+  struct dist_block *b = &fo->dist[ds->direction ? 1 : 0];
+  const size_t n = (size_t)ds->n_flanks, C = (size_t)ds->n_copies;
+  b->have = 1; b->n = ds->n_flanks; b->C = ds->n_copies;
+  b->core = (int32_t *)malloc(sizeof(int32_t) * (n ? n : 1));
+  b->sel = (int32_t *)malloc(sizeof(int32_t) * (C ? C : 1));
+  b->m = (ramx_copy_dist *)malloc(sizeof(ramx_copy_dist) * (C ? C * C : 1));
+  if (n) memcpy(b->core, ds->core_index, sizeof(int32_t) * n);
+  if (C) { memcpy(b->sel, ds->copies, sizeof(int32_t) * C); memcpy(b->m, ds->dist, sizeof(ramx_copy_dist) * C * C); }
+}
+
+/* one block: core[a] is the core of the a-th copy of the [C][C] matrix m */
+static void dist_block_write(FILE *fp, struct family_outputs *fo, const char *tag, int copies, const int32_t *core, int32_t C, const ramx_copy_dist *m)
+{
+  char ida[1024], idb[1024];
+  for (int32_t a = 0; a < C; a++)
+  {
+    record_id(ida, sizeof(ida), fo, core[a], "dist");
+    for (int32_t b = a + 1; b < C; b++)
+    {
+      const ramx_copy_dist *r = &m[(size_t)a * C + b];
+      fprintf(fp, "%s\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t", tag, ida, record_id(idb, sizeof(idb), fo, core[b], "dist"), r->cover, r->sites,
+              r->ts, r->tv, r->del_one, r->del_both);
+      const double k = ramx_dist_kimura(r);
+      if (k < 0) fputs("NA\n", fp);
+      else fprintf(fp, "%.4f\n", k);
+    }
+  }
+  ramx_dist_family s;
+  if (ramx_dist_summary(m, C, fo->o->distmin, &s) != RAMX_OK) { fprintf(stderr, "RAMExtend(ramx): pairwise distances: bad matrix\n"); exit(1); }
+  fprintf(fp, "#%s\tcopies=%d\tselected=%d\tpairs=%d\tused=%d\tkimura=%.4f\t", tag, copies, (int)C, (int)s.pairs, (int)s.used, s.mean);
+  if (s.medoid < 0) fputs("medoid=NA\tmedoid_kimura=NA\n", fp);
+  else fprintf(fp, "medoid=%s\tmedoid_kimura=%.4f\n", record_id(ida, sizeof(ida), fo, core[s.medoid], "dist"), s.medoid_mean);
+}
+
+/* after both directions: the file, then the buffers are released */
+static void dist_write(FILE *fp, struct family_outputs *fo)
+{
+  fputs("dir\tcopy_a\tcopy_b\tcover\tsites\tts\ttv\tdel_one\tdel_both\tkimura\n", fp);
+  for (int dir = 1; dir >= 0; dir--)
+  {
+    struct dist_block *b = &fo->dist[dir];
+    if (!b->have) continue;
+    int32_t *core = (int32_t *)malloc(sizeof(int32_t) * (size_t)(b->C > 0 ? b->C : 1));
+    for (int32_t a = 0; a < b->C; a++) core[a] = b->core[b->sel[a]];
+    dist_block_write(fp, fo, k_dir[dir], b->n, core, b->C, b->m);
+    free(core);
+  }
+  struct dist_block *r = &fo->dist[1], *l = &fo->dist[0];
+  if (r->have && l->have)
+  {
+    /* where a core stands in the left block's selection and whether it is a flank there at all */
+    const size_t nc = (size_t)(fo->n_cores > 0 ? fo->n_cores : 1);
+    int32_t *at = (int32_t *)malloc(sizeof(int32_t) * nc), *core = (int32_t *)malloc(sizeof(int32_t) * (size_t)(r->C > 0 ? r->C : 1));
+    int32_t *ra = (int32_t *)malloc(sizeof(int32_t) * (size_t)(r->C > 0 ? r->C : 1)), *la = (int32_t *)malloc(sizeof(int32_t) * (size_t)(r->C > 0 ? r->C : 1));
+    char *in_left = (char *)calloc(nc, 1);
+    for (size_t c = 0; c < nc; c++) at[c] = -1;
+    for (int i = 0; i < l->n; i++) if (l->core[i] >= 0 && l->core[i] < fo->n_cores) in_left[l->core[i]] = 1;
+    for (int32_t a = 0; a < l->C; a++) { const int32_t c = l->core[l->sel[a]]; if (c >= 0 && c < fo->n_cores) at[c] = a; }
+    int both = 0;
+    for (int i = 0; i < r->n; i++) both += r->core[i] >= 0 && r->core[i] < fo->n_cores && in_left[r->core[i]];
+    int32_t C = 0;
+    for (int32_t a = 0; a < r->C; a++)
+    {
+      const int32_t c = r->core[r->sel[a]];
+      if (c < 0 || c >= fo->n_cores || at[c] < 0) continue;
+      core[C] = c; ra[C] = a; la[C] = at[c]; C++;
+    }
+    ramx_copy_dist *m = (ramx_copy_dist *)malloc(sizeof(ramx_copy_dist) * (size_t)(C > 0 ? (size_t)C * C : 1));
+    for (int32_t a = 0; a < C; a++)
+      for (int32_t b = 0; b < C; b++)
+      {
+        const ramx_copy_dist *x = &r->m[(size_t)ra[a] * r->C + ra[b]], *y = &l->m[(size_t)la[a] * l->C + la[b]];
+        ramx_copy_dist *z = &m[(size_t)a * C + b];
+        z->cover = x->cover + y->cover; z->sites = x->sites + y->sites; z->ts = x->ts + y->ts; z->tv = x->tv + y->tv;
+        z->del_one = x->del_one + y->del_one; z->del_both = x->del_both + y->del_both;
+      }
+    dist_block_write(fp, fo, "both", both, core, C, m);
+    free(at); free(core); free(ra); free(la); free(in_left); free(m);
+  }
+  for (int dir = 0; dir < 2; dir++)
+  {
+    struct dist_block *b = &fo->dist[dir];
+    free(b->core); free(b->sel); free(b->m);
+    memset(b, 0, sizeof(*b));
+  }
+}
+
 static int any_wants(const struct family_outputs *fams, int F, int row)
 {
   for (int i = 0; fams != NULL && i < F; i++)
@@ -507,6 +607,7 @@ static void install_sinks(const struct cli_opts *o, struct family_outputs *fams,
   if (WANTED(OUT_SUBFAM))
     ramx_set_subfam_sink(fams ? subfam_sink : NULL, fams, o->linkcount, o->linkfrac, max_variants, (double)o->linkscore, o->subfamk, o->subfamiter,
                          o->subfammin, o->refine);
+  if (WANTED(OUT_DIST)) ramx_set_dist_sink(fams ? dist_sink : NULL, fams, o->distmin, o->distmax);
 #undef WANTED
 }
 
@@ -768,6 +869,7 @@ const struct output_row k_outputs[N_OUTPUTS] = {
   [OUT_TSD]     = { "-outtsd",     13, "target-site duplication", REFUSE("target-site duplication file is the thirteenth field of its line in the list"), .post = tsd_post },
   [OUT_PERIOD]  = { "-outperiod",  15, "periodicity",             REFUSE("periodicity file is the fifteenth field of its line in the list"), .post = period_post },
   [OUT_TERM]    = { "-outterm",    16, "terminal repeat",         REFUSE("terminal repeat file is the sixteenth field of its line in the list"), .post = term_post },
+  [OUT_DIST]    = { "-outdist",    17, "pairwise distance",       REFUSE("pairwise distance file is the seventeenth field of its line in the list"), .write = dist_write },
 };
 
 void outputs_refuse_flags(const struct cli_opts *o)
@@ -823,7 +925,8 @@ void outputs_post(const struct cli_opts *o, struct family_outputs *fams, int F, 
 void outputs_end(struct family_outputs *fams, int F)
 {
   static const struct cli_opts k_defaults = { .refine = DEF_REFINE, .cpgscore = DEF_CPGSCORE, .linkcount = DEF_LINKCOUNT, .linkfrac = DEF_LINKFRAC,
-                                              .linkscore = DEF_LINKSCORE, .subfamk = DEF_SUBFAMK, .subfammin = DEF_SUBFAMMIN, .subfamiter = DEF_SUBFAMITER };
+                                              .linkscore = DEF_LINKSCORE, .subfamk = DEF_SUBFAMK, .subfammin = DEF_SUBFAMMIN, .subfamiter = DEF_SUBFAMITER,
+                                              .distmin = 1, .distmax = DEF_DISTMAX };
   install_sinks(&k_defaults, NULL, 0);          /* the one reset */
   for (int i = 0; i < F; i++) { free(fams[i].cores); fams[i].cores = NULL; }
 }

@@ -4,19 +4,21 @@
 #define RAMX_CLI_OUTPUTS_H
 
 #include "ramx_internal.h"
+#include "ramx_dist.h"
 
 /* the rows of the table of analysis outputs (ramx_cli_outputs.c, k_outputs), in the order in which their files are started and
  * written */
 enum
 {
   OUT_PROFILE, OUT_ALN, OUT_PILEUP, OUT_REFINED, OUT_COPIES, OUT_CPG, OUT_DINUC, OUT_LINKAGE, OUT_SUBFAM, OUT_TSD, OUT_PERIOD,
-  OUT_TERM,
+  OUT_TERM, OUT_DIST,
   N_OUTPUTS
 };
-#define BATCH_FIELDS 16          /* of a -batch line: ranges, log, -cons, -outtsv, -outfa and the rows' batch_field */
+#define BATCH_FIELDS 17          /* of a -batch line: ranges, log, -cons, -outtsv, -outfa and the rows' batch_field */
 
 /* the defaults of the options the sinks take: what the command line starts from and what a sink is reset to */
-enum { DEF_REFINE = 10, DEF_CPGSCORE = 0, DEF_LINKCOUNT = 4, DEF_LINKFRAC = 100, DEF_LINKSCORE = 3, DEF_SUBFAMK = 4, DEF_SUBFAMMIN = 4, DEF_SUBFAMITER = 8 };
+enum { DEF_REFINE = 10, DEF_CPGSCORE = 0, DEF_LINKCOUNT = 4, DEF_LINKFRAC = 100, DEF_LINKSCORE = 3, DEF_SUBFAMK = 4, DEF_SUBFAMMIN = 4, DEF_SUBFAMITER = 8,
+       DEF_DISTMIN = 20, DEF_DISTMAX = 256 };
 
 /* everything the command line decides */
 struct cli_opts
@@ -27,7 +29,7 @@ struct cli_opts
   ramx_period_params period;
   int periodwhole;
   ramx_term_params term;
-  int refine, cpgscore, linkcount, linkfrac, linkscore, subfamk, subfammin, subfamiter;
+  int refine, cpgscore, linkcount, linkfrac, linkscore, subfamk, subfammin, subfamiter, distmin, distmax;
   int flanking, L, bandwidth, maxn, when_to_stop, num_threads, verbose;
   int gap_ext, gap_open, match, mismatch, cappenalty, minimprovement, is_rs;
   struct scoringSystem *sp;
@@ -81,6 +83,7 @@ struct flank_rec { int core, end_row, start, end, score; char *body; ramx_copy_s
 struct flank_block { int have, ret, n; char *cons; struct flank_rec *rec; };
 struct kept_fasta { int have[2], rows[2], replays[2], converged[2], n_cpg[2]; char *seq[2]; };
 struct linkage_block { int have, P; ramx_plane *planes; int32_t *co; };
+struct dist_block { int have, n, C; int32_t *core, *sel; ramx_copy_dist *m; };   /* core: [n] every flank's; sel: [C] flanks; m: [C][C] */
 struct subfam_block { int have, n, K, iterations, converged; int32_t *core, *labels, *dist, *size; char **pattern, **cons; int *rows, *replays, *conv; };
 
 /* one family's outputs; the sinks get the array of these as `user` and index it by the record's family */
@@ -96,6 +99,7 @@ struct family_outputs
   struct kept_fasta refined, cpg;
   struct linkage_block linkage[2];
   struct subfam_block subfam[2];
+  struct dist_block dist[2];
 };
 
 FILE *open_or_die(const char *path, const char *mode, const char *word);

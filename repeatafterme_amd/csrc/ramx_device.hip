@@ -57,6 +57,7 @@
 #include "ramx_dinuc_api.h"
 #include "ramx_copystats_api.h"
 #include "ramx_linkage_api.h"
+#include "ramx_dist_api.h"
 #include "ramx_subfam_api.h"
 #include "ramx_tsd_api.h"
 #include "ramx_period_api.h"
@@ -183,6 +184,11 @@ struct ramx_dev
   size_t cap_lk_planes, cap_lk_base, cap_lk_at, cap_lk_coat, cap_lk_block, cap_lk_gfam, cap_lk_co;
   int planes_ready, lk_families; long long *lk_fam;
   double lk_gram_ms;        // HIP-event time of the last Gram kernel (ramx_dev_plane_gram_ms)
+  // ramx_dev_copy_dist (allocated on its first call): the chosen copies' bit streams over the rows, the lists it uploads and
+  // the pair records
+  unsigned long long *d_lk_streams; DistFam *d_lk_dfam; int4 *d_lk_ditem, *d_lk_dblock; int *d_lk_dslot; ramx_copy_dist *d_lk_dist;
+  size_t cap_lk_streams, cap_lk_dfam, cap_lk_ditem, cap_lk_dblock, cap_lk_dslot, cap_lk_dist;
+  double lk_dist_ms[2];     // HIP-event times of the transposition and the pair kernel of the last ramx_dev_copy_dist
   // ramx_dev_subfamilies (allocated on its first call): the lists it uploads, the labels, the mask planes and the counts; the
   // host keeps where the resident families' flanks lie (lk_place: first and count per family) and the replay's n_padded
   SubfamFam *d_sf_fam; long long *d_sf_at; longlong2 *d_sf_var; unsigned char *d_sf_pat; int2 *d_sf_tile, *d_sf_item;
@@ -289,6 +295,8 @@ extern "C" void ramx_dev_destroy(ramx_dev *d)
   (void)hipFree(d->d_dn_slab); (void)hipFree(d->d_dn_cols);
   (void)hipFree(d->d_lk_planes); (void)hipFree(d->d_lk_base); (void)hipFree(d->d_lk_at); (void)hipFree(d->d_lk_coat);
   (void)hipFree(d->d_lk_block); (void)hipFree(d->d_lk_gfam); (void)hipFree(d->d_lk_co);
+  (void)hipFree(d->d_lk_streams); (void)hipFree(d->d_lk_dfam); (void)hipFree(d->d_lk_ditem); (void)hipFree(d->d_lk_dblock);
+  (void)hipFree(d->d_lk_dslot); (void)hipFree(d->d_lk_dist);
   free(d->lk_fam);
   (void)hipFree(d->d_sf_fam); (void)hipFree(d->d_sf_at); (void)hipFree(d->d_sf_var); (void)hipFree(d->d_sf_pat);
   (void)hipFree(d->d_sf_tile); (void)hipFree(d->d_sf_item); (void)hipFree(d->d_sf_count); (void)hipFree(d->d_sf_labels);
@@ -2696,6 +2704,112 @@ extern "C" int ramx_dev_plane_gram(ramx_dev *d, int32_t n_families, const ramx_p
 }
 
 extern "C" double ramx_dev_plane_gram_ms(ramx_dev *d) { return d ? d->lk_gram_ms : 0; }
+
+// pairwise divergence between chosen copies of the resident replay (ramx_dist.h, ramx_kernels_dist.h): the planes transposed
+// into bit streams over the rows, then the pair matrix of the streams
+extern "C" int ramx_dev_copy_dist(ramx_dev *d, int32_t n_families, const int32_t *copies, const int32_t *copy_first,
+                                  const int32_t *copy_count, ramx_copy_dist *out, const int64_t *out_first)
+{
+  if (d) d->lk_dist_ms[0] = d->lk_dist_ms[1] = 0;
+  if (!d || n_families < 0 || (n_families && (!copy_first || !copy_count)))
+  { ramx_set_error("ramx_dev_copy_dist: bad argument"); return RAMX_ERR_ARG; }
+  if (!d->planes_ready)
+  { ramx_set_error("ramx_dev_copy_dist: no resident bit planes (ramx_dev_planes has not run on this device, or a later call dropped them)"); return RAMX_ERR_STATE; }
+  if (n_families != d->lk_families)
+  { ramx_set_error("ramx_dev_copy_dist: %d families, the resident replay has %d", n_families, d->lk_families); return RAMX_ERR_ARG; }
+  // everything is checked before anything is launched or written
+  std::vector<DistFam> dfam((size_t)(n_families > 0 ? n_families : 1));
+  std::vector<int4> item, block;
+  std::vector<int> slot;
+  size_t stream_words = 0, records = 0;
+  memset(dfam.data(), 0, dfam.size() * sizeof(DistFam));
+  for (int f = 0; f < n_families; f++)
+  {
+    const int C = copy_count[f], count = d->lk_place[2 * f + 1];
+    const long long frows = d->lk_fam[3 * (size_t)f], T = d->lk_fam[3 * (size_t)f + 1], base = d->lk_fam[3 * (size_t)f + 2];
+    if (C < 0 || C > RAMX_DIST_MAX_COPIES)
+    { ramx_set_error("ramx_dev_copy_dist: family %d: %d copies outside [0, %d]", f, C, RAMX_DIST_MAX_COPIES); return RAMX_ERR_ARG; }
+    if (C == 0) continue;
+    if (copy_first[f] < 0 || !copies || !out || !out_first || out_first[f] < 0)
+    { ramx_set_error("ramx_dev_copy_dist: family %d: bad argument", f); return RAMX_ERR_ARG; }
+    const int32_t *cp = copies + copy_first[f];
+    for (int i = 0; i < C; i++)
+    {
+      if (cp[i] < 0 || cp[i] >= count)
+      { ramx_set_error("ramx_dev_copy_dist: family %d, entry %d: copy %d outside the family's %d flanks", f, i, cp[i], count); return RAMX_ERR_ARG; }
+      if (i > 0 && cp[i] <= cp[i - 1])
+      { ramx_set_error("ramx_dev_copy_dist: family %d, entry %d: the copies are not strictly increasing", f, i); return RAMX_ERR_ARG; }
+    }
+    if (frows == 0) continue;                         // all-zero records, written below on the host
+    DistFam &fd = dfam[f];
+    fd.plane_base = base; fd.stream_base = (long long)stream_words; fd.out_base = (long long)records;
+    fd.T = (int)T; fd.rows = (int)frows; fd.RW = (int)((frows + 63) / 64); fd.C = C;
+    stream_words += (size_t)C * RAMX_DIST_STREAMS * fd.RW;
+    records += (size_t)C * C;
+    // one wave per tile that holds a chosen copy and per block of 64 rows (the list is ascending: a tile's copies are adjacent)
+    for (int i = 0; i < C; )
+    {
+      const int tile = cp[i] >> 6, s0 = (int)slot.size();
+      slot.resize(slot.size() + 64, -1);
+      for (; i < C && (cp[i] >> 6) == tile; i++) slot[(size_t)s0 + (cp[i] & 63)] = i;
+      for (int rb = 0; rb < fd.RW; rb++) item.push_back(make_int4(f, tile, s0, rb));
+    }
+    const int nb = (C + RAMX_DIST_BLOCK - 1) / RAMX_DIST_BLOCK;
+    for (int bi = 0; bi < nb; bi++)
+      for (int bj = bi; bj < nb; bj++) block.push_back(make_int4(f, bi, bj, 0));
+  }
+  int rc = RAMX_OK;
+  if (!block.empty())
+  {
+    // a copy to count has passed rows[f] > 0 of a family with flanks: that replay has run and its buffer exists
+    HIPCHK(hipSetDevice(d->ordinal));
+    if ((rc = ensure(&d->d_lk_streams, &d->cap_lk_streams, stream_words * sizeof(unsigned long long)))) return rc;
+    if ((rc = ensure(&d->d_lk_dfam, &d->cap_lk_dfam, dfam.size() * sizeof(DistFam)))) return rc;
+    if ((rc = ensure(&d->d_lk_ditem, &d->cap_lk_ditem, item.size() * sizeof(int4)))) return rc;
+    if ((rc = ensure(&d->d_lk_dslot, &d->cap_lk_dslot, slot.size() * sizeof(int)))) return rc;
+    if ((rc = ensure(&d->d_lk_dblock, &d->cap_lk_dblock, block.size() * sizeof(int4)))) return rc;
+    if ((rc = ensure(&d->d_lk_dist, &d->cap_lk_dist, records * sizeof(ramx_copy_dist)))) return rc;
+    HIPCHK(hipMemcpyAsync(d->d_lk_dfam, dfam.data(), dfam.size() * sizeof(DistFam), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(d->d_lk_ditem, item.data(), item.size() * sizeof(int4), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(d->d_lk_dslot, slot.data(), slot.size() * sizeof(int), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(d->d_lk_dblock, block.data(), block.size() * sizeof(int4), hipMemcpyHostToDevice, d->stream));
+    DistArgs da;
+    da.planes = d->d_lk_planes; da.fam = d->d_lk_dfam; da.item = d->d_lk_ditem; da.slot = d->d_lk_dslot; da.block = d->d_lk_dblock;
+    da.streams = d->d_lk_streams; da.out = d->d_lk_dist;
+    hipEvent_t ev[3] = { NULL, NULL, NULL };
+    const bool timed = hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess && hipEventCreate(&ev[2]) == hipSuccess;
+    if (timed) (void)hipEventRecord(ev[0], d->stream);
+    rc = ramx_dist_transpose_launch(d->stream, (int)item.size(), da);
+    if (timed && rc == RAMX_OK) (void)hipEventRecord(ev[1], d->stream);
+    if (rc == RAMX_OK) rc = ramx_dist_pairs_launch(d->stream, (int)block.size(), da);
+    if (timed && rc == RAMX_OK) (void)hipEventRecord(ev[2], d->stream);
+    const hipError_t se = hipStreamSynchronize(d->stream);           // the uploads above read this function's vectors
+    float ms = 0;
+    if (timed && rc == RAMX_OK && se == hipSuccess)
+      for (int i = 0; i < 2; i++) d->lk_dist_ms[i] = hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess ? ms : 0;
+    for (int i = 0; i < 3; i++) if (ev[i]) (void)hipEventDestroy(ev[i]);
+    if (rc != RAMX_OK)
+    {
+      ramx_set_error("ramx_dev_copy_dist: the launch of %d waves and %d workgroups failed", (int)item.size(), (int)block.size());
+      return rc;
+    }
+    HIPCHK(se);
+  }
+  for (int f = 0; f < n_families; f++)
+  {
+    const size_t C = (size_t)copy_count[f];
+    if (C == 0) continue;
+    if (dfam[f].C == 0) memset(out + out_first[f], 0, C * C * sizeof(ramx_copy_dist));     // rows == 0
+    else HIPCHK(hipMemcpy(out + out_first[f], d->d_lk_dist + dfam[f].out_base, C * C * sizeof(ramx_copy_dist), hipMemcpyDeviceToHost));
+  }
+  return RAMX_OK;
+}
+
+extern "C" void ramx_dev_copy_dist_ms(ramx_dev *d, double ms[2])
+{
+  if (!ms) return;
+  ms[0] = d ? d->lk_dist_ms[0] : 0; ms[1] = d ? d->lk_dist_ms[1] : 0;
+}
 
 // one timed launch on d->stream: ms is added to *sum
 template <typename F>

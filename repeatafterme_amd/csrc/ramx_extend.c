@@ -13,6 +13,7 @@
 #include <pthread.h>
 
 #include "ramx_internal.h"
+#include "ramx_dist.h"
 
 /* the reference's hot-path globals (ram_extend.c:40,52,61) */
 static int g_verbose = 0;
@@ -935,7 +936,62 @@ static int subfam_families(const struct sink_view *v)
   return rc;
 }
 
-static int any_sink(void) { return g_profile_cb || g_align_cb || g_refine_cb || g_cpg_cb || g_copies_cb || g_linkage_cb || g_subfam_cb; }
+static ramx_dist_cb g_dist_cb = NULL;
+static void *g_dist_user = NULL;
+static int32_t g_dist_cols = 1, g_dist_max = 256;
+void ramx_set_dist_sink(ramx_dist_cb cb, void *user, int32_t min_cols, int32_t max_copies)
+{
+  g_dist_cb = cb;
+  g_dist_user = user;
+  g_dist_cols = min_cols;
+  g_dist_max = max_copies < 0 ? 0 : max_copies > RAMX_DIST_MAX_COPIES ? RAMX_DIST_MAX_COPIES : max_copies;
+}
+
+/* With a distance sink set: the bit planes of the families along their kept consensus (rows = ret), the copies selected from the
+ * ends of that replay and their pair matrix, handed over family by family. */
+static int dist_families(const struct sink_view *v)
+{
+  if (ramx_dev_is_multi(v->d))
+  { ramx_set_error("dist sink: not with a communicator or mailbox route active (a rank sees only its own copies)"); return RAMX_ERR_UNSUPPORTED; }
+  const ramx_params *p = v->p;
+  const int nb = v->nb;
+  const size_t L = (size_t)(p->L > 0 ? p->L : 1), n = (size_t)(nb > 0 ? nb : 1), np = (size_t)(v->npad > 0 ? v->npad : 1);
+  int32_t *cfirst = (int32_t *)calloc(n, sizeof(int32_t)), *ccount = (int32_t *)calloc(n, sizeof(int32_t));
+  int64_t *ofirst = (int64_t *)calloc(n, sizeof(int64_t));
+  ramx_col_pileup *cols = (ramx_col_pileup *)calloc(n * L, sizeof(ramx_col_pileup));
+  ramx_aln_end *ends = (ramx_aln_end *)malloc(sizeof(ramx_aln_end) * np);
+  int32_t *copies = (int32_t *)calloc(n * (size_t)(g_dist_max > 0 ? g_dist_max : 1), sizeof(int32_t));
+  ramx_copy_dist *dist = NULL;
+  for (int32_t i = 0; i < v->npad; i++) { ends[i].end_row = -1; ends[i].end_idx = -1; ends[i].score = 0; ends[i].start_idx = 0; ends[i].tail_ins = 0; }
+  int rc = ramx_dev_planes(v->d, v->fl, v->npad, v->first, v->count, nb, p, v->cons, v->ret, cols, ends, NULL);
+  if (rc == RAMX_OK)
+  {
+    int32_t at = 0;
+    int64_t cells = 0;
+    for (int b = 0; b < nb; b++)
+    {
+      cfirst[b] = at;
+      ccount[b] = v->count[b] > 0 && v->ret[b] > 0 ? ramx_select_copies(ends + v->first[b], v->count[b], v->ret[b], g_dist_cols, g_dist_max, copies + at) : 0;
+      ofirst[b] = cells;
+      at += ccount[b]; cells += (int64_t)ccount[b] * ccount[b];
+    }
+    dist = (ramx_copy_dist *)calloc((size_t)(cells > 0 ? cells : 1), sizeof(ramx_copy_dist));
+    rc = ramx_dev_copy_dist(v->d, nb, copies, cfirst, ccount, dist, ofirst);
+  }
+  for (int b = 0; b < nb && rc == RAMX_OK; b++)
+  {
+    ramx_dist ds;
+    memset(&ds, 0, sizeof(ds));
+    ds.direction = v->direction; ds.family = v->fidx[b]; ds.rows = v->ret[b]; ds.n_flanks = v->count[b]; ds.n_copies = ccount[b];
+    ds.cons = v->cons + (size_t)b * p->L; ds.core_index = v->map + v->first[b]; ds.ends = ends + v->first[b];
+    ds.copies = copies + cfirst[b]; ds.dist = dist + ofirst[b];
+    g_dist_cb(&ds, g_dist_user);
+  }
+  free(cfirst); free(ccount); free(ofirst); free(cols); free(ends); free(copies); free(dist);
+  return rc;
+}
+
+static int any_sink(void) { return g_profile_cb || g_align_cb || g_refine_cb || g_cpg_cb || g_copies_cb || g_linkage_cb || g_subfam_cb || g_dist_cb; }
 
 /* one RAMX_TIMING line: the time since the phase before, under the caller's name */
 static void phase_line(const char *who, int width, const char *name, double *since)
@@ -956,6 +1012,7 @@ static int run_sinks(const struct sink_view *v, const char *who, int width, int 
     { g_cpg_cb != NULL, cpg_families, "CpG-aware refinement" },
     { g_linkage_cb != NULL, linkage_families, "linkage" },
     { g_subfam_cb != NULL, subfam_families, "subfamilies" },
+    { g_dist_cb != NULL, dist_families, "pairwise distances" },
   };
   int rc = RAMX_OK;
   for (size_t i = 0; i < sizeof(sinks) / sizeof(sinks[0]) && rc == RAMX_OK; i++)

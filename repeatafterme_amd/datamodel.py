@@ -165,6 +165,36 @@ class Linkage:
     co: np.ndarray                   # int32 [P][P]
 
 
+# pairwise divergence between copies: C-ABI ramx_copy_dist (24 bytes), include/ramx_dist.h
+COPY_DIST_FIELDS = ("cover", "sites", "ts", "tv", "del_one", "del_both")
+COPY_DIST_DTYPE = np.dtype([(k, np.int32) for k in COPY_DIST_FIELDS])
+assert COPY_DIST_DTYPE.itemsize == 24
+DIST_MAX_COPIES = 2048               # RAMX_DIST_MAX_COPIES
+
+
+@dataclass
+class DistSummary:
+    """What a pair matrix says together (C-ABI ramx_dist_family)."""
+    n: int
+    pairs: int
+    used: int
+    medoid: int                      # place in the list, -1: none
+    mean: float
+    medoid_mean: float
+
+
+@dataclass
+class Dist:
+    """Pairwise divergence between selected copies of one direction of one family along its kept consensus (C-ABI ramx_dist)."""
+    direction: int
+    family: int                      # index in a batch, else 0
+    cons: np.ndarray                 # int8 [rows]: the kept consensus (rows = ret)
+    core_index: np.ndarray           # position in the core list of every flank
+    ends: np.ndarray                 # ALN_END_DTYPE [n_flanks]
+    copies: np.ndarray               # int32 [C]: the selected flanks, ascending
+    dist: np.ndarray                 # COPY_DIST_DTYPE [C][C]
+
+
 SUBFAM_MAX = 8                       # RAMX_SUBFAM_MAX
 
 

@@ -10,7 +10,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from .datamodel import (ALN_END_DTYPE, ALN_NONE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, DINUC_DTYPE, LINK_DTYPE, PILEUP_DTYPE, PILEUP_INS, PLANE_DTYPE,
+from .datamodel import (ALN_END_DTYPE, ALN_NONE, COL_PROFILE_DTYPE, COPY_DIST_DTYPE, COPY_STATS_DTYPE, DistSummary, DINUC_DTYPE, LINK_DTYPE, PILEUP_DTYPE, PILEUP_INS, PLANE_DTYPE,
                         TSD_DTYPE, TSD_SITE_DTYPE, PERIOD_DTYPE, PERIOD_SEG_DTYPE, TERM_DTYPE, CoreSet, ExtendParams, PeriodParams, TermParams, TsdParams)
 from .extend import RunInfo, _info, _params
 
@@ -151,6 +151,32 @@ class SubfamResult:
     iterations: int                        # assignments made
     converged: int
     masks: Optional[np.ndarray]            # uint64 [K][T]: the groups as bit planes, or None
+
+
+def select_copies(ends, rows: int, min_cols: int = 1, max_copies: int = 256) -> np.ndarray:
+    """Which copies to compare (C-ABI ramx_select_copies, host C): those of at least min_cols columns along `rows` rows, the
+    longest max_copies of them.  -> int32 [C], ascending."""
+    e = np.ascontiguousarray(ends, ALN_END_DTYPE).reshape(-1)
+    out = np.zeros(max(len(e), 1), np.int32)
+    n = _lib.lib().ramx_select_copies(e.ctypes.data if len(e) else None, len(e), int(rows), int(min_cols), int(max_copies), out.ctypes.data)
+    return out[:n].copy()
+
+
+def dist_kimura(rec) -> float:
+    """Kimura two-parameter distance (percent) of one COPY_DIST_DTYPE record (C-ABI ramx_dist_kimura); < 0: undefined."""
+    r = np.ascontiguousarray(rec, COPY_DIST_DTYPE).reshape(-1)
+    assert len(r) == 1
+    return float(_lib.lib().ramx_dist_kimura(r.ctypes.data))
+
+
+def dist_summary(m, min_sites: int = 1) -> DistSummary:
+    """Mean Kimura distance and medoid of a COPY_DIST_DTYPE [n][n] matrix (C-ABI ramx_dist_summary, host C)."""
+    a = np.ascontiguousarray(m, COPY_DIST_DTYPE)
+    n = int(round(a.size ** 0.5))
+    assert n * n == a.size
+    out = _lib.DistFamily()
+    _lib.check(_lib.lib().ramx_dist_summary(a.ctypes.data if n else None, n, int(min_sites), C.byref(out)), "ramx_dist_summary")
+    return DistSummary(int(out.n), int(out.pairs), int(out.used), int(out.medoid), float(out.mean), float(out.medoid_mean))
 
 
 def copy_kimura(stats) -> float:
@@ -486,6 +512,32 @@ class Device:
             return cos[0] if one else cos
         bws = [bw[b_first[f]:b_first[f] + bsz[f]].reshape(int(cnt[f]), tiles[f]) for f in range(nf)]
         return (cos[0], bws[0]) if one else (cos, bws)
+
+    def copy_dist(self, copies, fill=None):
+        """The pair matrix of chosen copies of the resident replay (C-ABI ramx_dev_copy_dist).  `copies`: one int32 array of
+        flank indices within the family (one family), or a list of them, one per family of the planes() call.  -> COPY_DIST_DTYPE
+        [C][C]; a list of them for a list.  fill: the byte the result buffer holds before the call (tests)."""
+        one = not isinstance(copies, (list, tuple))
+        lists = [np.ascontiguousarray(x, np.int32).reshape(-1) for x in ([copies] if one else copies)]
+        nf = len(lists)
+        cnt = np.array([len(x) for x in lists], np.int32)
+        first = np.concatenate([[0], np.cumsum(cnt)[:-1]]).astype(np.int32) if nf else np.zeros(0, np.int32)
+        allc = np.concatenate(lists + [np.zeros(1, np.int32)])
+        cells = cnt.astype(np.int64) ** 2
+        o_first = np.concatenate([[0], np.cumsum(cells)[:-1]]).astype(np.int64) if nf else np.zeros(0, np.int64)
+        out = np.zeros(max(int(cells.sum()), 1), COPY_DIST_DTYPE)
+        if fill is not None:
+            out.view(np.uint8)[:] = fill
+        _lib.check(self._L.ramx_dev_copy_dist(self._h, nf, allc.ctypes.data, first.ctypes.data, cnt.ctypes.data, out.ctypes.data,
+                                              o_first.ctypes.data), "ramx_dev_copy_dist")
+        ms = [out[o_first[f]:o_first[f] + int(cells[f])].reshape(int(cnt[f]), int(cnt[f])) for f in range(nf)]
+        return ms[0] if one else ms
+
+    def copy_dist_ms(self):
+        """HIP-event times of the transposition and the pair kernel of the last copy_dist() (C-ABI ramx_dev_copy_dist_ms)."""
+        ms = (C.c_double * 2)()
+        self._L.ramx_dev_copy_dist_ms(self._h, ms)
+        return float(ms[0]), float(ms[1])
 
     def subfamilies(self, planes, init, max_iter: int = 8, masks: bool = False, K: Optional[int] = None):
         """The copies of every family of the resident replay split by the variants they carry (C-ABI ramx_dev_subfamilies).

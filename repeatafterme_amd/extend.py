@@ -13,7 +13,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .datamodel import (ALN_END_DTYPE, COL_PROFILE_DTYPE, COPY_STATS_DTYPE, DINUC_DTYPE, FLANK_DTYPE, PILEUP_DTYPE, PLANE_DTYPE, Alignment, Copies, SubfamGroup, Subfamilies,
+from .datamodel import (ALN_END_DTYPE, COL_PROFILE_DTYPE, COPY_DIST_DTYPE, COPY_STATS_DTYPE, Dist, DINUC_DTYPE, FLANK_DTYPE, PILEUP_DTYPE, PLANE_DTYPE, Alignment, Copies, SubfamGroup, Subfamilies,
                         CoreSet, CpgRefinement, ExtendParams, Linkage, Profile, Refinement, TSD_DTYPE, TSD_SITE_DTYPE, TsdParams, TsdSummary,
                         PERIOD_DTYPE, PERIOD_SEG_DTYPE, PeriodParams, PeriodSummary, TERM_DTYPE, TermParams, TermSummary)
 
@@ -272,9 +272,42 @@ class _SubfamSink:
         return False
 
 
+class _DistSink:
+    """Collects what seam 1 hands to the distance sink (ramx_set_dist_sink) while the block runs.  select: (min_cols,
+    max_copies)."""
+    DEFAULT = (1, 256)
+
+    def __init__(self, select=DEFAULT):
+        self.got = []
+        self.select = tuple(int(x) for x in select)
+        assert len(self.select) == 2
+
+        def _cb(ptr, _user):
+            ds = ptr.contents
+
+            def grab(src, count, dtype):
+                out = np.zeros(count, dtype)
+                if count and src:
+                    C.memmove(out.ctypes.data, src, count * out.dtype.itemsize)
+                return out
+            n, c = ds.n_flanks, ds.n_copies
+            self.got.append(Dist(ds.direction, ds.family, grab(ds.cons, ds.rows, np.int8), grab(ds.core_index, n, np.int32),
+                                 grab(ds.ends, n, ALN_END_DTYPE), grab(ds.copies, c, np.int32),
+                                 grab(ds.dist, c * c, COPY_DIST_DTYPE).reshape(c, c)))
+        self._cb = _lib.DIST_CB(_cb)
+
+    def __enter__(self):
+        _lib.lib().ramx_set_dist_sink(self._cb, None, *self.select)
+        return self
+
+    def __exit__(self, *exc):
+        _lib.lib().ramx_set_dist_sink(_lib.DIST_CB(), None, *self.DEFAULT)
+        return False
+
+
 def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, master: np.ndarray,
                      p: ExtendParams, profile: bool = False, align: bool = False, refine: int = 0, copies: bool = False,
-                     linkage=None, subfam=None, cpg=None, period=None):
+                     linkage=None, subfam=None, cpg=None, period=None, dist=None):
     """direction: 1 = right, 0 = left (reference ram_extend.c:424,506).  profile=True: returns (RunInfo, Profile) -- the
     direction is replayed along the consensus it chose (C-ABI ramx_dev_profile) after the loop.  align=True: returns
     (RunInfo, Alignment), or (RunInfo, Profile, Alignment) with both -- every flank aligned to the kept consensus (C-ABI
@@ -287,7 +320,15 @@ def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, maste
     cpg=n > 0 or (n, cpg_ts): a CpgRefinement comes last of all -- the kept consensus refined over at most n replays with the
     CpG-aware re-call (C-ABI ramx_dev_refine_cpg).  period=True or a PeriodParams: the tandem periodicity of every core's
     extension in this direction, PERIOD_DTYPE [cores.n], comes behind everything (C-ABI ramx_period_flat with which = direction,
-    on the library the call left on the device)."""
+    on the library the call left on the device).  dist=True or (min_cols, max_copies): a Dist comes last of all, behind the
+    periodicity -- the pairwise divergence between the selected copies along the kept consensus (C-ABI ramx_dev_planes,
+    ramx_select_copies, ramx_dev_copy_dist; include/ramx_dist.h)."""
+    if dist:
+        with _DistSink(_DistSink.DEFAULT if dist is True else dist) as dsink:
+            res = extend_alignment(direction, cores, sequence, master, p, profile=profile, align=align, refine=refine, copies=copies,
+                                   linkage=linkage, subfam=subfam, cpg=cpg, period=period)
+        assert len(dsink.got) == 1
+        return (res + (dsink.got[0],)) if isinstance(res, tuple) else (res, dsink.got[0])
     if period:
         res = extend_alignment(direction, cores, sequence, master, p, profile=profile, align=align, refine=refine, copies=copies,
                                linkage=linkage, subfam=subfam, cpg=cpg)
@@ -345,14 +386,22 @@ def extend_alignment(direction: int, cores: CoreSet, sequence: np.ndarray, maste
 
 
 def extend_batch(direction: int, families, p: ExtendParams, profile: bool = False, align: bool = False, copies: bool = False,
-                 linkage=None, subfam=None, period=None):
+                 linkage=None, subfam=None, period=None, dist=None):
     """Many families in one launch (C-ABI ramx_extend_batch).  `families` is a list of (cores, sequence, master);
     every family is updated in place exactly like extend_alignment does for one.  Returns one RunInfo per family;
     profile=True: (RunInfos, Profiles), one Profile per family in the order of `families`; align=True: (RunInfos,
     Alignments), or (RunInfos, Profiles, Alignments) with both.  copies=True: the families' Copies come last in the tuple.
     linkage (as extend_alignment): the families' Linkages come behind everything else; subfam (as extend_alignment): their
     Subfamilies last of all.  period (as extend_alignment): one PERIOD_DTYPE array per family behind everything (C-ABI
-    ramx_period_batch with which = direction)."""
+    ramx_period_batch with which = direction).  dist (as extend_alignment): the families' Dists last of all."""
+    if dist:
+        with _DistSink(_DistSink.DEFAULT if dist is True else dist) as dsink:
+            res = extend_batch(direction, families, p, profile=profile, align=align, copies=copies, linkage=linkage, subfam=subfam,
+                               period=period)
+        by_family = {ds.family: ds for ds in dsink.got}
+        assert len(by_family) == len(dsink.got) == len(families)
+        dss = [by_family[i] for i in range(len(families))]
+        return (res + (dss,)) if isinstance(res, tuple) else (res, dss)
     if period:
         res = extend_batch(direction, families, p, profile=profile, align=align, copies=copies, linkage=linkage, subfam=subfam)
         recs = period_batch(families, 1 if direction else 0, None if period is True else period)

@@ -26,6 +26,7 @@ per direction the family's mean Kimura divergence over the extension beside the 
 simple repeat or a satellite? -- and the family's modal period per part (RAMExtend -outperiod).
 <id>-term.tsv: with -term, the terminal repeats of every extended copy -- its first bases repeated at its end, directly (LTR) or
 as their reverse complement (TIR) -- and the family's verdict (RAMExtend -outterm).
+<id>-dist.tsv: with -dist, the pairwise divergence between the extended copies (RAMExtend -outdist).
 
 (the re-alignment and Stockholm rewriting that follow in the wrapper belong to RepeatModeler and are out of scope).
 """
@@ -64,6 +65,8 @@ def main(argv=None):
                     "modal period of the copies' extensions")
     ap.add_argument("-term", action="store_true", help="also write <id>-term.tsv per family (RAMExtend -outterm) and print the "
                     "family's verdict (none, LTR, TIR) and the median lengths of the anchored repeats")
+    ap.add_argument("-dist", action="store_true", help="also write <id>-dist.tsv per family (RAMExtend -outdist): the pairwise "
+                    "divergence between the extended copies")
     ap.add_argument("-cpg", action="store_true", help="also write <id>-cpg-cons.fa per family (RAMExtend -outcpg)")
     ap.add_argument("-one_by_one", action="store_true", help="start one RAMExtend per family, as the wrapper does")
     a = ap.parse_args(argv)
@@ -110,7 +113,8 @@ def main(argv=None):
                                        (["-outtsd", base + "-tsd.tsv"] if a.tsd else []) +
                                        (["-outcpg", base + "-cpg-cons.fa"] if a.cpg else []) +
                                        (["-outperiod", base + "-period.tsv"] if a.period else []) +
-                                       (["-outterm", base + "-term.tsv"] if a.term else []),
+                                       (["-outterm", base + "-term.tsv"] if a.term else []) +
+                                       (["-outdist", base + "-dist.tsv"] if a.dist else []),
                                        stdout=log, stderr=subprocess.STDOUT).returncode
                 if rc:
                     sys.exit(f"  RAMExtend failed! [{rc}] see {base}-repam.log")
@@ -118,12 +122,13 @@ def main(argv=None):
             lst = os.path.join(a.outdir, f"batch-{matrix}-{minimp}.list")
             with open(lst, "w") as fh:
                 for seed, base in fams:
-                    # fields six to sixteen are optional (the twelfth, the subfamily file, is never asked for here): "-" holds the place of one that is not asked for before one that is
+                    # fields six to seventeen are optional (the twelfth, the subfamily file, is never asked for here): "-" holds the place of one that is not asked for before one that is
                     opt = [base + "-profile.tsv" if a.profile else "-", base + "-aln.a2m" if a.aln else "-",
                            base + "-pileup.tsv" if a.refine > 0 else "-", base + "-refined-cons.fa" if a.refine > 0 else "-",
                            base + "-copies.tsv" if a.copies else "-", base + "-linkage.tsv" if a.linkage else "-", "-",
                            base + "-tsd.tsv" if a.tsd else "-", base + "-cpg-cons.fa" if a.cpg else "-",
-                           base + "-period.tsv" if a.period else "-", base + "-term.tsv" if a.term else "-"]
+                           base + "-period.tsv" if a.period else "-", base + "-term.tsv" if a.term else "-",
+                           base + "-dist.tsv" if a.dist else "-"]
                     while opt and opt[-1] == "-":
                         opt.pop()
                     fh.write("\t".join([base + "-linup.tsv", base + "-repam.log", base + "-ext-cons.fa",

@@ -94,6 +94,7 @@ int main(void)
   o.tsd = (ramx_tsd_params){ 3, 4, 20, 10 };
   o.period = (ramx_period_params){ 1024, 3, 16, 0 };
   o.term = (ramx_term_params){ 512, 2, 3, 5, 40, 3, { 0, 0 } };
+  o.distmin = 2; o.distmax = DEF_DISTMAX;
 
   struct family_outputs fams[2];
   memset(fams, 0, sizeof(fams));
@@ -127,9 +128,17 @@ int main(void)
   const uint8_t patterns[4] = { 0, 1, 0, 1 };
   const ramx_subfam_group group1 = { 1, 1, 3, 1, 1, cons3, pile }, group_empty = { 0, 0, 0, 1, 1, NULL, NULL };
 
+  /* both flanks selected to the right, one pair: three columns covered by both, two sites, one of them a transition, one
+   * column deleted in one of them; to the left the same two cores in the other order, one site */
+  const int32_t sel2[2] = { 0, 1 }, core_left[2] = { 1, 0 };
+  const ramx_copy_dist pair_r = { 3, 2, 1, 0, 1, 0 }, self_r = { 3, 3, 0, 0, 0, 0 }, pair_l = { 2, 1, 0, 0, 0, 0 }, self_l = { 2, 2, 0, 0, 0, 0 };
+  const ramx_copy_dist dist_r[4] = { self_r, pair_r, pair_r, self_r }, dist_l[4] = { self_l, pair_l, pair_l, self_l };
+
   for (int f = 0; f < 2; f++)
     for (int d = 1; d >= 0; d--)
     {
+      const ramx_dist ds = { d, f, d ? 3 : 2, 2, 2, d ? cons3 : cons_left, d ? core_index : core_left, ends, sel2, d ? dist_r : dist_l };
+      dist_sink(&ds, fams);
       const ramx_profile pr = { d, f, d ? 3 : 0, d ? 2 : 0, d ? 2 : 0, prof, core_index, NULL };
       profile_sink(&pr, fams);
       const ramx_alignment al = { d, f, d ? 3 : 2, d ? 2 : 0, 2, d ? cons3 : cons_left, flanks, core_index, ends, d ? col_idx : NULL, d ? col_ins : NULL };
@@ -195,6 +204,13 @@ int main(void)
   expect_line(p[OUT_PERIOD], 8, "0\ts0\t36\t57\t+\tleft\t5\t0\t0.00\t0\t0\t0\t0\t0\t-");
   expect_line(p[OUT_PERIOD], 9, "0\ts0\t36\t57\t+\tright\t7\t2\t5.00\t20\t52\t61\t10\t0\tTA");
   expect_line(p[OUT_PERIOD], -1, "2\ts2\t38\t50\t+\twhole\t22\t0\t0.00");
+  expect_line(p[OUT_DIST], 0, "dir\tcopy_a\tcopy_b\tcover\tsites\tts\ttv\tdel_one\tdel_both\tkimura");
+  expect_line(p[OUT_DIST], 1, "right\ts0:34-59_+\ts1:1045-1062_-\t3\t2\t1\t0\t1\t0\tNA");
+  expect_line(p[OUT_DIST], 2, "#right\tcopies=2\tselected=2\tpairs=1\tused=0\tkimura=0.0000\tmedoid=NA\tmedoid_kimura=NA");
+  expect_line(p[OUT_DIST], 3, "left\ts1:1045-1062_-\ts0:34-59_+\t2\t1\t0\t0\t0\t0\t0.0000");
+  expect_line(p[OUT_DIST], 4, "#left\tcopies=2\tselected=2\tpairs=1\tused=0\t");
+  expect_line(p[OUT_DIST], 5, "both\ts0:34-59_+\ts1:1045-1062_-\t5\t3\t1\t0\t1\t0\t");
+  expect_line(p[OUT_DIST], -1, "#both\tcopies=2\tselected=2\tpairs=1\tused=1\tkimura=");
 
   /* the family without a path wrote nothing and kept nothing */
   int files = 0;

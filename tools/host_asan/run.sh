@@ -17,6 +17,9 @@ gcc -std=gnu11 -O1 -Wno-alloc-size-larger-than $san $inc -o "$out/pad_to_tiles" 
 # the selection, the pair statistic and the components of the linkage (ramx_linkage.c is compiled into the program, under the sanitizers too)
 gcc -std=gnu11 -O1 $san $inc -o "$out/linkage" "$here/linkage_main.c" -lm
 "$out/linkage"
+# the selection of copies, the Kimura distance of a pair and the summary of a pair matrix (ramx_dist.c is compiled into the program, under the sanitizers too)
+gcc -std=gnu11 -O1 $san $inc -o "$out/dist" "$here/dist_main.c" -lm
+"$out/dist"
 # the CpG-aware re-call on random records (ramx_recall.c is compiled into the program, under the sanitizers too)
 gcc -std=gnu11 -O1 $san $inc -o "$out/recall_cpg" "$here/recall_cpg_main.c" "$root/repeatafterme_amd/csrc/ramx_recall.c"
 "$out/recall_cpg"
