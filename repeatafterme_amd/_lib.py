@@ -1,4 +1,4 @@
-"""ctypes loader for libramx.so (include/ramx.h, include/ramx_dist.h).  Fails loudly: there is no CPU path."""
+"""ctypes loader for libramx.so (include/ramx.h, include/ramx_dist.h, include/ramx_xfam.h).  Fails loudly: there is no CPU path."""
 from __future__ import annotations
 
 import ctypes as C
@@ -34,6 +34,11 @@ EXPORTS = [
 # every symbol include/ramx_dist.h declares (tests/test_cabi_dist.py checks the .so exports all of them)
 EXPORTS_DIST = [
     "ramx_dev_copy_dist", "ramx_dev_copy_dist_ms", "ramx_select_copies", "ramx_dist_kimura", "ramx_dist_summary", "ramx_set_dist_sink",
+]
+
+# every symbol include/ramx_xfam.h declares (tests/test_cabi_xfam.py checks the .so exports all of them)
+EXPORTS_XFAM = [
+    "ramx_seq_pair_host", "ramx_dev_seq_pairs", "ramx_xfam_candidates", "ramx_xfam_groups",
 ]
 
 
@@ -189,6 +194,18 @@ class DistRec(C.Structure):         # ramx_dist
 
 
 DIST_CB = C.CFUNCTYPE(None, C.POINTER(DistRec), C.c_void_p)
+
+
+class PairParams(C.Structure):      # ramx_pair_params
+    _fields_ = [(k, C.c_int32) for k in ("match", "mismatch", "gap", "min_score")]
+
+
+class SeqPair(C.Structure):         # ramx_seq_pair
+    _fields_ = [(k, C.c_int32) for k in ("a", "b", "inverted", "reserved")]
+
+
+class XfamLinkParams(C.Structure):  # ramx_xfam_link_params
+    _fields_ = [(k, C.c_int32) for k in ("min_columns", "min_permille")]
 
 
 def build(force: bool = False) -> None:
@@ -361,6 +378,16 @@ def lib() -> C.CDLL:
         L.ramx_dist_summary.restype = C.c_int
         L.ramx_set_dist_sink.argtypes = [DIST_CB, C.c_void_p, C.c_int32, C.c_int32]
         L.ramx_set_dist_sink.restype = None
+        L.ramx_seq_pair_host.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(PairParams), C.c_void_p]
+        L.ramx_seq_pair_host.restype = C.c_int
+        L.ramx_dev_seq_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(PairParams),
+                                         C.c_void_p, C.POINTER(C.c_double)]
+        L.ramx_dev_seq_pairs.restype = C.c_int
+        L.ramx_xfam_candidates.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
+        L.ramx_xfam_candidates.restype = C.c_int64
+        L.ramx_xfam_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(XfamLinkParams),
+                                       C.c_void_p, C.c_void_p]
+        L.ramx_xfam_groups.restype = C.c_int
         if hasattr(L, "ramx_cli_main"):
             L.ramx_cli_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
         _lib = L

@@ -120,6 +120,16 @@ static void usage(void)
     "                           #   it structure, which copy is the medoid? ) to a TSV file: one line per pair.\n"
     "     -distmin <num>        # ... a copy is compared from this many columns, a pair counts from as many sites (20),\n"
     "     -distmax <num>        # ... at most this many copies a direction, those of the most columns, 2..2048 (256).\n"
+    "     -outxfam <file>       # Save the overlaps between the extended consensi ( does one family's extension run into\n"
+    "                           #   another's, or into its own other end? ) and the groups of families that belong\n"
+    "                           #   together to a TSV file; with -batch one file for all the families of the list.\n"
+    "     -xfamseed <num>       # ... two consensi are aligned if they share a word of this length, 8..16, 0 = always (16),\n"
+    "     -xfammatch <num>      # ... what an agreeing pair scores, 1..15 (2),\n"
+    "     -xfammismatch <num>   # ... what a disagreeing pair costs, 1..15 (3),\n"
+    "     -xfamgap <num>        # ... what a base left out costs, 1..31 (5),\n"
+    "     -xfammin <num>        # ... the lowest score reported (80),\n"
+    "     -xfamcols <num>       # ... an overlap links two families from this many columns (80)\n"
+    "     -xfamident <num>      # ... at this many matches per thousand columns, 0..1000 (800).\n"
     "     -version              # Print out one-line version information\n"
     "     -v[v[v[v]]]           # How verbose do you want it to be?  -vvvv is super-verbose.\n"
     "\n"
@@ -687,6 +697,14 @@ static int run_batch(struct cli_opts *o, time_t t_start)
    * two launches left on the device */
   struct batch_ctx bc = { it, fam, F };
   outputs_post(o, fo, (int)F, &k_batch_compute, &bc);
+  if (o->outxfam != NULL)
+  {
+    /* once for the whole batch: every family's two extensions against those of every other, and against each other */
+    const char **names = (const char **)malloc(sizeof(char *) * (F ? F : 1));
+    for (size_t i = 0; i < F; i++) names[i] = it[i].ranges;
+    outputs_xfam(o, fo, (int)F, names);
+    free(names);
+  }
   printf("RAMExtend(ramx) batch: %zu families done\n", F);
   outputs_end(fo, (int)F);
   for (size_t i = 0; i < F; i++)
@@ -754,6 +772,15 @@ int ramx_cli_main(int argc, char **argv)
   if (!opt_int(argc, argv, "-distmax", &o.distmax)) o.distmax = DEF_DISTMAX;
   if (o.distmax < 2 || o.distmax > RAMX_DIST_MAX_COPIES)
   { fprintf(stderr, "RAMExtend(ramx): -distmax %d outside 2..%d\n", o.distmax, RAMX_DIST_MAX_COPIES); exit(1); }
+  opt_string(argc, argv, "-outxfam", &o.outxfam);
+  if (!opt_int(argc, argv, "-xfamseed", &o.xfamseed)) o.xfamseed = 16;
+  if (!opt_int(argc, argv, "-xfammatch", &o.xfam.match)) o.xfam.match = 2;
+  if (!opt_int(argc, argv, "-xfammismatch", &o.xfam.mismatch)) o.xfam.mismatch = 3;
+  if (!opt_int(argc, argv, "-xfamgap", &o.xfam.gap)) o.xfam.gap = 5;
+  if (!opt_int(argc, argv, "-xfammin", &o.xfam.min_score)) o.xfam.min_score = 80;
+  if (!opt_int(argc, argv, "-xfamcols", &o.xfamlink.min_columns)) o.xfamlink.min_columns = 80;
+  if (!opt_int(argc, argv, "-xfamident", &o.xfamlink.min_permille)) o.xfamlink.min_permille = 800;
+  if (outputs_xfam_check(&o) != RAMX_OK) { fprintf(stderr, "RAMExtend(ramx): the options of -outxfam: %s\n", ramx_last_error()); exit(1); }
   if (!opt_int(argc, argv, "-refine", &o.refine)) o.refine = DEF_REFINE;
   if (o.refine < 1) { fprintf(stderr, "RAMExtend(ramx): -refine takes the largest number of replays, at least 1\n"); exit(1); }
   if (!opt_int(argc, argv, "-L", &o.L)) o.L = 10000;
@@ -851,6 +878,7 @@ int ramx_cli_main(int argc, char **argv)
   outputs_family_done(&fo, cores, master, rightbp, leftbp);
   struct single_ctx sc = { cores, lib, N };
   outputs_post(&o, &fo, 1, &k_single_compute, &sc);
+  if (o.outxfam != NULL) outputs_xfam(&o, &fo, 1, &o.ranges_file);       /* the family's own two extensions, both orientations */
   outputs_end(&fo, 1);
   if (fp_mat != NULL) fclose(fp_mat);     /* ram_extend.c:778-779 */
   phase_done("report + outputs");

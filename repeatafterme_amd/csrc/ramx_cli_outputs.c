@@ -930,3 +930,82 @@ void outputs_end(struct family_outputs *fams, int F)
   install_sinks(&k_defaults, NULL, 0);          /* the one reset */
   for (int i = 0; i < F; i++) { free(fams[i].cores); fams[i].cores = NULL; }
 }
+
+/* -outxfam <file>: the overlaps between the extended consensi (include/ramx_xfam.h), once per run, after the post-passes.  The
+ * sequences are every family's left and right extension as -cons writes them, index 2 f and 2 f + 1; within = 1, so a family's
+ * own two extensions are compared too (the LTR or TIR at consensus level, at any length).  One header line; one line per record
+ * with a score, in pair order: family index, ranges file and left|right of A, the same of B, +|-, score, a_from, a_to, len_a,
+ * b_from, b_to (in B's own reading coordinates, b_from <= b_to whatever the orientation), len_b, matches, columns, identity
+ * with three decimals, link (the record counts and joins two different families); then one "#group" line per component: its
+ * id, its size and its families.  A consensus above RAMX_XFAM_MAXLEN is left out and named by a "#skipped" line.  Standard
+ * output gets one summary line. */
+int outputs_xfam_check(const struct cli_opts *o)
+{
+  extern int ramx_pair_check_params(const ramx_pair_params *pp);
+  if (!(o->xfamseed == 0 || (o->xfamseed >= 8 && o->xfamseed <= 16)))
+  { ramx_set_error("-xfamseed %d: 0, or a word of 8..16 bases", o->xfamseed); return RAMX_ERR_ARG; }
+  if (o->xfamlink.min_columns < 0 || o->xfamlink.min_permille < 0 || o->xfamlink.min_permille > 1000)
+  { ramx_set_error("-xfamcols %d (>= 0), -xfamident %d (0..1000)", o->xfamlink.min_columns, o->xfamlink.min_permille); return RAMX_ERR_ARG; }
+  return ramx_pair_check_params(&o->xfam);
+}
+
+void outputs_xfam(const struct cli_opts *o, const struct family_outputs *fams, int F, const char *const *names)
+{
+  const int L = o->L, l = 1, S = 2 * F;
+  FILE *fp = open_or_die(o->outxfam, "w", "cross-family overlap");
+  fprintf(fp, "#family_a\tranges_a\tside_a\tfamily_b\tranges_b\tside_b\torient\tscore\ta_from\ta_to\tlen_a\tb_from\tb_to\tlen_b\tmatches\tcolumns\tidentity\tlink\n");
+  int64_t *off = (int64_t *)calloc((size_t)S + 1, sizeof(int64_t));
+  int32_t *owner = (int32_t *)malloc(sizeof(int32_t) * (size_t)(S ? S : 1)), *group = (int32_t *)malloc(sizeof(int32_t) * (size_t)(F ? F : 1));
+  for (int s = 0; s < S; s++)
+  {
+    const struct family_outputs *fo = &fams[s / 2];
+    int n = s % 2 ? fo->rightbp : fo->leftbp;
+    if (n < 0) n = 0;
+    if (n > RAMX_XFAM_MAXLEN) { fprintf(fp, "#skipped\t%d\t%s\t%s\t%d\n", s / 2, names[s / 2], s % 2 ? "right" : "left", n); n = 0; }
+    off[s + 1] = off[s] + n;
+    owner[s] = s / 2;
+  }
+  int8_t *codes = (int8_t *)malloc((size_t)(off[S] ? off[S] : 1));
+  int *len = (int *)malloc(sizeof(int) * (size_t)(S ? S : 1));
+  for (int s = 0; s < S; s++)
+  {
+    const struct family_outputs *fo = &fams[s / 2];
+    len[s] = (int)(off[s + 1] - off[s]);
+    if (len[s]) memcpy(codes + off[s], fo->master + (s % 2 ? (long)L + l : (long)L - len[s]), (size_t)len[s]);
+  }
+  const int64_t n = ramx_xfam_candidates(codes, off, S, owner, o->xfamseed, 1, NULL, 0);
+  if (n < 0 || n > INT32_MAX) { fprintf(stderr, "RAMExtend(ramx): cross-family candidates failed: %s\n", n < 0 ? ramx_last_error() : "too many pairs"); exit(1); }
+  ramx_seq_pair *pairs = (ramx_seq_pair *)malloc(sizeof(ramx_seq_pair) * (size_t)(n ? n : 1));
+  ramx_term *rec = (ramx_term *)malloc(sizeof(ramx_term) * (size_t)(n ? n : 1));
+  int32_t *counts = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n ? n : 1));
+  if (ramx_xfam_candidates(codes, off, S, owner, o->xfamseed, 1, pairs, n) != n ||
+      ramx_dev_seq_pairs(NULL, codes, off, S, pairs, (int32_t)n, &o->xfam, rec, NULL) != RAMX_OK ||
+      ramx_xfam_groups(pairs, rec, (int32_t)n, owner, F, &o->xfamlink, counts, group) != RAMX_OK)
+  { fprintf(stderr, "RAMExtend(ramx): cross-family overlap failed: %s\n", ramx_last_error()); exit(1); }
+  long n_rec = 0, n_link = 0, n_big = 0;
+  for (int64_t p = 0; p < n; p++)
+  {
+    const ramx_term *r = &rec[p];
+    if (r->score <= 0) continue;
+    const int a = pairs[p].a, b = pairs[p].b, inv = pairs[p].inverted, link = counts[p] && owner[a] != owner[b];
+    const int b_from = inv ? len[b] - 1 - r->b_end : r->b_start, b_to = inv ? len[b] - 1 - r->b_start : r->b_end;
+    const long ident = (2000L * r->matches + r->columns) / (2L * r->columns);       /* per thousand, rounded half up */
+    fprintf(fp, "%d\t%s\t%s\t%d\t%s\t%s\t%c\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%ld.%03ld\t%d\n", owner[a], names[owner[a]], a % 2 ? "right" : "left",
+            owner[b], names[owner[b]], b % 2 ? "right" : "left", inv ? '-' : '+', r->score, r->a_start, r->a_end, len[a], b_from, b_to, len[b],
+            r->matches, r->columns, ident / 1000, ident % 1000, link);
+    n_rec++; n_link += link;
+  }
+  for (int g = 0; g < F; g++)
+  {
+    int size = 0;
+    for (int f = 0; f < F; f++) size += group[f] == g;
+    if (!size) continue;
+    n_big += size > 1;
+    fprintf(fp, "#group\t%d\t%d\t", g, size);
+    for (int f = 0, k = 0; f < F; f++) if (group[f] == g) fprintf(fp, "%s%d", k++ ? "," : "", f);
+    fprintf(fp, "\n");
+  }
+  fclose(fp);
+  printf("xfam: %lld candidates, %ld records, %ld links, %ld groups with more than one family\n", (long long)n, n_rec, n_link, n_big);
+  free(off); free(owner); free(group); free(codes); free(len); free(pairs); free(rec); free(counts);
+}

@@ -5,6 +5,7 @@
 
 #include "ramx_internal.h"
 #include "ramx_dist.h"
+#include "ramx_xfam.h"
 
 /* the rows of the table of analysis outputs (ramx_cli_outputs.c, k_outputs), in the order in which their files are started and
  * written */
@@ -30,6 +31,10 @@ struct cli_opts
   int periodwhole;
   ramx_term_params term;
   int refine, cpgscore, linkcount, linkfrac, linkscore, subfamk, subfammin, subfamiter, distmin, distmax;
+  const char *outxfam;                 /* one file a run, not a family's: no row of the table */
+  ramx_pair_params xfam;
+  ramx_xfam_link_params xfamlink;
+  int xfamseed;
   int flanking, L, bandwidth, maxn, when_to_stop, num_threads, verbose;
   int gap_ext, gap_open, match, mismatch, cappenalty, minimprovement, is_rs;
   struct scoringSystem *sp;
@@ -118,6 +123,10 @@ void outputs_family_done(struct family_outputs *fo, const struct coreAlignment *
 void outputs_family_cores(struct family_outputs *fo, const struct coreAlignment *cores);
 /* after outputs_family_done of every family: the rows with a post-pass that some family wants */
 void outputs_post(const struct cli_opts *o, struct family_outputs *fams, int F, const struct outputs_post_fns *fns, void *ctx);
+/* -outxfam: the options' ranges (RAMX_OK, or RAMX_ERR_ARG with the error text set), and the file itself: once a run, after
+ * outputs_post and before outputs_end, from the families' masters; names[f] is family f's ranges file */
+int outputs_xfam_check(const struct cli_opts *o);
+void outputs_xfam(const struct cli_opts *o, const struct family_outputs *fams, int F, const char *const *names);
 /* every sink reset, everything the families kept released */
 void outputs_end(struct family_outputs *fams, int F);
 

@@ -43,6 +43,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
+#include <algorithm>
 #include <memory>
 #include <vector>
 
@@ -62,6 +63,7 @@
 #include "ramx_tsd_api.h"
 #include "ramx_period_api.h"
 #include "ramx_term_api.h"
+#include "ramx_xfam_api.h"
 
 // ------------------------------------------------------------------------------------------
 // error plumbing
@@ -205,6 +207,9 @@ struct ramx_dev
   size_t cap_per_bases, cap_per_valid, cap_per_len, cap_per_out;
   // ramx_dev_term (allocated on its first call; its streams and window lengths live in the buffers of ramx_dev_period): the records
   ramx_term *d_term_out; size_t cap_term_out;
+  // ramx_dev_seq_pairs (allocated on its first call): the sequences, pair descriptors, strip borders and records of a group
+  signed char *d_xf_codes; XfamPair *d_xf_pairs; int4 *d_xf_border; ramx_term *d_xf_out;
+  size_t cap_xf_codes, cap_xf_pairs, cap_xf_border, cap_xf_out;
 };
 
 extern "C" int ramx_device_count(void)
@@ -305,6 +310,7 @@ extern "C" void ramx_dev_destroy(ramx_dev *d)
   (void)hipFree(d->d_tsd_room); (void)hipFree(d->d_tsd_out);
   (void)hipFree(d->d_per_bases); (void)hipFree(d->d_per_valid); (void)hipFree(d->d_per_len); (void)hipFree(d->d_per_out);
   (void)hipFree(d->d_term_out);
+  (void)hipFree(d->d_xf_codes); (void)hipFree(d->d_xf_pairs); (void)hipFree(d->d_xf_border); (void)hipFree(d->d_xf_out);
   if (d->hostbox_mirror) (void)hipFree(d->hostbox_mirror);
   if (d->d_peer) (void)hipFree(d->d_peer);
   for (int i = 0; i < 2; i++) if (d->ev_chk[i]) (void)hipEventDestroy(d->ev_chk[i]);
@@ -2547,6 +2553,144 @@ extern "C" int ramx_dev_term(ramx_dev *d, const ramx_tsd_site *sites, int32_t n_
     if ((lrc = ramx_term_align_launch(d->stream, ta, Tgroup)) != RAMX_OK) return lrc;
     mark();
     HIPCHK(hipMemcpyAsync(out + (size_t)2 * s0, d->d_term_out, (size_t)2 * n * sizeof(ramx_term), hipMemcpyDeviceToHost, d->stream));
+    return RAMX_OK;      // (the next group writes the host and device buffers of this one again: host_reuse)
+  });
+}
+
+// ------------------------------------------------------------------------------------------
+// cross-family overlap (include/ramx_xfam.h): pairs of sequences of any two lengths, one wave a pair (ramx_kernels_xfam.h)
+// ------------------------------------------------------------------------------------------
+// what a pair adds to its group: its strip border, its descriptor and its record; and what a sequence adds
+static size_t xfam_pair_bytes(long long na) { return (size_t)16 * (size_t)na + sizeof(XfamPair) + sizeof(ramx_term) + 8; }
+static size_t xfam_seq_bytes(long long n) { return ((size_t)n + 15) & ~(size_t)15; }
+static_assert(sizeof(XfamPair) + sizeof(ramx_term) + 8 == 80, "the 80 bytes a pair of include/ramx_xfam.h");
+
+extern "C" int ramx_dev_seq_pairs(ramx_dev *d, const int8_t *codes, const int64_t *seq_off, int32_t n_seqs, const ramx_seq_pair *pairs,
+                                  int32_t n_pairs, const ramx_pair_params *pp, ramx_term *out, double *kernel_ms)
+{
+  if (kernel_ms) *kernel_ms = 0;
+  int rc;
+  if ((rc = ramx_pair_check_params(pp)) != RAMX_OK) return rc;
+  if (n_seqs < 0 || n_pairs < 0 || !seq_off || (n_pairs && (!pairs || !out)))
+  { ramx_set_error("ramx_dev_seq_pairs: bad argument"); return RAMX_ERR_ARG; }
+  for (int s = 0; s < n_seqs; s++)
+    if (seq_off[s] < 0 || seq_off[s + 1] < seq_off[s] || (seq_off[s + 1] > seq_off[s] && !codes))
+    { ramx_set_error("ramx_dev_seq_pairs: seq_off decreases at sequence %d, or codes missing", s); return RAMX_ERR_ARG; }
+  for (int p = 0; p < n_pairs; p++)
+    if (pairs[p].a < 0 || pairs[p].a >= n_seqs || pairs[p].b < 0 || pairs[p].b >= n_seqs || pairs[p].a == pairs[p].b ||
+        pairs[p].inverted < 0 || pairs[p].inverted > 1 || pairs[p].reserved)
+    { ramx_set_error("ramx_dev_seq_pairs: pair %d: a %d b %d (two different sequences of 0..%d), inverted %d (0, 1), reserved %d (0)", p,
+                     pairs[p].a, pairs[p].b, n_seqs - 1, pairs[p].inverted, pairs[p].reserved); return RAMX_ERR_ARG; }
+  auto len_of = [&](int s) { return (long long)(seq_off[s + 1] - seq_off[s]); };
+  for (int p = 0; p < n_pairs; p++)
+    if (len_of(pairs[p].a) > RAMX_XFAM_MAXLEN || len_of(pairs[p].b) > RAMX_XFAM_MAXLEN)
+    { ramx_set_error("ramx_dev_seq_pairs: pair %d: %lld and %lld bases, at most %d", p, len_of(pairs[p].a), len_of(pairs[p].b), RAMX_XFAM_MAXLEN);
+      return RAMX_ERR_UNSUPPORTED; }
+  if (n_pairs == 0) return RAMX_OK;
+  if (!d) d = ramx_default_device();      // seam 1's process-wide session
+  if (!d) return RAMX_ERR_NO_DEVICE;
+  size_t budget = (size_t)1 << 30;
+  if (const char *e = getenv("RAMX_XFAM_BYTES")) { const long long v = atoll(e); if (v > 0) budget = (size_t)v; }
+  int force_cols = 0;                     // RAMX_XFAM_COLS = 4, 8, 16: that specialisation for every pair (the tests' way to each of them)
+  if (const char *e = getenv("RAMX_XFAM_COLS")) { const int v = atoi(e); if (v == 4 || v == 8 || v == 16) force_cols = v; }
+  // consecutive pairs in groups that fit: a group's sequences once each, and every pair's border, descriptor and record
+  auto empty = [&](int p) { return len_of(pairs[p].a) == 0 || len_of(pairs[p].b) == 0; };
+  std::vector<int> gfirst;                // the first pair of every group, and n_pairs at the end
+  std::vector<int> stamp((size_t)n_seqs, -1);
+  size_t need_codes = 0, need_border = 0, need_pairs = 0;
+  {
+    size_t bytes = 0, cbytes = 0, bbytes = 0;
+    int g = 0;
+    gfirst.push_back(0);
+    for (int p = 0; p < n_pairs; p++)
+    {
+      if (empty(p)) continue;
+      const int sa = pairs[p].a, sb = pairs[p].b;
+      auto add_of = [&]() {
+        return xfam_pair_bytes(len_of(sa)) + (stamp[(size_t)sa] == g ? 0 : xfam_seq_bytes(len_of(sa))) + (stamp[(size_t)sb] == g ? 0 : xfam_seq_bytes(len_of(sb)));
+      };
+      if (bytes && bytes + add_of() > budget) { g++; gfirst.push_back(p); bytes = cbytes = bbytes = 0; }
+      const size_t add = add_of();
+      if (add > budget)
+      { ramx_set_error("ramx_dev_seq_pairs: pair %d alone (%zu bytes) does not fit RAMX_XFAM_BYTES = %zu", p, add, budget); return RAMX_ERR_UNSUPPORTED; }
+      if (stamp[(size_t)sa] != g) { stamp[(size_t)sa] = g; cbytes += xfam_seq_bytes(len_of(sa)); }
+      if (stamp[(size_t)sb] != g) { stamp[(size_t)sb] = g; cbytes += xfam_seq_bytes(len_of(sb)); }
+      bytes += add; bbytes += (size_t)16 * (size_t)len_of(sa);
+      if (cbytes > need_codes) need_codes = cbytes;
+      if (bbytes > need_border) need_border = bbytes;
+      if ((size_t)(p + 1 - gfirst.back()) > need_pairs) need_pairs = (size_t)(p + 1 - gfirst.back());
+    }
+    gfirst.push_back(n_pairs);
+    // (a group's records are copied back in one piece, the empty pairs at its end included)
+    for (size_t k = 0; k + 1 < gfirst.size(); k++)
+      if ((size_t)(gfirst[k + 1] - gfirst[k]) > need_pairs) need_pairs = (size_t)(gfirst[k + 1] - gfirst[k]);
+  }
+  // self-contained, as the site-window analyses: a direction begun before is over, resident planes are dropped
+  HIPCHK(hipSetDevice(d->ordinal));
+  if ((rc = pack_settle(d, true)) != RAMX_OK) return rc;
+  d->ready = 0;
+  d->planes_ready = 0;
+  if ((rc = ensure(&d->d_xf_codes, &d->cap_xf_codes, need_codes))) return rc;
+  if ((rc = ensure(&d->d_xf_border, &d->cap_xf_border, need_border))) return rc;
+  if ((rc = ensure(&d->d_xf_pairs, &d->cap_xf_pairs, need_pairs * sizeof(XfamPair)))) return rc;
+  if ((rc = ensure(&d->d_xf_out, &d->cap_xf_out, need_pairs * sizeof(ramx_term)))) return rc;
+  std::vector<signed char> hcodes(need_codes ? need_codes : 1);
+  std::vector<XfamPair> hpairs(need_pairs ? need_pairs : 1);
+  std::vector<long long> where((size_t)n_seqs, 0);
+  std::fill(stamp.begin(), stamp.end(), -1);
+  XfamArgs xa;
+  memset(&xa, 0, sizeof(xa));
+  xa.codes = d->d_xf_codes; xa.border = d->d_xf_border; xa.out = d->d_xf_out;
+  xa.match = pp->match; xa.mismatch = pp->mismatch; xa.gap = pp->gap; xa.min_score = pp->min_score;
+  const int ngroups = (int)gfirst.size() - 1;
+  return tile_groups(d, "ramx_dev_seq_pairs", ngroups, 1, 1, kernel_ms, true, [&](int g, int, auto &mark) {
+    const int p0 = gfirst[(size_t)g], p1 = gfirst[(size_t)g + 1];
+    size_t cat = 0;
+    long long bat = 0;
+    int m = 0;
+    for (int p = p0; p < p1; p++)
+    {
+      if (empty(p)) { memset(&out[p], 0, sizeof(ramx_term)); continue; }
+      const int two[2] = { pairs[p].a, pairs[p].b };
+      for (int s : two)
+        if (stamp[(size_t)s] != g)
+        {
+          stamp[(size_t)s] = g; where[(size_t)s] = (long long)cat;
+          memcpy(hcodes.data() + cat, codes + seq_off[s], (size_t)len_of(s));
+          cat += xfam_seq_bytes(len_of(s));
+        }
+      XfamPair &x = hpairs[(size_t)m++];
+      x.a_off = where[(size_t)two[0]]; x.b_off = where[(size_t)two[1]]; x.border_off = bat;
+      x.na = (int)len_of(two[0]); x.nb = (int)len_of(two[1]); x.inverted = pairs[p].inverted; x.out_index = p - p0;
+      bat += x.na;                                            // (in records of 16 bytes)
+    }
+    if (m == 0) { mark(); mark(); return RAMX_OK; }
+    // pairs differ by orders of magnitude in cells: by specialisation, then the largest first; the kernel writes a pair's record
+    // at its place in the group, whatever its place in the launch
+    auto cols_of = [&](const XfamPair &x) { return force_cols ? force_cols : ramx_xfam_cols(x.nb); };
+    std::sort(hpairs.begin(), hpairs.begin() + m, [&](const XfamPair &x, const XfamPair &y) {
+      const int cx = cols_of(x), cy = cols_of(y);
+      if (cx != cy) return cx < cy;
+      const long long wx = (long long)x.na * x.nb, wy = (long long)y.na * y.nb;
+      return wx != wy ? wx > wy : x.out_index < y.out_index;
+    });
+    HIPCHK(hipMemcpyAsync(d->d_xf_codes, hcodes.data(), cat, hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(d->d_xf_pairs, hpairs.data(), (size_t)m * sizeof(XfamPair), hipMemcpyHostToDevice, d->stream));
+    mark();
+    for (int lo = 0; lo < m;)
+    {
+      int hi = lo, na_max = 0;
+      while (hi < m && cols_of(hpairs[(size_t)hi]) == cols_of(hpairs[(size_t)lo])) { if (hpairs[(size_t)hi].na > na_max) na_max = hpairs[(size_t)hi].na; hi++; }
+      xa.pairs = d->d_xf_pairs + lo; xa.n = hi - lo;
+      const int lrc = ramx_xfam_align_launch(d->stream, xa, cols_of(hpairs[(size_t)lo]), na_max);
+      if (lrc != RAMX_OK) return lrc;
+      lo = hi;
+    }
+    mark();
+    // (an empty pair's record in between is copied as the device left it and written again below, after the copy)
+    HIPCHK(hipMemcpyAsync(out + p0, d->d_xf_out, (size_t)(p1 - p0) * sizeof(ramx_term), hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    for (int p = p0; p < p1; p++) if (empty(p)) memset(&out[p], 0, sizeof(ramx_term));
     return RAMX_OK;      // (the next group writes the host and device buffers of this one again: host_reuse)
   });
 }

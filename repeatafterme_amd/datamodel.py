@@ -351,6 +351,28 @@ class TermSummary:
     inverted_columns: int
 
 
+# cross-family overlap (include/ramx_xfam.h): C-ABI ramx_seq_pair (16 bytes), ramx_pair_params, ramx_xfam_link_params; the
+# records are TERM_DTYPE
+SEQ_PAIR_FIELDS = ("a", "b", "inverted", "reserved")
+SEQ_PAIR_DTYPE = np.dtype([(k, np.int32) for k in SEQ_PAIR_FIELDS])
+assert SEQ_PAIR_DTYPE.itemsize == 16
+XFAM_MAXLEN = 32767                  # RAMX_XFAM_MAXLEN
+
+
+@dataclass
+class PairParams:
+    match: int = 2
+    mismatch: int = 3
+    gap: int = 5
+    min_score: int = 80
+
+
+@dataclass
+class XfamLinkParams:
+    min_columns: int = 80
+    min_permille: int = 800
+
+
 FLANK_DTYPE = np.dtype([("start", np.int64), ("t_lo", np.int32), ("t_hi", np.int32), ("step", np.int8), ("compl_", np.int8),
                         ("pad_", np.int8, (6,))])
 assert FLANK_DTYPE.itemsize == 24

@@ -27,6 +27,9 @@ simple repeat or a satellite? -- and the family's modal period per part (RAMExte
 <id>-term.tsv: with -term, the terminal repeats of every extended copy -- its first bases repeated at its end, directly (LTR) or
 as their reverse complement (TIR) -- and the family's verdict (RAMExtend -outterm).
 <id>-dist.tsv: with -dist, the pairwise divergence between the extended copies (RAMExtend -outdist).
+xfam.tsv: with -xfam, after every scoring group has finished (a -outxfam per process would miss the pairs across groups), the
+overlaps between the families' combined consensi -- left extension + reference + right extension, so the core is included --
+and the groups of families that belong together, in the format of RAMExtend -outxfam with the family id in place of the index.
 
 (the re-alignment and Stockholm rewriting that follow in the wrapper belong to RepeatModeler and are out of scope).
 """
@@ -67,6 +70,8 @@ def main(argv=None):
                     "family's verdict (none, LTR, TIR) and the median lengths of the anchored repeats")
     ap.add_argument("-dist", action="store_true", help="also write <id>-dist.tsv per family (RAMExtend -outdist): the pairwise "
                     "divergence between the extended copies")
+    ap.add_argument("-xfam", action="store_true", help="also write <outdir>/xfam.tsv: the overlaps between the combined consensi of "
+                    "all families and the groups of families they join")
     ap.add_argument("-cpg", action="store_true", help="also write <id>-cpg-cons.fa per family (RAMExtend -outcpg)")
     ap.add_argument("-one_by_one", action="store_true", help="start one RAMExtend per family, as the wrapper does")
     a = ap.parse_args(argv)
@@ -94,7 +99,9 @@ def main(argv=None):
         else:
             print(f"  **Too few extendable sequences ({extendable}) for RAMExtend**")
 
+    finished = []
     for (matrix, minimp), fams in groups.items():
+        finished += fams
         common = ["-twobit", a.assembly, "-L", str(a.L), "-bandwidth", str(a.bandwidth), "-matrix", matrix, "-vvv",
                   "-minimprovement", str(minimp)]
         print(f"  - Running RAMExtend [bandwidth={a.bandwidth}, matrix={matrix}, minimprovement={minimp}] on "
@@ -187,7 +194,32 @@ def main(argv=None):
                         kv = dict(f.split("=") for f in line.rstrip("\n").split("\t")[1:])
                         print(f"  - Terminal repeats: {kv['verdict']} (direct: {kv['direct_anchored']} of {kv['n']} copies anchored, median "
                               f"{kv['direct_median']} bp; inverted: {kv['inverted_anchored']}, median {kv['inverted_median']} bp)")
+    if a.xfam:
+        print(cross_family([(seed.name, base + "-combined-cons.fa") for seed, base in finished], os.path.join(a.outdir, "xfam.tsv")))
     return 0
+
+
+def cross_family(families, out_path):
+    """families: (id, combined consensus FASTA) of every family that was extended -> out_path, and the summary line."""
+    import numpy as np
+    from repeatafterme_amd import xfam
+    code = np.full(256, 99, np.int8)
+    for k, ch in enumerate("ACGTacgt"):
+        code[ord(ch)] = k
+    seqs = []
+    for _, path in families:
+        text = "".join(line.strip() for line in open(path) if not line.startswith(">"))
+        seqs.append(code[np.frombuffer(text.encode(), np.uint8)] if text else np.zeros(0, np.int8))
+    keep = [i for i, s in enumerate(seqs) if len(s) <= 32767]                # (a longer consensus is left out and named)
+    owner = list(range(len(keep)))
+    rec, pairs, counts, group = xfam.compare([seqs[i] for i in keep], owner, n_families=len(keep))
+    line = xfam.write_tsv(out_path, [families[i][1] for i in keep], ["all"] * len(keep), [len(seqs[i]) for i in keep], pairs, rec,
+                          counts, owner, group, labels=[families[i][0] for i in keep])
+    with open(out_path, "a") as fh:
+        for i in range(len(seqs)):
+            if i not in keep:
+                fh.write(f"#skipped\t{families[i][0]}\t{families[i][1]}\tall\t{len(seqs[i])}\n")
+    return line
 
 
 if __name__ == "__main__":

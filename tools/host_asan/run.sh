@@ -20,6 +20,9 @@ gcc -std=gnu11 -O1 $san $inc -o "$out/linkage" "$here/linkage_main.c" -lm
 # the selection of copies, the Kimura distance of a pair and the summary of a pair matrix (ramx_dist.c is compiled into the program, under the sanitizers too)
 gcc -std=gnu11 -O1 $san $inc -o "$out/dist" "$here/dist_main.c" -lm
 "$out/dist"
+# the pair record, the candidates and the groups of the cross-family overlap against a brute force (ramx_xfam.c and ramx_term.c are compiled into the program, under the sanitizers too)
+gcc -std=gnu11 -O1 $san $inc -o "$out/xfam" "$here/xfam_main.c"
+"$out/xfam"
 # the CpG-aware re-call on random records (ramx_recall.c is compiled into the program, under the sanitizers too)
 gcc -std=gnu11 -O1 $san $inc -o "$out/recall_cpg" "$here/recall_cpg_main.c" "$root/repeatafterme_amd/csrc/ramx_recall.c"
 "$out/recall_cpg"
