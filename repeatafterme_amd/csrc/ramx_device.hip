@@ -112,6 +112,12 @@ static double now_ms(void)
 // ------------------------------------------------------------------------------------------
 #define RAMX_NGROUP (RAMX_CP_NCLASS + 4)   // batch mode: cell-parallel classes, then the four lane-per-flank workgroup shapes
 
+// a family of the replay whose bit planes are resident: its rows, its tiles, where its flanks lie, and the first word of its
+// rows * 8 planes of `tiles` words each
+struct ResidentFam { int rows, tiles, first, count; long long base; };
+// a family of the last split: the first word of its K mask planes of `tiles` words each
+struct SubfamLay { long long mask0; int tiles; };
+
 struct ramx_dev
 {
   int ordinal, cus;   // cus: compute units (what every co-resident launch is planned against)
@@ -181,24 +187,22 @@ struct ramx_dev
   size_t cap_dn_slab, cap_dn_cols;
   // ramx_dev_planes / ramx_dev_plane_gram (allocated on their first call): the bit planes of the whole flank set, which stay
   // resident between the two calls (planes_ready, dropped like `ready` by whatever reuses the replays' buffers); the host keeps
-  // the resident families' rows, tiles and places (lk_fam: 3 x int64 per family)
+  // the resident replay's families (res_fam, malloc'd) and its n_padded for every call that answers from the planes
   unsigned long long *d_lk_planes; long long *d_lk_base, *d_lk_at, *d_lk_coat; int4 *d_lk_block, *d_lk_gfam; int *d_lk_co;
   size_t cap_lk_planes, cap_lk_base, cap_lk_at, cap_lk_coat, cap_lk_block, cap_lk_gfam, cap_lk_co;
-  int planes_ready, lk_families; long long *lk_fam;
+  int planes_ready, res_families, res_npadded; ResidentFam *res_fam;
   double lk_gram_ms;        // HIP-event time of the last Gram kernel (ramx_dev_plane_gram_ms)
   // ramx_dev_copy_dist (allocated on its first call): the chosen copies' bit streams over the rows, the lists it uploads and
   // the pair records
   unsigned long long *d_lk_streams; DistFam *d_lk_dfam; int4 *d_lk_ditem, *d_lk_dblock; int *d_lk_dslot; ramx_copy_dist *d_lk_dist;
   size_t cap_lk_streams, cap_lk_dfam, cap_lk_ditem, cap_lk_dblock, cap_lk_dslot, cap_lk_dist;
   double lk_dist_ms[2];     // HIP-event times of the transposition and the pair kernel of the last ramx_dev_copy_dist
-  // ramx_dev_subfamilies (allocated on its first call): the lists it uploads, the labels, the mask planes and the counts; the
-  // host keeps where the resident families' flanks lie (lk_place: first and count per family) and the replay's n_padded
+  // ramx_dev_subfamilies (allocated on its first call): the lists it uploads, the labels, the mask planes and the counts
   SubfamFam *d_sf_fam; long long *d_sf_at; longlong2 *d_sf_var; unsigned char *d_sf_pat; int2 *d_sf_tile, *d_sf_item;
   int *d_sf_count, *d_sf_labels, *d_sf_changed, *d_sf_cnt; unsigned long long *d_sf_mask;
   size_t cap_sf_fam, cap_sf_at, cap_sf_var, cap_sf_pat, cap_sf_tile, cap_sf_item, cap_sf_count, cap_sf_labels, cap_sf_changed,
          cap_sf_cnt, cap_sf_mask;
-  int *lk_place, lk_npadded;
-  long long *sf_lay; int sf_families, sf_K;       // the last result's mask planes: (first word, tiles) per family
+  SubfamLay *sf_lay; int sf_families, sf_K;       // the last result's mask planes, per family (malloc'd)
   double sf_ms[2];          // HIP-event times of the assign and the count kernels of the last ramx_dev_subfamilies, summed
   // ramx_dev_tsd (allocated on its first call): per site the room between the two words, and its record
   int *d_tsd_room; ramx_tsd *d_tsd_out; size_t cap_tsd_room, cap_tsd_out;
@@ -302,11 +306,11 @@ extern "C" void ramx_dev_destroy(ramx_dev *d)
   (void)hipFree(d->d_lk_block); (void)hipFree(d->d_lk_gfam); (void)hipFree(d->d_lk_co);
   (void)hipFree(d->d_lk_streams); (void)hipFree(d->d_lk_dfam); (void)hipFree(d->d_lk_ditem); (void)hipFree(d->d_lk_dblock);
   (void)hipFree(d->d_lk_dslot); (void)hipFree(d->d_lk_dist);
-  free(d->lk_fam);
+  free(d->res_fam);
   (void)hipFree(d->d_sf_fam); (void)hipFree(d->d_sf_at); (void)hipFree(d->d_sf_var); (void)hipFree(d->d_sf_pat);
   (void)hipFree(d->d_sf_tile); (void)hipFree(d->d_sf_item); (void)hipFree(d->d_sf_count); (void)hipFree(d->d_sf_labels);
   (void)hipFree(d->d_sf_changed); (void)hipFree(d->d_sf_cnt); (void)hipFree(d->d_sf_mask);
-  free(d->lk_place); free(d->sf_lay);
+  free(d->sf_lay);
   (void)hipFree(d->d_tsd_room); (void)hipFree(d->d_tsd_out);
   (void)hipFree(d->d_per_bases); (void)hipFree(d->d_per_valid); (void)hipFree(d->d_per_len); (void)hipFree(d->d_per_out);
   (void)hipFree(d->d_term_out);
@@ -459,6 +463,17 @@ static int ensure(T **p, size_t *cap, size_t need_bytes)
   *p = NULL;
   HIPCHK(hipMalloc((void **)p, need_bytes ? need_bytes : 16));
   *cap = need_bytes;
+  return RAMX_OK;
+}
+
+// a host vector into a device buffer of at least its size, on d->stream: the caller synchronises before the vector goes; an
+// empty one leaves a buffer that exists
+template <typename T>
+static int upload(ramx_dev *d, T **p, size_t *cap, const std::vector<T> &v)
+{
+  int rc;
+  if ((rc = ensure(p, cap, v.size() * sizeof(T)))) return rc;
+  if (!v.empty()) HIPCHK(hipMemcpyAsync(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, d->stream));
   return RAMX_OK;
 }
 
@@ -2721,13 +2736,16 @@ extern "C" int ramx_dev_planes(ramx_dev *d, const ramx_flank *flanks, int32_t n_
   if (pl.maxrows > 0 && !cols) { ramx_set_error("ramx_dev_planes: cols missing"); return RAMX_ERR_ARG; }
   d->planes_ready = 0;
   // where every family's planes lie: rows * 8 planes of its tiles' words each, family after family
-  std::vector<long long> lay((size_t)(n_families > 0 ? n_families : 1) * 3, 0), base((size_t)(n_families > 0 ? n_families : 1), 0);
+  const size_t nf1 = (size_t)(n_families > 0 ? n_families : 1);
+  std::vector<ResidentFam> fam(nf1);
+  std::vector<long long> base(nf1, 0);
   size_t words = 0;
   const size_t budget = linkage_budget();
   for (int f = 0; f < n_families; f++)
   {
     const size_t nt = (size_t)((fam_count[f] + 63) / 64), need = (size_t)rows[f] * RAMX_PLANE_CLASSES * nt;
-    lay[3 * (size_t)f] = rows[f]; lay[3 * (size_t)f + 1] = (long long)nt; lay[3 * (size_t)f + 2] = base[f] = (long long)words;
+    fam[f] = ResidentFam{ rows[f], (int)nt, fam_first[f], fam_count[f], (long long)words };
+    base[f] = fam[f].base;
     words += need;
     if (words * sizeof(unsigned long long) > budget)
     {
@@ -2754,15 +2772,73 @@ extern "C" int ramx_dev_planes(ramx_dev *d, const ramx_flank *flanks, int32_t n_
   }
   if ((rc = pileup_fetch(d, run, n_padded, fam_first, fam_count, n_families, p->L, cons, rows, NULL, cols, ends)) != RAMX_OK) return rc;
   // resident from here on (where nothing ran there is no plane a Gram could be asked for)
-  long long *keep = (long long *)realloc(d->lk_fam, lay.size() * sizeof(long long));
+  ResidentFam *keep = (ResidentFam *)realloc(d->res_fam, nf1 * sizeof(ResidentFam));
   if (!keep) { ramx_set_error("ramx_dev_planes: out of memory"); return RAMX_ERR_ARG; }
-  memcpy(keep, lay.data(), lay.size() * sizeof(long long));
-  d->lk_fam = keep; d->lk_families = n_families;
-  int *place = (int *)realloc(d->lk_place, (size_t)(n_families > 0 ? n_families : 1) * 2 * sizeof(int));
-  if (!place) { ramx_set_error("ramx_dev_planes: out of memory"); return RAMX_ERR_ARG; }
-  for (int f = 0; f < n_families; f++) { place[2 * f] = fam_first[f]; place[2 * f + 1] = fam_count[f]; }
-  d->lk_place = place; d->lk_npadded = n_padded;
+  memcpy(keep, fam.data(), nf1 * sizeof(ResidentFam));
+  d->res_fam = keep; d->res_families = n_families; d->res_npadded = n_padded;
   d->planes_ready = 1;
+  return RAMX_OK;
+}
+
+// the shared host path of the calls that answer from the resident planes: Gram, pair matrix, split
+static int resident_check(const char *who, const ramx_dev *d, int32_t n_families)
+{
+  if (!d->planes_ready)
+  { ramx_set_error("%s: no resident bit planes (ramx_dev_planes has not run on this device, or a later call dropped them)", who); return RAMX_ERR_STATE; }
+  if (n_families != d->res_families)
+  { ramx_set_error("%s: %d families, the resident replay has %d", who, n_families, d->res_families); return RAMX_ERR_ARG; }
+  return RAMX_OK;
+}
+
+// family f's list of P planes (pp == NULL: the caller has found an argument of this family wrong; that is reported behind the
+// count's range): in [0, RAMX_LINKAGE_MAX_PLANES], every plane inside the resident replay, strictly increasing in (row, class).
+// at != NULL: the planes' first words are appended to it.  No HIP call.
+static int plane_list(const char *who, int f, const ResidentFam &rf, const ramx_plane *pp, int P, std::vector<long long> *at)
+{
+  if (P < 0 || P > RAMX_LINKAGE_MAX_PLANES)
+  { ramx_set_error("%s: family %d: %d planes outside [0, %d]", who, f, P, RAMX_LINKAGE_MAX_PLANES); return RAMX_ERR_ARG; }
+  if (P > 0 && !pp) { ramx_set_error("%s: family %d: bad argument", who, f); return RAMX_ERR_ARG; }
+  for (int i = 0; i < P; i++)
+  {
+    if (pp[i].row < 0 || pp[i].row >= rf.rows || pp[i].cls < 0 || pp[i].cls >= RAMX_PLANE_CLASSES)
+    { ramx_set_error("%s: family %d, plane %d: (row %d, class %d) outside the resident replay (%lld rows, classes 0..7)", who, f, i, pp[i].row, pp[i].cls, (long long)rf.rows); return RAMX_ERR_ARG; }
+    if (i > 0 && (pp[i].row < pp[i - 1].row || (pp[i].row == pp[i - 1].row && pp[i].cls <= pp[i - 1].cls)))
+    { ramx_set_error("%s: family %d, plane %d: the planes are not strictly increasing in (row, class)", who, f, i); return RAMX_ERR_ARG; }
+    if (at) at->push_back(rf.base + ((long long)pp[i].row * RAMX_PLANE_CLASSES + pp[i].cls) * rf.tiles);
+  }
+  return RAMX_OK;
+}
+
+// the blocks (f, bi, bj, 0), bi <= bj, of family f's n x n matrix in blocks of `side`: the upper triangle with the diagonal
+static void upper_blocks(std::vector<int4> &block, int f, int n, int side)
+{
+  const int nb = (n + side - 1) / side;
+  for (int bi = 0; bi < nb; bi++)
+    for (int bj = bi; bj < nb; bj++) block.push_back(make_int4(f, bi, bj, 0));
+}
+
+// k <= 2 launches in a row on d->stream between k + 1 events, and one synchronisation behind them (which the uploads before
+// need too: they read the caller's vectors).  The event interval of launch i is added to ms[i] when all went well; *failed: the
+// launch that was refused, -1 if none was
+template <typename F>
+static int timed_launches(ramx_dev *d, int k, F launch, double *ms, int *failed)
+{
+  hipEvent_t ev[3] = { NULL, NULL, NULL };
+  bool timed = true;
+  for (int i = 0; i <= k; i++) timed = timed && hipEventCreate(&ev[i]) == hipSuccess;
+  if (timed) (void)hipEventRecord(ev[0], d->stream);
+  int rc = RAMX_OK;
+  *failed = -1;
+  for (int i = 0; i < k && rc == RAMX_OK; i++)
+    if ((rc = launch(i)) != RAMX_OK) *failed = i;
+    else if (timed) (void)hipEventRecord(ev[i + 1], d->stream);
+  const hipError_t se = hipStreamSynchronize(d->stream);
+  float t = 0;
+  for (int i = 0; i < k; i++)
+    if (timed && rc == RAMX_OK && se == hipSuccess && hipEventElapsedTime(&t, ev[i], ev[i + 1]) == hipSuccess) ms[i] += t;
+  for (int i = 0; i <= k; i++) if (ev[i]) (void)hipEventDestroy(ev[i]);
+  if (rc != RAMX_OK) return rc;
+  HIPCHK(se);
   return RAMX_OK;
 }
 
@@ -2771,10 +2847,8 @@ extern "C" int ramx_dev_plane_gram(ramx_dev *d, int32_t n_families, const ramx_p
 {
   if (!d || n_families < 0 || (n_families && (!plane_first || !plane_count)))
   { ramx_set_error("ramx_dev_plane_gram: bad argument"); return RAMX_ERR_ARG; }
-  if (!d->planes_ready)
-  { ramx_set_error("ramx_dev_plane_gram: no resident bit planes (ramx_dev_planes has not run on this device, or a later call dropped them)"); return RAMX_ERR_STATE; }
-  if (n_families != d->lk_families)
-  { ramx_set_error("ramx_dev_plane_gram: %d families, the resident replay has %d", n_families, d->lk_families); return RAMX_ERR_ARG; }
+  int rc;
+  if ((rc = resident_check("ramx_dev_plane_gram", d, n_families)) != RAMX_OK) return rc;
   // everything is checked before anything is launched or written
   std::vector<long long> at, co_at((size_t)(n_families > 0 ? n_families : 1), 0);
   std::vector<int4> gfam((size_t)(n_families > 0 ? n_families : 1), make_int4(0, 0, 0, 0)), block;
@@ -2782,59 +2856,33 @@ extern "C" int ramx_dev_plane_gram(ramx_dev *d, int32_t n_families, const ramx_p
   for (int f = 0; f < n_families; f++)
   {
     const int P = plane_count[f];
-    const long long frows = d->lk_fam[3 * (size_t)f], T = d->lk_fam[3 * (size_t)f + 1], base = d->lk_fam[3 * (size_t)f + 2];
-    if (P < 0 || P > RAMX_LINKAGE_MAX_PLANES)
-    { ramx_set_error("ramx_dev_plane_gram: family %d: %d planes outside [0, %d]", f, P, RAMX_LINKAGE_MAX_PLANES); return RAMX_ERR_ARG; }
-    if (P == 0) continue;
-    if (plane_first[f] < 0 || !planes || !co || !co_first || co_first[f] < 0 || (bits && (!bits_first || bits_first[f] < 0)))
-    { ramx_set_error("ramx_dev_plane_gram: family %d: bad argument", f); return RAMX_ERR_ARG; }
-    const ramx_plane *pp = planes + plane_first[f];
-    for (int i = 0; i < P; i++)
-    {
-      if (pp[i].row < 0 || pp[i].row >= frows || pp[i].cls < 0 || pp[i].cls >= RAMX_PLANE_CLASSES)
-      { ramx_set_error("ramx_dev_plane_gram: family %d, plane %d: (row %d, class %d) outside the resident replay (%lld rows, classes 0..7)", f, i, pp[i].row, pp[i].cls, frows); return RAMX_ERR_ARG; }
-      if (i > 0 && (pp[i].row < pp[i - 1].row || (pp[i].row == pp[i - 1].row && pp[i].cls <= pp[i - 1].cls)))
-      { ramx_set_error("ramx_dev_plane_gram: family %d, plane %d: the planes are not strictly increasing in (row, class)", f, i); return RAMX_ERR_ARG; }
-    }
-    if (T == 0) continue;                             // a family without tiles writes nothing
-    gfam[f] = make_int4((int)at.size(), P, (int)T, 0);
+    const ResidentFam &rf = d->res_fam[f];
+    const ramx_plane *pp = P > 0 && plane_first[f] >= 0 && planes && co && co_first && co_first[f] >= 0 &&
+                           (!bits || (bits_first && bits_first[f] >= 0)) ? planes + plane_first[f] : NULL;
+    const int at0 = (int)at.size();
+    // a family without tiles writes nothing: its planes are checked, their words are not listed
+    if ((rc = plane_list("ramx_dev_plane_gram", f, rf, pp, P, rf.tiles ? &at : NULL)) != RAMX_OK) return rc;
+    if (P == 0 || rf.tiles == 0) continue;
+    gfam[f] = make_int4(at0, P, rf.tiles, 0);
     co_at[f] = (long long)co_words;
     co_words += (size_t)P * P;
-    for (int i = 0; i < P; i++) at.push_back(base + ((long long)pp[i].row * RAMX_PLANE_CLASSES + pp[i].cls) * T);
-    const int nb = (P + RAMX_GRAM_BLOCK - 1) / RAMX_GRAM_BLOCK;
-    for (int bi = 0; bi < nb; bi++)
-      for (int bj = bi; bj < nb; bj++) block.push_back(make_int4(f, bi, bj, 0));
+    upper_blocks(block, f, P, RAMX_GRAM_BLOCK);
   }
   if (block.empty()) return RAMX_OK;
   // a plane to count has passed row < rows[f] of a family with tiles: that replay has run and its buffer exists
   HIPCHK(hipSetDevice(d->ordinal));
-  int rc;
-  if ((rc = ensure(&d->d_lk_at, &d->cap_lk_at, at.size() * sizeof(long long)))) return rc;
-  if ((rc = ensure(&d->d_lk_coat, &d->cap_lk_coat, co_at.size() * sizeof(long long)))) return rc;
-  if ((rc = ensure(&d->d_lk_gfam, &d->cap_lk_gfam, gfam.size() * sizeof(int4)))) return rc;
-  if ((rc = ensure(&d->d_lk_block, &d->cap_lk_block, block.size() * sizeof(int4)))) return rc;
+  if ((rc = upload(d, &d->d_lk_at, &d->cap_lk_at, at))) return rc;
+  if ((rc = upload(d, &d->d_lk_coat, &d->cap_lk_coat, co_at))) return rc;
+  if ((rc = upload(d, &d->d_lk_gfam, &d->cap_lk_gfam, gfam))) return rc;
+  if ((rc = upload(d, &d->d_lk_block, &d->cap_lk_block, block))) return rc;
   if ((rc = ensure(&d->d_lk_co, &d->cap_lk_co, co_words * sizeof(int)))) return rc;
-  HIPCHK(hipMemcpyAsync(d->d_lk_at, at.data(), at.size() * sizeof(long long), hipMemcpyHostToDevice, d->stream));
-  HIPCHK(hipMemcpyAsync(d->d_lk_coat, co_at.data(), co_at.size() * sizeof(long long), hipMemcpyHostToDevice, d->stream));
-  HIPCHK(hipMemcpyAsync(d->d_lk_gfam, gfam.data(), gfam.size() * sizeof(int4), hipMemcpyHostToDevice, d->stream));
-  HIPCHK(hipMemcpyAsync(d->d_lk_block, block.data(), block.size() * sizeof(int4), hipMemcpyHostToDevice, d->stream));
   GramArgs ga;
   ga.planes = d->d_lk_planes; ga.block = d->d_lk_block; ga.fam = d->d_lk_gfam; ga.at = d->d_lk_at; ga.co_at = d->d_lk_coat; ga.co = d->d_lk_co;
-  hipEvent_t ev[2] = { NULL, NULL };
-  const bool timed = hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
-  if (timed) (void)hipEventRecord(ev[0], d->stream);
-  rc = ramx_plane_gram_launch(d->stream, (int)block.size(), ga);
-  if (timed && rc == RAMX_OK) (void)hipEventRecord(ev[1], d->stream);
-  const hipError_t se = hipStreamSynchronize(d->stream);           // the uploads above read this function's vectors
-  float ms = 0;
-  d->lk_gram_ms = timed && rc == RAMX_OK && se == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess ? ms : 0;
-  for (int i = 0; i < 2; i++) if (ev[i]) (void)hipEventDestroy(ev[i]);
-  if (rc != RAMX_OK)
-  {
-    ramx_set_error("ramx_dev_plane_gram: the launch of %d workgroups failed", (int)block.size());
-    return rc;
-  }
-  HIPCHK(se);
+  int failed;
+  d->lk_gram_ms = 0;
+  rc = timed_launches(d, 1, [&](int) { return ramx_plane_gram_launch(d->stream, (int)block.size(), ga); }, &d->lk_gram_ms, &failed);
+  if (failed >= 0) ramx_set_error("ramx_dev_plane_gram: the launch of %d workgroups failed", (int)block.size());
+  if (rc != RAMX_OK) return rc;
   for (int f = 0; f < n_families; f++)
   {
     const int P = gfam[f].y, T = gfam[f].z;
@@ -2857,10 +2905,8 @@ extern "C" int ramx_dev_copy_dist(ramx_dev *d, int32_t n_families, const int32_t
   if (d) d->lk_dist_ms[0] = d->lk_dist_ms[1] = 0;
   if (!d || n_families < 0 || (n_families && (!copy_first || !copy_count)))
   { ramx_set_error("ramx_dev_copy_dist: bad argument"); return RAMX_ERR_ARG; }
-  if (!d->planes_ready)
-  { ramx_set_error("ramx_dev_copy_dist: no resident bit planes (ramx_dev_planes has not run on this device, or a later call dropped them)"); return RAMX_ERR_STATE; }
-  if (n_families != d->lk_families)
-  { ramx_set_error("ramx_dev_copy_dist: %d families, the resident replay has %d", n_families, d->lk_families); return RAMX_ERR_ARG; }
+  int rc;
+  if ((rc = resident_check("ramx_dev_copy_dist", d, n_families)) != RAMX_OK) return rc;
   // everything is checked before anything is launched or written
   std::vector<DistFam> dfam((size_t)(n_families > 0 ? n_families : 1));
   std::vector<int4> item, block;
@@ -2869,8 +2915,8 @@ extern "C" int ramx_dev_copy_dist(ramx_dev *d, int32_t n_families, const int32_t
   memset(dfam.data(), 0, dfam.size() * sizeof(DistFam));
   for (int f = 0; f < n_families; f++)
   {
-    const int C = copy_count[f], count = d->lk_place[2 * f + 1];
-    const long long frows = d->lk_fam[3 * (size_t)f], T = d->lk_fam[3 * (size_t)f + 1], base = d->lk_fam[3 * (size_t)f + 2];
+    const int C = copy_count[f];
+    const ResidentFam &rf = d->res_fam[f];
     if (C < 0 || C > RAMX_DIST_MAX_COPIES)
     { ramx_set_error("ramx_dev_copy_dist: family %d: %d copies outside [0, %d]", f, C, RAMX_DIST_MAX_COPIES); return RAMX_ERR_ARG; }
     if (C == 0) continue;
@@ -2879,15 +2925,15 @@ extern "C" int ramx_dev_copy_dist(ramx_dev *d, int32_t n_families, const int32_t
     const int32_t *cp = copies + copy_first[f];
     for (int i = 0; i < C; i++)
     {
-      if (cp[i] < 0 || cp[i] >= count)
-      { ramx_set_error("ramx_dev_copy_dist: family %d, entry %d: copy %d outside the family's %d flanks", f, i, cp[i], count); return RAMX_ERR_ARG; }
+      if (cp[i] < 0 || cp[i] >= rf.count)
+      { ramx_set_error("ramx_dev_copy_dist: family %d, entry %d: copy %d outside the family's %d flanks", f, i, cp[i], rf.count); return RAMX_ERR_ARG; }
       if (i > 0 && cp[i] <= cp[i - 1])
       { ramx_set_error("ramx_dev_copy_dist: family %d, entry %d: the copies are not strictly increasing", f, i); return RAMX_ERR_ARG; }
     }
-    if (frows == 0) continue;                         // all-zero records, written below on the host
+    if (rf.rows == 0) continue;                       // all-zero records, written below on the host
     DistFam &fd = dfam[f];
-    fd.plane_base = base; fd.stream_base = (long long)stream_words; fd.out_base = (long long)records;
-    fd.T = (int)T; fd.rows = (int)frows; fd.RW = (int)((frows + 63) / 64); fd.C = C;
+    fd.plane_base = rf.base; fd.stream_base = (long long)stream_words; fd.out_base = (long long)records;
+    fd.T = rf.tiles; fd.rows = rf.rows; fd.RW = (rf.rows + 63) / 64; fd.C = C;
     stream_words += (size_t)C * RAMX_DIST_STREAMS * fd.RW;
     records += (size_t)C * C;
     // one wave per tile that holds a chosen copy and per block of 64 rows (the list is ascending: a tile's copies are adjacent)
@@ -2898,46 +2944,27 @@ extern "C" int ramx_dev_copy_dist(ramx_dev *d, int32_t n_families, const int32_t
       for (; i < C && (cp[i] >> 6) == tile; i++) slot[(size_t)s0 + (cp[i] & 63)] = i;
       for (int rb = 0; rb < fd.RW; rb++) item.push_back(make_int4(f, tile, s0, rb));
     }
-    const int nb = (C + RAMX_DIST_BLOCK - 1) / RAMX_DIST_BLOCK;
-    for (int bi = 0; bi < nb; bi++)
-      for (int bj = bi; bj < nb; bj++) block.push_back(make_int4(f, bi, bj, 0));
+    upper_blocks(block, f, C, RAMX_DIST_BLOCK);
   }
-  int rc = RAMX_OK;
   if (!block.empty())
   {
     // a copy to count has passed rows[f] > 0 of a family with flanks: that replay has run and its buffer exists
     HIPCHK(hipSetDevice(d->ordinal));
     if ((rc = ensure(&d->d_lk_streams, &d->cap_lk_streams, stream_words * sizeof(unsigned long long)))) return rc;
-    if ((rc = ensure(&d->d_lk_dfam, &d->cap_lk_dfam, dfam.size() * sizeof(DistFam)))) return rc;
-    if ((rc = ensure(&d->d_lk_ditem, &d->cap_lk_ditem, item.size() * sizeof(int4)))) return rc;
-    if ((rc = ensure(&d->d_lk_dslot, &d->cap_lk_dslot, slot.size() * sizeof(int)))) return rc;
-    if ((rc = ensure(&d->d_lk_dblock, &d->cap_lk_dblock, block.size() * sizeof(int4)))) return rc;
+    if ((rc = upload(d, &d->d_lk_dfam, &d->cap_lk_dfam, dfam))) return rc;
+    if ((rc = upload(d, &d->d_lk_ditem, &d->cap_lk_ditem, item))) return rc;
+    if ((rc = upload(d, &d->d_lk_dslot, &d->cap_lk_dslot, slot))) return rc;
+    if ((rc = upload(d, &d->d_lk_dblock, &d->cap_lk_dblock, block))) return rc;
     if ((rc = ensure(&d->d_lk_dist, &d->cap_lk_dist, records * sizeof(ramx_copy_dist)))) return rc;
-    HIPCHK(hipMemcpyAsync(d->d_lk_dfam, dfam.data(), dfam.size() * sizeof(DistFam), hipMemcpyHostToDevice, d->stream));
-    HIPCHK(hipMemcpyAsync(d->d_lk_ditem, item.data(), item.size() * sizeof(int4), hipMemcpyHostToDevice, d->stream));
-    HIPCHK(hipMemcpyAsync(d->d_lk_dslot, slot.data(), slot.size() * sizeof(int), hipMemcpyHostToDevice, d->stream));
-    HIPCHK(hipMemcpyAsync(d->d_lk_dblock, block.data(), block.size() * sizeof(int4), hipMemcpyHostToDevice, d->stream));
     DistArgs da;
     da.planes = d->d_lk_planes; da.fam = d->d_lk_dfam; da.item = d->d_lk_ditem; da.slot = d->d_lk_dslot; da.block = d->d_lk_dblock;
     da.streams = d->d_lk_streams; da.out = d->d_lk_dist;
-    hipEvent_t ev[3] = { NULL, NULL, NULL };
-    const bool timed = hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess && hipEventCreate(&ev[2]) == hipSuccess;
-    if (timed) (void)hipEventRecord(ev[0], d->stream);
-    rc = ramx_dist_transpose_launch(d->stream, (int)item.size(), da);
-    if (timed && rc == RAMX_OK) (void)hipEventRecord(ev[1], d->stream);
-    if (rc == RAMX_OK) rc = ramx_dist_pairs_launch(d->stream, (int)block.size(), da);
-    if (timed && rc == RAMX_OK) (void)hipEventRecord(ev[2], d->stream);
-    const hipError_t se = hipStreamSynchronize(d->stream);           // the uploads above read this function's vectors
-    float ms = 0;
-    if (timed && rc == RAMX_OK && se == hipSuccess)
-      for (int i = 0; i < 2; i++) d->lk_dist_ms[i] = hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess ? ms : 0;
-    for (int i = 0; i < 3; i++) if (ev[i]) (void)hipEventDestroy(ev[i]);
-    if (rc != RAMX_OK)
-    {
-      ramx_set_error("ramx_dev_copy_dist: the launch of %d waves and %d workgroups failed", (int)item.size(), (int)block.size());
-      return rc;
-    }
-    HIPCHK(se);
+    // the pair kernel goes behind the transposition without a round trip to the host
+    int failed;
+    rc = timed_launches(d, 2, [&](int i) { return i == 0 ? ramx_dist_transpose_launch(d->stream, (int)item.size(), da)
+                                                         : ramx_dist_pairs_launch(d->stream, (int)block.size(), da); }, d->lk_dist_ms, &failed);
+    if (failed >= 0) ramx_set_error("ramx_dev_copy_dist: the launch of %d waves and %d workgroups failed", (int)item.size(), (int)block.size());
+    if (rc != RAMX_OK) return rc;
   }
   for (int f = 0; f < n_families; f++)
   {
@@ -2955,24 +2982,6 @@ extern "C" void ramx_dev_copy_dist_ms(ramx_dev *d, double ms[2])
   ms[0] = d ? d->lk_dist_ms[0] : 0; ms[1] = d ? d->lk_dist_ms[1] : 0;
 }
 
-// one timed launch on d->stream: ms is added to *sum
-template <typename F>
-static int timed_launch(ramx_dev *d, F launch, double *sum)
-{
-  hipEvent_t ev[2] = { NULL, NULL };
-  const bool timed = hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
-  if (timed) (void)hipEventRecord(ev[0], d->stream);
-  const int rc = launch();
-  if (timed && rc == RAMX_OK) (void)hipEventRecord(ev[1], d->stream);
-  const hipError_t se = hipStreamSynchronize(d->stream);
-  float ms = 0;
-  if (timed && rc == RAMX_OK && se == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) *sum += ms;
-  for (int i = 0; i < 2; i++) if (ev[i]) (void)hipEventDestroy(ev[i]);
-  if (rc != RAMX_OK) return rc;
-  HIPCHK(se);
-  return RAMX_OK;
-}
-
 extern "C" int ramx_dev_subfamilies(ramx_dev *d, int32_t n_families, const ramx_plane *planes, const int32_t *plane_first,
                                     const int32_t *plane_count, const uint8_t *init, int32_t K, int32_t max_iter, int32_t *labels,
                                     uint8_t *patterns_out, int32_t *cnt_out, int32_t *size_out, int32_t *iterations, int32_t *converged)
@@ -2981,11 +2990,9 @@ extern "C" int ramx_dev_subfamilies(ramx_dev *d, int32_t n_families, const ramx_
   { ramx_set_error("ramx_dev_subfamilies: bad argument"); return RAMX_ERR_ARG; }
   if (K < 1 || K > RAMX_SUBFAM_K) { ramx_set_error("ramx_dev_subfamilies: K = %d outside [1, %d]", K, RAMX_SUBFAM_K); return RAMX_ERR_ARG; }
   if (max_iter < 1) { ramx_set_error("ramx_dev_subfamilies: max_iter = %d below 1", max_iter); return RAMX_ERR_ARG; }
-  if (!d->planes_ready)
-  { ramx_set_error("ramx_dev_subfamilies: no resident bit planes (ramx_dev_planes has not run on this device, or a later call dropped them)"); return RAMX_ERR_STATE; }
-  if (n_families != d->lk_families)
-  { ramx_set_error("ramx_dev_subfamilies: %d families, the resident replay has %d", n_families, d->lk_families); return RAMX_ERR_ARG; }
-  if (d->lk_npadded > 0 && !labels) { ramx_set_error("ramx_dev_subfamilies: labels missing"); return RAMX_ERR_ARG; }
+  int rc;
+  if ((rc = resident_check("ramx_dev_subfamilies", d, n_families)) != RAMX_OK) return rc;
+  if (d->res_npadded > 0 && !labels) { ramx_set_error("ramx_dev_subfamilies: labels missing"); return RAMX_ERR_ARG; }
   // everything is checked before anything is launched or written
   const size_t nf1 = (size_t)(n_families > 0 ? n_families : 1);
   std::vector<SubfamFam> fam(nf1);
@@ -2996,28 +3003,18 @@ extern "C" int ramx_dev_subfamilies(ramx_dev *d, int32_t n_families, const ramx_
   std::vector<unsigned char> pat;
   std::vector<int> count(nf1, 0);
   size_t mask_words = 0, cnt_words = 0;
-  int max_tiles = 0;
   for (int f = 0; f < n_families; f++)
   {
     const int P = plane_count[f];
-    const long long frows = d->lk_fam[3 * (size_t)f], T = d->lk_fam[3 * (size_t)f + 1], base = d->lk_fam[3 * (size_t)f + 2];
-    if (P < 0 || P > RAMX_LINKAGE_MAX_PLANES)
-    { ramx_set_error("ramx_dev_subfamilies: family %d: %d planes outside [0, %d]", f, P, RAMX_LINKAGE_MAX_PLANES); return RAMX_ERR_ARG; }
-    if (P > 0 && (plane_first[f] < 0 || !planes || !cnt_out))
-    { ramx_set_error("ramx_dev_subfamilies: family %d: bad argument", f); return RAMX_ERR_ARG; }
-    const ramx_plane *pp = P > 0 ? planes + plane_first[f] : NULL;
+    const ResidentFam &rf = d->res_fam[f];
+    const int T = rf.tiles;
+    const ramx_plane *pp = P > 0 && plane_first[f] >= 0 && planes && cnt_out ? planes + plane_first[f] : NULL;
     SubfamFam &fd = fam[f];
-    fd.var0 = (int)var.size(); fd.at0 = (int)at.size(); fd.P = P; fd.T = (int)T; fd.flank0 = d->lk_place[2 * f];
+    fd.var0 = (int)var.size(); fd.at0 = (int)at.size(); fd.P = P; fd.T = T; fd.flank0 = rf.first;
     fd.mask0 = (long long)mask_words; fd.cnt0 = (long long)cnt_words;
-    count[f] = d->lk_place[2 * f + 1];
-    for (int i = 0; i < P; i++)
-    {
-      if (pp[i].row < 0 || pp[i].row >= frows || pp[i].cls < 0 || pp[i].cls >= RAMX_PLANE_CLASSES)
-      { ramx_set_error("ramx_dev_subfamilies: family %d, plane %d: (row %d, class %d) outside the resident replay (%lld rows, classes 0..7)", f, i, pp[i].row, pp[i].cls, frows); return RAMX_ERR_ARG; }
-      if (i > 0 && (pp[i].row < pp[i - 1].row || (pp[i].row == pp[i - 1].row && pp[i].cls <= pp[i - 1].cls)))
-      { ramx_set_error("ramx_dev_subfamilies: family %d, plane %d: the planes are not strictly increasing in (row, class)", f, i); return RAMX_ERR_ARG; }
-      at.push_back(base + ((long long)pp[i].row * RAMX_PLANE_CLASSES + pp[i].cls) * T);
-    }
+    count[f] = rf.count;
+    // the words of every family's planes are listed, those of a family without tiles too: cnt_out is laid out by at0
+    if ((rc = plane_list("ramx_dev_subfamilies", f, rf, pp, P, &at)) != RAMX_OK) return rc;
     for (int i = 0; i < P; i++)
     {
       if (pp[i].cls == RAMX_PLANE_COVER) continue;
@@ -3039,19 +3036,17 @@ extern "C" int ramx_dev_subfamilies(ramx_dev *d, int32_t n_families, const ramx_
     }
     mask_words += (size_t)K * T;
     cnt_words += (size_t)K * (P + 1);
-    if (T > max_tiles) max_tiles = (int)T;
   }
   {
-    long long *lay = (long long *)realloc(d->sf_lay, nf1 * 2 * sizeof(long long));
+    SubfamLay *lay = (SubfamLay *)realloc(d->sf_lay, nf1 * sizeof(SubfamLay));
     if (!lay) { ramx_set_error("ramx_dev_subfamilies: out of memory"); return RAMX_ERR_ARG; }
-    for (int f = 0; f < n_families; f++) { lay[2 * f] = fam[f].mask0; lay[2 * f + 1] = fam[f].T; }
+    for (int f = 0; f < n_families; f++) lay[f] = SubfamLay{ fam[f].mask0, fam[f].T };
     d->sf_lay = lay; d->sf_families = 0; d->sf_K = K;       // no result until the call has succeeded
   }
   // the answers of a family that never reaches the device (no tile): one assignment of nobody
-  for (int i = 0; i < d->lk_npadded; i++) labels[i] = -1;
+  for (int i = 0; i < d->res_npadded; i++) labels[i] = -1;
   std::vector<char> active(nf1, 0);
   int n_active = 0;
-  size_t total_tiles = 0, total_items = 0;
   for (int f = 0; f < n_families; f++)
   {
     iterations[f] = 1; converged[f] = 1;
@@ -3060,34 +3055,24 @@ extern "C" int ramx_dev_subfamilies(ramx_dev *d, int32_t n_families, const ramx_
     for (size_t i = 0; i < (size_t)K * fam[f].V; i++) patterns_out[(size_t)K * fam[f].var0 + i] = init[(size_t)K * fam[f].var0 + i] ? 1 : 0;
     if (fam[f].T == 0) continue;
     active[f] = 1; n_active++;
-    total_tiles += (size_t)fam[f].T; total_items += (size_t)fam[f].P + 1;
   }
   d->sf_ms[0] = d->sf_ms[1] = 0;
   if (n_active == 0) { d->sf_families = n_families; return RAMX_OK; }
   HIPCHK(hipSetDevice(d->ordinal));
-  int rc;
-  if ((rc = ensure(&d->d_sf_fam, &d->cap_sf_fam, nf1 * sizeof(SubfamFam)))) return rc;
-  if ((rc = ensure(&d->d_sf_at, &d->cap_sf_at, (at.size() + 1) * sizeof(long long)))) return rc;
-  if ((rc = ensure(&d->d_sf_var, &d->cap_sf_var, (var.size() + 1) * sizeof(longlong2)))) return rc;
-  if ((rc = ensure(&d->d_sf_pat, &d->cap_sf_pat, pat.size() + 1))) return rc;
-  if ((rc = ensure(&d->d_sf_tile, &d->cap_sf_tile, total_tiles * sizeof(int2)))) return rc;
-  if ((rc = ensure(&d->d_sf_item, &d->cap_sf_item, total_items * sizeof(int2)))) return rc;
-  if ((rc = ensure(&d->d_sf_count, &d->cap_sf_count, nf1 * sizeof(int)))) return rc;
-  if ((rc = ensure(&d->d_sf_labels, &d->cap_sf_labels, (size_t)d->lk_npadded * sizeof(int)))) return rc;
-  if ((rc = ensure(&d->d_sf_changed, &d->cap_sf_changed, total_tiles * sizeof(int)))) return rc;
+  if ((rc = upload(d, &d->d_sf_fam, &d->cap_sf_fam, fam))) return rc;
+  if ((rc = upload(d, &d->d_sf_at, &d->cap_sf_at, at))) return rc;
+  if ((rc = upload(d, &d->d_sf_var, &d->cap_sf_var, var))) return rc;
+  if ((rc = upload(d, &d->d_sf_count, &d->cap_sf_count, count))) return rc;
+  if ((rc = ensure(&d->d_sf_labels, &d->cap_sf_labels, (size_t)d->res_npadded * sizeof(int)))) return rc;
   if ((rc = ensure(&d->d_sf_cnt, &d->cap_sf_cnt, cnt_words * sizeof(int)))) return rc;
   if ((rc = ensure(&d->d_sf_mask, &d->cap_sf_mask, mask_words * sizeof(unsigned long long)))) return rc;
-  HIPCHK(hipMemcpyAsync(d->d_sf_fam, fam.data(), nf1 * sizeof(SubfamFam), hipMemcpyHostToDevice, d->stream));
-  if (!at.empty()) HIPCHK(hipMemcpyAsync(d->d_sf_at, at.data(), at.size() * sizeof(long long), hipMemcpyHostToDevice, d->stream));
-  if (!var.empty()) HIPCHK(hipMemcpyAsync(d->d_sf_var, var.data(), var.size() * sizeof(longlong2), hipMemcpyHostToDevice, d->stream));
-  HIPCHK(hipMemcpyAsync(d->d_sf_count, count.data(), nf1 * sizeof(int), hipMemcpyHostToDevice, d->stream));
-  HIPCHK(hipMemsetAsync(d->d_sf_labels, 0xff, (size_t)d->lk_npadded * sizeof(int), d->stream));      // no label yet: -1
+  HIPCHK(hipMemsetAsync(d->d_sf_labels, 0xff, (size_t)d->res_npadded * sizeof(int), d->stream));     // no label yet: -1
   HIPCHK(hipMemsetAsync(d->d_sf_cnt, 0, cnt_words * sizeof(int), d->stream));
   SubfamArgs sa;
   memset(&sa, 0, sizeof(sa));
-  sa.planes = d->d_lk_planes; sa.fam = d->d_sf_fam; sa.at = d->d_sf_at; sa.var = d->d_sf_var; sa.pat = d->d_sf_pat;
-  sa.tile = d->d_sf_tile; sa.item = d->d_sf_item; sa.count = d->d_sf_count; sa.labels = d->d_sf_labels; sa.mask = d->d_sf_mask;
-  sa.changed = d->d_sf_changed; sa.cnt = d->d_sf_cnt; sa.K = K;
+  sa.planes = d->d_lk_planes; sa.fam = d->d_sf_fam; sa.at = d->d_sf_at; sa.var = d->d_sf_var;
+  sa.count = d->d_sf_count; sa.labels = d->d_sf_labels; sa.mask = d->d_sf_mask;
+  sa.cnt = d->d_sf_cnt; sa.K = K;
   std::vector<int2> tile, item;
   std::vector<int> changed, cnt(cnt_words, 0);
   // between two assignments only the per-tile change counts and the counts come to the host: the update rule runs here
@@ -3101,12 +3086,16 @@ extern "C" int ramx_dev_subfamilies(ramx_dev *d, int32_t n_families, const ramx_
       for (int i = 0; i <= fam[f].P; i++) item.push_back(make_int2(f, i));
     }
     changed.assign(tile.size(), 0);
-    if (!pat.empty()) HIPCHK(hipMemcpyAsync(d->d_sf_pat, pat.data(), pat.size(), hipMemcpyHostToDevice, d->stream));
-    HIPCHK(hipMemcpyAsync(d->d_sf_tile, tile.data(), tile.size() * sizeof(int2), hipMemcpyHostToDevice, d->stream));
-    HIPCHK(hipMemcpyAsync(d->d_sf_item, item.data(), item.size() * sizeof(int2), hipMemcpyHostToDevice, d->stream));
-    if ((rc = timed_launch(d, [&] { return ramx_subfam_assign_launch(d->stream, (int)tile.size(), sa); }, &d->sf_ms[0])) != RAMX_OK)
+    // (the lists only shrink: the first iteration's buffers serve the later ones)
+    if ((rc = upload(d, &d->d_sf_pat, &d->cap_sf_pat, pat))) return rc;
+    if ((rc = upload(d, &d->d_sf_tile, &d->cap_sf_tile, tile))) return rc;
+    if ((rc = upload(d, &d->d_sf_item, &d->cap_sf_item, item))) return rc;
+    if ((rc = ensure(&d->d_sf_changed, &d->cap_sf_changed, tile.size() * sizeof(int)))) return rc;
+    sa.pat = d->d_sf_pat; sa.tile = d->d_sf_tile; sa.item = d->d_sf_item; sa.changed = d->d_sf_changed;
+    int failed;
+    if ((rc = timed_launches(d, 1, [&](int) { return ramx_subfam_assign_launch(d->stream, (int)tile.size(), sa); }, &d->sf_ms[0], &failed)) != RAMX_OK)
     { if (rc == RAMX_ERR_HIP) ramx_set_error("ramx_dev_subfamilies: the assign launch of %d waves failed", (int)tile.size()); return rc; }
-    if ((rc = timed_launch(d, [&] { return ramx_subfam_count_launch(d->stream, (int)item.size(), sa); }, &d->sf_ms[1])) != RAMX_OK)
+    if ((rc = timed_launches(d, 1, [&](int) { return ramx_subfam_count_launch(d->stream, (int)item.size(), sa); }, &d->sf_ms[1], &failed)) != RAMX_OK)
     { if (rc == RAMX_ERR_HIP) ramx_set_error("ramx_dev_subfamilies: the count launch of %d waves failed", (int)item.size()); return rc; }
     HIPCHK(hipMemcpy(changed.data(), d->d_sf_changed, tile.size() * sizeof(int), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(cnt.data(), d->d_sf_cnt, cnt_words * sizeof(int), hipMemcpyDeviceToHost));
@@ -3159,8 +3148,8 @@ extern "C" int ramx_dev_subfam_masks(ramx_dev *d, int32_t family, uint64_t *mask
   if (!d || !mask || family < 0) { ramx_set_error("ramx_dev_subfam_masks: bad argument"); return RAMX_ERR_ARG; }
   if (!d->planes_ready || !d->sf_lay || family >= d->sf_families)
   { ramx_set_error("ramx_dev_subfam_masks: no ramx_dev_subfamilies result of family %d on the resident planes", family); return RAMX_ERR_STATE; }
-  const long long mask0 = d->sf_lay[2 * (size_t)family], T = d->sf_lay[2 * (size_t)family + 1];
-  if (T > 0) HIPCHK(hipMemcpy(mask, d->d_sf_mask + mask0, (size_t)d->sf_K * T * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  const SubfamLay &lay = d->sf_lay[family];
+  if (lay.tiles > 0) HIPCHK(hipMemcpy(mask, d->d_sf_mask + lay.mask0, (size_t)d->sf_K * lay.tiles * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return RAMX_OK;
 }
 

@@ -234,6 +234,18 @@ def pad_flanks(flanks):
     return out, npad
 
 
+def _flatten(lists, dtype):
+    """Per-family arrays as the C-ABI takes them -> (all of them in one array, which is never empty; first and count per family,
+    int32)."""
+    cnt = np.array([len(x) for x in lists], np.int32)
+    return np.concatenate(list(lists) + [np.zeros(1, dtype)]), (np.cumsum(cnt) - cnt).astype(np.int32), cnt
+
+
+def _starts(sizes):
+    """int64 sizes per family -> where each family begins in one array of them all"""
+    return (np.cumsum(sizes) - sizes).astype(np.int64)
+
+
 class Device:
     def __init__(self, ordinal: int = 0):
         self._L = _lib.lib()
@@ -483,9 +495,14 @@ class Device:
         _lib.check(self._L.ramx_dev_planes(self._h, arr, npad, first.ctypes.data, count.ctypes.data, nf, C.byref(cp),
                                            cons.ctypes.data, rows_a.ctypes.data, cols.ctypes.data, ends.ctypes.data, ms),
                    "ramx_dev_planes")
-        self._plane_tiles = (count + 63) // 64
-        self._plane_place = (first.copy(), count.copy(), npad)
+        self._resident = ((count + 63) // 64, first.copy(), count.copy(), npad)
         return PlanesResult(cols, ends, tuple(ms), count)
+
+    def _resident_families(self, nf):
+        """(tiles, first flank, flanks) of nf families and n_padded of the last planes(); zeros before any, and for the families
+        it did not have (the library refuses such a call)."""
+        tiles, first, count, npad = getattr(self, "_resident", (np.zeros(0, np.int32),) * 3 + (0,))
+        return tuple([int(a[f]) if f < len(a) else 0 for f in range(nf)] for a in (tiles, first, count)) + (npad,)
 
     def plane_gram(self, planes, bits: bool = False):
         """The Gram matrix of chosen planes of the resident replay (C-ABI ramx_dev_plane_gram).  `planes`: one PLANE_DTYPE
@@ -494,15 +511,13 @@ class Device:
         one = not isinstance(planes, (list, tuple))
         lists = [np.ascontiguousarray(x, PLANE_DTYPE).reshape(-1) for x in ([planes] if one else planes)]
         nf = len(lists)
-        tiles = getattr(self, "_plane_tiles", np.zeros(nf, np.int64))
-        tiles = [int(tiles[f]) if f < len(tiles) else 0 for f in range(nf)]
-        cnt = np.array([len(x) for x in lists], np.int32)
-        first = np.concatenate([[0], np.cumsum(cnt)[:-1]]).astype(np.int32) if nf else np.zeros(0, np.int32)
-        allp = np.concatenate(lists) if nf and cnt.sum() else np.zeros(1, PLANE_DTYPE)
-        co_first = np.concatenate([[0], np.cumsum(cnt.astype(np.int64) ** 2)[:-1]]).astype(np.int64) if nf else np.zeros(0, np.int64)
-        co = np.full(max(int((cnt.astype(np.int64) ** 2).sum()), 1), -1, np.int32)
-        bsz = np.array([int(cnt[f]) * tiles[f] for f in range(nf)], np.int64)
-        b_first = np.concatenate([[0], np.cumsum(bsz)[:-1]]).astype(np.int64) if nf else np.zeros(0, np.int64)
+        tiles = self._resident_families(nf)[0]
+        allp, first, cnt = _flatten(lists, PLANE_DTYPE)
+        cells = cnt.astype(np.int64) ** 2
+        co_first = _starts(cells)
+        co = np.full(max(int(cells.sum()), 1), -1, np.int32)
+        bsz = cnt.astype(np.int64) * np.array(tiles, np.int64)
+        b_first = _starts(bsz)
         bw = np.zeros(max(int(bsz.sum()), 1), np.uint64) if bits else None
         _lib.check(self._L.ramx_dev_plane_gram(self._h, nf, allp.ctypes.data, first.ctypes.data, cnt.ctypes.data, co.ctypes.data,
                                                co_first.ctypes.data, bw.ctypes.data if bits else None,
@@ -520,11 +535,9 @@ class Device:
         one = not isinstance(copies, (list, tuple))
         lists = [np.ascontiguousarray(x, np.int32).reshape(-1) for x in ([copies] if one else copies)]
         nf = len(lists)
-        cnt = np.array([len(x) for x in lists], np.int32)
-        first = np.concatenate([[0], np.cumsum(cnt)[:-1]]).astype(np.int32) if nf else np.zeros(0, np.int32)
-        allc = np.concatenate(lists + [np.zeros(1, np.int32)])
+        allc, first, cnt = _flatten(lists, np.int32)
         cells = cnt.astype(np.int64) ** 2
-        o_first = np.concatenate([[0], np.cumsum(cells)[:-1]]).astype(np.int64) if nf else np.zeros(0, np.int64)
+        o_first = _starts(cells)
         out = np.zeros(max(int(cells.sum()), 1), COPY_DIST_DTYPE)
         if fill is not None:
             out.view(np.uint8)[:] = fill
@@ -552,10 +565,8 @@ class Device:
             K = next((int(x.shape[1]) for x in inits if x.ndim == 2), 1)
         for f in range(nf):
             assert not 1 <= K <= 8 or inits[f].size == V[f] * K, (f, inits[f].shape, V[f], K)     # another K: the library refuses it
-        first_f, count_f, npad = getattr(self, "_plane_place", (np.zeros(nf, np.int32), np.zeros(nf, np.int32), 0))
-        cnt = np.array([len(x) for x in lists], np.int32)
-        first = np.concatenate([[0], np.cumsum(cnt)[:-1]]).astype(np.int32) if nf else np.zeros(0, np.int32)
-        allp = np.concatenate(lists) if nf and cnt.sum() else np.zeros(1, PLANE_DTYPE)
+        tiles, first_f, count_f, npad = self._resident_families(nf)
+        allp, first, cnt = _flatten(lists, PLANE_DTYPE)
         alli = np.concatenate([x.reshape(-1) for x in inits] + [np.zeros(1, np.uint8)])
         labels = np.full(max(npad, 1), -2, np.int32)
         pats = np.full(max(sum(V) * max(K, 1), 1), 255, np.uint8)
@@ -567,14 +578,14 @@ class Device:
                                                 size.ctypes.data, its.ctypes.data, conv.ctypes.data), "ramx_dev_subfamilies")
         out, v0 = [], 0
         for f in range(nf):
-            P, T = int(cnt[f]), int(self._plane_tiles[f]) if f < len(self._plane_tiles) else 0
+            P, T = int(cnt[f]), tiles[f]
             mk = None
             if masks:
                 mk = np.zeros((K, T), np.uint64)
                 buf = np.zeros(max(K * T, 1), np.uint64)
                 _lib.check(self._L.ramx_dev_subfam_masks(self._h, f, buf.ctypes.data), "ramx_dev_subfam_masks")
                 mk = buf[:K * T].reshape(K, T)
-            out.append(SubfamResult(labels[int(first_f[f]):int(first_f[f]) + int(count_f[f])].copy(),
+            out.append(SubfamResult(labels[first_f[f]:first_f[f] + count_f[f]].copy(),
                                     pats[K * v0:K * (v0 + V[f])].reshape(V[f], K).copy(),
                                     counts[K * int(first[f]):K * (int(first[f]) + P)].reshape(K, P).copy(),
                                     size[f * K:(f + 1) * K].copy(), int(its[f]), int(conv[f]), mk))

@@ -165,9 +165,9 @@ def test_tile_edges_and_the_limit_of_2048_copies(wide):
         d.close()
 
 
-def sentinel_call(d, lists, extra=0, expect=None, nf=None):
+def sentinel_call(d, lists, extra=0, expect=None, nf=None, why=None):
     """ramx_dev_copy_dist on a buffer of 0x5A bytes with `extra` records of room behind the result -> the buffer, or the error
-    code with `expect` (and the buffer untouched)."""
+    code with `expect` (and the buffer untouched; `why`: what the refusal's message holds)."""
     from repeatafterme_amd import _lib
     nf = len(lists) if nf is None else nf
     cnt = np.array([len(x) for x in lists], np.int32)
@@ -180,6 +180,7 @@ def sentinel_call(d, lists, extra=0, expect=None, nf=None):
     rc = d._L.ramx_dev_copy_dist(d._h, nf, allc.ctypes.data, first.ctypes.data, cnt.ctypes.data, out.ctypes.data, o_first.ctypes.data)
     if expect is not None:
         assert rc == expect, (rc, _lib.lib().ramx_last_error())
+        assert why is None or why in _lib.lib().ramx_last_error().decode(), (why, _lib.lib().ramx_last_error())
         assert (out.view(np.uint8) == 0x5A).all()
         return rc
     assert rc == 0, _lib.lib().ramx_last_error()
@@ -263,14 +264,18 @@ def test_state_and_argument_errors():
     try:
         d.load_library(c["seq"])
         flanks, idx = resolve_flanks(1, c["fs"].cores, 14, 60)
-        sentinel_call(d, [ok], expect=-104)                                                  # before any planes
+        sentinel_call(d, [ok], expect=-104, why="ramx_dev_copy_dist: no resident bit planes")  # before any planes
         d.planes(flanks, ep, cons)
         want = dr.matrix(c["maps"], ok)
         assert np.array_equal(d.copy_dist(ok), want)
-        for bad in ([3, 0], [3, 3], [-1, 2], [0, 37], list(range(37)) + list(range(2049 - 37))):
-            sentinel_call(d, [np.asarray(bad, np.int32)], expect=-103)
-        sentinel_call(d, [ok, ok], expect=-103)                                              # another n_families
-        sentinel_call(d, [], expect=-103, nf=0)
+        for bad, why in (([3, 0], "family 0, entry 1: the copies are not strictly increasing"),
+                         ([3, 3], "family 0, entry 1: the copies are not strictly increasing"),
+                         ([-1, 2], "family 0, entry 0: copy -1 outside the family's 37 flanks"),
+                         ([0, 37], "family 0, entry 1: copy 37 outside the family's 37 flanks"),
+                         (list(range(37)) + list(range(2049 - 37)), "family 0: 2049 copies outside [0, 2048]")):
+            sentinel_call(d, [np.asarray(bad, np.int32)], expect=-103, why=why)
+        sentinel_call(d, [ok, ok], expect=-103, why="2 families, the resident replay has 1")   # another n_families
+        sentinel_call(d, [], expect=-103, nf=0, why="0 families, the resident replay has 1")
         assert np.array_equal(d.copy_dist(ok), want)                                         # a refused list leaves the planes resident
         d.align(flanks, ep, cons)
         sentinel_call(d, [ok], expect=-104)                                                  # a later replay dropped them

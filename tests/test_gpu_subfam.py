@@ -209,6 +209,55 @@ def test_three_families_with_an_empty_one_in_the_middle():
     assert (labels_all[~inside] == -1).all() and (labels_all[inside] >= 0).all()
 
 
+def test_a_family_without_tiles_before_another_in_the_gram_and_in_the_split():
+    """The layout of tests/test_gpu_dist.py: three families, one of them with rows = 0, a family without flanks, a tile that
+    belongs to no family -- here the family without flanks stands third, with a list of its own, before the last family.  The
+    Gram call writes nothing for it (and takes none of its planes' offsets); the split answers it on the host, its counts
+    placed by its planes' offsets; the family behind it gets the restatement's answers from both."""
+    from repeatafterme_amd.device import Device, resolve_flanks
+    p = tp.params("20p43g", 14, 120, cappenalty=-10, when_to_stop=25)
+    fams = tp._three_families()
+    lib = np.concatenate([fs.sequence for fs in fams])
+    offs = np.cumsum([0] + [len(fs.sequence) for fs in fams])
+    cons = np.zeros((4, 120), np.int8)
+    rows, parts, want = [], [], []
+    for f, fs in enumerate(fams):
+        o = po.oracle_extend(1, fs.cores.copy(), fs.sequence, new_master(120), p, trace=True)
+        c = tp.foreign(o.col_base[:o.ret], at=8, k=5) if f else o.col_base[:0]               # family 0: rows = 0
+        cols, idx, results = pr.pileup(1, fs.cores, fs.sequence, p, c, with_walks=True)
+        (fl, nx), _ = resolve_flanks(1, fs.cores, 14, 120)
+        if f == 2:                                                                            # before it: a family without flanks
+            cons[len(rows), :len(c)] = c
+            rows.append(len(c)); parts.append((fl, 0, offs[f])); want.append(({}, 0))
+        cons[len(rows), :len(c)] = c
+        rows.append(len(c)); parts.append((fl, nx, offs[f]))
+        want.append((lr.planes_of(1, fs.cores, idx, results, fs.sequence, 14, c), len(idx)))
+    flanks, first, count = rl.lay_out(parts, hole_before=1)
+    assert rows[0] == 0 and count[2] == 0 and rows[2] == rows[3] > 10 and rows[1] > 10 and min(count[0], count[1], count[3]) > 0
+    K = 3
+    lists = [lr.as_planes([]), sr.list_with(rows[1], 9, 1), sr.list_with(rows[2], 12, 2), sr.list_with(rows[3], 20, 3)]
+    inits = [np.zeros((0, K), np.uint8), sr.copy_init(want[1][0], lists[1], K, want[1][1], 5), sr.random_init(12, K, 6),
+             sr.copy_init(want[3][0], lists[3], K, want[3][1], 7)]
+    assert inits[2].any()
+    d = Device(0)
+    try:
+        d.load_library(lib)
+        d.planes(flanks, to_extend_params(p), cons, rows=rows, fam_first=first, fam_count=count)
+        cos = d.plane_gram(lists)
+        res = d.subfamilies(lists, inits, masks=True)
+    finally:
+        d.close()
+    assert cos[0].shape == (0, 0) and cos[2].shape == (len(lists[2]),) * 2 and (cos[2] == -1).all()    # nothing written
+    e = res[2]
+    assert e.cnt.shape == (K, len(lists[2])) and not e.cnt.any() and e.size.shape == (K,) and not e.size.any()
+    assert (e.iterations, e.converged) == (1, 1) and np.array_equal(e.patterns, inits[2])
+    assert len(e.labels) == 0 and e.masks.shape == (K, 0)
+    for f in (1, 3):
+        pl, n = want[f]
+        assert np.array_equal(cos[f], lr.gram(pl, lists[f])) and cos[f].any(), f
+        same(res[f], sr.iterate(pl, lists[f], inits[f], n), f"family {f}")
+
+
 def test_one_assignment_only_and_an_init_whose_group_empties():
     c = lr.planted_case(0)
     d, n = open_case(c, 0)
@@ -272,6 +321,12 @@ def test_state_and_argument_errors_and_what_the_call_leaves():
             d.subfamilies(sel, init, max_iter=0)
         with pytest.raises(_lib.RamxError, match=r"\(-103\).*not strictly increasing"):
             d.subfamilies(sel[::-1].copy(), init)
+        with pytest.raises(_lib.RamxError, match=r"\(-103\).*2 families, the resident replay has 1"):
+            d.subfamilies([sel, sel], [init, init])
+        rows = len(c["cons"])
+        for bad in ((rows, 0), (0, 8)):
+            with pytest.raises(_lib.RamxError, match=r"\(-103\).*outside the resident replay \(%d rows" % rows):
+                d.subfamilies(lr.as_planes([bad]), np.zeros((1, 4), np.uint8))
         again = d.subfamilies(sel, init, masks=True)
         after = d.plane_gram(full, bits=True)
         d.copy_stats(flanks, ep, c["cons"])

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Host code of the replays under AddressSanitizer + UBSan, as stand-alone programs on the CPU (no GPU is opened, nothing is
-# loaded into python): replay_plan, the route gates, the batch's route plan and the site windows of ramx_device.hip, pad_to_tiles and the sinks' one-family view of ramx_extend.c, all static, so each program includes
+# loaded into python): replay_plan, the route gates, the batch's route plan, the site windows and the resident planes' lists of ramx_device.hip, pad_to_tiles and the sinks' one-family view of ramx_extend.c, all static, so each program includes
 # its source file and takes the rest of the library from the built libramx.so; and ramx_linkage.c, which stands alone.
 # usage: tools/host_asan/run.sh        (after the library has been built)
 set -euo pipefail
@@ -47,3 +47,8 @@ gcc -std=gnu11 -O1 $san $inc -o "$out/cli_outputs" "$here/cli_outputs_main.c" $l
 "$rocm/bin/hipcc" --offload-arch=gfx950 -x hip -std=c++17 -O1 -g -fno-omit-frame-pointer $inc -Xarch_host -fsanitize=address,undefined \
   -Xarch_host -fno-sanitize-recover=undefined -o "$out/site_windows" "$here/site_windows_main.cpp" $lib -L"$rocm/lib" -lrccl -lpthread
 "$out/site_windows"
+# a family's plane list at the edges of its contract and the block lists of the calls that answer from the resident planes
+# (plane_list / upper_blocks of ramx_device.hip)
+"$rocm/bin/hipcc" --offload-arch=gfx950 -x hip -std=c++17 -O1 -g -fno-omit-frame-pointer $inc -Xarch_host -fsanitize=address,undefined \
+  -Xarch_host -fno-sanitize-recover=undefined -o "$out/resident" "$here/resident_main.cpp" $lib -L"$rocm/lib" -lrccl -lpthread
+"$out/resident"
