@@ -521,6 +521,10 @@ static int profile_families(const struct sink_view *v)
   return rc;
 }
 
+/* "no alignment" in every end: what a replay leaves of a flank it does not walk */
+static void blank_ends(ramx_aln_end *ends, int32_t n)
+{ for (int32_t i = 0; i < n; i++) { ends[i].end_row = -1; ends[i].end_idx = -1; ends[i].score = 0; ends[i].start_idx = 0; ends[i].tail_ins = 0; } }
+
 /* With an alignment sink set: every family replayed in one call along its kept consensus (rows = ret), every flank walked back,
  * handed over family by family.  ramx_dev_align answers the families without a flank or a kept column over the prefilled ends. */
 static int align_families(const struct sink_view *v)
@@ -531,7 +535,7 @@ static int align_families(const struct sink_view *v)
   ramx_aln_end *ends = (ramx_aln_end *)malloc(sizeof(ramx_aln_end) * n);
   int32_t *idx = (int32_t *)malloc(sizeof(int32_t) * n * (size_t)(maxret > 0 ? maxret : 1));
   int32_t *ins = (int32_t *)malloc(sizeof(int32_t) * n * (size_t)(maxret > 0 ? maxret : 1));
-  for (int32_t i = 0; i < v->npad; i++) { ends[i].end_row = -1; ends[i].end_idx = -1; ends[i].score = 0; ends[i].start_idx = 0; ends[i].tail_ins = 0; }
+  blank_ends(ends, v->npad);
   const int rc = ramx_dev_align(v->d, v->fl, v->npad, v->first, v->count, v->nb, v->p, v->cons, v->ret, ends, idx, ins, NULL);
   for (int b = 0; b < v->nb && rc == RAMX_OK; b++)
   {
@@ -668,45 +672,70 @@ void ramx_set_linkage_sink(ramx_linkage_cb cb, void *user, int32_t min_count, in
   g_linkage_max = max_variants < 0 ? 0 : max_variants > RAMX_LINKAGE_MAX_PLANES / 2 ? RAMX_LINKAGE_MAX_PLANES / 2 : max_variants;
 }
 
-/* With a linkage sink set: the bit planes of the families along their kept consensus (rows = ret), the variants selected from the
- * pileup of that replay and their Gram matrix, handed over family by family. */
-static int linkage_families(const struct sink_view *v)
+/* The sinks that select over all copies of a family refuse a session that sees only its rank's. */
+static int refuse_multi(const struct sink_view *v, const char *who, const char *why)
 {
-  if (ramx_dev_is_multi(v->d))
-  { ramx_set_error("linkage sink: not with a communicator or mailbox route active (the selection needs the counts of every rank)"); return RAMX_ERR_UNSUPPORTED; }
+  if (!ramx_dev_is_multi(v->d)) return RAMX_OK;
+  ramx_set_error("%s sink: not with a communicator or mailbox route active (%s)", who, why);
+  return RAMX_ERR_UNSUPPORTED;
+}
+
+/* The head of the linkage and the subfamily sink: the bit planes of the families along their kept consensus (rows = ret), the
+ * variants selected from the pileup of that replay and their Gram matrix; with_bits: the selected planes' words too. */
+struct plane_head
+{
+  ramx_col_pileup *cols;             /* [nb][L] */
+  ramx_plane *planes;                /* family b's list: pcount[b] planes from pfirst[b] on, planes_total in all */
+  int32_t *pfirst, *pcount, planes_total;
+  int64_t *cfirst, *bfirst;          /* [nb]: where family b's [P][P] begins in co and its [P][T] in bits */
+  int32_t *co;
+  uint64_t *bits;                    /* NULL without the words */
+};
+static void free_plane_head(struct plane_head *h) { free(h->cols); free(h->planes); free(h->pfirst); free(h->cfirst); free(h->co); free(h->bits); }
+static int plane_head(const struct sink_view *v, int32_t min_count, int32_t min_permille, int32_t max_variants, int with_bits, struct plane_head *h)
+{
   const ramx_params *p = v->p;
   const int nb = v->nb;
   const size_t L = (size_t)(p->L > 0 ? p->L : 1), n = (size_t)(nb > 0 ? nb : 1);
-  int32_t *pfirst = (int32_t *)calloc(n, sizeof(int32_t)), *pcount = (int32_t *)calloc(n, sizeof(int32_t));
-  int64_t *cfirst = (int64_t *)calloc(n, sizeof(int64_t));
-  ramx_col_pileup *cols = (ramx_col_pileup *)calloc(n * L, sizeof(ramx_col_pileup));
-  ramx_plane *planes = (ramx_plane *)calloc(n * 2 * (size_t)(g_linkage_max > 0 ? g_linkage_max : 1), sizeof(ramx_plane));
-  int32_t *co = NULL;
-  int rc = ramx_dev_planes(v->d, v->fl, v->npad, v->first, v->count, nb, p, v->cons, v->ret, cols, NULL, NULL);
-  if (rc == RAMX_OK)
+  int64_t cells = 0, words = 0;
+  memset(h, 0, sizeof(*h));
+  h->pfirst = (int32_t *)calloc(n * 2, sizeof(int32_t)); h->pcount = h->pfirst + n;
+  h->cfirst = (int64_t *)calloc(n * 2, sizeof(int64_t)); h->bfirst = h->cfirst + n;
+  h->cols = (ramx_col_pileup *)calloc(n * L, sizeof(ramx_col_pileup));
+  h->planes = (ramx_plane *)calloc(n * 2 * (size_t)(max_variants > 0 ? max_variants : 1), sizeof(ramx_plane));
+  const int rc = ramx_dev_planes(v->d, v->fl, v->npad, v->first, v->count, nb, p, v->cons, v->ret, h->cols, NULL, NULL);
+  if (rc != RAMX_OK) return rc;
+  for (int b = 0; b < nb; b++)
   {
-    int32_t at = 0;
-    int64_t cells = 0;
-    for (int b = 0; b < nb; b++)
-    {
-      pfirst[b] = at;
-      /* a family without a flank has no tile to take a plane from */
-      pcount[b] = v->count[b] > 0 ? ramx_select_planes(v->cons + (size_t)b * p->L, v->ret[b], cols + (size_t)b * L, g_linkage_count, g_linkage_permille, g_linkage_max, planes + at) : 0;
-      cfirst[b] = cells;
-      at += pcount[b]; cells += (int64_t)pcount[b] * pcount[b];
-    }
-    co = (int32_t *)calloc((size_t)(cells > 0 ? cells : 1), sizeof(int32_t));
-    rc = ramx_dev_plane_gram(v->d, nb, planes, pfirst, pcount, co, cfirst, NULL, NULL);
+    h->pfirst[b] = h->planes_total;
+    /* a family without a flank has no tile to take a plane from */
+    h->pcount[b] = v->count[b] > 0 ? ramx_select_planes(v->cons + (size_t)b * p->L, v->ret[b], h->cols + (size_t)b * L, min_count, min_permille, max_variants, h->planes + h->planes_total) : 0;
+    h->cfirst[b] = cells; h->bfirst[b] = words;
+    h->planes_total += h->pcount[b];
+    cells += (int64_t)h->pcount[b] * h->pcount[b]; words += (int64_t)h->pcount[b] * ((v->count[b] + 63) / 64);
   }
-  for (int b = 0; b < nb && rc == RAMX_OK; b++)
+  h->co = (int32_t *)calloc((size_t)(cells > 0 ? cells : 1), sizeof(int32_t));
+  if (with_bits) h->bits = (uint64_t *)calloc((size_t)(words > 0 ? words : 1), sizeof(uint64_t));
+  return ramx_dev_plane_gram(v->d, nb, h->planes, h->pfirst, h->pcount, h->co, h->cfirst, h->bits, with_bits ? h->bfirst : NULL);
+}
+
+/* With a linkage sink set: the head at the sink's selection, handed over family by family. */
+static int linkage_families(const struct sink_view *v)
+{
+  struct plane_head h;
+  int rc = refuse_multi(v, "linkage", "the selection needs the counts of every rank");
+  if (rc != RAMX_OK) return rc;
+  rc = plane_head(v, g_linkage_count, g_linkage_permille, g_linkage_max, 0, &h);
+  for (int b = 0; b < v->nb && rc == RAMX_OK; b++)
   {
     ramx_linkage lk;
     memset(&lk, 0, sizeof(lk));
-    lk.direction = v->direction; lk.family = v->fidx[b]; lk.rows = v->ret[b]; lk.n_planes = pcount[b];
-    lk.cons = v->cons + (size_t)b * p->L; lk.cols = cols + (size_t)b * L; lk.planes = planes + pfirst[b]; lk.co = co + cfirst[b];
+    lk.direction = v->direction; lk.family = v->fidx[b]; lk.rows = v->ret[b]; lk.n_planes = h.pcount[b];
+    lk.cons = v->cons + (size_t)b * v->p->L; lk.cols = h.cols + (size_t)b * (size_t)(v->p->L > 0 ? v->p->L : 1);
+    lk.planes = h.planes + h.pfirst[b]; lk.co = h.co + h.cfirst[b];
     g_linkage_cb(&lk, g_linkage_user);
   }
-  free(pfirst); free(pcount); free(cfirst); free(cols); free(planes); free(co);
+  free_plane_head(&h);
   return rc;
 }
 
@@ -729,210 +758,246 @@ void ramx_set_subfam_sink(ramx_subfam_cb cb, void *user, int32_t min_count, int3
   g_subfam_replays = max_replays >= 1 ? max_replays : 1;
 }
 
-/* With a subfamily sink set: the linkage sink's planes, selection and Gram matrix; the linked pairs' components as initial
- * patterns; the split on the device, the families with the same number of patterns in one call (the others with an empty list:
- * their labels of that call are not used); the distances to the final patterns from the planes' words; and one refinement over
- * the flanks of every kept group as a family of its own. */
-static int subfam_families(const struct sink_view *v)
+/* What the subfamily sink's steps work on.  The result tables are laid out as the callback gets them, family b's block of each
+ * at RAMX_SUBFAM_MAX times its place: patterns [V][K] at vfirst[b], cnt [K][P] at pfirst[b], size [K] at b, dist [count][K] at
+ * first[b]; the labels at first[b]. */
+struct subfam_work
 {
-  if (ramx_dev_is_multi(v->d))
-  { ramx_set_error("subfamily sink: not with a communicator or mailbox route active (the selection needs the counts of every rank)"); return RAMX_ERR_UNSUPPORTED; }
-  const ramx_params *p = v->p;
-  const int nb = v->nb, KM = RAMX_SUBFAM_MAX;
-  const size_t L = (size_t)(p->L > 0 ? p->L : 1), n = (size_t)(nb > 0 ? nb : 1), np1 = (size_t)(v->npad > 0 ? v->npad : 1);
-  const size_t pcap = 2 * (size_t)(g_subfam_max > 0 ? g_subfam_max : 1);
-  int32_t *pfirst = (int32_t *)calloc(n * 8, sizeof(int32_t)), *pcount = pfirst + n, *Kb = pcount + n, *vfirst = Kb + n, *vcount = vfirst + n,
-          *iters = vcount + n, *conv = iters + n, *qcount = conv + n;
-  int64_t *cfirst = (int64_t *)calloc(n * 2, sizeof(int64_t)), *bfirst = cfirst + n;
-  ramx_col_pileup *cols = (ramx_col_pileup *)calloc(n * L, sizeof(ramx_col_pileup));
-  ramx_plane *planes = (ramx_plane *)calloc(n * pcap, sizeof(ramx_plane));
-  int32_t *labels = (int32_t *)malloc(sizeof(int32_t) * np1), *lab1 = (int32_t *)malloc(sizeof(int32_t) * np1);
-  int32_t *size = (int32_t *)calloc(n * KM, sizeof(int32_t)), *size1 = (int32_t *)calloc(n * KM, sizeof(int32_t));
-  int32_t *dist = (int32_t *)calloc(np1 * KM, sizeof(int32_t));
-  int32_t *co = NULL, *cnt = NULL, *cnt1 = NULL, *it1 = (int32_t *)calloc(n * 2, sizeof(int32_t)), *cv1 = it1 + n;
-  uint64_t *bits = NULL;
-  uint8_t *init = NULL, *pats = NULL, *init1 = NULL, *pats1 = NULL;
-  /* the kept groups as families of their own */
-  ramx_flank *gfl = NULL;
-  int32_t *gfirst = NULL, *gcount = NULL, *grows = NULL, *gout = NULL, *gof = NULL, *ggroup = NULL;
-  int8_t *gcons = NULL, *gref = NULL;
-  ramx_col_pileup *gcols = NULL;
-  ramx_subfam_group *groups = NULL;
-  int ng = 0;
-  int32_t planes_total = 0, var_total = 0;
-  for (int32_t i = 0; i < v->npad; i++) labels[i] = -1;
-  int rc = ramx_dev_planes(v->d, v->fl, v->npad, v->first, v->count, nb, p, v->cons, v->ret, cols, NULL, NULL);
-  if (rc == RAMX_OK)
+  struct plane_head h;
+  int32_t *on;                                   /* [nb]: the family takes part: it has a flank and a kept column */
+  int32_t *Kb, *vfirst, *vcount, *iters, *conv;  /* [nb]: its patterns, where its variants begin and how many, what its split took */
+  int32_t *labels, *cnt, *size, *dist;
+  uint8_t *init, *pats;
+  /* one ramx_dev_subfamilies call, from subfam_gather to subfam_scatter: its lists and what it returns */
+  int32_t *qfirst, *qcount, *lab1, *cnt1, *size1, *it1, *cv1;
+  ramx_plane *qplanes;
+  uint8_t *init1, *pats1;
+  /* the kept groups as families of their own: group ggroup[g] of family gof[g] */
+  int32_t ng, gpad, *gfirst, *gcount, *grows, *gout, *greplays, *gconv, *gof, *ggroup;
+  ramx_flank *gfl;
+  int8_t *gcons, *gref;
+  ramx_col_pileup *gcols;
+  ramx_subfam_group *groups;
+};
+static void free_subfam_work(struct subfam_work *w)
+{
+  free_plane_head(&w->h);
+  free(w->on); free(w->labels); free(w->cnt); free(w->size); free(w->dist); free(w->init); free(w->qplanes);
+  free(w->gfirst); free(w->gfl); free(w->gcons); free(w->gref); free(w->gcols); free(w->groups);
+}
+
+/* the linked pairs of a list, malloc'ed: room for 4096, and a list with more is asked again with room for all it has */
+static ramx_link *linked_pairs(const ramx_plane *planes, int32_t P, const int32_t *co, int32_t *nl)
+{
+  ramx_link *links = (ramx_link *)malloc(sizeof(ramx_link) * 4096);
+  *nl = P > 0 ? ramx_link_pairs(planes, P, co, g_subfam_score, links, 4096) : 0;
+  if (*nl <= 4096) return links;
+  free(links);
+  links = (ramx_link *)malloc(sizeof(ramx_link) * (size_t)*nl);
+  *nl = ramx_link_pairs(planes, P, co, g_subfam_score, links, *nl);
+  return links;
+}
+
+/* Behind the head: who takes part, the tables, and every family's initial patterns, the components of its linked pairs.  A
+ * family that no call splits keeps what it gets here: one group of all its flanks after one assignment. */
+static void subfam_initial(const struct sink_view *v, struct subfam_work *w)
+{
+  const size_t n = (size_t)(v->nb > 0 ? v->nb : 1), np1 = (size_t)(v->npad > 0 ? v->npad : 1), KM = RAMX_SUBFAM_MAX;
+  const size_t pt = (size_t)(w->h.planes_total > 0 ? w->h.planes_total : 1);
+  int32_t var_total = 0, nl;
+  w->on = (int32_t *)calloc(n * 10, sizeof(int32_t)); w->Kb = w->on + n; w->vfirst = w->Kb + n; w->vcount = w->vfirst + n;
+  w->iters = w->vcount + n; w->conv = w->iters + n; w->qfirst = w->conv + n; w->qcount = w->qfirst + n; w->it1 = w->qcount + n; w->cv1 = w->it1 + n;
+  for (int b = 0; b < v->nb; b++)
   {
-    int64_t cells = 0, words = 0;
-    for (int b = 0; b < nb; b++)
-    {
-      pfirst[b] = planes_total;
-      pcount[b] = v->count[b] > 0 ? ramx_select_planes(v->cons + (size_t)b * p->L, v->ret[b], cols + (size_t)b * L, g_subfam_count, g_subfam_permille, g_subfam_max, planes + planes_total) : 0;
-      cfirst[b] = cells; bfirst[b] = words;
-      vfirst[b] = var_total;
-      for (int i = 0; i < pcount[b]; i++) vcount[b] += planes[planes_total + i].cls != RAMX_PLANE_COVER;
-      planes_total += pcount[b]; var_total += vcount[b];
-      cells += (int64_t)pcount[b] * pcount[b]; words += (int64_t)pcount[b] * ((v->count[b] + 63) / 64);
-    }
-    co = (int32_t *)calloc((size_t)(cells > 0 ? cells : 1), sizeof(int32_t));
-    bits = (uint64_t *)calloc((size_t)(words > 0 ? words : 1), sizeof(uint64_t));
-    rc = ramx_dev_plane_gram(v->d, nb, planes, pfirst, pcount, co, cfirst, bits, bfirst);
+    w->on[b] = v->count[b] > 0 && v->ret[b] > 0;
+    w->vfirst[b] = var_total;
+    for (int32_t i = 0; i < w->h.pcount[b]; i++) w->vcount[b] += w->h.planes[w->h.pfirst[b] + i].cls != RAMX_PLANE_COVER;
+    var_total += w->vcount[b];
   }
-  const size_t pt = (size_t)(planes_total > 0 ? planes_total : 1), vt = (size_t)(var_total > 0 ? var_total : 1);
-  init = (uint8_t *)calloc(vt * KM, 1); pats = (uint8_t *)calloc(vt * KM, 1); init1 = (uint8_t *)calloc(vt * KM, 1); pats1 = (uint8_t *)calloc(vt * KM, 1);
-  cnt = (int32_t *)calloc(pt * KM, sizeof(int32_t)); cnt1 = (int32_t *)calloc(pt * KM, sizeof(int32_t));
-  if (rc == RAMX_OK)
+  const size_t vt = (size_t)(var_total > 0 ? var_total : 1);
+  w->labels = (int32_t *)malloc(sizeof(int32_t) * 2 * np1); w->lab1 = w->labels + np1;
+  w->size = (int32_t *)calloc(2 * n * KM, sizeof(int32_t)); w->size1 = w->size + n * KM;
+  w->cnt = (int32_t *)calloc(2 * pt * KM, sizeof(int32_t)); w->cnt1 = w->cnt + pt * KM;
+  w->dist = (int32_t *)calloc(np1 * KM, sizeof(int32_t));
+  w->init = (uint8_t *)calloc(4 * vt * KM, 1); w->pats = w->init + vt * KM; w->init1 = w->pats + vt * KM; w->pats1 = w->init1 + vt * KM;
+  w->qplanes = (ramx_plane *)calloc(pt, sizeof(ramx_plane));
+  for (int32_t i = 0; i < v->npad; i++) w->labels[i] = -1;
+  for (int b = 0; b < v->nb; b++)
   {
-    /* family b's initial patterns at KM * vfirst[b] as [V][Kb[b]] */
-    for (int b = 0; b < nb; b++)
-    {
-      const int32_t P = pcount[b];
-      /* room for 4096 linked pairs; a family with more is asked again with room for all it has */
-      int32_t cap = 4096;
-      ramx_link *links = (ramx_link *)malloc(sizeof(ramx_link) * (size_t)cap);
-      int32_t nl = P > 0 ? ramx_link_pairs(planes + pfirst[b], P, co + cfirst[b], g_subfam_score, links, cap) : 0;
-      if (nl > cap)
-      {
-        cap = nl;
-        free(links);
-        links = (ramx_link *)malloc(sizeof(ramx_link) * (size_t)cap);
-        nl = ramx_link_pairs(planes + pfirst[b], P, co + cfirst[b], g_subfam_score, links, cap);
-      }
-      Kb[b] = ramx_link_components(planes + pfirst[b], P, links, nl, g_subfam_K, init + (size_t)KM * vfirst[b], NULL);
-      free(links);
-      iters[b] = 1; conv[b] = 1;
-      for (int32_t i = 0; i < v->count[b]; i++) labels[v->first[b] + i] = 0;
-      size[(size_t)b * KM] = v->count[b];
-    }
-    /* one call per number of patterns: the families that have it with their lists, the others with none */
-    for (int K = 1; K <= g_subfam_K && rc == RAMX_OK; K++)
-    {
-      int any = 0;
-      int32_t at = 0, vat = 0;
-      for (int b = 0; b < nb; b++)
-      {
-        const int on = Kb[b] == K && v->count[b] > 0 && v->ret[b] > 0;
-        qcount[b] = on ? pcount[b] : 0;
-        if (!on) continue;
-        any = 1;
-        memcpy(init1 + (size_t)K * vat, init + (size_t)KM * vfirst[b], (size_t)K * vcount[b]);
-        at += pcount[b]; vat += vcount[b];
-      }
-      if (!any) continue;
-      /* the lists of this call are those families' lists one after the other: their places are the running sums */
-      int32_t *qfirst = (int32_t *)calloc(n, sizeof(int32_t));
-      ramx_plane *qplanes = (ramx_plane *)calloc(pt, sizeof(ramx_plane));
-      at = 0;
-      for (int b = 0; b < nb; b++)
-      {
-        qfirst[b] = at;
-        if (qcount[b]) memcpy(qplanes + at, planes + pfirst[b], sizeof(ramx_plane) * (size_t)qcount[b]);
-        at += qcount[b];
-      }
-      rc = ramx_dev_subfamilies(v->d, nb, qplanes, qfirst, qcount, init1, K, g_subfam_iter, lab1, pats1, cnt1, size1, it1, cv1);
-      vat = 0;
-      for (int b = 0; b < nb && rc == RAMX_OK; b++)
-      {
-        if (!(Kb[b] == K && v->count[b] > 0 && v->ret[b] > 0)) continue;
-        memcpy(labels + v->first[b], lab1 + v->first[b], sizeof(int32_t) * (size_t)v->count[b]);
-        memcpy(pats + (size_t)KM * vfirst[b], pats1 + (size_t)K * vat, (size_t)K * vcount[b]);
-        memcpy(cnt + (size_t)KM * pfirst[b], cnt1 + (size_t)K * qfirst[b], sizeof(int32_t) * (size_t)K * pcount[b]);
-        memcpy(size + (size_t)b * KM, size1 + (size_t)b * K, sizeof(int32_t) * (size_t)K);
-        iters[b] = it1[b]; conv[b] = cv1[b];
-        vat += vcount[b];
-      }
-      free(qfirst); free(qplanes);
-    }
+    const ramx_plane *pp = w->h.planes + w->h.pfirst[b];
+    ramx_link *links = linked_pairs(pp, w->h.pcount[b], w->h.co + w->h.cfirst[b], &nl);
+    w->Kb[b] = ramx_link_components(pp, w->h.pcount[b], links, nl, g_subfam_K, w->init + KM * w->vfirst[b], NULL);
+    free(links);
+    w->iters[b] = 1; w->conv[b] = 1;
+    for (int32_t i = 0; i < v->count[b]; i++) w->labels[v->first[b] + i] = 0;
+    w->size[KM * b] = v->count[b];
   }
-  if (rc == RAMX_OK)
+}
+
+/* The lists of the call for K patterns: those of the families that have K one after the other, their places the running sums,
+ * the others with none.  Returns how many families the call splits. */
+static int subfam_gather(struct subfam_work *w, int nb, int K)
+{
+  int any = 0;
+  int32_t at = 0, vat = 0;
+  for (int b = 0; b < nb; b++)
   {
-    /* the distances to the patterns handed over, from the words of the selected planes */
-    for (int b = 0; b < nb; b++)
-    {
-      const int32_t P = pcount[b], T = (v->count[b] + 63) / 64, K = Kb[b];
-      const ramx_plane *pp = planes + pfirst[b];
-      const uint64_t *w = bits + bfirst[b];
-      const uint8_t *pt_b = pats + (size_t)KM * vfirst[b];
-      if (!(v->count[b] > 0 && v->ret[b] > 0)) continue;
-      int32_t vn = 0;
-      for (int32_t i = 0; i < P; i++)
-      {
-        if (pp[i].cls == RAMX_PLANE_COVER) continue;
-        int32_t c = -1;
-        for (int32_t j = 0; j < P; j++) if (pp[j].row == pp[i].row && pp[j].cls == RAMX_PLANE_COVER) c = j;
-        for (int32_t f = 0; f < v->count[b]; f++)
-        {
-          const int x = (int)((w[(size_t)i * T + f / 64] >> (f % 64)) & 1), cv = (int)((w[(size_t)c * T + f / 64] >> (f % 64)) & 1);
-          for (int k = 0; k < K; k++) dist[((size_t)v->first[b] + f) * KM + k] += cv & (x ^ pt_b[(size_t)vn * K + k]);
-        }
-        vn++;
-      }
-    }
-    /* the kept groups */
-    for (int b = 0; b < nb; b++)
-      for (int k = 0; k < Kb[b]; k++) if (v->count[b] > 0 && v->ret[b] > 0 && size[(size_t)b * KM + k] >= g_subfam_members && size[(size_t)b * KM + k] > 0) ng++;
-    const size_t g1 = (size_t)(ng > 0 ? ng : 1);
-    gfirst = (int32_t *)calloc(g1 * 6, sizeof(int32_t)); gcount = gfirst + g1; grows = gcount + g1; gout = grows + g1; gof = gout + g1; ggroup = gof + g1;
-    int32_t *greplays = (int32_t *)calloc(g1 * 2, sizeof(int32_t)), *gconv = greplays + g1;
-    gcons = (int8_t *)calloc(g1 * L, 1); gref = (int8_t *)calloc(g1 * L, 1);
-    gcols = (ramx_col_pileup *)calloc(g1 * L, sizeof(ramx_col_pileup));
-    groups = (ramx_subfam_group *)calloc(g1, sizeof(ramx_subfam_group));
-    int32_t gpad = 0;
-    int g = 0;
-    for (int b = 0; b < nb; b++)
-      for (int k = 0; k < Kb[b]; k++)
-      {
-        const int32_t sz = size[(size_t)b * KM + k];
-        if (!(v->count[b] > 0 && v->ret[b] > 0 && sz >= g_subfam_members && sz > 0)) continue;
-        gfirst[g] = gpad; gcount[g] = sz; grows[g] = v->ret[b]; gof[g] = b; ggroup[g] = k;
-        memcpy(gcons + (size_t)g * L, v->cons + (size_t)b * p->L, (size_t)v->ret[b]);
-        gpad += (sz + 63) & ~63;
-        g++;
-      }
-    gfl = (ramx_flank *)malloc(sizeof(ramx_flank) * (size_t)(gpad > 0 ? gpad : 1));
-    for (int32_t i = 0; i < gpad; i++) gfl[i] = empty_flank();
-    for (g = 0; g < ng; g++)
-    {
-      const int b = gof[g];
-      int32_t at = gfirst[g];
-      for (int32_t f = 0; f < v->count[b]; f++) if (labels[v->first[b] + f] == ggroup[g]) gfl[at++] = v->fl[v->first[b] + f];
-    }
-    if (ng > 0)
-      rc = ramx_dev_refine(v->d, gfl, gpad, gfirst, gcount, ng, p, gcons, grows, g_subfam_replays, gref, gout, greplays, gconv, gcols, NULL, NULL);
-    for (g = 0; g < ng; g++)
-    {
-      groups[g].group = ggroup[g]; groups[g].size = gcount[g]; groups[g].refined_rows = gout[g]; groups[g].replays = greplays[g];
-      groups[g].converged = gconv[g]; groups[g].refined_cons = gref + (size_t)g * L; groups[g].refined_cols = gcols + (size_t)g * L;
-    }
-    free(greplays);
+    const int in = w->on[b] && w->Kb[b] == K;
+    w->qfirst[b] = at; w->qcount[b] = in ? w->h.pcount[b] : 0;
+    if (!in) continue;
+    memcpy(w->qplanes + at, w->h.planes + w->h.pfirst[b], sizeof(ramx_plane) * (size_t)w->h.pcount[b]);
+    memcpy(w->init1 + (size_t)K * vat, w->init + (size_t)RAMX_SUBFAM_MAX * w->vfirst[b], (size_t)K * w->vcount[b]);
+    at += w->h.pcount[b]; vat += w->vcount[b]; any++;
   }
+  return any;
+}
+/* what that call returned, into the blocks of the families it split (the labels it gave the others are not used) */
+static void subfam_scatter(struct subfam_work *w, const int32_t *first, const int32_t *count, int nb, int K)
+{
+  const size_t KM = RAMX_SUBFAM_MAX;
+  int32_t vat = 0;
+  for (int b = 0; b < nb; b++)
+  {
+    if (!(w->on[b] && w->Kb[b] == K)) continue;
+    memcpy(w->labels + first[b], w->lab1 + first[b], sizeof(int32_t) * (size_t)count[b]);
+    memcpy(w->pats + KM * w->vfirst[b], w->pats1 + (size_t)K * vat, (size_t)K * w->vcount[b]);
+    memcpy(w->cnt + KM * w->h.pfirst[b], w->cnt1 + (size_t)K * w->qfirst[b], sizeof(int32_t) * (size_t)K * w->h.pcount[b]);
+    memcpy(w->size + KM * b, w->size1 + (size_t)K * b, sizeof(int32_t) * (size_t)K);
+    w->iters[b] = w->it1[b]; w->conv[b] = w->cv1[b];
+    vat += w->vcount[b];
+  }
+}
+
+/* the distances of every flank to the patterns handed over (include/ramx.h: cover AND (bit XOR pattern), summed over the
+ * variants), from the words of the selected planes, into the family's [count][K] block */
+static void subfam_distances(struct subfam_work *w, const int32_t *first, const int32_t *count, int nb)
+{
+  for (int b = 0; b < nb; b++)
+  {
+    const int32_t P = w->h.pcount[b], T = (count[b] + 63) / 64, K = w->Kb[b];
+    const ramx_plane *pp = w->h.planes + w->h.pfirst[b];
+    const uint64_t *wd = w->h.bits + w->h.bfirst[b];
+    const uint8_t *pat = w->pats + (size_t)RAMX_SUBFAM_MAX * w->vfirst[b];
+    int32_t *d = w->dist + (size_t)RAMX_SUBFAM_MAX * first[b], vn = 0;
+    if (!w->on[b]) continue;
+    /* the cover plane of every plane's row, looked up once as ramx_link_pairs does: ramx_select_planes emits the cover of every
+     * row it lists, so every entry is set */
+    int32_t *cover = (int32_t *)malloc(sizeof(int32_t) * (size_t)(P > 0 ? P : 1));
+    for (int32_t i = 0; i < P; i++)
+    {
+      if (pp[i].cls != RAMX_PLANE_COVER) continue;
+      for (int32_t j = i; j >= 0 && pp[j].row == pp[i].row; j--) cover[j] = i;
+      for (int32_t j = i + 1; j < P && pp[j].row == pp[i].row; j++) cover[j] = i;
+    }
+    for (int32_t i = 0; i < P; i++)
+    {
+      if (pp[i].cls == RAMX_PLANE_COVER) continue;
+      const uint64_t *xw = wd + (size_t)i * T, *cw = wd + (size_t)cover[i] * T;
+      for (int32_t f = 0; f < count[b]; f++)
+      {
+        const int x = (int)((xw[f / 64] >> (f % 64)) & 1), cv = (int)((cw[f / 64] >> (f % 64)) & 1);
+        for (int k = 0; k < K; k++) d[(size_t)f * K + k] += cv & (x ^ pat[(size_t)vn * K + k]);
+      }
+      vn++;
+    }
+    free(cover);
+  }
+}
+
+/* the groups of at least min_members flanks as families of their own: each one's flanks in whole tiles, padded with empty ones,
+ * under the kept consensus of the family it comes from */
+static void subfam_kept_groups(const struct sink_view *v, struct subfam_work *w)
+{
+  const size_t L = (size_t)(v->p->L > 0 ? v->p->L : 1), gmax = (size_t)(v->nb > 0 ? v->nb : 1) * RAMX_SUBFAM_MAX;
+  w->gfirst = (int32_t *)calloc(gmax * 8, sizeof(int32_t)); w->gcount = w->gfirst + gmax; w->grows = w->gcount + gmax; w->gout = w->grows + gmax;
+  w->greplays = w->gout + gmax; w->gconv = w->greplays + gmax; w->gof = w->gconv + gmax; w->ggroup = w->gof + gmax;
+  for (int b = 0; b < v->nb; b++)
+    for (int k = 0; k < w->Kb[b]; k++)
+    {
+      const int32_t sz = w->size[(size_t)b * RAMX_SUBFAM_MAX + k], g = w->ng;
+      if (!(w->on[b] && sz >= g_subfam_members && sz > 0)) continue;
+      w->gfirst[g] = w->gpad; w->gcount[g] = sz; w->grows[g] = v->ret[b]; w->gof[g] = b; w->ggroup[g] = k;
+      w->gpad += (sz + 63) & ~63;
+      w->ng++;
+    }
+  const size_t g1 = (size_t)(w->ng > 0 ? w->ng : 1);
+  w->gcons = (int8_t *)calloc(g1 * L, 1); w->gref = (int8_t *)calloc(g1 * L, 1);
+  w->gcols = (ramx_col_pileup *)calloc(g1 * L, sizeof(ramx_col_pileup));
+  w->groups = (ramx_subfam_group *)calloc(g1, sizeof(ramx_subfam_group));
+  w->gfl = (ramx_flank *)malloc(sizeof(ramx_flank) * (size_t)(w->gpad > 0 ? w->gpad : 1));
+  for (int32_t i = 0; i < w->gpad; i++) w->gfl[i] = empty_flank();
+  for (int g = 0; g < w->ng; g++)
+  {
+    const int b = w->gof[g];
+    int32_t at = w->gfirst[g];
+    memcpy(w->gcons + (size_t)g * L, v->cons + (size_t)b * v->p->L, (size_t)v->ret[b]);
+    for (int32_t f = 0; f < v->count[b]; f++) if (w->labels[v->first[b] + f] == w->ggroup[g]) w->gfl[at++] = v->fl[v->first[b] + f];
+  }
+}
+/* one refinement over all of them, and their records */
+static int subfam_refine_groups(const struct sink_view *v, struct subfam_work *w)
+{
+  const size_t L = (size_t)(v->p->L > 0 ? v->p->L : 1);
+  const int rc = w->ng == 0 ? RAMX_OK : ramx_dev_refine(v->d, w->gfl, w->gpad, w->gfirst, w->gcount, w->ng, v->p, w->gcons, w->grows, g_subfam_replays,
+                                                       w->gref, w->gout, w->greplays, w->gconv, w->gcols, NULL, NULL);
+  for (int g = 0; g < w->ng; g++)
+  {
+    ramx_subfam_group *gr = &w->groups[g];
+    gr->group = w->ggroup[g]; gr->size = w->gcount[g]; gr->refined_rows = w->gout[g]; gr->replays = w->greplays[g];
+    gr->converged = w->gconv[g]; gr->refined_cons = w->gref + (size_t)g * L; gr->refined_cols = w->gcols + (size_t)g * L;
+  }
+  return rc;
+}
+
+/* family by family; a family that does not take part is handed over without planes, as one group */
+static void subfam_hand_over(const struct sink_view *v, const struct subfam_work *w)
+{
+  const size_t KM = RAMX_SUBFAM_MAX;
   int g0 = 0;
-  for (int b = 0; b < nb && rc == RAMX_OK; b++)
+  for (int b = 0; b < v->nb; b++)
   {
     ramx_flank *own_fl = own_flanks(v, b);
     ramx_subfamilies sf;
     memset(&sf, 0, sizeof(sf));
-    const int on = v->count[b] > 0 && v->ret[b] > 0;
     sf.direction = v->direction; sf.family = v->fidx[b]; sf.rows = v->ret[b]; sf.n_flanks = v->count[b];
-    sf.n_planes = on ? pcount[b] : 0; sf.n_variants = on ? vcount[b] : 0; sf.K = on ? Kb[b] : 1;
-    sf.iterations = iters[b]; sf.converged = conv[b];
-    while (g0 + sf.n_groups < ng && gof[g0 + sf.n_groups] == b) sf.n_groups++;
-    sf.cons = v->cons + (size_t)b * p->L; sf.flanks = own_fl; sf.core_index = v->map + v->first[b];
-    sf.planes = planes + pfirst[b]; sf.labels = labels + v->first[b];
-    /* the callback's tables are [.][K], the work tables [.][RAMX_SUBFAM_MAX]: the distances are repacked, the others are [.][K] already */
-    int32_t *d1 = (int32_t *)calloc((size_t)(v->count[b] > 0 ? v->count[b] : 1) * (size_t)sf.K, sizeof(int32_t));
-    for (int32_t f = 0; f < v->count[b]; f++)
-      for (int k = 0; k < sf.K; k++) d1[(size_t)f * sf.K + k] = dist[((size_t)v->first[b] + f) * KM + k];
-    sf.patterns = pats + (size_t)KM * vfirst[b]; sf.cnt = cnt + (size_t)KM * pfirst[b]; sf.size = size + (size_t)b * KM; sf.dist = d1;
-    sf.groups = groups ? groups + g0 : NULL;
+    sf.n_planes = w->on[b] ? w->h.pcount[b] : 0; sf.n_variants = w->on[b] ? w->vcount[b] : 0; sf.K = w->on[b] ? w->Kb[b] : 1;
+    sf.iterations = w->iters[b]; sf.converged = w->conv[b];
+    while (g0 + sf.n_groups < w->ng && w->gof[g0 + sf.n_groups] == b) sf.n_groups++;
+    sf.cons = v->cons + (size_t)b * v->p->L; sf.flanks = own_fl; sf.core_index = v->map + v->first[b];
+    sf.planes = w->h.planes + w->h.pfirst[b]; sf.labels = w->labels + v->first[b];
+    sf.patterns = w->pats + KM * w->vfirst[b]; sf.cnt = w->cnt + KM * w->h.pfirst[b]; sf.size = w->size + KM * b; sf.dist = w->dist + KM * v->first[b];
+    sf.groups = w->groups + g0;
     g_subfam_cb(&sf, g_subfam_user);
     g0 += sf.n_groups;
-    free(d1); free(own_fl);
+    free(own_fl);
   }
-  free(pfirst); free(cfirst); free(cols); free(planes); free(labels); free(lab1); free(size); free(size1); free(dist); free(co);
-  free(cnt); free(cnt1); free(it1); free(bits); free(init); free(pats); free(init1); free(pats1);
-  free(gfl); free(gfirst); free(gcons); free(gref); free(gcols); free(groups);
+}
+
+/* With a subfamily sink set: the linkage sink's head with the planes' words; the linked pairs' components as initial patterns;
+ * the split on the device, one call per number of patterns that some family has, ascending; the distances to the final patterns;
+ * and one refinement over the flanks of every kept group as a family of its own. */
+static int subfam_families(const struct sink_view *v)
+{
+  struct subfam_work w;
+  int rc = refuse_multi(v, "subfamily", "the selection needs the counts of every rank");
+  if (rc != RAMX_OK) return rc;
+  memset(&w, 0, sizeof(w));
+  rc = plane_head(v, g_subfam_count, g_subfam_permille, g_subfam_max, 1, &w.h);
+  if (rc == RAMX_OK) subfam_initial(v, &w);
+  for (int K = 1; K <= g_subfam_K && rc == RAMX_OK; K++)
+  {
+    if (!subfam_gather(&w, v->nb, K)) continue;
+    rc = ramx_dev_subfamilies(v->d, v->nb, w.qplanes, w.qfirst, w.qcount, w.init1, K, g_subfam_iter, w.lab1, w.pats1, w.cnt1, w.size1, w.it1, w.cv1);
+    if (rc == RAMX_OK) subfam_scatter(&w, v->first, v->count, v->nb, K);
+  }
+  if (rc == RAMX_OK)
+  {
+    subfam_distances(&w, v->first, v->count, v->nb);
+    subfam_kept_groups(v, &w);
+    rc = subfam_refine_groups(v, &w);
+  }
+  if (rc == RAMX_OK) subfam_hand_over(v, &w);
+  free_subfam_work(&w);
   return rc;
 }
 
@@ -951,19 +1016,19 @@ void ramx_set_dist_sink(ramx_dist_cb cb, void *user, int32_t min_cols, int32_t m
  * ends of that replay and their pair matrix, handed over family by family. */
 static int dist_families(const struct sink_view *v)
 {
-  if (ramx_dev_is_multi(v->d))
-  { ramx_set_error("dist sink: not with a communicator or mailbox route active (a rank sees only its own copies)"); return RAMX_ERR_UNSUPPORTED; }
+  int rc = refuse_multi(v, "dist", "a rank sees only its own copies");
+  if (rc != RAMX_OK) return rc;
   const ramx_params *p = v->p;
   const int nb = v->nb;
   const size_t L = (size_t)(p->L > 0 ? p->L : 1), n = (size_t)(nb > 0 ? nb : 1), np = (size_t)(v->npad > 0 ? v->npad : 1);
-  int32_t *cfirst = (int32_t *)calloc(n, sizeof(int32_t)), *ccount = (int32_t *)calloc(n, sizeof(int32_t));
+  int32_t *cfirst = (int32_t *)calloc(n * 2, sizeof(int32_t)), *ccount = cfirst + n;
   int64_t *ofirst = (int64_t *)calloc(n, sizeof(int64_t));
   ramx_col_pileup *cols = (ramx_col_pileup *)calloc(n * L, sizeof(ramx_col_pileup));
   ramx_aln_end *ends = (ramx_aln_end *)malloc(sizeof(ramx_aln_end) * np);
   int32_t *copies = (int32_t *)calloc(n * (size_t)(g_dist_max > 0 ? g_dist_max : 1), sizeof(int32_t));
   ramx_copy_dist *dist = NULL;
-  for (int32_t i = 0; i < v->npad; i++) { ends[i].end_row = -1; ends[i].end_idx = -1; ends[i].score = 0; ends[i].start_idx = 0; ends[i].tail_ins = 0; }
-  int rc = ramx_dev_planes(v->d, v->fl, v->npad, v->first, v->count, nb, p, v->cons, v->ret, cols, ends, NULL);
+  blank_ends(ends, v->npad);
+  rc = ramx_dev_planes(v->d, v->fl, v->npad, v->first, v->count, nb, p, v->cons, v->ret, cols, ends, NULL);
   if (rc == RAMX_OK)
   {
     int32_t at = 0;
@@ -987,7 +1052,7 @@ static int dist_families(const struct sink_view *v)
     ds.copies = copies + cfirst[b]; ds.dist = dist + ofirst[b];
     g_dist_cb(&ds, g_dist_user);
   }
-  free(cfirst); free(ccount); free(ofirst); free(cols); free(ends); free(copies); free(dist);
+  free(cfirst); free(ofirst); free(cols); free(ends); free(copies); free(dist);
   return rc;
 }
 

@@ -191,15 +191,20 @@ CLI_SCORE = 3
 UNPLANTED_PAIR = ((0, 5), (1, 7))
 
 
+def planted_family(spec=PLANTED_FAMILY, columns=PLANTED_COLUMNS, every=PLANTED_EVERY):
+    """The planted family of a spec, computed once however the spec is spelled (the defaults left out or written out)."""
+    return _planted_family(spec, tuple(columns), every)
+
+
 @functools.lru_cache(maxsize=None)
-def planted_family():
+def _planted_family(spec, columns, every):
     """-> (fs, sequence with the variants planted, p, {direction: kept consensus}, {direction: the planted (row, cls)}).  The
-    kept consensus of each direction is the oracle's on the family as generated; the base matched to columns 8, 30 and 55 of
-    every third flank is then overwritten by (cons[r] + 1) % 4, complemented on the reverse strand."""
+    kept consensus of each direction is the oracle's on the family as generated; the base matched to `columns` (8, 30 and 55) of
+    every `every`-th (third) flank is then overwritten by (cons[r] + 1) % 4, complemented on the reverse strand."""
     from oracle import pyoracle as po
     from repeatafterme_amd.datamodel import new_master
     from repeatafterme_amd.synth import synth_family
-    (n, L, W, K, seed), matrix, stop = PLANTED_FAMILY
+    (n, L, W, K, seed), matrix, stop = spec
     fs = synth_family(n, L, W, K=K, seed=seed, both_sides=True, minus_frac=0.4, n_run_frac=0.1)
     seq = np.ascontiguousarray(fs.sequence, np.int8).copy()
     p = po.Params.named(matrix, bandwidth=W, L=L, when_to_stop=stop)
@@ -211,11 +216,11 @@ def planted_family():
         walks[d] = ar.walk_family(d, fs.cores, seq, p, cons[d])
     for d in (1, 0):
         idx, results = walks[d]
-        planted[d] = tuple((r, (int(cons[d][r]) + 1) % 4) for r in PLANTED_COLUMNS)
-        for k in range(0, len(idx), PLANTED_EVERY):
+        planted[d] = tuple((r, (int(cons[d][r]) + 1) % 4) for r in columns)
+        for k in range(0, len(idx), every):
             fl = ar.Flank(d, fs.cores, idx[k], W)
             for op in results[k]["ops"]:
-                if op[0] == "M" and op[1] in PLANTED_COLUMNS and fl.inside(op[2]):
+                if op[0] == "M" and op[1] in columns and fl.inside(op[2]):
                     write_base(fl, op[2], seq, (int(cons[d][op[1]]) + 1) % 4)
     seq.setflags(write=False)
     for d in cons:
@@ -234,11 +239,15 @@ def write_base(fl, t, sequence, base):
     raise AssertionError("no code gives that base")
 
 
-@functools.lru_cache(maxsize=None)
-def planted_case(direction):
+def planted_case(direction, spec=PLANTED_FAMILY, columns=PLANTED_COLUMNS, every=PLANTED_EVERY):
     """The planted family walked again along the kept consensus: planes, pileup, selection, Gram and pairs, computed once."""
+    return _planted_case(direction, spec, tuple(columns), every)
+
+
+@functools.lru_cache(maxsize=None)
+def _planted_case(direction, spec, columns, every):
     from pileup_ref import pileup_of
-    fs, seq, p, cons, planted = planted_family()
+    fs, seq, p, cons, planted = planted_family(spec, columns, every)
     c = cons[direction]
     idx, results = ar.walk_family(direction, fs.cores, seq, p, c)
     cols = pileup_of(direction, fs.cores, idx, results, seq, p.bandwidth, c)

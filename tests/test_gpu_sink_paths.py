@@ -2,7 +2,9 @@
 run one at a time through extend_alignment and together through extend_batch, both directions, all five sinks set at once.
 Every record the batch hands over is the single call's, byte for byte, and the corners are what include/ramx.h documents: a
 family without an extendable core, and ret = 0 after rows were executed.  Ordinary families are tied to independent
-restatements elsewhere (align_ref.py, pileup_ref.py, copystats_ref.py, linkage_ref.py); this file does not repeat that.
+restatements elsewhere (align_ref.py, pileup_ref.py, copystats_ref.py, linkage_ref.py); this file does not repeat that.  The
+sinks that answer from the resident planes (linkage again, subfamilies, distance) have tests/test_gpu_plane_sinks.py, on families
+that share a ramx_dev_subfamilies call.
 
 Four families (bandwidth 5, L = 30, matrix 14p43g, about 20 recoverable columns), in this order in the batch:
   0: 70 flanks          two tiles, the second uneven
@@ -127,7 +129,8 @@ def same_bytes(a, b):
 
 
 def assert_same_record(a, b, where):
-    """every field of two records of one kind but `family`: arrays byte for byte"""
+    """every field of two records of one kind but `family`: arrays byte for byte, a list of records (Subfamilies.groups) record by
+    record"""
     assert type(a) is type(b), where
     for fld in dataclasses.fields(a):
         if fld.name == "family":
@@ -135,6 +138,10 @@ def assert_same_record(a, b, where):
         x, y = getattr(a, fld.name), getattr(b, fld.name)
         if isinstance(x, np.ndarray):
             assert same_bytes(x, y), where + (fld.name,)
+        elif isinstance(x, list):
+            assert isinstance(y, list) and len(x) == len(y), where + (fld.name, len(x))
+            for i, (p, q) in enumerate(zip(x, y)):
+                assert_same_record(p, q, where + (fld.name, i))
         else:
             assert x == y, where + (fld.name, x, y)
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Host code of the replays under AddressSanitizer + UBSan, as stand-alone programs on the CPU (no GPU is opened, nothing is
-# loaded into python): replay_plan, the route gates, the batch's route plan, the site windows and the resident planes' lists of ramx_device.hip, pad_to_tiles and the sinks' one-family view of ramx_extend.c, all static, so each program includes
+# loaded into python): replay_plan, the route gates, the batch's route plan, the site windows and the resident planes' lists of ramx_device.hip, pad_to_tiles, the sinks' one-family view and the subfamily sink's host steps of ramx_extend.c, all static, so each program includes
 # its source file and takes the rest of the library from the built libramx.so; and ramx_linkage.c, which stands alone.
 # usage: tools/host_asan/run.sh        (after the library has been built)
 set -euo pipefail
@@ -14,6 +14,9 @@ lib="-L$root/repeatafterme_amd -lramx -Wl,-rpath,$root/repeatafterme_amd -Wl,-rp
 san="-fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g"
 gcc -std=gnu11 -O1 -Wno-alloc-size-larger-than $san $inc -o "$out/pad_to_tiles" "$here/pad_to_tiles_main.c" $lib -lm -lpthread
 "$out/pad_to_tiles"
+# the pure host steps of the subfamily sink of ramx_extend.c on hand-made tables: gather and scatter of a per-K call, the distances, the kept groups
+gcc -std=gnu11 -O1 -Wno-alloc-size-larger-than $san $inc -o "$out/subfam_sink" "$here/subfam_sink_main.c" $lib -lm -lpthread
+"$out/subfam_sink"
 # the selection, the pair statistic and the components of the linkage (ramx_linkage.c is compiled into the program, under the sanitizers too)
 gcc -std=gnu11 -O1 $san $inc -o "$out/linkage" "$here/linkage_main.c" -lm
 "$out/linkage"
