@@ -133,6 +133,52 @@ int main()
     c.cus = 100;
     CHECK(gates(c).k == 0 && gates(c).cp_try && settled(c).pk);
   }
+  // the class table itself: a matrix whose 36 entries [candidate][A C G T a c g t N] are pairwise distinct (the `distinct` system
+  // of tests/class_table.py) through class_tab -- tab[class][candidate] = matrix[candidate][code(class)] -- entry by entry
+  static const int distinct[4][RAMX_NCLASS] = { {  12, -18, -10, -21,   8, -16,  -8, -24, -1 }, { -19,  11, -20,  -7, -14,   7, -22,  -5,  2 },
+                                                {  -6, -17,  10, -15,  -4, -25,   6, -12, -2 }, { -23,  -9, -13,   9, -26, -11,  -3,   5,  1 } };
+  static int32_t matrix[100 * 100];
+  for (int i = 0; i < 100 * 100; i++) matrix[i] = 1000 + i;      // (nothing outside [0..3] x {0..7, 99} may show in the table)
+  for (int k = 0; k < 4; k++)
+    for (int c = 0; c < RAMX_NCLASS; c++) matrix[k * 100 + (c == 8 ? 99 : c)] = distinct[k][c];
+  ramx_params prm = {};
+  prm.matrix = matrix;
+  {
+    class_tab(&prm, g_tab);
+    static const int want[RAMX_NCLASS][4] = { { 12, -19, -6, -23 }, { -18, 11, -17, -9 }, { -10, -20, 10, -13 }, { -21, -7, -15, 9 },      // A C G T
+                                              { 8, -14, -4, -26 }, { -16, 7, -25, -11 }, { -8, -22, 6, -3 }, { -24, -5, -12, 5 },          // a c g t
+                                              { -1, 2, -2, 1 } };                                                                          // N
+    for (int c = 0; c < RAMX_NCLASS; c++)
+      for (int k = 0; k < 4; k++) CHECK(g_tab[c][k] == want[c][k]);
+    DirRoute rt = settled(base);
+    CHECK(rt.int32_can && rt.pk && rt.k == 16 && fast_pack_ok(g_tab, base.go, base.ge, base.L, base.W));
+  }
+  // one lone extreme entry -- in a lower-case class, in N, in an upper-case class: the int8 range closes the fast band and the
+  // cell-parallel kernel wherever the entry sits, the packed rows' plan sees it as P or mn (admitted at W = 14, refused at
+  // W = 80, where the table without it is admitted: tests/score_gates.py and tests/test_class_table_ref.py say the same)
+  {
+    static const int where[3][2] = { { 6, 2 }, { 8, 1 }, { 1, 1 } };
+    static const int values[4] = { 127, 128, -128, -129 };
+    Case wide; wide.W = 80;
+    CHECK(gates(wide).pk && gates(wide).k > 0);
+    for (int w = 0; w < 3; w++)
+      for (int v = 0; v < 4; v++)
+      {
+        const int code = where[w][0] == 8 ? 99 : where[w][0], cand = where[w][1];
+        const int32_t kept = matrix[cand * 100 + code];
+        matrix[cand * 100 + code] = values[v];
+        class_tab(&prm, g_tab);
+        const bool int8 = values[v] >= -128 && values[v] <= 127;
+        CHECK(g_tab[where[w][0]][cand] == values[v]);
+        CHECK((fast_pack_ok(g_tab, base.go, base.ge, base.L, base.W) != 0) == int8);
+        CHECK((ramx_cp_max_family(base.W, base.go, base.ge, g_tab, base.L) > 0) == int8);
+        DirRoute rt = settled(base);
+        CHECK(rt.int32_can && rt.pk && (rt.k == 16) == int8 && (rt.k == 0) == !int8);
+        CHECK(!gates(wide).pk && gates(wide).int32_can && (gates(wide).k > 0) == int8);
+        matrix[cand * 100 + code] = kept;
+      }
+    class_tab(&prm, g_tab);
+  }
   if (g_failed) return 1;
   printf("route_gates: ok\n");
   return 0;
